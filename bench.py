@@ -23,6 +23,11 @@ Each rank processes its own batch (independent utterances): weak scaling.
 The default run (N = 1, train) also times, AFTER the headline loop and outside its timed region, the other lines of the
 round on the same box and attaches them as `secondary` (inference, ragged inference, training in bf16 -- the literal
 BASELINE configs[1] dtype -- and in 'mixed'); `value` / `config` / `dtype` describe the headline loop only.
+
+`--dump-outputs DIR` writes what the LAST timed step of the headline loop returned to its caller (train: the denoiser's
+predicted noise, mask and two losses, the detector's logits and loss; inference: the denoised waveforms) as DIR/<name>.npy,
+under 64 MB in all.  Inputs and initial weights are seeded, so two builds run with the same arguments can be compared
+array for array.
 """
 import argparse
 import json
@@ -233,17 +238,17 @@ class Workload:
                 # itself (run_timed's roofline pre-pass; --serial)
                 prev, jnet.JointModel.BRANCH_STREAMS = jnet.JointModel.BRANCH_STREAMS, False
                 try:
-                    ag_det.train_func(batch_det)
-                    ag_jm.train_func(batch_jm)
+                    out_det = ag_det.train_func(batch_det)
+                    return [ag_jm.train_func(batch_jm), out_det]
                 finally:
                     jnet.JointModel.BRANCH_STREAMS = prev
             self.serial_step = serial_step
 
             def step():
                 if serial:
-                    serial_step()
-                else:           # the two models are independent: one HIP stream each (+ the denoiser's branch stream)
-                    agent.train_concurrent([(ag_jm, batch_jm), (ag_det, batch_det)])
+                    return serial_step()
+                # the two models are independent: one HIP stream each (+ the denoiser's branch stream)
+                return agent.train_concurrent([(ag_jm, batch_jm), (ag_det, batch_det)])
             if loader:
                 # --loader N: every step draws a FRESH batch from sos_amd.dataset.get_dataloader -- N worker
                 # processes make the host draws, the producer thread uploads them from pinned memory and runs bits -> mask, the mix
@@ -256,7 +261,7 @@ class Workload:
 
                 def step():       # noqa: F811
                     b = next(it)
-                    agent.train_concurrent([(ag_jm, b), (ag_det, {"audio": b["mixed"], "label": b["_bits"].float()})])
+                    return agent.train_concurrent([(ag_jm, b), (ag_det, {"audio": b["mixed"], "label": b["_bits"].float()})])
                 self._loader_iter = it
             self.eager = step
             self.concurrent = not serial
@@ -299,6 +304,48 @@ class Workload:
         if self.lens is not None:                                         # FLOPs scale with the frames of a clip: 2 s = 178 frames
             g *= sum(1 + n // 158 for n in self.lens) / (178.0 * self.B)
         return g
+
+    def outputs(self, result):
+        """What a caller of the timed path receives from one step, as named tensors (--dump-outputs)."""
+        if self.mode == "train":
+            ((pred_noise, mask), jl), (logits, dl) = result
+            return {"denoiser_pred_noise": pred_noise, "denoiser_mask": mask, "denoiser_loss_stage1": jl["stage1"],
+                    "denoiser_loss_stage2": jl["stage2"], "detector_logits": logits, "detector_loss_bce": dl["bce"]}
+        if self.mode == "train-av":
+            logits, dl = result
+            return {"detector_logits": logits, "detector_loss_bce": dl["bce"]}
+        if self.mode == "infer-ragged":        # clips of different lengths: concatenated, with the lengths
+            return {"denoised_concat": torch.cat(list(result)),
+                    "denoised_lengths": torch.tensor([len(y) for y in result], dtype=torch.float64)}
+        if isinstance(result, tuple):          # PipelinedDenoiser: (output, completion event)
+            result = result[0]
+        return {"denoised": result}
+
+
+DUMP_BYTES = 60 << 20         # --dump-outputs: array bytes in all (the files, headers included, stay under 64 MB)
+
+
+def dump_outputs(named, out_dir):
+    """Write each named tensor as out_dir/<name>.npy (float32; float64 tensors stay float64).  When the whole would exceed
+    DUMP_BYTES, every array above 1 MiB is replaced by a seeded sample of its flattened elements (sorted indices, the same
+    for every run of the same shapes), the large arrays sharing what the small ones leave of the budget equally."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for k, t in named.items():
+        t = t.detach()
+        arrs[k] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    if sum(a.nbytes for a in arrs.values()) > DUMP_BYTES:
+        large = [k for k, a in arrs.items() if a.nbytes > 1 << 20]
+        room = DUMP_BYTES - sum(a.nbytes for k, a in arrs.items() if k not in large)
+        for k in large:
+            a = arrs[k].reshape(-1)
+            n = room // len(large) // a.itemsize
+            if a.size > n:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+                arrs[k] = a[idx]
+                sys.stderr.write(f"bench.py: {k}: {n} of {a.size} elements (seeded sample)\n")
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def _dominant(summ):
@@ -366,10 +413,13 @@ def run_timed(wl, steps, warmup, barrier, profile=True):
             ag.bucketer.comm_reset()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        wl.step()
+    for i in range(steps):
+        out = wl.step()
+        if i + 1 < steps:
+            out = None              # only the last step's result is kept (wl.last_output, --dump-outputs)
     barrier()
     dt = time.perf_counter() - t0
+    wl.last_output = out if steps > 0 else None
     if profile and not use_graph:
         prof = engine.PROFILER.summary()[dom]
     engine.PROFILER = None
@@ -407,6 +457,8 @@ def main():
     ap.add_argument("--force-buckets", action="store_true",
                     help="world of one: run the data-parallel gradient path anyway (bucket copies + RCCL all-reduce of every "
                          "bucket on a 1-rank group) to measure its overhead on a single GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -464,6 +516,9 @@ def main():
     wl = Workload(args.mode, args.precision, B, rank, serial=args.serial, graph=args.graph, train_detector=args.train_detector,
                   pipelined=args.pipelined, loader=args.loader if args.mode == "train" else 0)
     dt, dom, prof = run_timed(wl, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(wl.last_output), args.dump_outputs)
+    wl.last_output = None
     ddp = None
     if dist is not None:
         # what the data-parallel path did: per-rank time of the K steps (min / max over the ranks: rank skew), and
