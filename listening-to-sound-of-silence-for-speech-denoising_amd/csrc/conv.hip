@@ -1054,19 +1054,11 @@ __device__ __forceinline__ void conv16_epilogue(const ConvParams& p, f32x4 (&acc
 #endif
 
 // MODE 0: two window-slab buffers, the next window's DMA issued at the start of a window (lands in ~600 cycles of MFMAs or
-// is waited for); 1: ONE buffer refilled behind a barrier (three workgroups per CU cover each other's refill latency);
-// 2 (round 3, an A/B switch only: SOS_CONV16_MODE=2): a RING OF THREE buffers, the DMA of window w + 2 issued at the start of
-// window w, counted vmcnt waits, one barrier per window, two workgroups per CU (66 KB).  Written on the hypothesis that the
-// per-window refill wait is what holds mode 1 at 52 % MFMA-pipe busy; MEASURED SLOWER (48 -> 48 5x5 at B = 64: 0.410 ms
-// against 0.348 ms in mode 1 and 0.395 ms in mode 0; the ISA shows no wait inside the window): what the kernel needs is the
-// third resident workgroup, i.e. more waves to cover the fragment reads' LDS latency (7 ds_read_b128 per 12 MFMAs keep the
-// LDS pipe ~55 % busy), not a hidden refill.
-// PT: 16-pixel column tiles per wave.  4: a 256-pixel workgroup (three per CU in MODE 1).  8 (round 4): a wave owns 128 pixels x
-// all NT16 * 16 output channels -- NT16 + 8 fragment reads per 8 NT16 MFMAs instead of NT16 + 4 per 4 NT16 (48 channels: 11 per 24
-// instead of 7 per 12 ds_read_b128), and a 512-pixel workgroup streams every window slab once for twice the pixels (half the
-// L2 -> LDS weight traffic and half the barriers per pixel); 96 accumulator registers, two workgroups per CU.
+// is waited for); 1: ONE buffer refilled behind a barrier (three workgroups per CU cover each other's refill latency).
+// (A ring of three buffers and 512-pixel workgroups were built and measured slower: EXPERIMENTS.md section 3.1b.)
+// PT: 16-pixel column tiles per wave (4: a 256-pixel workgroup).
 template <int NT16, int KS, int MODE, int PT = 4>
-__global__ __launch_bounds__(256, (MODE == 1 && PT == 4) ? 3 : 2) void conv16_kernel(ConvParams p) {
+__global__ __launch_bounds__(256, MODE == 1 ? 3 : 2) void conv16_kernel(ConvParams p) {
 #if __HIP_DEVICE_COMPILE__
     constexpr int KC = 16 * KS, G8 = 2 * KS;     // channels / 8-channel groups per tap
     // unpadded row pitches: lanes 16..31 of a fragment read address the SAME 16 rows as lanes 0..15, 16 bytes further
@@ -1079,8 +1071,7 @@ __global__ __launch_bounds__(256, (MODE == 1 && PT == 4) ? 3 : 2) void conv16_ke
     // the double-buffered variant fills the window slab by LDS-DMA (whole 1 KB instructions; the slab image is piece-linear)
     constexpr int WINSTR = (WPIECES + 63) / 64, WPW = (WINSTR + 3) / 4;
     constexpr bool SB = MODE == 1;
-    constexpr int NBUF = MODE == 1 ? 1 : (MODE == 2 ? 3 : 2);
-    static_assert(MODE != 2 || WPW <= 3, "ring mode: the counted vmcnt waits cover at most three DMA instructions per wave and window");
+    constexpr int NBUF = MODE == 1 ? 1 : 2;
     constexpr int WBYTES = SB ? 2 * TAPBYTES : WINSTR * 1024;
     constexpr int OROW = NT16 * 32 + 16;          // bytes per staged output pixel row
     constexpr int SLOTS = 64 * PT;                // pixel slots of the workgroup's tile
@@ -1185,11 +1176,9 @@ __global__ __launch_bounds__(256, (MODE == 1 && PT == 4) ? 3 : 2) void conv16_ke
     if (!CDBG(1)) stage_patch_dma<CPR, false>(p, patch, (unsigned)(uintptr_t)pixtab, lane, __builtin_amdgcn_readfirstlane(wave), in_rsrc,
                                 (unsigned)((p.cin_off + sg * p.seg_stride) * 2));
     if (!CDBG(8)) dma_window(0, 0);
-    if constexpr (MODE == 2) { if (nwin > 1 && !CDBG(8)) dma_window(1, 1); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's patch pieces have landed
     __syncthreads();
 
-    int ring = 0;                                         // MODE 2: buffer of window w (w mod 3 without the division)
 #if SOS_C16_XPF
     // pixel fragments of the NEXT window's first K-block: requested before the barrier(s) that close a window (the patch does
     // not change inside a segment), so that behind the barrier only the three weight fragments are still to be read
@@ -1201,10 +1190,8 @@ __global__ __launch_bounds__(256, (MODE == 1 && PT == 4) ? 3 : 2) void conv16_ke
     }
 #endif
     for (int w = 0; w < nwin; ++w) {
-        const int cur = MODE == 2 ? ring : (SB ? 0 : (w & 1));
+        const int cur = SB ? 0 : (w & 1);
         if constexpr (MODE == 0) { if (w + 1 < nwin && !CDBG(8)) dma_window(w + 1, cur ^ 1); }       // next window's slab (lands while the MFMAs run)
-        // ring: window w + 2 into the buffer window w - 1 was read from (every wave has passed the barrier that closed it)
-        if constexpr (MODE == 2) { if (w + 2 < nwin && !CDBG(8)) dma_window(w + 2, ring == 0 ? 2 : ring - 1); }
         __builtin_amdgcn_sched_barrier(0);
         // patch byte offsets of the window's two taps: lane t of tapoff16 (two v_readlane instead of four scalar divisions by
         // kw per window: SQ counters showed 2.7 SALU per MFMA in this kernel against 1.5 in the 32-row one)
@@ -1282,18 +1269,7 @@ __global__ __launch_bounds__(256, (MODE == 1 && PT == 4) ? 3 : 2) void conv16_ke
             __syncthreads();
             if (w + 1 < nwin && !CDBG(8)) dma_window(w + 1, 0);
         }
-        if constexpr (MODE == 2) {
-            // window w + 1 must have landed; this wave's pieces of window w + 2 (issued above: instructions wv, wv + 4, ...
-            // of WINSTR) may stay in flight
-            const int mine = (w + 2 < nwin && !CDBG(8)) ? (WINSTR - wv + 3) / 4 : 0;
-            if (mine >= 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else if (mine == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if (mine == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            ring = ring == 2 ? 0 : ring + 1;
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
     }
@@ -1313,82 +1289,11 @@ static const size_t LDS_LIMIT = 160 * 1024;
 
 typedef void (*conv_kernel_t)(ConvParams);
 
-template <int NT, int KS, bool SB, bool INBN = false, int PT = 2, bool W3 = false>
-static int launch_one(const ConvParams& p, dim3 grid, size_t lds, hipStream_t stream) {
-    static sos_device_once attr_once;           // one per instantiation
-    conv_kernel_t k = conv_mfma_kernel<NT, KS, SB, INBN, PT, W3>;
-    const int arc = sos_per_device_once(attr_once, [k] {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-        if (e != hipSuccess) {
-            sos_set_error("sos_conv2d_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)SOS_ELAUNCH;
-        }
-        return (int)SOS_OK;
-    });
-    if (arc) return arc;
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, stream, p);
-    return sos_check_launch("sos_conv2d_fwd");
-}
-
-// ks: k-steps per channel chunk; + 100: single weight-slab buffer (NT <= 3, ks <= 4 only)
-template <int NT>
-static int launch_ks(int ks, const ConvParams& p, dim3 grid, size_t lds, hipStream_t stream) {
-    if (p.in_scale) {
-        // fused input BatchNorm: the 96-channel context layers' tilings only (three n-tiles, 2 or 3 k-steps per chunk, double slab)
-        // (stage_issue_bn loads in_scale / in_shift per KC-channel chunk: cin must be whole chunks, or it reads past the
-        // f32[cin] arrays -- ADVICE r5)
-        if constexpr (NT == 3) {
-            if (ks == 3 && p.cin % 48 == 0) return launch_one<3, 3, false, true>(p, grid, lds, stream);
-            if (ks == 2 && p.cin % 32 == 0) return launch_one<3, 2, false, true>(p, grid, lds, stream);
-        }
-        sos_set_error("sos_conv2d_fwd: fused input BatchNorm (in_scale) is not built for this tiling (nt=%d ks=%d)", NT, ks);
-        return SOS_EINVAL;
-    }
-    if constexpr (NT == 3) {                    // 384-slot tiles (ks + 300): a wave owns 96 pixels x 96 output channels
-        switch (ks) {
-            case 302: return launch_one<3, 2, false, false, 3>(p, grid, lds, stream);
-            case 303: return launch_one<3, 3, false, false, 3>(p, grid, lds, stream);
-            // ks + 200: double slab, three workgroups per CU (<= 168 registers, TIGHT epilogue layout)
-            case 201: return launch_one<3, 1, false, false, 2, true>(p, grid, lds, stream);
-            case 202: return launch_one<3, 2, false, false, 2, true>(p, grid, lds, stream);
-        }
-    }
-    if constexpr (NT <= 3) {
-        switch (ks) {
-            case 101: return launch_one<NT, 1, true>(p, grid, lds, stream);
-            case 102: return launch_one<NT, 2, true>(p, grid, lds, stream);
-            case 103: return launch_one<NT, 3, true>(p, grid, lds, stream);
-            case 104: return launch_one<NT, 4, true>(p, grid, lds, stream);
-        }
-    }
-    switch (ks) {
-        case 1: return launch_one<NT, 1, false>(p, grid, lds, stream);
-        case 2: return launch_one<NT, 2, false>(p, grid, lds, stream);
-        case 3: return launch_one<NT, 3, false>(p, grid, lds, stream);
-        case 4: return launch_one<NT, 4, false>(p, grid, lds, stream);
-        case 5: return launch_one<NT, 5, false>(p, grid, lds, stream);
-        case 6: return launch_one<NT, 6, false>(p, grid, lds, stream);
-        case 8: return launch_one<NT, 8, false>(p, grid, lds, stream);
-    }
-    sos_set_error("sos_conv2d_fwd: unsupported k-steps %d", ks);
-    return SOS_EINVAL;
-}
-
-static size_t lds_bytes(int npix, int nt, int ks) {           // ks 100..199: single slab buffer; 200..: three per CU; 300..: 384-slot tile (double slab)
-    if (ks >= 300) ks -= 300;
-    if (ks >= 200) ks -= 200;
-    const bool single = ks >= 100;
-    if (single) ks -= 100;
-    const size_t row = (size_t)ks * 32 + 16;
-    const size_t slab = single ? (size_t)nt * 32 * row : ((size_t)nt * 32 * (2 * ks + 1) + 63) / 64 * 1024;   // BBYTES of the kernel
-    return (size_t)npix * row + (single ? 1 : 2) * slab + (size_t)npix * 4;
-}
-
-// the 16-row kernel (conv16_kernel) handles: one bf16 channel segment of 16 or 48 channels, bf16 NHWC output,
-// cout <= 16 or 33..48 (i.e. shapes where tiles of 32 output channels waste MFMA rows)
 // contracted channel ranges: hi|hi|lo thirds x temporal taps
 static inline int nseg_eff(const sos_conv_desc* d) { return d->in_nseg * (d->t_taps > 1 ? d->t_taps : 1); }
 
+// the 16-row kernel (conv16_kernel) handles: one bf16 channel segment of 16 or 48 channels, bf16 NHWC output,
+// cout <= 16 or 33..48 (i.e. shapes where tiles of 32 output channels waste MFMA rows)
 static int nt16_for(const sos_conv_desc* d) {
     // plain 16-bit in -> out, or the three-segment hi|hi|lo mode in -> out (the parity-precision detector of 'mixed')
     const bool plain = d->in_nseg == 1 && d->out_dtype == SOS_DT_BF16, x3 = d->in_nseg == 3 && d->out_dtype == SOS_DT_BF16X3;
@@ -1397,14 +1302,15 @@ static int nt16_for(const sos_conv_desc* d) {
     if (d->cout > 32 && d->cout <= 48) return 3;
     return 0;
 }
-static size_t lds_bytes16(int npix, int nt16, int ks, int mode) {     // mode 0: two slab buffers, 1: one, 2: ring of three
-    const size_t row = (size_t)ks * 32;            // unpadded pitches
-    const size_t slab = mode == 1 ? (size_t)2 * nt16 * 16 * row : ((size_t)2 * nt16 * 16 * 2 * ks + 63) / 64 * 1024;   // WBYTES
-    return (size_t)npix * row + (mode == 1 ? 1 : (mode == 2 ? 3 : 2)) * slab + (size_t)npix * 4;
+
+static int nt_for(const sos_conv_desc* d) {
+    // output-channel tiles per block: as many as fit (<= 4), balanced over the n-blocks
+    const int ntiles = d->cout_pad / 32;
+    const int nby = (ntiles + 3) / 4;
+    return (ntiles + nby - 1) / nby;
 }
 
-// One tiling choice: NC residue classes x (1<<lth) x (1<<ltw) pixels, 16*ks channels per chunk (ks == 0: the
-// 16-row kernel, whole cin in one chunk).
+// One tiling choice: NC residue classes x (1<<lth) x (1<<ltw) pixels and the kernel instance `ks` (see decode()).
 struct ConvCfg {
     int NC, lth, ltw, ks;     // lth / ltw < 16: log2 of the tile height / width; >= 16: the (non-power-of-two) size + 16 (tdim())
     double cost;
@@ -1417,51 +1323,104 @@ static inline int tenc(int v) {                                           // and
     return v + 16;
 }
 
-static int nt_for(const sos_conv_desc* d) {
-    // output-channel tiles per block: as many as fit (<= 4), balanced over the n-blocks
-    const int ntiles = d->cout_pad / 32;
-    const int nby = (ntiles + 3) / 4;
-    return (ntiles + nby - 1) / nby;
+// ConvCfg.ks names the kernel instance (it is the tiling table's file format):
+//   0 / -1       16-row kernel, the whole cin of a channel segment per chunk: two / one window-slab buffers
+//   1..8         32-row kernel, k-steps (16 channels each) per channel chunk, two weight-slab buffers
+//   + 100        one weight-slab buffer
+//   + 200        three workgroups per CU (W3: <= 168 registers, TIGHT epilogue layout)
+//   + 300        384-slot tile (three 32-pixel column tiles per wave)
+//   + 1000 * nt  nt n-tiles per workgroup instead of nt_for()
+struct KsCode {
+    bool row16;     // conv16_kernel (else conv_mfma_kernel)
+    int nt;         // n-tiles per workgroup: of 32 output channels (16 in the 16-row kernel)
+    int ks;         // k-steps per channel chunk
+    int nbuf;       // weight-slab buffers (0: an encoding this build does not have)
+    bool w3;        // three workgroups per CU
+    int slots;      // pixel slots of a workgroup's tile
+};
+static KsCode decode(int ks, const sos_conv_desc* d) {
+    if (ks <= 0) return {true, nt16_for(d), d->cin / 16, ks == 0 ? 2 : (ks == -1 ? 1 : 0), false, 256};
+    KsCode v = {false, nt_for(d), 0, 2, false, 256};
+    if (ks >= 1000) { v.nt = ks / 1000; ks %= 1000; }
+    v.ks = ks % 100;
+    switch (ks / 100) {
+        case 0: break;
+        case 1: v.nbuf = 1; break;
+        case 2: v.w3 = true; break;
+        case 3: v.slots = 384; break;
+        default: v.nbuf = 0;
+    }
+    return v;
 }
+
+// LDS of the tap loop (patch + weight-slab buffers + pixel table) for a patch of npix pixels
+static size_t loop_lds(int npix, const KsCode& v) {
+    const size_t row = (size_t)v.ks * 32 + (v.row16 ? 0 : 16);          // (the 16-row kernel's pitches are unpadded)
+    const size_t slab = v.row16 ? (v.nbuf == 1 ? (size_t)2 * v.nt * 16 * row : ((size_t)2 * v.nt * 16 * 2 * v.ks + 63) / 64 * 1024)   // WBYTES
+                                : (v.nbuf == 1 ? (size_t)v.nt * 32 * row : ((size_t)v.nt * 32 * (2 * v.ks + 1) + 63) / 64 * 1024);  // BBYTES
+    return (size_t)npix * row + v.nbuf * slab + (size_t)npix * 4;
+}
+static size_t loop_lds(const sos_conv_desc* d, int npix, int ks) { return loop_lds(npix, decode(ks, d)); }
+
+// Every compiled kernel instance: its template arguments, decoded, and what it supports beyond them (inbn: the fused input
+// BatchNorm, sos_conv_desc.in_scale).  plan() picks from this table; nothing else names an instantiation.
+struct ConvInstance {
+    conv_kernel_t k;
+    bool row16;
+    int nt, ks, nbuf;
+    bool w3;
+    int slots;
+    bool inbn;
+};
+#define SOS_K32(NT, KS, SB, INBN, PT, W3) {conv_mfma_kernel<NT, KS, SB, INBN, PT, W3>, false, NT, KS, (SB) ? 1 : 2, W3, 128 * (PT), INBN}
+#define SOS_K32_DOUBLE(NT) SOS_K32(NT, 1, false, false, 2, false), SOS_K32(NT, 2, false, false, 2, false),                 \
+    SOS_K32(NT, 3, false, false, 2, false), SOS_K32(NT, 4, false, false, 2, false), SOS_K32(NT, 5, false, false, 2, false), \
+    SOS_K32(NT, 6, false, false, 2, false), SOS_K32(NT, 8, false, false, 2, false)
+#define SOS_K32_SINGLE(NT) SOS_K32(NT, 1, true, false, 2, false), SOS_K32(NT, 2, true, false, 2, false),                   \
+    SOS_K32(NT, 3, true, false, 2, false), SOS_K32(NT, 4, true, false, 2, false)
+#define SOS_K16(NT16, KS) {conv16_kernel<NT16, KS, 0>, true, NT16, KS, 2, false, 256, false},                              \
+    {conv16_kernel<NT16, KS, 1>, true, NT16, KS, 1, false, 256, false}
+static const ConvInstance conv_instances[] = {
+    SOS_K32_DOUBLE(1), SOS_K32_DOUBLE(2), SOS_K32_DOUBLE(3), SOS_K32_DOUBLE(4),
+    SOS_K32_SINGLE(1), SOS_K32_SINGLE(2), SOS_K32_SINGLE(3),
+    SOS_K32(3, 1, false, false, 2, true), SOS_K32(3, 2, false, false, 2, true),       // three workgroups per CU
+    SOS_K32(3, 2, false, false, 3, false), SOS_K32(3, 3, false, false, 3, false),     // 384-slot tiles
+    SOS_K32(3, 2, false, true, 2, false), SOS_K32(3, 3, false, true, 2, false),       // fused input BatchNorm (the 96-channel context layers)
+    SOS_K16(1, 1), SOS_K16(1, 3), SOS_K16(3, 1), SOS_K16(3, 3),
+};
+#undef SOS_K16
+#undef SOS_K32_SINGLE
+#undef SOS_K32_DOUBLE
+#undef SOS_K32
+
+// What a launch of a tiling needs; plan() below fills it or says why the tiling cannot run a descriptor.
+struct ConvPlan {
+    conv_kernel_t k;
+    dim3 grid;
+    size_t lds;
+    ConvParams p;
+};
+static const char* plan(const sos_conv_desc* d, const ConvCfg& c, ConvPlan* out);
 
 // Enumerate every legal tiling with a cost estimate: MFMA work wasted on out-of-range pixels,
 // patch traffic (halo amplification), per-chunk overheads, and a bonus when two workgroups fit a
-// CU's LDS (their load / epilogue phases then overlap each other's MFMA phase).
-static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
+// CU's LDS (their load / epilogue phases then overlap each other's MFMA phase).  Only tilings plan() accepts for d are
+// offered; *why (optional) gets the reason of the first one it refused.
+static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d, const char** why = nullptr) {
     std::vector<ConvCfg> out;
     const int nt = nt_for(d);
     const int Hc = (d->Ho + d->dil_h - 1) / d->dil_h, Wc = (d->Wo + d->dil_w - 1) / d->dil_w;
     const int taps = d->kh * d->kw;
     static const int kscand[] = {8, 6, 5, 4, 3, 2, 1};
     const int k16 = d->cin / 16;
-    // 16-row kernel with 512-pixel workgroups (conv16_kernel<.., PT = 8>; ks -4: double, -5: single slab): the wave owns 128
-    // pixels x all output channels; candidates are the tiles of <= 512 slots whose patch still lets two workgroups into a CU
-    // (or one, for the tuner to reject)
-    auto add_tile16x = [&](const int NC, const int TH, const int TW) {
-        const int nt16 = nt16_for(d);
-        if (!nt16 || NC * TH * TW > 512 || NC * TH * TW <= 256) return;
-        const int PH = (TH - 1) * d->stride + d->kh, PW = (TW - 1) * d->stride + d->kw;
-        const int npix = NC * PH * PW;
-        const long long th = (Hc + TH - 1) / TH, tw = (Wc + TW - 1) / TW, ngw = (d->dil_w + NC - 1) / NC;
-        const double blocks = (double)th * tw * ngw * d->dil_h;
-        const size_t stage = (size_t)512 * (nt16 * 32 + 16) * (d->out_dtype == SOS_DT_BF16X3 ? 2 : 1) + 2048 + 16384;
-        for (int mode = 0; mode < 2; ++mode) {
-            const size_t lds = std::max(lds_bytes16(npix, nt16, k16, mode), stage);
-            if (lds > LDS_LIMIT) continue;
-            double per_block = 0.75 * nseg_eff(d) * (0.9 * 512.0 * taps * k16 + 3.0 * npix * k16 + 40.0 * (6 + taps / 2));
-            if (lds > LDS_LIMIT / 2) per_block *= 1.3;
-            out.push_back({NC, tenc(TH), tenc(TW), -4 - mode, blocks * per_block});
-        }
-    };
     auto add_tile = [&](const int NC, const int TH, const int TW) {
         const int PH = (TH - 1) * d->stride + d->kh, PW = (TW - 1) * d->stride + d->kw;
         const int npix = NC * PH * PW;
         const long long th = (Hc + TH - 1) / TH, tw = (Wc + TW - 1) / TW, ngw = (d->dil_w + NC - 1) / NC;
         const double blocks = (double)th * tw * ngw * d->dil_h;
-        if (const int nt16 = nt16_for(d)) {               // 16-row kernel on the same pixel tiling (ks 0: double, -1: single slab)
-            // (the ring-of-three schedule, mode 2, is never a candidate: measured slower, see conv16_kernel; SOS_CONV16_MODE=2 forces it)
+        if (nt16_for(d)) {                                // 16-row kernel on the same pixel tiling (ks 0: double, -1: single slab)
             for (int mode = 0; mode < 2; ++mode) {
-                const size_t lds = lds_bytes16(npix, nt16, k16, mode);
+                const size_t lds = loop_lds(d, npix, -mode);
                 if (lds > LDS_LIMIT) continue;
                 double per_block = 0.75 * nseg_eff(d) * (256.0 * taps * k16 + 3.0 * npix * k16 + 40.0 * (6 + taps / 2));
                 if (lds > LDS_LIMIT / 2) per_block *= 1.3;
@@ -1471,14 +1430,14 @@ static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
         }
         for (int ks : kscand) {
             if (k16 % ks) continue;
-            const size_t lds = lds_bytes(npix, nt, ks);
+            const size_t lds = loop_lds(d, npix, ks);
             if (lds > LDS_LIMIT) continue;
             const int nchunks = nseg_eff(d) * k16 / ks;
             double per_block = 256.0 * taps * nchunks * ks + 3.0 * npix * nchunks * ks + 40.0 * nchunks * (6 + taps);
             if (lds > LDS_LIMIT / 2) per_block *= 1.3;     // a lone workgroup per CU hides nothing
             out.push_back({NC, tenc(TH), tenc(TW), ks, blocks * per_block});
             // single slab buffer: worth it only when it lets a third workgroup into the CU
-            const size_t lds1 = lds_bytes(npix, nt, ks + 100);
+            const size_t lds1 = loop_lds(d, npix, ks + 100);
             // (three n-tiles: the instance sits at the 168-register limit of three waves per SIMD -- ks >= 3 spills, 65-342 registers:
             // 11 ms instead of 1.5 on the 96 -> 96 layer; never a candidate)
             if ((nt <= 2 ? ks <= 4 : (nt == 3 && ks <= 2)) && lds1 <= LDS_LIMIT / 3 && lds > LDS_LIMIT / 3)
@@ -1486,7 +1445,7 @@ static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
             // 128 output channels per workgroup need ~400 registers and > 80 KB of LDS (one workgroup per CU): two
             // n-blocks of 64 stage the patch twice but fit two or three workgroups (ks + 2000)
             if (nt == 4) {
-                const size_t lds2 = lds_bytes(npix, 2, ks);
+                const size_t lds2 = loop_lds(d, npix, ks + 2000);
                 if (lds2 <= LDS_LIMIT / 2)
                     out.push_back({NC, tenc(TH), tenc(TW), ks + 2000, blocks * 2.0 * (128.0 * taps * nchunks * ks + 3.0 * npix * nchunks * ks + 40.0 * nchunks * (6 + taps)) * 0.9});
             }
@@ -1502,15 +1461,14 @@ static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
     // SOS_CONV_NO_W3=1 removes them (A/B).
     static const size_t LDS_THIRD = (LDS_LIMIT / 3) / 1280 * 1280;      // 53 760: LDS is allocated in 1 280-byte granules on gfx950
     static const char* no_w3 = getenv("SOS_CONV_NO_W3");
-    if (!(no_w3 && atoi(no_w3)) && nt == 3 && nseg_eff(d) == 1 && d->out_dtype == SOS_DT_BF16 && d->out_sc == 1 && d->cout_store % 8 == 0 &&
-        !d->accumulate) {
+    if (!(no_w3 && atoi(no_w3)) && nt == 3) {
         const size_t base = out.size();
         for (size_t i = 0; i < base; ++i) {
             const ConvCfg c = out[i];
             if (c.ks != 1 && c.ks != 2) continue;
             const int TH = tdim(c.lth), TW = tdim(c.ltw);
             const int PH = (TH - 1) * d->stride + d->kh, PW = (TW - 1) * d->stride + d->kw;
-            if (lds_bytes(c.NC * PH * PW, 3, c.ks) > LDS_THIRD || (size_t)256 * (3 * 64 + 16) > LDS_THIRD) continue;
+            if (loop_lds(d, c.NC * PH * PW, c.ks + 200) > LDS_THIRD || (size_t)256 * (3 * 64 + 16) > LDS_THIRD) continue;
             out.push_back({c.NC, c.lth, c.ltw, c.ks + 200, c.cost * 0.93});
         }
     }
@@ -1518,8 +1476,7 @@ static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
     // stride-1 layers.  Every (classes, height) with the widest width that fits, plus the widths / heights that cut the strided
     // image into equal parts (178 columns: 12 x 15 instead of 16 x 12).  SOS_CONV_NO_PT3=1 removes them (A/B).
     static const char* no_pt3 = getenv("SOS_CONV_NO_PT3");
-    if (!(no_pt3 && atoi(no_pt3)) && nt == 3 && d->stride == 1 && nseg_eff(d) == 1 && d->out_dtype == SOS_DT_BF16 && d->out_sc == 1 &&
-        !d->wl_tab && d->cout_store % 8 == 0) {
+    if (!(no_pt3 && atoi(no_pt3)) && nt == 3 && d->stride == 1) {
         static const int ncs[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32}, ths[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
         std::vector<std::array<int, 3>> seen;
         auto add384 = [&](const int NC, const int TH, const int TW) {
@@ -1534,7 +1491,7 @@ static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
             for (int ks : {2, 3}) {
                 if (k16 % ks) continue;
                 const size_t stage = (size_t)384 * (3 * 64 + 16) + 384 * 4;
-                const size_t lds = std::max(lds_bytes(npix, 3, ks + 300), stage);
+                const size_t lds = std::max(loop_lds(d, npix, ks + 300), stage);
                 if (lds > LDS_LIMIT / 2) continue;           // (one workgroup per CU: never better than the 256-slot tiles)
                 const int nchunks = k16 / ks;
                 const double per_block = 0.94 * 384.0 * taps * nchunks * ks + 3.0 * npix * nchunks * ks + 40.0 * nchunks * (6 + taps);
@@ -1555,24 +1512,6 @@ static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
                   const int TWb = std::min(384 / (NC * THb), std::min(Wc, 64));
                   add384(NC, THb, TWb);
                   if (TWb >= 2) { const int pw = (Wc + TWb - 1) / TWb; add384(NC, THb, (Wc + pw - 1) / pw); } }
-            }
-        }
-    }
-    // 512-pixel workgroups of the 16-row kernel: OPT-IN (SOS_CONV16_512=1, or SOS_CONV16_FORCE512=1 of the tests).  Round 4
-    // measured them slower on every 5x5 shape (48 -> 48 at B = 64: 0.396 vs 0.369 ms forced against the table's 256-pixel tile on
-    // the same box; a re-tune over 48 candidates per shape kept the 256-pixel tiles for all but two B = 8 1x1 heads): the
-    // kernel wants its third resident workgroup more than fewer fragment reads per MFMA.
-    static const char* en512 = getenv("SOS_CONV16_512");
-    static const char* f512e = getenv("SOS_CONV16_FORCE512");
-    if (nt16_for(d) && d->stride == 1 && ((en512 && atoi(en512)) || (f512e && atoi(f512e)))) {
-        for (int lnc = 0; lnc <= 6; ++lnc) {
-            const int NC = 1 << lnc;
-            if (NC > 1 && NC > d->dil_w) break;
-            for (int lth = 1; lth + lnc <= 7; ++lth) {
-                const int TH = 1 << lth, TWf = 512 / (NC * TH);
-                // the full 512 slots and the next narrower even widths (a 16 x 32 tile's 69 KB patch + slab + table is 1 KB over
-                // half a CU's LDS; 16 x 30 fits two workgroups)
-                for (int TW = TWf; TW >= TWf - 4 && TW >= 4; TW -= 2) add_tile16x(NC, TH, TW);
             }
         }
     }
@@ -1598,6 +1537,14 @@ static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d) {
                 add_tile(NC, TH, TW);
             }
     }
+    // (dropped before the sort: the candidates plan() accepts keep the order they have without the others)
+    const char* refused = nullptr;
+    out.erase(std::remove_if(out.begin(), out.end(), [&](const ConvCfg& c) {
+                  const char* r = plan(d, c, nullptr);
+                  if (r && !refused) refused = r;
+                  return r != nullptr;
+              }), out.end());
+    if (why) *why = refused;
     std::sort(out.begin(), out.end(), [](const ConvCfg& a, const ConvCfg& b) { return a.cost < b.cost; });
     return out;
 }
@@ -1633,12 +1580,35 @@ static bool tuned_lookup(const ShapeKey& k, ConvCfg* out) {
     *out = it->second;
     return true;
 }
-static std::vector<ConvCfg> enumerate_cfgs(const sos_conv_desc* d);
+// The cheapest candidate enumerate_cfgs(d) offers that `pick` selects
+template <class Pick>
+static bool first_offered(const sos_conv_desc* d, Pick pick, ConvCfg* out) {
+    for (const ConvCfg& e : enumerate_cfgs(d))
+        if (pick(e)) { *out = e; return true; }
+    return false;
+}
+// whether the tiling c is among them
+static bool offered(const sos_conv_desc* d, const ConvCfg& c) {
+    ConvCfg e;
+    return first_offered(d, [&](const ConvCfg& x) { return x.NC == c.NC && x.lth == c.lth && x.ltw == c.ltw && x.ks == c.ks; }, &e);
+}
+
+// the sos_conv_desc fields of a shape key, nothing else set: the table holds tilings legal for a SHAPE (plan() decides
+// per descriptor at launch)
+static sos_conv_desc desc_of_key(const ShapeKey& k) {
+    sos_conv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.B = k.v[0]; d.H = k.v[1]; d.W = k.v[2]; d.Wl = k.v[3]; d.cin = k.v[4]; d.in_nseg = k.v[5]; d.cout_pad = k.v[6];
+    d.kh = k.v[7]; d.kw = k.v[8]; d.stride = k.v[9]; d.dil_h = k.v[10]; d.dil_w = k.v[11]; d.Ho = k.v[12]; d.Wo = k.v[13];
+    d.out_dtype = k.v[14]; d.out_sc = k.v[15] ? 1 : 2; d.pad_mode = k.v[16]; d.cout = k.v[18];
+    return d;
+}
+
 // A shape the table does not hold (another batch size, another clip length, a ragged batch's maxima) borrows the tiling
 // of the SAME LAYER measured at another geometry: every key field equal except B, H, W, Wl, Ho, Wo; among those the
 // entry with the same H / Ho and the most pixels wins (the BASELINE batch), provided the tiling is legal for the new
 // shape.  Depends only on the (static) table: deterministic across processes.  The result is stored under the new key.
-static bool tuned_borrow(const sos_conv_desc* d, const ShapeKey& k, ConvCfg* out) {
+static bool tuned_borrow(const ShapeKey& k, ConvCfg* out) {
     static const int same[] = {4, 5, 6, 7, 8, 9, 10, 11, 14, 15, 16, 17, 18};
     ConvCfg best;
     long long best_score = -1;
@@ -1653,15 +1623,12 @@ static bool tuned_borrow(const sos_conv_desc* d, const ShapeKey& k, ConvCfg* out
             if (score > best_score) { best_score = score; best = kv.second; }
         }
     }
-    if (best_score < 0) return false;
-    for (const ConvCfg& e : enumerate_cfgs(d))
-        if (e.NC == best.NC && e.lth == best.lth && e.ltw == best.ltw && e.ks == best.ks) {
-            *out = best;
-            std::lock_guard<std::mutex> g(tuned_mutex());
-            tuned_cache().emplace(k, best);
-            return true;
-        }
-    return false;
+    const sos_conv_desc shape = desc_of_key(k);
+    if (best_score < 0 || !offered(&shape, best)) return false;
+    *out = best;
+    std::lock_guard<std::mutex> g(tuned_mutex());
+    tuned_cache().emplace(k, best);
+    return true;
 }
 static void tuned_store(const ShapeKey& k, const ConvCfg& c, bool overwrite) {
     std::lock_guard<std::mutex> g(tuned_mutex());
@@ -1945,8 +1912,51 @@ static int pick_lane_map(const ConvParams& p, int pstride) {
     return best;
 }
 
-static int launch_cfg(const sos_conv_desc* d, const ConvCfg& c, hipStream_t s) {
-    ConvParams p;
+// Whether the tiling c can run the descriptor d -- a compiled instance that supports d's flags, a tile within the workgroup's
+// slots, the LDS, the grid -- and, if out != nullptr, the launch: nullptr, or why not.
+static const char* plan(const sos_conv_desc* d, const ConvCfg& c, ConvPlan* out) {
+    KsCode v = decode(c.ks, d);
+    const int TH = tdim(c.lth), TW = tdim(c.ltw);
+    if (c.NC < 1 || TH < 1 || TW < 1 || c.NC * TH * TW > v.slots) return "the pixel tile does not fit the workgroup";
+    if (v.row16 ? !v.nt : (v.ks < 1 || d->cin % (16 * v.ks))) return "no kernel takes this shape with these k-steps";
+    const bool x3 = d->out_dtype == SOS_DT_BF16X3, staged = d->out_dtype != SOS_DT_F32 && d->out_sc == 1;
+    // the TIGHT epilogue (W3) and the 384-slot tiles store one 16-bit plane of whole 8-channel pieces; the 384-slot tiles'
+    // statistics scratch lies over the staged tile, which the general store path (partial pieces) does not allow for
+    const bool dense16 = d->out_dtype == SOS_DT_BF16 && d->out_sc == 1 && nseg_eff(d) == 1 && d->cout_store % 8 == 0;
+    if (v.w3 && (!dense16 || d->accumulate)) return "three workgroups per CU need a dense 16-bit output of whole 8-channel pieces, no accumulation";
+    if (v.slots == 384 && (!dense16 || d->wl_tab)) return "384-slot tiles need a dense 16-bit output of whole 8-channel pieces, no ragged batch";
+    const int PH = (TH - 1) * d->stride + d->kh, PW = (TW - 1) * d->stride + d->kw, npix = c.NC * PH * PW;
+    if (v.row16) {                                       // SOS_CONV16_MODE=0|1 (A/B): the 16-row kernel's slab schedule, where it fits
+        static const char* e = getenv("SOS_CONV16_MODE");
+        KsCode m = v;
+        if (e && (atoi(e) == 0 || atoi(e) == 1)) m.nbuf = atoi(e) == 1 ? 1 : 2;
+        if (loop_lds(npix, m) <= LDS_LIMIT) v = m;
+    }
+    const ConvInstance* inst = nullptr;
+    for (const ConvInstance& i : conv_instances)
+        if (i.row16 == v.row16 && i.nt == v.nt && i.ks == v.ks && i.nbuf == v.nbuf && i.w3 == v.w3 && i.slots == v.slots &&
+            i.inbn == (d->in_scale != nullptr))
+            inst = &i;
+    if (!inst) return d->in_scale ? "fused input BatchNorm (in_scale) is built for three n-tiles, 2 or 3 k-steps, two slab buffers only"
+                                  : "no kernel instance is built for this tiling";
+    // LDS: the tap loop's, or the epilogue's staged output tile (+ pixel offsets + statistics scratch) if that is more
+    size_t lds = loop_lds(npix, v);
+    if (v.row16 || staged) {
+        const size_t orow = v.row16 ? (size_t)v.nt * 32 + 16 : (size_t)v.nt * 64 + 16, slots = v.slots;
+        const size_t stage = v.w3 ? slots * orow           // TIGHT: nothing but the staged tile
+                                  : slots * orow * (x3 ? 2 : 1) + slots * 4 + ((d->stats && slots == 256) ? 16384 : 0);
+        lds = std::max(lds, stage);
+    }
+    if (lds > LDS_LIMIT) return "the tile needs more LDS than a CU has";
+    const int Hc = (d->Ho + d->dil_h - 1) / d->dil_h, Wc = (d->Wo + d->dil_w - 1) / d->dil_w;
+    const int tiles_h = (Hc + TH - 1) / TH, tiles_w = (Wc + TW - 1) / TW, ngw = (d->dil_w + c.NC - 1) / c.NC;
+    const long long nblk = (long long)d->B * d->dil_h * tiles_h * ngw * tiles_w;
+    // (n * d < 2^32 for every division the kernels make: block ids < 2^31 / (B dil_h) are divided by extents whose product is nblk / B)
+    if (nblk > 0x7fffffffLL || nblk * std::max(std::max(tiles_w, ngw), std::max(tiles_h, (int)d->dil_h)) >= (1ll << 32))
+        return "grid too large";
+    if (!out) return nullptr;
+
+    ConvParams& p = out->p;
     p.in = (const bf16_t*)d->in; p.wgt = (const bf16_t*)d->wgt; p.out = d->out;
     p.scale = d->scale; p.shift = d->shift; p.slope = d->act_param; p.wgather = d->w_gather;
     p.B = d->B; p.H = d->H; p.W = d->W; p.Wl = d->Wl; p.in_cs = d->in_cs; p.cin_off = d->cin_off; p.cin = d->cin;
@@ -1959,97 +1969,54 @@ static int launch_cfg(const sos_conv_desc* d, const ConvCfg& c, hipStream_t s) {
     p.act = d->act; p.accum = d->accumulate; p.sb = d->out_sb; p.sh = d->out_sh; p.sw = d->out_sw; p.sc = d->out_sc; p.third = d->out_third;
     p.out2 = d->fold_pad_out; p.fP = d->fold_pad; p.fH = d->fold_H; p.fW = d->fold_W; p.fsy = d->fold_sy; p.foy = d->fold_oy;
     p.fsx = d->fold_sx; p.fox = d->fold_ox; p.frow = d->fold_row; p.fthird = d->fold_third;
-    // c.ks encodes: k-steps per chunk (% 100), + 100 single slab buffer, + 1000 * n-tiles per workgroup (0: default)
-    const int nt = c.ks >= 1000 ? c.ks / 1000 : nt_for(d);
-    const int ks_enc = c.ks >= 1000 ? c.ks % 1000 : c.ks;
-    const int nby = (d->cout_pad / 32 + nt - 1) / nt;
-    const int Hc = (d->Ho + d->dil_h - 1) / d->dil_h, Wc = (d->Wo + d->dil_w - 1) / d->dil_w;
-    const int TH = tdim(c.lth), TW = tdim(c.ltw);
-    p.NC = c.NC; p.TH = TH; p.TW = TW;
-    const bool pt8 = c.ks <= -4;                          // 16-row kernel, 512-pixel workgroup
-    const bool pt3 = c.ks >= 300 && c.ks < 400;           // 32-row kernel, 384-slot tile (three column tiles per wave)
-    if (c.NC < 1 || TH < 1 || TW < 1 || c.NC * TH * TW > (pt8 ? 512 : (pt3 ? 384 : 256))) { sos_set_error("sos_conv2d_fwd: internal: tile %d x %d x %d", c.NC, TH, TW); return SOS_EINVAL; }
-    p.PH = (TH - 1) * d->stride + d->kh; p.PW = (TW - 1) * d->stride + d->kw;
-    p.npix = p.NC * p.PH * p.PW;
-    p.cps = c.ks > 0 ? d->cin / (16 * (ks_enc % 100)) : 1;
+    p.NC = c.NC; p.TH = TH; p.TW = TW; p.PH = PH; p.PW = PW; p.npix = npix;
+    p.cps = v.row16 ? 1 : d->cin / (16 * v.ks);        // (16-row kernel: the whole cin of a segment per chunk)
     p.nchunks = p.cps * nseg_eff(d);
     p.ktot = d->cin * nseg_eff(d);
     p.tk = d->t_taps > 1 ? d->t_taps : 1; p.tT = d->t_taps > 1 ? d->t_frames : 1; p.tpad = d->t_taps > 1 ? d->t_pad : 0;
     p.seg_stride = d->in_seg_stride;
-    p.tiles_h = (Hc + TH - 1) / TH; p.tiles_w = (Wc + TW - 1) / TW; p.ngw = (d->dil_w + p.NC - 1) / p.NC;
-    const long long nblk = (long long)d->B * d->dil_h * p.tiles_h * p.ngw * p.tiles_w;
-    if (nblk > 0x7fffffffLL) { sos_set_error("sos_conv2d_fwd: grid too large"); return SOS_EINVAL; }
-    p.nblk = (int)nblk;
-    // (n * d < 2^32 for every division the kernels make: block ids < 2^31 / (B dil_h) are divided by extents whose product is nblk / B)
-    if (nblk * std::max(std::max(p.tiles_w, p.ngw), std::max(p.tiles_h, (int)d->dil_h)) >= (1ll << 32)) { sos_set_error("sos_conv2d_fwd: grid too large"); return SOS_EINVAL; }
-    p.mgTW = mg_of(TW); p.mgTH = mg_of(TH); p.mgPW = mg_of(p.PW); p.mgPH = mg_of(p.PH);
-    p.mg_tiles_w = mg_of(p.tiles_w); p.mg_ngw = mg_of(p.ngw); p.mg_tiles_h = mg_of(p.tiles_h); p.mg_dh = mg_of(d->dil_h); p.mg_kw = mg_of(d->kw);
+    p.tiles_h = tiles_h; p.tiles_w = tiles_w; p.ngw = ngw; p.nblk = (int)nblk;
+    p.mgTW = mg_of(TW); p.mgTH = mg_of(TH); p.mgPW = mg_of(PW); p.mgPH = mg_of(PH);
+    p.mg_tiles_w = mg_of(tiles_w); p.mg_ngw = mg_of(ngw); p.mg_tiles_h = mg_of(tiles_h); p.mg_dh = mg_of(d->dil_h); p.mg_kw = mg_of(d->kw);
     { const char* e = getenv("SOS_CONV_DBG"); p.dbg = e ? atoi(e) : 0; }
     p.lmap = 0;
-    if (c.ks > 0) {
+    if (!v.row16) {
         static const char* nomap = getenv("SOS_CONV_NO_LANE_MAP");          // A/B switch
-        if (!nomap) p.lmap = pick_lane_map(p, (ks_enc % 100) * 32 + 16);
+        if (!nomap) p.lmap = pick_lane_map(p, v.ks * 32 + 16);
     }
-    if (c.ks <= 0) {                                     // 16-row kernel (ks 0: double-buffered slab, -1: single, -2: ring of three; -4 / -5: 512-pixel workgroups)
-        int mode = pt8 ? -c.ks - 4 : -c.ks;
-        if (!pt8) { static const char* e = getenv("SOS_CONV16_MODE"); if (e) mode = atoi(e); }      // A/B: force a slab mode
-        const int nt16 = nt16_for(d), ks16 = d->cin / 16;
-        if (!nt16) { sos_set_error("sos_conv2d_fwd: internal: 16-row tiling for an ineligible shape"); return SOS_EINVAL; }
-        p.cps = 1; p.nchunks = nseg_eff(d);              // channel segments (3 in the hi|hi|lo mode), whole cin per segment
-        if (mode < 0 || mode > (pt8 ? 1 : 2) || lds_bytes16(p.npix, nt16, ks16, mode) > LDS_LIMIT) mode = pt8 ? -c.ks - 4 : -c.ks;
-        size_t lds16 = lds_bytes16(p.npix, nt16, ks16, mode);
-        const size_t slots = pt8 ? 512 : 256;
-        const size_t stage16 = slots * (nt16 * 32 + 16) * (d->out_dtype == SOS_DT_BF16X3 ? 2 : 1) + slots * 4 + (d->stats ? 16384 : 0);
-        if (stage16 > lds16) lds16 = stage16;
-        if (lds16 > LDS_LIMIT) { sos_set_error("sos_conv2d_fwd: internal: 16-row tile needs %zu bytes of LDS", lds16); return SOS_EINVAL; }
-        conv_kernel_t k = nullptr;
-#define SOS_C16(NTV, KSV)                                                                        \
-        if (nt16 == NTV && ks16 == KSV) k = pt8 ? (mode == 1 ? conv16_kernel<NTV, KSV, 1, 8> : conv16_kernel<NTV, KSV, 0, 8>)     \
-                                                : (mode == 1 ? conv16_kernel<NTV, KSV, 1> : (mode == 2 ? conv16_kernel<NTV, KSV, 2> : conv16_kernel<NTV, KSV, 0>));
-        SOS_C16(1, 1) SOS_C16(1, 3) SOS_C16(3, 1) SOS_C16(3, 3)
-#undef SOS_C16
-        static sos_device_once attr16;
-        (void)sos_per_device_once(attr16, [] {
-#define SOS_C16A(NTV, KSV)                                                                                                        \
-            (void)hipFuncSetAttribute((const void*)conv16_kernel<NTV, KSV, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);  \
-            (void)hipFuncSetAttribute((const void*)conv16_kernel<NTV, KSV, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);  \
-            (void)hipFuncSetAttribute((const void*)conv16_kernel<NTV, KSV, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);  \
-            (void)hipFuncSetAttribute((const void*)conv16_kernel<NTV, KSV, 0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);  \
-            (void)hipFuncSetAttribute((const void*)conv16_kernel<NTV, KSV, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-            SOS_C16A(1, 1) SOS_C16A(1, 3) SOS_C16A(3, 1) SOS_C16A(3, 3)
-#undef SOS_C16A
-            return (int)SOS_OK;
-        });
-        hipLaunchKernelGGL(k, dim3((unsigned)nblk, 1), dim3(256), lds16, s, p);
-        return sos_check_launch("sos_conv2d_fwd(16)");
-    }
-    dim3 grid((unsigned)nblk, (unsigned)nby);
-    int ks_run = ks_enc;
-    // fused input BatchNorm: built for the plain double-slab instances only -- a three-per-CU entry (ks + 200) runs as its plain
-    // twin (same tile, same k-steps per chunk: the same summation order, bit-identical output)
-    if (d->in_scale && ks_run >= 200 && ks_run < 300) ks_run -= 200;
-    size_t lds = lds_bytes(p.npix, nt, ks_run);
-    if (d->out_dtype != SOS_DT_F32 && d->out_sc == 1) {
-        const size_t slots = pt3 ? 384 : 256;
-        const bool w3 = ks_run >= 200 && ks_run < 300;               // three per CU: TIGHT epilogue layout (nothing but the staged tile)
-        const size_t stage = w3 ? slots * (nt * 64 + 16)
-                                : slots * (nt * 64 + 16) * (d->out_dtype == SOS_DT_BF16X3 ? 2 : 1) + slots * 4 +   // + pixel offsets
-                                  ((d->stats && !pt3) ? 16384 : 0);  // + statistics scratch (384-slot tiles: over the staged tile)
-        if (stage > lds) lds = stage;
-        if (w3 && (d->out_dtype == SOS_DT_BF16X3 || nt != 3 || d->accumulate || d->cout_store % 8)) { sos_set_error("sos_conv2d_fwd: internal: three-per-CU tiling for an ineligible shape"); return SOS_EINVAL; }
-        if (pt3 && (d->out_dtype == SOS_DT_BF16X3 || nt != 3)) { sos_set_error("sos_conv2d_fwd: internal: 384-slot tiling for an ineligible shape"); return SOS_EINVAL; }
-    }
+    out->k = inst->k;
+    out->grid = dim3((unsigned)nblk, v.row16 ? 1u : (unsigned)((d->cout_pad / 32 + v.nt - 1) / v.nt));
+    out->lds = lds;
 #ifdef SOS_ABLATE
-    { static const char* e = getenv("SOS_CONV_LDS_PAD"); if (e) lds = std::min(lds + (size_t)atoi(e), LDS_LIMIT); }   // occupancy experiments
+    { static const char* e = getenv("SOS_CONV_LDS_PAD"); if (e) out->lds = std::min(out->lds + (size_t)atoi(e), LDS_LIMIT); }   // occupancy experiments
 #endif
-    switch (nt) {
-        case 1: return launch_ks<1>(ks_run, p, grid, lds, s);
-        case 2: return launch_ks<2>(ks_run, p, grid, lds, s);
-        case 3: return launch_ks<3>(ks_run, p, grid, lds, s);
-        case 4: return launch_ks<4>(ks_run, p, grid, lds, s);
+    return nullptr;
+}
+
+static int launch_plan(const ConvPlan& pl, hipStream_t s) {
+    static sos_device_once attr_once;       // every instance may use all of a CU's LDS
+    const int arc = sos_per_device_once(attr_once, [] {
+        for (const ConvInstance& i : conv_instances) {
+            const hipError_t e = hipFuncSetAttribute((const void*)i.k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
+            if (e != hipSuccess) {
+                sos_set_error("sos_conv2d_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+                return (int)SOS_ELAUNCH;
+            }
+        }
+        return (int)SOS_OK;
+    });
+    if (arc) return arc;
+    hipLaunchKernelGGL(pl.k, pl.grid, dim3(256), pl.lds, s, pl.p);
+    return sos_check_launch("sos_conv2d_fwd");
+}
+
+static int launch_cfg(const sos_conv_desc* d, const ConvCfg& c, hipStream_t s) {
+    ConvPlan pl;
+    if (const char* why = plan(d, c, &pl)) {
+        sos_set_error("sos_conv2d_fwd: tiling NC=%d TH=%d TW=%d ks=%d: %s", c.NC, tdim(c.lth), tdim(c.ltw), c.ks, why);
+        return SOS_EINVAL;
     }
-    sos_set_error("sos_conv2d_fwd: internal: nt=%d", nt);
-    return SOS_EINVAL;
+    return launch_plan(pl, s);
 }
 
 static long long tiles_of(const sos_conv_desc* d, const ConvCfg& c) {
@@ -2058,63 +2025,61 @@ static long long tiles_of(const sos_conv_desc* d, const ConvCfg& c) {
     return (long long)d->B * d->dil_h * ((Hc + TH - 1) / TH) * ((d->dil_w + c.NC - 1) / c.NC) * ((Wc + TW - 1) / TW);
 }
 
-// SOS_CONV16_FORCE512=1 (testing): every shape the 16-row kernel takes runs its cheapest 512-pixel-workgroup candidate (ks -5 / -4)
-static bool forced_512(const sos_conv_desc* d, ConvCfg* out) {
-    static const char* f512 = getenv("SOS_CONV16_FORCE512");
-    if (!(f512 && atoi(f512)) || !nt16_for(d)) return false;
-    for (const ConvCfg& e : enumerate_cfgs(d))
-        if (e.ks <= -4) { *out = e; return true; }
-    return false;
-}
-
-// SOS_CONV_FORCE_PT3=1 / SOS_CONV_FORCE_W3=1 (testing / A-B): every shape that has a 384-slot candidate (ks + 300) / a
-// three-per-CU candidate (ks + 200) runs its cheapest one
-static bool forced_pt3(const sos_conv_desc* d, ConvCfg* out) {
-    static const char* f = getenv("SOS_CONV_FORCE_PT3");
-    static const char* f3 = getenv("SOS_CONV_FORCE_W3");
-    const bool pt3 = f && atoi(f), w3 = f3 && atoi(f3);
-    if (!(pt3 || w3) || d->in_scale) return false;
-    for (const ConvCfg& e : enumerate_cfgs(d))
-        if ((pt3 && e.ks >= 300 && e.ks < 400) || (w3 && e.ks >= 200 && e.ks < 300)) { *out = e; return true; }
-    return false;
+// The tiling d runs, in this order: a forcing switch (testing / A-B); the table's entry for d's shape, else the one borrowed
+// from the same layer at another geometry -- if plan() accepts it for d, or else its plain twin (a three-per-CU entry ks + 200
+// runs as ks: same tile, same summation order); the cost model's first candidate.  Fills *pl (optional) with the launch.
+static int resolve(const sos_conv_desc* d, const char* who, ConvCfg* c, ConvPlan* pl) {
+    auto take = [&](const ConvCfg& e) {
+        if (plan(d, e, pl)) return false;
+        *c = e;
+        return true;
+    };
+    auto take_entry = [&](const ConvCfg& e) { return take(e) || (decode(e.ks, d).w3 && take({e.NC, e.lth, e.ltw, e.ks - 200, 0.0})); };
+    // SOS_CONV_FORCE_PT3=1 / SOS_CONV_FORCE_W3=1 (testing / A-B): every descriptor that has a 384-slot / a three-per-CU candidate
+    // runs its cheapest one
+    static const char* fpt3 = getenv("SOS_CONV_FORCE_PT3");
+    static const char* fw3 = getenv("SOS_CONV_FORCE_W3");
+    const bool pt3 = fpt3 && atoi(fpt3), w3 = fw3 && atoi(fw3);
+    ConvCfg e;
+    if ((pt3 || w3) && first_offered(d, [&](const ConvCfg& x) { const KsCode v = decode(x.ks, d); return (pt3 && v.slots == 384) || (w3 && v.w3); }, &e) &&
+        take(e))
+        return SOS_OK;
+    // SOS_CONV_FORCE_CFG=k (testing): the k-th candidate tiling (mod count) instead of the table's
+    static const char* force = getenv("SOS_CONV_FORCE_CFG");
+    if (!force) {
+        const ShapeKey k = shape_key(d);
+        if (tuned_lookup(k, &e) && take_entry(e)) return SOS_OK;
+        if (tuned_borrow(k, &e) && take_entry(e)) return SOS_OK;
+    }
+    const char* why = nullptr;
+    const std::vector<ConvCfg> cfgs = enumerate_cfgs(d, &why);
+    if (cfgs.empty()) {
+        if (why) sos_set_error("%s: no tiling runs this descriptor: %s", who, why);
+        else sos_set_error("%s: no tile fits LDS (cin=%d k=%dx%d)", who, d->cin, d->kh, d->kw);
+        return why ? SOS_EINVAL : SOS_ENOSPC;
+    }
+    const size_t pick = force ? (size_t)atol(force) % cfgs.size() : 0;
+    if (getenv("SOS_CONV_LIST"))      // debugging aid: the chosen candidate of the cost-ordered list
+        fprintf(stderr, "%s: cfg %zu/%zu NC=%d TH=%d TW=%d ks=%d\n", who, pick, cfgs.size(), cfgs[pick].NC, tdim(cfgs[pick].lth),
+                tdim(cfgs[pick].ltw), cfgs[pick].ks);
+    take(cfgs[pick]);                 // (offered: plan() accepts it)
+    return SOS_OK;
 }
 
 extern "C" int64_t sos_conv2d_tile_count(const sos_conv_desc* d) {
-    if (validate(d)) return -1;
-    { ConvCfg c5; if (forced_512(d, &c5) || forced_pt3(d, &c5)) return tiles_of(d, c5); }
-    static const char* force = getenv("SOS_CONV_FORCE_CFG");
-    if (!force) {
-        ConvCfg c;
-        const ShapeKey k = shape_key(d);
-        if (tuned_lookup(k, &c) || tuned_borrow(d, k, &c)) return tiles_of(d, c);
-    }
-    std::vector<ConvCfg> cfgs = enumerate_cfgs(d);
-    if (cfgs.empty()) { sos_set_error("sos_conv2d_tile_count: no tile fits LDS"); return -1; }
-    return tiles_of(d, cfgs[force ? (size_t)atol(force) % cfgs.size() : 0]);
+    ConvCfg c;
+    if (validate(d) || resolve(d, "sos_conv2d_tile_count", &c, nullptr)) return -1;
+    return tiles_of(d, c);
 }
 
 extern "C" int sos_conv2d_fwd(const sos_conv_desc* d, sos_stream_t stream) {
     int rc = validate(d);
     if (rc) return rc;
     if (thin_conv_shape(d)) return thin_conv_launch(d, (hipStream_t)stream);
-    { ConvCfg c5; if (forced_512(d, &c5) || forced_pt3(d, &c5)) return launch_cfg(d, c5, (hipStream_t)stream); }
-    // SOS_CONV_FORCE_CFG=k (testing): use the k-th candidate tiling (mod count) instead of the tuned one
-    static const char* force = getenv("SOS_CONV_FORCE_CFG");
-    if (!force) {
-        ConvCfg c;
-        const ShapeKey k = shape_key(d);
-        if (tuned_lookup(k, &c) || tuned_borrow(d, k, &c)) return launch_cfg(d, c, (hipStream_t)stream);
-    }
-    std::vector<ConvCfg> cfgs = enumerate_cfgs(d);
-    if (cfgs.empty()) {
-        sos_set_error("sos_conv2d_fwd: no tile fits LDS (cin=%d k=%dx%d)", d->cin, d->kh, d->kw);
-        return SOS_ENOSPC;
-    }
-    const size_t pick = force ? (size_t)atol(force) % cfgs.size() : 0;
-    if (getenv("SOS_CONV_LIST"))      // debugging aid: the chosen candidate of the cost-ordered list
-        fprintf(stderr, "sos_conv2d_fwd: cfg %zu/%zu NC=%d TH=%d TW=%d ks=%d\n", pick, cfgs.size(), cfgs[pick].NC, tdim(cfgs[pick].lth),
-                tdim(cfgs[pick].ltw), cfgs[pick].ks);
-    return launch_cfg(d, cfgs[pick], (hipStream_t)stream);
+    ConvCfg c;
+    ConvPlan pl;
+    if ((rc = resolve(d, "sos_conv2d_fwd", &c, &pl))) return rc;
+    return launch_plan(pl, (hipStream_t)stream);
 }
 
 // Measure the best few tilings of this descriptor's shape on the device (HIP events on `stream`,
@@ -2204,16 +2169,6 @@ extern "C" int sos_conv2d_tune(const sos_conv_desc* d, int max_candidates, int i
 #define SOS_TUNE_FORMAT 2
 #define SOS_TUNE_KEY_GEN 3
 
-// the sos_conv_desc fields enumerate_cfgs() / nt16_for() read, rebuilt from a shape key
-static sos_conv_desc desc_of_key(const ShapeKey& k) {
-    sos_conv_desc d;
-    memset(&d, 0, sizeof(d));
-    d.B = k.v[0]; d.H = k.v[1]; d.W = k.v[2]; d.Wl = k.v[3]; d.cin = k.v[4]; d.in_nseg = k.v[5]; d.cout_pad = k.v[6];
-    d.kh = k.v[7]; d.kw = k.v[8]; d.stride = k.v[9]; d.dil_h = k.v[10]; d.dil_w = k.v[11]; d.Ho = k.v[12]; d.Wo = k.v[13];
-    d.out_dtype = k.v[14]; d.out_sc = k.v[15] ? 1 : 2; d.pad_mode = k.v[16]; d.cout = k.v[18];
-    return d;
-}
-
 extern "C" int sos_conv2d_tune_save(const char* path) {
     if (!path) { sos_set_error("sos_conv2d_tune_save: null path"); return SOS_EINVAL; }
     // written to a temporary and renamed: a reader (another rank) never sees a half-written table
@@ -2263,10 +2218,7 @@ extern "C" int sos_conv2d_tune_load(const char* path) {
         if (d.cin < 16 || d.cin % 16 || d.cout_pad < 32 || d.cout_pad % 32 || d.kh < 1 || d.kw < 1 || d.kh * d.kw > 64 ||
             d.stride < 1 || d.dil_h < 1 || d.dil_w < 1 || d.Ho < 1 || d.Wo < 1 || d.in_nseg < 1 || d.cout < 1)
             continue;
-        bool legal = false;
-        for (const ConvCfg& e : enumerate_cfgs(&d))
-            if (e.NC == c.NC && e.lth == c.lth && e.ltw == c.ltw && e.ks == c.ks) { legal = true; break; }
-        if (!legal) continue;
+        if (!offered(&d, c)) continue;
         tuned_store(k, c, true);
         ++n;
     }

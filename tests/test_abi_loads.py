@@ -55,6 +55,30 @@ def test_tune_table_load_rejects_foreign_and_illegal_entries(tmp_path):
         assert h.sos_conv2d_tune_load(engine.SHIPPED_TUNE_TABLE.encode()) == len(lines) > 0
 
 
+def test_tile_count_refuses_fused_input_batchnorm_where_no_kernel_applies_it():
+    """sos_conv2d_tile_count (host only, no launch) resolves a descriptor's tiling exactly as sos_conv2d_fwd does.  A fused input
+    BatchNorm (sos_conv_desc.in_scale) on 48 -> 48 has no tiling whose kernel applies it (the 16-row kernel never reads in_scale,
+    the fused instances are three n-tiles wide): the descriptor is refused with the reason, not given a tile count for a launch
+    that would skip the BatchNorm."""
+    import ctypes as C
+    from sos_amd import _lib as L
+    h = L.lib()
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p).value
+    d = L.ConvDesc()
+    d.in_, d.wgt, d.out = p, p, p
+    d.B, d.H, d.W, d.Wl = 2, 20, 20, 20
+    d.in_cs, d.cin, d.in_nseg, d.in_seg_stride = 48, 48, 1, 48
+    d.kh, d.kw, d.cout, d.cout_pad, d.cout_store = 5, 5, 48, 64, 48
+    d.stride, d.dil_h, d.dil_w, d.pad_top, d.pad_left = 1, 1, 1, 2, 2
+    d.Ho, d.Wo = 20, 20
+    d.out_dtype, d.out_sc, d.out_sw, d.out_sh, d.out_sb = L.DT_BF16, 1, 48, 20 * 48, 400 * 48
+    assert h.sos_conv2d_tile_count(C.byref(d)) > 0
+    d.in_scale, d.in_shift = p, p
+    assert h.sos_conv2d_tile_count(C.byref(d)) < 0
+    assert "fused input BatchNorm" in h.sos_last_error().decode()
+
+
 def test_wgrad_table_load_rejects_foreign_and_illegal_entries(tmp_path):
     """sos_wgrad_tune_load (host only, no GPU; ABI 7): a table of another format is an error, a plan the build would not offer
     for that shape is dropped, a legal one is accepted; the shipped table of measured weight-gradient plans loads completely."""

@@ -638,3 +638,31 @@ def test_thin_input_streaming_conv_equals_the_tiled_kernel(case, monkeypatch):
             assert float(got[:, cout:].abs().max()) == 0.0
     finally:
         sos_amd.set_precision("bf16")
+
+
+def test_accumulating_launch_of_a_three_per_cu_table_entry():
+    """The shipped table's tiling of the 96 -> 96 5x5 layer at the BASELINE batch is a three-workgroups-per-CU instance (ks + 200),
+    which stores only: an accumulating launch of that shape (gradient fan-in, tuned on a non-accumulating copy) runs the entry's
+    plain twin -- same tile, same k-steps per chunk, same summation order -- and adds the stored launch's result to what the buffer
+    held, rounded once to the storage type."""
+    from sos_amd import engine as E, _lib as L
+    dev = torch.device("cuda")
+    B, H, W, Cc = 64, 256, 178, 96
+    torch.manual_seed(9)
+    src = E.Act(B, H, W, Cc, False, dev)
+    src.t.normal_()
+    w = E.pack_weight(torch.randn(Cc, Cc, 5, 5, device=dev) * 0.05, Cc, False)
+
+    def launch(dst, accumulate):
+        E.conv_to_act(src, 0, Cc, w, 5, 5, Cc, None, None, L.ACT_NONE, dst, cout_store=Cc, pad=(2, 2), Ho=H, Wo=W,
+                      accumulate=accumulate)
+
+    stored = E.Act(B, H, W, Cc, False, dev, zero=True)
+    launch(stored, False)
+    acc = E.Act(B, H, W, Cc, False, dev)
+    acc.t.normal_()
+    want = acc.t.float() + stored.t.float()
+    launch(acc, True)
+    got = acc.t.float()
+    assert float(stored.t.float().abs().max()) > 0.1
+    assert float(((got - want).abs() - 2.0 ** -8 * want.abs()).max()) <= 0.0

@@ -24,7 +24,7 @@ EXTEND_AV = "--extend-av" in sys.argv        # keep the committed table, add the
 RETUNE_X3 = "--retune-x3" in sys.argv        # keep the committed table, re-measure the three-segment shapes the 16-row kernel now takes
 RETUNE_NPOT = "--retune-npot" in sys.argv    # keep the committed table, re-measure the shapes that gained non-power-of-two tile candidates
 RETUNE_16ROW = "--retune-16row" in sys.argv  # keep the committed table, re-measure the 16- / 48-channel-input shapes (round 4: the 16-row
-                                             # kernel's 512-pixel workgroups; the first layers with their horizontal taps on the channel axis)
+                                             # kernel's 512-pixel workgroups, since deleted; the first layers with their horizontal taps on the channel axis)
 RETUNE_WIDE = "--retune-wide" in sys.argv    # keep the committed table, re-measure the B = 64 single-segment shapes (the bench's training / fp16
                                              # inference step) over up to 400 candidates with sos_conv2d_tune's two-stage decision (round 4)
 RETUNE_WIDE_ALL = "--retune-wide-all" in sys.argv   # every entry of the committed table re-measured that way (all batch sizes, the
@@ -63,7 +63,7 @@ if RETUNE_X3:
     print("dropped", len(lines) - len(keep), "entries to re-measure")
 
 if RETUNE_16ROW:
-    os.environ.setdefault("SOS_CONV_TUNE_CANDIDATES", "48")       # the 512-pixel candidates sit anywhere in the cost-ordered list
+    os.environ.setdefault("SOS_CONV_TUNE_CANDIDATES", "48")       # (round 4: the 512-pixel candidates sat anywhere in the cost-ordered list)
     lines = open(SHIPPED).read().splitlines()
     keep = [lines[0]] + [ln for ln in lines[1:] if ln.split()[4] not in ("16", "48")]      # column 4: cin (conv.hip, shape_key)
     for path in (OUT, OUT + ".f16"):
