@@ -20,9 +20,14 @@ A "step" is one pass of the hot path over one batch of synthetic 2 s clips resid
                U(1 s, 10 s) with seed 99, per-clip geometry inside the kernels (pipeline.denoise_ragged)
 Each rank processes its own batch (independent utterances): weak scaling.
 
-The default run (N = 1, train) also times, AFTER the headline loop and outside its timed region, the other lines of the
-round on the same box and attaches them as `secondary` (inference, ragged inference, training in bf16 -- the literal
-BASELINE configs[1] dtype -- and in 'mixed'); `value` / `config` / `dtype` describe the headline loop only.
+A plain run does only what the headline needs: it builds the workload, warms up, times the K steps, writes --dump-outputs and
+prints the line.  Its `roofline` comes from what run_timed does before and inside the timed steps, unchanged: the training
+line's serial pre-pass is part of the state the timed steps start from (its Adam steps move the weights), the other modes
+bracket their warm-up and timed steps, --graph its three eager steps before the capture.
+`--full` adds what takes runs of its own, AFTER the headline loop and outside its timed region: for N = 1, train, the other
+lines of the round on the same box as `secondary` (inference, ragged inference, training in bf16 -- the literal BASELINE
+configs[1] dtype -- and in other precisions, geometries and schedules), and for N = 1 the CPU oracle as `cpu_baseline`.  `value` / `config` / `dtype`
+describe the headline loop only.
 
 `--dump-outputs DIR` writes what the LAST timed step of the headline loop returned to its caller (train: the denoiser's
 predicted noise, mask and two losses, the detector's logits and loss; inference: the denoised waveforms) as DIR/<name>.npy,
@@ -439,8 +444,11 @@ def main():
                     help="16-bit storage type of activations/weights (MFMA rate is the same for bf16 and fp16); bf16x3 = "
                          "three-pass hi/lo split (3x the MACs, ~fp32 accuracy); mixed = detector in bf16x3 (frame decisions "
                          "equal the f32 reference's), everything else fp16.  Default: fp16 for train, mixed for inference")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (inference, ragged, bf16 / mixed training)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop, also time the secondary lines (N = 1, train: inference, ragged, other precisions, "
+                         "geometries and schedules) and the CPU baseline (N = 1); a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary lines (inference, ragged, bf16 / mixed training)")
     ap.add_argument("--serial", action="store_true", help="train mode: run the two models back to back on one stream")
     ap.add_argument("--graph", action="store_true",
                     help="infer / infer-ragged: replay hipGraph-captured launch sequences (pipeline.GraphedDenoiser) instead "
@@ -609,7 +617,7 @@ def main():
         if "in_region_avg_ms" in prof:
             line["roofline"]["in_timed_region"] = {"avg_ms": prof["in_region_avg_ms"], "launches": prof["in_region_launches"],
                                                    "frac": prof["flops"] / (prof["in_region_avg_ms"] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS}
-        if world == 1 and train and not args.no_secondary and not args.force_buckets and not args.serial:
+        if args.full and world == 1 and train and not args.no_secondary and not args.force_buckets and not args.serial:
             # the round's other lines on the same box, AFTER (and outside) the headline's timed region
             del wl
             torch.cuda.empty_cache()
@@ -806,7 +814,7 @@ def main():
                            "stream, two batches ahead) against the resident batch of the headline, alternated the same way")
             line["secondary"] = sec
             sos_amd.set_precision(args.precision)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if dist is not None:

@@ -41,7 +41,7 @@ json.dump(out, open("gpurun_out/refresh/pmc_conv96.json", "w"), indent=1)
 print(json.dumps(out))
 PY
 cp $O/pmc_conv96.json profiles/${R}_pmc_conv96.json     # bench.py reports this record as roofline.traffic
-python bench.py --steps 10 --warmup 3 > $O/bench_train_fp16.json 2> $O/bench_train_fp16.err
+python bench.py --full --steps 10 --warmup 3 > $O/bench_train_fp16.json 2> $O/bench_train_fp16.err
 python bench.py --precision bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_train_bf16.json 2> $O/bench_train_bf16.err
 python bench.py --precision bf16x3 --steps 6 --warmup 2 --no-cpu-baseline --no-secondary > $O/bench_train_bf16x3.json 2> $O/bench_train_bf16x3.err
 python bench.py --mode infer --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_infer_mixed.json 2> $O/bench_infer_mixed.err
