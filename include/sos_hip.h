@@ -42,14 +42,20 @@ const char* sos_last_error(void);
  * says "bf16" for an activation / packed-weight buffer it means "the library's 16-bit storage type". */
 const char* sos_storage_dtype(void);
 
-/* ---- a1  fast_stft: M1/transform.py:188-193 (librosa.stft(data,510,158,400), hann-periodic window centred in
+/* Front-end geometry (a1, a2): librosa 0.7.1 stft / istft semantics (hann-periodic window of win_length centred in n_fft,
+ * center=True, reflect padding, length=None) for even 16 <= n_fft <= 2048, 16 <= win_length <= n_fft,
+ * 1 <= hop <= n_fft (odd hops included) and ceil(win_length/hop) <= 16; clips need n_samples > n_fft/2.  Any other
+ * geometry is SOS_EINVAL from every a1 / a2 entry point (the *_matrix_bytes functions return -1) and sos_last_error()
+ * names the rule violated.
+ *
+ * ---- a1  fast_stft: M1/transform.py:188-193 (librosa.stft(data,510,158,400), hann-periodic window centred in
  * n_fft, center=True, reflect pad) fused with real_imag_expand (:10-17) and the caller's transpose to [2,F,T]
  * (M2/dataset.py:255).  The transform is a windowed-DFT GEMM on the matrix cores (csrc/stft_mfma.hip): the constant
  * matrix is packed ONCE on the host into MFMA fragment order, as hi + lo half-precision parts (the product is taken as
  * hi*hi + hi*lo + lo*hi with fp32 accumulation, ~22 significand bits), and uploaded by the caller:
  *   sos_stft_matrix_bytes(): bytes of ONE part; sos_stft_pack_matrix(): fills two HOST buffers of that size.
- * wave f32 [B][wave_stride], out f32 [B][2][n_fft/2+1][T], T = 1 + n_samples/hop.  Supported geometry: (n_fft+2) % 32
- * == 0, win_length % 16 == 0, even hop, ceil(win/hop) <= 3 (the reference's 510/158/400); anything else is EINVAL. */
+ * wave f32 [B][wave_stride], out f32 [B][2][n_fft/2+1][T], T = 1 + n_samples/hop.  Geometry: see above; the packed
+ * matrix is zero-padded to ceil(2*(n_fft/2+1)/32) row tiles and ceil(win_length/16) k-steps. */
 int64_t sos_stft_matrix_bytes(int n_fft, int hop, int win_length);
 int sos_stft_pack_matrix(int n_fft, int hop, int win_length, void* hi /* host */, void* lo /* host */);
 int sos_stft_f32(const float* wave, int64_t batch, int64_t n_samples, int64_t wave_stride,
@@ -62,7 +68,9 @@ int sos_stft_f32(const float* wave, int64_t batch, int64_t n_samples, int64_t wa
 /* ---- a2  fast_istft: M1/transform.py:196-202 (librosa.istft(S,158,400)): inverse real DFT, synthesis window,
  * overlap-add, division by the window-sum-square (where > tiny), trim n_fft/2 both ends -- the synthesis GEMM
  * (window and irfft weights folded into the packed matrix, same hi/lo scheme), then a fixed-order overlap-add of the
- * <= 3 frames covering a sample with the window-sum-square taken over those same frames.
+ * <= ceil(win/hop) frames covering a sample with the window-sum-square taken over those same frames; samples whose
+ * window-sum-square is <= FLT_MIN (gaps when hop > win) are not divided.  Geometry: see above; the packed matrix is
+ * zero-padded to ceil(win_length/32) row tiles and K = 2*(n_fft/2+1) rounded up to a multiple of 64.
  * sos_istft_pack_matrix also fills win_sq f32 [win_length] (HOST), the squared window.
  * spec f32 [B][2][F][T]; out f32 [B][out_stride], hop*(T-1) samples written. */
 int64_t sos_istft_matrix_bytes(int n_fft, int hop, int win_length);

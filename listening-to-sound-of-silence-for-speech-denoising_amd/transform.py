@@ -19,6 +19,15 @@ WIN_LENGTH = 400
 _tables = {}
 
 
+def check_geometry(n_fft, hop_length, win_length):
+    """Raise ValueError, naming the rule, unless the front-end kernels support this librosa geometry: even
+    16 <= n_fft <= 2048, 16 <= win_length <= n_fft, 1 <= hop_length <= n_fft, ceil(win_length/hop_length) <= 16.
+    The rules are the library's own (sos_stft_matrix_bytes checks them and launches nothing)."""
+    h = L.lib()
+    if h.sos_stft_matrix_bytes(int(n_fft), int(hop_length), int(win_length)) < 0:
+        raise ValueError((h.sos_last_error() or b"").decode())
+
+
 def _front_tables(device, n_fft, hop, win_length, inverse=False):
     """The packed windowed-DFT matrix of the STFT (or the synthesis matrix + squared window of the ISTFT) in MFMA
     fragment order, hi and lo half-precision parts: packed once on the host by the library (sos_*_pack_matrix) and
@@ -45,7 +54,9 @@ def _front_tables(device, n_fft, hop, win_length, inverse=False):
 def stft_batch(wave, n_fft=N_FFT, hop_length=HOP_LENGTH, win_length=WIN_LENGTH, clip_samples=None):
     """wave f32 (B, N) on the GPU -> (B, 2, n_fft//2+1, 1+N//hop) f32 (a1, fused with the
     [F,T,2] -> [2,F,T] transpose of M2/dataset.py:255).  clip_samples: optional int32 device (B,), ragged batch: clip b
-    has clip_samples[b] <= N samples (frames past its own 1 + n//hop are left unwritten)."""
+    has clip_samples[b] <= N samples (frames past its own 1 + n//hop are left unwritten).  Any geometry check_geometry
+    accepts."""
+    check_geometry(n_fft, hop_length, win_length)
     L.require_cuda(wave)
     if wave.dim() != 2 or wave.dtype != torch.float32:
         raise ValueError("stft_batch expects a float32 (B, N) tensor")
@@ -61,15 +72,17 @@ def stft_batch(wave, n_fft=N_FFT, hop_length=HOP_LENGTH, win_length=WIN_LENGTH, 
 
 def istft_batch(spec, hop_length=HOP_LENGTH, win_length=WIN_LENGTH, clip_frames=None):
     """spec f32 (B, 2, F, T) on the GPU -> (B, hop*(T-1)) f32 (a2).  clip_frames: optional int32 device (B,), ragged
-    batch: clip b has clip_frames[b] <= T frames and gets hop*(clip_frames[b]-1) samples."""
-    L.require_cuda(spec)
+    batch: clip b has clip_frames[b] <= T frames and gets hop*(clip_frames[b]-1) samples.  n_fft = 2*(F-1); any
+    geometry check_geometry accepts."""
     if spec.dim() != 4 or spec.shape[1] != 2 or spec.dtype != torch.float32:
         raise ValueError("istft_batch expects a float32 (B, 2, F, T) tensor")
-    spec = spec.contiguous()
     B, _, F, T = spec.shape
     n_fft = 2 * (F - 1)
+    check_geometry(n_fft, hop_length, win_length)
+    L.require_cuda(spec)
+    spec = spec.contiguous()
     mhi, mlo, wsq = _front_tables(spec.device, n_fft, hop_length, win_length, inverse=True)
-    # the window-sum-square normalisation is computed inside the kernel (the <= 3 frames covering a sample)
+    # the window-sum-square normalisation is computed inside the kernel (the <= ceil(win/hop) frames covering a sample)
     n_out = hop_length * (T - 1)
     out = torch.empty((B, n_out), dtype=torch.float32, device=spec.device)
     L.check(L.lib().sos_istft_f32(L.ptr(spec), B, T, L.ptr(mhi), L.ptr(mlo), L.ptr(wsq), n_fft, hop_length,
@@ -119,6 +132,7 @@ def power_law(data, power=0.3):
 
 def fast_stft(data, power=False, n_fft=N_FFT, hop_length=HOP_LENGTH, win_length=WIN_LENGTH):
     """M1/transform.py:188-193: 1-D waveform -> ndarray [F, T, 2].  power=True: A**0.3 companding first (:191-192)."""
+    check_geometry(n_fft, hop_length, win_length)
     w = torch.as_tensor(np.asarray(data, dtype=np.float32), device=_device()).reshape(1, -1)
     if power:
         w = power_law_batch(w, 0.3)
@@ -128,7 +142,9 @@ def fast_stft(data, power=False, n_fft=N_FFT, hop_length=HOP_LENGTH, win_length=
 
 def fast_istft(F, power=False, hop_length=HOP_LENGTH, win_length=WIN_LENGTH):
     """M1/transform.py:196-202: [F, T, 2] -> 1-D float32 of length hop*(T-1) (float64 with power=True, like the reference)."""
-    S = torch.as_tensor(np.asarray(F, dtype=np.float32), device=_device()).permute(2, 0, 1).unsqueeze(0)
+    F = np.asarray(F, dtype=np.float32)
+    check_geometry(2 * (F.shape[0] - 1), hop_length, win_length)
+    S = torch.as_tensor(F, device=_device()).permute(2, 0, 1).unsqueeze(0)
     y = istft_batch(S, hop_length, win_length)
     if power:                                                   # :200-201, the inverse companding
         return power_law_batch(y, 1.0 / 0.3)[0].cpu().numpy().astype(np.float64)
