@@ -485,6 +485,21 @@ int sos_metric_wss(const float* ref, const float* deg, int64_t n, int winlength,
                    const double* window, int n_fft, const float* crit_filter, double eps, float* out, sos_stream_t stream);
 int sos_metric_l1(const float* output, int64_t n_out, const float* target, int64_t n_t, double* result, sos_stream_t stream);
 
+/* ---- 8f-4  STOI / extended STOI (Taal et al. 2011; Jensen & Taal 2016) of a ragged batch, pystoi's
+ * stoi(x, y, fs_sig, extended) contract (float64 restatement: tests/stoi_reference.py; csrc/stoi.hip).
+ * x, y: f32 clean / processed clips concatenated; clip b is x[offsets[b] .. offsets[b] + lengths[b]) (int64 device tables;
+ * lengths_host: the same lengths on the HOST, which size the workspace and the grids).  p / q = 10000 / fs_sig reduced by
+ * their gcd; for p != q, taps = f64 [ntaps] (ntaps = 2L+1 odd): Octave's resample filter normalised to unit sum and
+ * multiplied by p (scipy.signal.resample_poly's window).  extended: 0 = classic STOI, 1 = ESTOI.
+ * sos_stoi_workspace_bytes: workspace size for these lengths (worst case: no frame removed), -1 on bad args.
+ * sos_stoi_batch: out f64 [nclips][3] = {sum of the per-segment correlations (fixed order), segments, kept frames}; the score
+ * is sum / (segments * 15) (classic) or sum / segments (extended); segments = 0 means fewer than 30 STFT frames (pystoi
+ * returns 1e-5); kept frames = -1: device lengths that overrun a workspace sized from lengths_host (not scored). */
+int64_t sos_stoi_workspace_bytes(const int64_t* lengths_host, int nclips, int p, int q);
+int sos_stoi_batch(const float* x, const float* y, const int64_t* offsets, const int64_t* lengths, const int64_t* lengths_host,
+                   int nclips, int p, int q, const double* taps, int ntaps, int extended, void* workspace, int64_t workspace_bytes,
+                   double* out, sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,7 +338,8 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
     `clean` spectrogram (unknown_clean_signal=False) also get the objective measures of the output resampled to
     16 kHz against the clean signal (:455-460) and the ground-truth WAVE files; `pesq_fn(clean, output, sr)` /
     `stoi_fn(clean, output, sr)` supply the two third-party scores (None entries otherwise) and the averages of the
-    available measures go to `denoise_statistics`."""
+    available measures go to `denoise_statistics`.  `stoi_fn=metrics.stoi` computes STOI in HIP (pypesq has no
+    counterpart here)."""
     data_list, data_info = data_list_info
     data_info = OrderedDict(data_info)
     data_info['snr'] = snr

@@ -4,10 +4,18 @@ llr (:561-623), wss (:404-558), CompositeEval (:346-402), evaluate_metrics (:16-
 
 The per-sample / per-frame work runs in HIP kernels (csrc/metrics.hip); the per-frame results (a few thousand numbers)
 are finalised here on the host exactly like the reference does (log10, clamp, means, the 95 % trimmed means and the
-composite regression formulas).  PESQ and STOI come from third-party packages (pypesq, pystoi) that are absent:
-`evaluate_metrics` / `CompositeEval` take them as arguments and return None for everything that depends on a
-missing one.  Signals: 1-D numpy arrays or GPU tensors.  No CPU fallback."""
+composite regression formulas).
+
+STOI and extended STOI (`stoi`, `stoi_batch`: pystoi's `stoi(x, y, fs_sig, extended)` contract, Taal et al. 2011 and
+Jensen & Taal 2016) run in HIP as well (csrc/stoi.hip): resampling to 10 kHz, silent-frame removal, third-octave band
+envelopes and the segment correlations of a whole ragged batch in one launch sequence, one synchronisation at the end.
+Their float64 restatement is tests/stoi_reference.py; parity against pystoi itself is unpinned (not installed here).
+PESQ comes from a third-party package (pypesq) that is absent: `evaluate_metrics` / `CompositeEval` take it, and STOI, as
+arguments and return None for everything that depends on a missing one (`handoff.denoise_files(..., stoi_fn=stoi)`
+fills in STOI).  Signals: 1-D numpy arrays or GPU tensors.  No CPU fallback."""
 import ctypes as C
+import math
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -169,7 +177,7 @@ def CompositeEval(ref_wav, deg_wav, srate=16000, eps=1e-10, pesq_raw=None):
 
 def evaluate_metrics(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None):
     """Same keys and order as the reference (M2/metrics.py:16-33); `pesq` / `stoi`: values computed elsewhere
-    (pypesq.pesq(clean, noisy, sr), pystoi.stoi(clean, noisy, sr)) or None."""
+    (pypesq.pesq(clean, noisy, sr); stoi(clean, noisy, sr) of this module or pystoi's) or None."""
     csig, cbak, covl, pesq_raw, ssnr, overall_snr = CompositeEval(clean, noisy, sr, eps=eps, pesq_raw=pesq)
     m = OrderedDict()
     m['l1'] = metrics_L1(noisy, clean)
@@ -181,3 +189,98 @@ def evaluate_metrics(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None):
     m['ssnr_exsi'] = metrics_ssnr_exclude_silence(clean, noisy, srate=sr, eps=eps)[1]
     m['overall_snr'] = overall_snr
     return m
+
+
+# ---- STOI / extended STOI (pystoi's constants: 10 kHz, 256-sample frames at hop 128, 15 third-octave bands from 150 Hz,
+# 30-frame segments, clipping at BETA = -15 dB, 40 dB dynamic range)
+STOI_FS = 10000
+STOI_NUMBAND = 15
+_STOI_MAX_CLIPS = 65535             # clips per launch sequence (the kernels' grid.y)
+
+
+def _stoi_ratio(fs_sig):
+    if isinstance(fs_sig, bool) or int(fs_sig) != fs_sig or fs_sig <= 0:
+        raise ValueError(f"fs_sig must be a positive integer sample rate, got {fs_sig!r}")
+    g = math.gcd(STOI_FS, int(fs_sig))
+    return STOI_FS // g, int(fs_sig) // g
+
+
+def _stoi_taps(p, q, device):
+    """pystoi's resample_oct filter (a port of Octave's resample): fc = 1/(2 max(p,q)), roll-off fc/10, 60 dB rejection,
+    Kaiser window; normalised to unit sum and scaled by p, as scipy.signal.resample_poly applies it."""
+    key = ("stoi", p, q, str(device))
+    if key not in _tables:
+        fc = 1. / (2 * max(p, q))
+        L_ = int(np.ceil((60. - 8) / (28.714 * (fc / 10))))
+        t = np.arange(-L_, L_ + 1)
+        h = np.kaiser(2 * L_ + 1, 0.1102 * (60. - 8.7)) * (2 * p * fc * np.sinc(2 * fc * t))
+        _tables[key] = torch.from_numpy(h / h.sum() * p).to(device)
+    return _tables[key]
+
+
+def _concat(signals):
+    """One f32 device buffer holding the signals back to back (plus a zero sentinel, so that it is never empty), and
+    their lengths.  numpy inputs go up in one copy; tensors must live on the GPU."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
+    if not any(torch.is_tensor(s) for s in signals):
+        flat = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
+        buf = np.concatenate(flat + [np.zeros(1, np.float32)])
+        return torch.from_numpy(buf).cuda(), [len(f) for f in flat]
+    ts = [_dev(s) for s in signals]
+    return torch.cat(ts + [torch.zeros(1, dtype=torch.float32, device=ts[0].device)]), [t.numel() for t in ts]
+
+
+def stoi_batch(clean, processed, fs_sig, extended=False, return_frames=False):
+    """STOI (or, extended=True, ESTOI) of every pair (clean[i], processed[i]) of 1-D signals sampled at fs_sig; the
+    clips may have any lengths, each pair equal.  One launch sequence for the whole batch and one synchronisation at the
+    end; a clip's score does not depend on the other clips of the batch.  A clip with fewer than 30 STFT frames after
+    silent-frame removal scores 1e-5 with a RuntimeWarning, as pystoi does.  Returns the list of scores, or
+    (scores, kept-frame counts) with return_frames=True."""
+    clean, processed = list(clean), list(processed)
+    if len(clean) != len(processed):
+        raise ValueError(f"{len(clean)} clean signals but {len(processed)} processed ones")
+    for i, (x, y) in enumerate(zip(clean, processed)):
+        if tuple(np.shape(x)) != tuple(np.shape(y)):
+            raise ValueError(f"clip {i}: x and y should have the same length, found {tuple(np.shape(x))} and {tuple(np.shape(y))}")
+    p, q = _stoi_ratio(fs_sig)
+    scores, frames = [], []
+    if not clean:
+        return (scores, frames) if return_frames else scores
+    outs = []
+    for c0 in range(0, len(clean), _STOI_MAX_CLIPS):
+        x, n = _concat(clean[c0:c0 + _STOI_MAX_CLIPS])
+        y, _ = _concat(processed[c0:c0 + _STOI_MAX_CLIPS])
+        lens = np.asarray(n, dtype=np.int64)
+        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(x.device)      # offsets, lengths
+        taps = _stoi_taps(p, q, x.device) if p != q else None
+        h = L.lib()
+        nbytes = h.sos_stoi_workspace_bytes(lens.ctypes.data_as(C.c_void_p), len(lens), p, q)
+        if nbytes < 0:
+            L.check(-22, "sos_stoi_workspace_bytes")
+        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=x.device)
+        out = torch.empty((len(lens), 3), dtype=torch.float64, device=x.device)
+        L.check(h.sos_stoi_batch(L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens.ctypes.data_as(C.c_void_p), len(lens),
+                                 p, q, L.ptr(taps), 0 if taps is None else taps.numel(), int(bool(extended)), L.ptr(ws),
+                                 ws.numel(), L.ptr(out), L.stream_ptr()), "sos_stoi_batch")
+        outs.append(out)
+    res = torch.cat(outs).cpu().numpy()
+    for total, segments, kept in res:
+        if kept < 0:
+            raise RuntimeError("sos_stoi_batch: device lengths disagree with the host's")
+        frames.append(int(kept))
+        if segments == 0:
+            warnings.warn("Not enough STFT frames to compute intermediate intelligibility measure after removing silent "
+                          "frames. Returning 1e-5. Please check you wav files", RuntimeWarning)
+            scores.append(1e-5)
+        else:
+            scores.append(float(total / (segments * (1 if extended else STOI_NUMBAND))))
+    return (scores, frames) if return_frames else scores
+
+
+def stoi(x, y, fs_sig, extended=False):
+    """pystoi's stoi(x, y, fs_sig, extended=False): x clean, y processed (1-D, same shape), fs_sig in Hz -> float.
+    stoi_batch of one clip."""
+    if tuple(np.shape(x)) != tuple(np.shape(y)):
+        raise ValueError(f"x and y should have the same length, found {tuple(np.shape(x))} and {tuple(np.shape(y))}")
+    return stoi_batch([x], [y], fs_sig, extended)[0]
