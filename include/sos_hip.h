@@ -333,7 +333,8 @@ int sos_conv2d_wgrad_reduce(const sos_wgrad_desc* desc, sos_stream_t stream);
  * counterpart of sos_conv2d_tune: times the candidate plans for the SHAPE of `desc` (`iters` launches each, the fastest few
  * again over 8x as many; HIP events on `stream`, SYNCHRONISES, overwrites desc->dw / desc->partial: pass accumulate = 0 and
  * scratch outputs) and caches the winner for every later sos_conv2d_wgrad of that shape.  *best_ms (optional) = the winning time,
- * -1 if the shape already had a plan (or takes the GEMM path).  save / load: host text file; load returns the entries accepted
+ * -1 if the shape already had a plan (or takes the GEMM or a streaming path, which have none).  A descriptor sos_conv2d_wgrad
+ * refuses is refused here with the same code and message, before anything is launched.  save / load: host text file; load returns the entries accepted
  * (0: no file).  The package ships wgrad_table_gfx950.txt so that every process and rank runs the same plans. */
 int sos_wgrad_tune(const sos_wgrad_desc* desc, int iters, float* best_ms, sos_stream_t stream);
 int sos_wgrad_tune_save(const char* path);

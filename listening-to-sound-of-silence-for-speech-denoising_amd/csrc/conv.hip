@@ -990,12 +990,6 @@ __global__ __launch_bounds__(256, (SB || W3) ? 3 : (PT > 2 ? 2 : 1)) void conv_m
 // weight fragment (from the window's [2 taps][rows][cin] slab) and the pixel fragment (patch shifted by THAT tap).
 // These per-lane offsets are window invariant.  One barrier per TWO taps; an odd last tap gets a zero slab.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifndef SOS_C16_UPFRONT
-#define SOS_C16_UPFRONT 0
-#endif
-#ifndef SOS_C16_XPF
-#define SOS_C16_XPF 0       // 1: the next window's first pixel fragments requested before the barrier that closes a window (experiment: inside the noise)
-#endif
 
 #if __HIP_DEVICE_COMPILE__
 // ---- epilogue of the 16-row kernels: D[m = cout][n = pixel]: lane = pixel + 16 * (cout / 4), register = cout % 4
@@ -1179,16 +1173,6 @@ __global__ __launch_bounds__(256, MODE == 1 ? 3 : 2) void conv16_kernel(ConvPara
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's patch pieces have landed
     __syncthreads();
 
-#if SOS_C16_XPF
-    // pixel fragments of the NEXT window's first K-block: requested before the barrier(s) that close a window (the patch does
-    // not change inside a segment), so that behind the barrier only the three weight fragments are still to be read
-    bf16x8 fbn[PT];
-    {
-        const int po = (tap1[0] ? __builtin_amdgcn_readlane(tapoff16, min(1, ntaps - 1)) : __builtin_amdgcn_readlane(tapoff16, 0)) + coff[0];
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt) fbn[pt] = lds_frag(patch + pbase[pt] + po);
-    }
-#endif
     for (int w = 0; w < nwin; ++w) {
         const int cur = SB ? 0 : (w & 1);
         if constexpr (MODE == 0) { if (w + 1 < nwin && !CDBG(8)) dma_window(w + 1, cur ^ 1); }       // next window's slab (lands while the MFMAs run)
@@ -1206,36 +1190,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? 3 : 2) void conv16_kernel(ConvPara
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) fb[buf][pt] = lds_frag(patch + pbase[pt] + po);
         };
-#if SOS_C16_UPFRONT
-        // experiment (round 3): every fragment of the window's BW K-blocks requested up front (7 BW ds_read_b128 in flight), the
-        // MFMAs of block kb wait only for their own operands (LDS returns in order)
-        bf16x8 ga[BW][NT16], gb[BW][PT];
-#pragma unroll
-        for (int kb = 0; kb < BW; ++kb) {
-#pragma unroll
-            for (int nt = 0; nt < NT16; ++nt) ga[kb][nt] = lds_frag(slab + aoff[kb] + nt * 16 * BSTRIDE);
-            const int po = (tap1[kb] ? toff1 : toff0) + coff[kb];
-#pragma unroll
-            for (int pt = 0; pt < PT; ++pt) gb[kb][pt] = lds_frag(patch + pbase[pt] + po);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int kb = 0; kb < BW; ++kb) {
-#pragma unroll
-            for (int nt = 0; nt < NT16; ++nt)
-#pragma unroll
-                for (int pt = 0; pt < PT; ++pt)
-                    acc[pt][nt] = SOS_MFMA_16x16x32(ga[kb][nt], gb[kb][pt], acc[pt][nt], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        (void)fa; (void)fb; (void)read_block;
-#else
-#if SOS_C16_XPF
-#pragma unroll
-        for (int nt = 0; nt < NT16; ++nt) fa[0][nt] = lds_frag(slab + aoff[0] + nt * 16 * BSTRIDE);
-#else
         read_block(0, 0);
-#endif
 #pragma unroll
         for (int kb = 0; kb < BW; ++kb) {
             const int cb = kb & 1;
@@ -1245,24 +1200,10 @@ __global__ __launch_bounds__(256, MODE == 1 ? 3 : 2) void conv16_kernel(ConvPara
             for (int nt = 0; nt < NT16; ++nt)
 #pragma unroll
                 for (int pt = 0; pt < PT; ++pt) {
-#if SOS_C16_XPF
-                    acc[pt][nt] = SOS_MFMA_16x16x32(fa[cb][nt], kb == 0 ? fbn[pt] : fb[cb][pt], acc[pt][nt], 0, 0, 0);
-#else
                     acc[pt][nt] = SOS_MFMA_16x16x32(fa[cb][nt], fb[cb][pt], acc[pt][nt], 0, 0, 0);
-#endif
                 }
             __builtin_amdgcn_sched_barrier(0);
         }
-#if SOS_C16_XPF
-        if (w + 1 < nwin) {
-            const int t0n = __builtin_amdgcn_readlane(tapoff16, 2 * w + 2);
-            const int t1n = __builtin_amdgcn_readlane(tapoff16, min(2 * w + 3, ntaps - 1));
-            const int po = (tap1[0] ? t1n : t0n) + coff[0];
-#pragma unroll
-            for (int pt = 0; pt < PT; ++pt) fbn[pt] = lds_frag(patch + pbase[pt] + po);
-        }
-#endif
-#endif
         if constexpr (SB) {
             // single buffer: refilled behind a barrier; the DMA's latency is covered by the two other workgroups of the
             // CU, and the LDS pipe is spared the ds_write_b128s of a register path (48->48 5x5: 0.356 -> 0.340 ms)

@@ -16,6 +16,7 @@
 // walks a slice of the pixels (split-K); partial sums go to a [ksplit][taps][M][N] fp32 buffer
 // that a deterministic reduce kernel folds into the OIHW gradient (no atomics).
 #include "sos_common.h"
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,7 +25,6 @@
 #include <map>
 #include <vector>
 #include <mutex>
-#include <type_traits>
 
 typedef sos_half_t bf16x8 __attribute__((ext_vector_type(8)));   // 8 storage-type (bf16, or fp16 in the SOS_F16 build) MFMA operands
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -32,9 +32,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define WG_WAVES 8            // waves per workgroup (512 threads, two per SIMD)
 #define WG_THREADS (WG_WAVES * 64)
-#ifndef SOS_WGRAD_PIPE
-#define SOS_WGRAD_PIPE 0      // 1: register double-buffered k-step pipeline of the 25-tap kernels (measured SLOWER)
-#endif
 #define WG_PAIRS 4            // (tap, n-tile) pairs per wave; x MT m-tiles = accumulator tiles per wave
 
 // Ablation switches (SOS_WGRAD_DBG bit mask: 1 no prefetch DMA, 8 DMA lanes all out of range, 16 ... all offset 0)
@@ -387,84 +384,6 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(WgParams p) {
         unsigned kmask = (unsigned)__builtin_amdgcn_ballot_w64(cgh0 + kfh < p.Hg && cgw0 + kfw < p.Wg) & 0xffffu;   // wave-uniform
         if (WDBG(32)) kmask = 0xffffu;
         cgh0 = onext.gh0; cgw0 = onext.gw0;
-        if constexpr (BAL && SOS_WGRAD_PIPE) {
-            // ---- software pipeline over the k-steps (round 3).  The counted waits of the loop below do not survive hipcc's
-            // scheduler (the MFMAs sink below them: every k-step waited for ALL of its reads before its first MFMA, and the
-            // in-order MFMA issue of a k-step -- 9..10 x 32 cycles -- then kept the wave from issuing the next reads: LDS
-            // latency and MFMA issue were serial, the MFMA pipe 57 % busy).  Here the fragments are double buffered in
-            // registers: the reads of k-step ks + 1 are issued BEFORE the MFMAs of ks, whose operands landed during the
-            // MFMAs of ks - 1; one wait per k-step, pinned with scheduling barriers.
-            struct Frag { u32x4 av[MT], bv[NP]; };
-            Frag F0, F1;
-            u32x4 avx, bvx;               // the wave's part of the 25th tap: read at the top of ITS k-step, used last (8 registers, not 16)
-            auto rd2 = [&](const unsigned a0addr, const unsigned a1addr) {
-                const uint2 lo = lds_tr(a0addr), hi = lds_tr(a1addr);
-                return u32x4{lo.x, lo.y, hi.x, hi.y};
-            };
-            auto issue_reads = [&](const int ks, Frag& F) {
-                const unsigned ga = (gb + (unsigned)ks * 1024u) + glane;
-                const unsigned xk = xb + (unsigned)__builtin_amdgcn_readlane((int)ppk, ks);
-                { const uint2 lo = lds_tr(ga), hi = lds_tr_off<256>(ga); F.av[0] = u32x4{lo.x, lo.y, hi.x, hi.y}; }
-                if constexpr (MT >= 2) { const uint2 lo = lds_tr_off<16384>(ga), hi = lds_tr_off<16384 + 256>(ga); F.av[1] = u32x4{lo.x, lo.y, hi.x, hi.y}; }
-                if constexpr (MT >= 3) { const uint2 lo = lds_tr_off<32768>(ga), hi = lds_tr_off<32768 + 256>(ga); F.av[2] = u32x4{lo.x, lo.y, hi.x, hi.y}; }
-#pragma unroll
-                for (int u = 0; u < NP; ++u) F.bv[u] = rd2(xlane0 + (xk + toff[u]), xlane1 + (xk + toff[u]));
-            };
-            // hx / last are compile-time tags: the k-loop below exists twice (waves with / without a part of the 25th tap) and
-            // only the last k-step is peeled (two full copies of the loop, one per wave kind, made hipcc spill 483 registers)
-            auto kstep = [&](auto last, const int ks, Frag& C, Frag& N) {
-                constexpr bool LAST = decltype(last)::value;
-                uint2 ent = make_uint2(0u, 0u);
-                const int di = ks * nlight + lw;                      // this wave's DMA instruction in this k-step
-                const bool dma = prefetch && lw >= 0 && di < ninstr;
-                if (dma) ent = lds_read64(st.entry_addr(di));          // ahead of the next reads: it returns before them
-                if (hasx) {
-                    const unsigned gax = (gb + (unsigned)ks * 1024u) + glane + (unsigned)wave * 16384u;
-                    const unsigned xk = xb + (unsigned)__builtin_amdgcn_readlane((int)ppk, ks);
-                    const uint2 lo = lds_tr(gax), hi = lds_tr_off<256>(gax);
-                    avx = u32x4{lo.x, lo.y, hi.x, hi.y};
-                    bvx = rd2(xlane0 + (xk + toffx), xlane1 + (xk + toffx));
-                }
-                if constexpr (!LAST) issue_reads(ks + 1, N);
-                __builtin_amdgcn_sched_barrier(0);
-                // LDS returns in order: when no more than the reads issued in THIS k-step are outstanding, `ent` and C (issued
-                // a k-step ago) have landed.  lgkmcnt is a 4-bit counter: 15 = "at most 15 outstanding".
-                constexpr int NOUT = LAST ? 0 : 2 * (MT + NP);
-                if (hasx) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ent) : "n"(NOUT + 4 > 15 ? 15 : NOUT + 4));
-                else asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ent) : "n"(NOUT));
-#pragma unroll
-                for (int a = 0; a < MT; ++a) asm volatile("" : "+v"(C.av[a]));
-#pragma unroll
-                for (int u = 0; u < NP; ++u) asm volatile("" : "+v"(C.bv[u]));
-                __builtin_amdgcn_sched_barrier(0);
-                if (dma) st.issue(di, ent, onext, cur ^ 1);
-#pragma unroll
-                for (int u = 0; u < NP; ++u) {
-                    const bf16x8 bfr = __builtin_bit_cast(bf16x8, C.bv[u]);
-#pragma unroll
-                    for (int a = 0; a < MT; ++a)
-                        acc[a][u] = SOS_MFMA_32x32x16(__builtin_bit_cast(bf16x8, C.av[a]), bfr, acc[a][u], 0, 0, 0);
-                }
-                if (hasx) {          // its four reads were the first of this k-step: landed once only the next k-step's are outstanding
-                    __builtin_amdgcn_sched_barrier(0);
-                    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(avx), "+v"(bvx) : "n"(LAST ? 0 : 2 * (MT + NP)));
-                    accx = SOS_MFMA_32x32x16(__builtin_bit_cast(bf16x8, avx), __builtin_bit_cast(bf16x8, bvx), accx, 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            {
-                constexpr std::false_type more_t{};
-                constexpr std::true_type last_t{};
-                issue_reads(0, F0);
-#pragma unroll 1
-                for (int ks = 0; ks < 14; ks += 2) {
-                    kstep(more_t, ks, F0, F1);
-                    kstep(more_t, ks + 1, F1, F0);
-                }
-                kstep(more_t, 14, F0, F1);
-                kstep(last_t, 15, F1, F0);
-            }
-        } else {
         int it = 0;                                 // k-steps done: the DMA slots of the next tile are counted in these
 #pragma unroll 1
         for (; kmask; ++it) {
@@ -546,7 +465,6 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(WgParams p) {
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ent));
                 st.issue(di, ent, onext, cur ^ 1);
             }
-        }
         }
         if (p.dbuf) {
             cur ^= 1;
@@ -1153,74 +1071,69 @@ __global__ __launch_bounds__(256) void wgrad_thin_taps_kernel(WgThinTapParams p)
 #endif
 }
 
-// which 1x1 gradients take the streaming kernel, and with how many workgroups (= partial planes)
-static bool wg_thin_shape(const sos_wgrad_desc* d, bool is_flat, int* m16, int* n16) {
-    if (!is_flat || getenv("SOS_WGRAD_NO_THIN")) return false;
-    const int a = (d->M + 15) / 16, b = (d->N + 15) / 16;
-    if (!((a == 1 && b >= 1 && b <= 6) || (b == 1 && a >= 1 && a <= 6))) return false;
-    if (a == 5 || b == 5) return false;                       // (no instance)
-    // the kernel's buffer resources and offsets are 32-bit ((unsigned)(k * cs * 2)); a descriptor that ARRIVES flat
-    // (B = Hg = 1, a huge Wg) has not been through the flatten step's range check -- and the 16-channel sub-images the kernel
-    // fetches (16 m16 / 16 n16 channels from g_off / x_off) must lie inside a pixel's channel run.  Anything else: tiled kernel.
-    const uint64_t npx = (uint64_t)d->B * d->Hg * d->Wg;
-    if (npx * (uint64_t)d->g_cs * 2 >= 0xfff00000ull || npx * (uint64_t)d->x_cs * 2 >= 0xfff00000ull) return false;
-    if (d->g_off + 16 * a > d->g_cs || d->x_off + 16 * b > d->x_cs) return false;
-    *m16 = a; *n16 = b;
-    return true;
+// ---------------------------------------------------------------------------------------------------------------------------
+// Host side.  Every entry point takes one path from the caller's descriptor to the launch: wg_route() validates, flattens a 1x1
+// gradient and picks the route (split-K GEMM, thin 1x1 or thin 5x1 streaming kernel, tiled kernels); the tiled route takes a
+// PLAN from the forced knobs, else the measured table, else the cost model, and only wg_make_plan() makes plans; wg_resolve()
+// turns route + plan into kernel instance, grid, LDS, parameters and number of partial planes without launching; wg_run()
+// launches the kernel (sos_conv2d_wgrad_partial), the reduce (sos_conv2d_wgrad_reduce) or both.
+static const int WG_MT_MAX = 3, WG_NTB_MAX = 4, WG_OCC_MAX = 4;     // channel tile (instances: wg_instances) and workgroups per CU of a plan
+
+// The run-time knobs.  Read here and nowhere else, at the top of every call and not cached: the tests and the
+// sweep tools under tools/probe change them inside one process.
+struct WgKnobs {
+    bool no_thin, no_gemm, no16, no16_7, nobal, noxcd, even_pitch, verbose, tune_verbose;
+    bool forced;                   // SOS_WGRAD_TILE / MT / NTB / OCC is set: the measured table and the model cache are bypassed
+    int fnc, fth, ftw, fko;        // SOS_WGRAD_TILE="nc,lth,ltw,kord" (experiments), -1: free
+    int mt, ntb, occ;              // SOS_WGRAD_MT (1..3) / NTB (1..4) / OCC (1..4), 0: free
+    int thin_occ, gemm_split, dbg; // SOS_WGT_OCC (1..8), SOS_WGG_SPLIT, 0: free; SOS_WGRAD_DBG (ablation builds)
+};
+static WgKnobs wg_knobs() {
+    auto env = [](const char* name) { return getenv(name); };
+    auto num = [&](const char* name, int lo, int hi) { const char* e = env(name); const int v = e ? atoi(e) : 0; return v >= lo && v <= hi ? v : 0; };
+    WgKnobs k;
+    k.no_thin = env("SOS_WGRAD_NO_THIN"); k.no_gemm = env("SOS_WGRAD_NO_GEMM"); k.no16 = env("SOS_WGRAD_NO16"); k.no16_7 = env("SOS_WGRAD_NO16_7");
+    k.nobal = env("SOS_WGRAD_NOBAL"); k.noxcd = env("SOS_WGRAD_NOXCD"); k.even_pitch = env("SOS_WGRAD_EVEN_PITCH");
+    k.verbose = env("SOS_WGRAD_VERBOSE"); k.tune_verbose = env("SOS_CONV_TUNE_VERBOSE");
+    k.forced = env("SOS_WGRAD_TILE") || env("SOS_WGRAD_MT") || env("SOS_WGRAD_NTB") || env("SOS_WGRAD_OCC");
+    k.fnc = k.fth = k.ftw = k.fko = -1;
+    if (const char* e = env("SOS_WGRAD_TILE")) sscanf(e, "%d,%d,%d,%d", &k.fnc, &k.fth, &k.ftw, &k.fko);
+    k.mt = num("SOS_WGRAD_MT", 1, WG_MT_MAX); k.ntb = num("SOS_WGRAD_NTB", 1, WG_NTB_MAX); k.occ = num("SOS_WGRAD_OCC", 1, WG_OCC_MAX);
+    k.thin_occ = num("SOS_WGT_OCC", 1, 8); k.gemm_split = num("SOS_WGG_SPLIT", 1, INT_MAX); k.dbg = num("SOS_WGRAD_DBG", INT_MIN, INT_MAX);
+    return k;
 }
 
-// ksplit <= 0 in the descriptor = automatic: one workgroup per CU (MI355X: 256) over (pixel split, m-group, n-group),
-// bounded by 256 MB of partial sums.
+// Partial sums: [ksplit][taps][Mp][Np] fp32, M and N rounded up to 32.  ksplit <= 0 in the descriptor = automatic, bounded by
+// 256 MB of partial sums.
 static const int WG_NCU = 256;
-static const int WG_MAXSPLIT = 1024;      // several workgroups per CU for gradients whose tiles are short (see sos_conv2d_wgrad)
+static const int WG_MAXSPLIT = 1024;      // several workgroups per CU for gradients whose tiles are short (see wg_resolve)
+static int wg_pad32(int n) { return (n + 31) / 32 * 32; }
+static int64_t wg_split_bytes(const sos_wgrad_desc* d) { return (int64_t)d->kh * d->kw * wg_pad32(d->M) * wg_pad32(d->N) * 4; }
 static int wg_max_split(const sos_wgrad_desc* d) {
-    const int64_t Mp = (d->M + 31) / 32 * 32, Np = (d->N + 31) / 32 * 32;
-    const int64_t per = (int64_t)d->kh * d->kw * Mp * Np * 4;
-    const int64_t cap = ((int64_t)256 << 20) / per;
+    const int64_t cap = ((int64_t)256 << 20) / wg_split_bytes(d);
     return (int)(cap < 1 ? 1 : (cap > WG_MAXSPLIT ? WG_MAXSPLIT : cap));
 }
-// the kh x 1 gradients of a thin input that take wgrad_thin_taps_kernel (instance: 49..64 output channels, 5 taps)
-static bool wg_thin_taps_shape(const sos_wgrad_desc* d, bool temporal) {
-    if (temporal || getenv("SOS_WGRAD_NO_THIN") || d->kw != 1 || d->kh != 5 || d->stride != 1 || d->N > 16 || (d->M + 15) / 16 != 4) return false;
-    if (d->Hg != d->Hx || d->Wg != d->Wx || d->pad_left != 0 || d->Wg < 32) return false;
-    if (d->pad_mode == SOS_PAD_REFLECT && d->pad_top >= d->Hg) return false;
+static int wg_split_cap(const sos_wgrad_desc* d) { return d->ksplit > 0 ? d->ksplit : wg_max_split(d); }   // planes the workspace holds
+// all pixels of the batch lie within the 32-bit buffer offsets ((unsigned)(k * cs * 2)) of the GEMM and the streaming kernels
+static bool wg_batch_fits32(const sos_wgrad_desc* d) {
     const uint64_t npx = (uint64_t)d->B * d->Hg * d->Wg;
     return npx * (uint64_t)d->g_cs * 2 < 0xfff00000ull && npx * (uint64_t)d->x_cs * 2 < 0xfff00000ull;
 }
-// workgroups (= partial planes) of wgrad_thin_kernel: one per CU, at least 16 stages per wave
-static int wg_thin_split(const sos_wgrad_desc* d, int subs) {
-    int occ = 1;                                   // measured (48 + 16 channels, 2.9 M pixels): 1 -> 73 us, 2 -> 81, 3 -> 90
-    { const char* e = getenv("SOS_WGT_OCC"); if (e && atoi(e) >= 1 && atoi(e) <= 8) occ = atoi(e); }
-    int n = WG_NCU * occ;
-    const int cap = d->ksplit > 0 ? d->ksplit : wg_max_split(d);
-    if (n > cap) n = cap;
-    const int by_work = d->Wg / (4 * 32 * 16);
-    if (n > by_work) n = by_work;
-    return n < 1 ? 1 : n;
+
+extern "C" int64_t sos_wgrad_workspace_bytes(const sos_wgrad_desc* d) {
+    if (!d || d->kh < 1 || d->kw < 1 || d->M < 1 || d->N < 1) return -1;
+    return wg_split_cap(d) * wg_split_bytes(d);
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Host side of wgrad_kernel / wgrad16_kernel: a PLAN = the workgroup's channel tile (MT m-tiles x NTB n-tiles of 32), its pixel
-// tile (NC residue classes x 2^lth x 2^ltw = 256 pixels), the order of those pixels along the contraction and the number of
-// workgroups per CU.  Plans come from (1) the measured table (round 4: sos_wgrad_tune / sos_wgrad_tune_load, the shipped
-// wgrad_table_gfx950.txt -- every process and every rank then runs the same plans, hence the same summation order), else (2) the
-// calibrated cost model below.
-struct WgPlan { int mt, ntb, nc, lth, ltw, kord, occ, db, bufbytes, npixp, pw; double cost; };
+// What the tiled kernels need to know about a shape (temporal / is_flat / m16 / n16: every route).
 struct WgCtx {
+    WgKnobs kn;
     bool temporal, is_flat, use16;
     int khg, ntg, taps, taps_all, ntiles_m, ntiles_n, m16, n16, Hc, Wc;
 };
-struct WgKey {
-    int v[12];
-    bool operator<(const WgKey& o) const { return memcmp(v, o.v, sizeof(v)) < 0; }
-};
-static std::mutex& wg_mu() { static std::mutex m; return m; }
-static std::map<WgKey, WgPlan>& wg_table() { static std::map<WgKey, WgPlan> t; return t; }      // measured plans
-static std::map<WgKey, WgPlan>& wg_model_cache() { static std::map<WgKey, WgPlan> t; return t; } // the cost model's picks
-
-static WgCtx wg_ctx(const sos_wgrad_desc* d, bool temporal, bool is_flat) {
+static WgCtx wg_ctx(const sos_wgrad_desc* d, bool temporal, bool is_flat, const WgKnobs& kn) {
     WgCtx c;
+    c.kn = kn;
     c.temporal = temporal; c.is_flat = is_flat;
     // more taps than one workgroup's 32 (tap, n-tile) pairs (7x7): the tap ROWS are divided over ntg workgroups that read the
     // same G tile at the same time on the same XCD (one launch, G fetched from HBM once instead of once per row)
@@ -1232,22 +1145,151 @@ static WgCtx wg_ctx(const sos_wgrad_desc* d, bool temporal, bool is_flat) {
     c.ntiles_m = (d->M + 31) / 32; c.ntiles_n = (d->N + 31) / 32;
     c.m16 = (d->M + 15) / 16; c.n16 = (d->N + 15) / 16;
     // small channel counts: the 16x16x32 kernel owns all of dW in one workgroup (no padding to 32)
-    c.use16 = !temporal && c.ntg == 1 && c.m16 == 3 && c.n16 == 3 && (c.taps == 25 || c.taps == 9 || (c.taps == 7 && !getenv("SOS_WGRAD_NO16_7"))) &&
-              !getenv("SOS_WGRAD_NO16");      // (7 taps: one per wave, the eighth wave only stages)
+    c.use16 = !temporal && c.ntg == 1 && c.m16 == 3 && c.n16 == 3 && (c.taps == 25 || c.taps == 9 || (c.taps == 7 && !kn.no16_7)) &&
+              !kn.no16;                       // (7 taps: one per wave, the eighth wave only stages)
     c.Hc = (d->Hg + d->dil_h - 1) / d->dil_h; c.Wc = (d->Wg + d->dil_w - 1) / d->dil_w;
     return c;
 }
+
+// Every compiled kernel instance of this file; nothing else names an instantiation.  a, b, v are the template arguments:
+// wgrad_kernel<MT, NTB, BAL (the balanced 25-tap variant)>, wgrad16_kernel<M16, N16, FT (taps per wave: 3 for 25 taps, 1 for
+// 9 and 7)>, wgrad_thin_kernel<M16, N16>, wgrad_thin_taps_kernel<M16, KH>.
+enum WgKernelKind { WG_K32, WG_K16, WG_KTHIN, WG_KTAPS, WG_KGEMM };
+struct WgInstance { const void* k; WgKernelKind kind; int a, b, v; };
+#define SOS_WG32(MT, NTB) {(const void*)wgrad_kernel<MT, NTB>, WG_K32, MT, NTB, 0}
+#define SOS_WGT(A, B) {(const void*)wgrad_thin_kernel<A, B>, WG_KTHIN, A, B, 0}
+static const WgInstance wg_instances[] = {
+    SOS_WG32(1, 1), SOS_WG32(1, 2), SOS_WG32(1, 4), SOS_WG32(2, 1), SOS_WG32(2, 2), SOS_WG32(2, 4),
+    SOS_WG32(3, 1), SOS_WG32(3, 2), SOS_WG32(3, 4), SOS_WG32(1, 3), SOS_WG32(2, 3), SOS_WG32(3, 3),
+    {(const void*)wgrad_kernel<3, 1, true>, WG_K32, 3, 1, 1}, {(const void*)wgrad_kernel<2, 1, true>, WG_K32, 2, 1, 1},
+    {(const void*)wgrad16_kernel<3, 3, 3>, WG_K16, 3, 3, 3}, {(const void*)wgrad16_kernel<3, 3, 1>, WG_K16, 3, 3, 1},
+    SOS_WGT(1, 1), SOS_WGT(2, 1), SOS_WGT(3, 1), SOS_WGT(4, 1), SOS_WGT(6, 1), SOS_WGT(1, 2), SOS_WGT(1, 3), SOS_WGT(1, 4), SOS_WGT(1, 6),
+    {(const void*)wgrad_thin_taps_kernel<4, 5>, WG_KTAPS, 4, 5, 0}, {(const void*)wgrad_gemm_kernel, WG_KGEMM, 0, 0, 0},
+};
+#undef SOS_WGT
+#undef SOS_WG32
+static const void* wg_kernel(WgKernelKind kind, int a, int b, int v) {          // null: no such instance
+    for (const WgInstance& i : wg_instances)
+        if (i.kind == kind && i.a == a && i.b == b && i.v == v) return i.k;
+    return nullptr;
+}
+// the tiled kernel that runs the channel tile (mt, ntb) of a shape
+static const void* wg_tiled_kernel(const WgCtx& c, int mt, int ntb) {
+    if (c.use16) return wg_kernel(WG_K16, c.m16, c.n16, c.taps == 25 ? 3 : 1);
+    return wg_kernel(WG_K32, mt, ntb, c.taps == 25 && ntb == 1 && mt >= 2 && !c.kn.nobal);
+}
+static int wg_set_attributes() {            // every instance may use the full 160 KB of LDS (the GEMM: its two stages)
+    static sos_device_once once;
+    return sos_per_device_once(once, [] {
+        for (const WgInstance& i : wg_instances)
+            if (hipFuncSetAttribute(i.k, hipFuncAttributeMaxDynamicSharedMemorySize, i.kind == WG_KGEMM ? 2 * WGG_BUF : 160 * 1024) != hipSuccess) {
+                sos_set_error("sos_conv2d_wgrad: hipFuncSetAttribute failed");
+                return (int)SOS_ELAUNCH;
+            }
+        return (int)SOS_OK;
+    });
+}
+
+// which 1x1 gradients take the streaming kernel: one side of at most 16 channels, and an instance for the other
+static bool wg_thin_shape(const sos_wgrad_desc* d, const WgCtx& c) {
+    if (!c.is_flat || c.kn.no_thin || !wg_kernel(WG_KTHIN, c.m16, c.n16, 0)) return false;
+    // A descriptor that ARRIVES flat (B = Hg = 1, a huge Wg) has not been through the flatten step's range check -- and the
+    // 16-channel sub-images the kernel fetches (16 m16 / 16 n16 channels from g_off / x_off) must lie inside a pixel's channel
+    // run.  Anything else: tiled kernel.
+    return wg_batch_fits32(d) && d->g_off + 16 * c.m16 <= d->g_cs && d->x_off + 16 * c.n16 <= d->x_cs;
+}
+// the kh x 1 gradients of a thin input that take wgrad_thin_taps_kernel (instance: 49..64 output channels, 5 taps)
+static bool wg_thin_taps_shape(const sos_wgrad_desc* d, const WgCtx& c) {
+    if (c.temporal || c.kn.no_thin || d->kw != 1 || d->kh != 5 || d->stride != 1 || d->N > 16 || c.m16 != 4) return false;
+    if (d->Hg != d->Hx || d->Wg != d->Wx || d->pad_left != 0 || d->Wg < 32) return false;
+    return !(d->pad_mode == SOS_PAD_REFLECT && d->pad_top >= d->Hg) && wg_batch_fits32(d);
+}
+// workgroups (= partial planes) of the streaming kernels over `npix` pixels: one per CU, at least 16 stages per wave
+static int wg_thin_split(const sos_wgrad_desc* d, const WgCtx& c, int npix) {
+    const int occ = c.kn.thin_occ ? c.kn.thin_occ : 1;   // measured (48 + 16 channels, 2.9 M pixels): 1 -> 73 us, 2 -> 81, 3 -> 90
+    const int n = std::min(std::min(WG_NCU * occ, wg_split_cap(d)), npix / (4 * 32 * 16));
+    return n < 1 ? 1 : n;
+}
+
+// The one route decision: validates the caller's descriptor like sos_conv2d_wgrad always did (`who` names the entry point in
+// the null-pointer message only), flattens, picks the route; for the tiled route it also refuses what no plan can run.
+enum WgRouteKind { WG_GEMM, WG_THIN, WG_THIN_TAPS, WG_TILED };
+struct WgRoute {
+    sos_wgrad_desc d;          // the caller's descriptor, a 1x1 gradient flattened
+    WgRouteKind kind;
+    WgCtx cx;
+};
+static int wg_route(const sos_wgrad_desc* in, const char* who, WgRoute* r) {
+    if (!in || !in->g || !in->x || !in->partial || !in->dw) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
+    r->d = *in;
+    sos_wgrad_desc* d = &r->d;
+    if (d->M < 1 || d->N < 1 || d->g_cs % 8 || d->x_cs % 8 || d->g_off % 8 || d->x_off % 8 || d->kh < 1 || d->kw < 1 ||
+        d->stride < 1 || d->dil_h < 1 || d->dil_w < 1 || (d->stride > 1 && (d->dil_h > 1 || d->dil_w > 1)) ||
+        d->B < 1) {
+        sos_set_error("sos_conv2d_wgrad: bad descriptor");
+        return SOS_EINVAL;
+    }
+    const bool temporal = d->t_taps > 1;
+    if (temporal && (d->t_frames < 1 || d->B % d->t_frames || d->t_cin < 128 || d->t_cin % 128 || d->N != d->t_taps * d->t_cin ||
+                     d->t_pad < 0 || d->t_pad >= d->t_taps || d->x_off + d->t_cin > d->x_cs)) {
+        sos_set_error("sos_conv2d_wgrad: bad temporal taps (B=%d frames=%d taps=%d cin=%d N=%d)", d->B, d->t_frames, d->t_taps,
+                      d->t_cin, d->N);
+        return SOS_EINVAL;
+    }
+    // 1x1 kernels (Linear layers, LSTM projections): the pixel arrays of G and X are congruent, so the batch
+    // is one long row -- full 256-pixel tiles instead of one ragged tile per (short) image.
+    const bool congruent = !temporal && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_top == 0 && d->pad_left == 0 &&
+                           d->Hg == d->Hx && d->Wg == d->Wx;
+    if (congruent && wg_batch_fits32(d)) {
+        d->Wg = d->Wx = (int)((uint64_t)d->B * d->Hg * d->Wg);
+        d->B = d->Hg = d->Hx = 1;
+    }
+    const bool is_flat = congruent && d->B == 1 && d->Hg == 1;
+    const WgCtx& c = r->cx = wg_ctx(d, temporal, is_flat, wg_knobs());
+    if (is_flat && d->M >= 128 && d->N >= 128 && !c.kn.no_gemm) r->kind = WG_GEMM;
+    else if (wg_thin_shape(d, c)) r->kind = WG_THIN;
+    else if (wg_thin_taps_shape(d, c)) r->kind = WG_THIN_TAPS;
+    else {
+        r->kind = WG_TILED;
+        if (c.taps > WG_WAVES * WG_PAIRS) { sos_set_error("sos_conv2d_wgrad: kernel with %d taps per row not supported", c.taps); return SOS_ENOSPC; }
+        if ((uint64_t)d->Hg * d->Wg * d->g_cs * 2 >= 0xffffff00ull || (uint64_t)d->Hx * d->Wx * d->x_cs * 2 >= 0xffffff00ull) {
+            sos_set_error("sos_conv2d_wgrad: one image of an operand exceeds 4 GB");
+            return SOS_ENOSPC;
+        }
+    }
+    return SOS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Plans of wgrad_kernel / wgrad16_kernel: a PLAN = the workgroup's channel tile (MT m-tiles x NTB n-tiles of 32), its pixel
+// tile (NC residue classes x 2^lth x 2^ltw = 256 pixels), the order of those pixels along the contraction and the number of
+// workgroups per CU.  Plans come from (0) the forced knobs (experiments), else (1) the measured table (round 4: sos_wgrad_tune /
+// sos_wgrad_tune_load, the shipped wgrad_table_gfx950.txt -- every process and every rank then runs the same plans, hence the
+// same summation order), else (2) the calibrated cost model below.  wg_make_plan() is the one place that says whether a plan
+// can run a shape: the table loader, the tuner's candidates, the cost model and the forced knobs all get their plans from it.
+struct WgPlan { int mt, ntb, nc, lth, ltw, kord, occ, db, bufbytes, npixp, pw; double cost; };
+struct WgKey {
+    int v[12];
+    bool operator<(const WgKey& o) const { return memcmp(v, o.v, sizeof(v)) < 0; }
+};
+static std::mutex& wg_mu() { static std::mutex m; return m; }
+static std::map<WgKey, WgPlan>& wg_table() { static std::map<WgKey, WgPlan> t; return t; }      // measured plans
+static std::map<WgKey, WgPlan>& wg_model_cache() { static std::map<WgKey, WgPlan> t; return t; } // the cost model's picks
 static WgKey wg_key(const sos_wgrad_desc* d, const WgCtx& c) {
     return WgKey{{d->Hg, d->Wg, d->kh, d->kw, d->stride, d->dil_h, d->dil_w, d->M, d->N, c.use16 ? 1 : 0, c.temporal ? d->t_taps : 0,
                   c.is_flat ? 1 : 0}};
 }
 
 // Completes a plan (patch pitch, LDS bytes, double buffering) for the given channel / pixel tile and prices it with the cost
-// model; false: the tile is not legal for this shape (dilation classes, coordinate range, LDS).
+// model; false: the plan is not legal for this shape (channel tile beyond the shape or the 32 (tap, n-tile) pairs of a
+// workgroup, no kernel instance, dilation classes, coordinate range, LDS).
 static bool wg_make_plan(const sos_wgrad_desc* d, const WgCtx& c, int mt, int ntb, int lnc, int lth, int kord, int occ, WgPlan* out) {
+    if (mt < 1 || mt > WG_MT_MAX || mt > c.ntiles_m || ntb < 1 || ntb > WG_NTB_MAX || ntb > c.ntiles_n || ntb * c.taps > WG_WAVES * WG_PAIRS ||
+        lnc < 0 || lnc > 6 || lth < 0 || kord < 0 || kord > 1 || occ < 1 || occ > WG_OCC_MAX || !wg_tiled_kernel(c, mt, ntb))
+        return false;
     const size_t lds_max = 160 * 1024;
     const int NC = 1 << lnc, ltw = 8 - lnc - lth;
-    if (ltw < 2 || lth < 0) return false;
+    if (ltw < 2) return false;
     if (NC > 1 && (d->stride > 1 || NC > d->dil_w || d->dil_w % NC)) return false;
     const int TH = 1 << lth, TW = 1 << ltw;
     const int PH = (TH - 1) * d->stride + c.khg, PW = (TW - 1) * d->stride + d->kw;
@@ -1258,7 +1300,7 @@ static bool wg_make_plan(const sos_wgrad_desc* d, const WgCtx& c, int mt, int nt
     // pitches apart; with an even PWl their 64-byte (32-byte) runs land on the same banks (PW = 12: 768 B = 0 mod
     // 256 -- SQ_LDS_BANK_CONFLICT was 59 % of the LDS-active cycles of the 96 -> 96 gradient), with an odd one
     // they tile the 64 banks.  One more (never multiplied) patch column buys that.
-    const int PWl = (kord == 1 && (PW & 1) == 0 && !getenv("SOS_WGRAD_EVEN_PITCH")) ? PW + 1 : PW;
+    const int PWl = (kord == 1 && (PW & 1) == 0 && !c.kn.even_pitch) ? PW + 1 : PW;
     const bool use16 = c.use16;
     const int npixp = use16 ? (NC * PH * PWl + 31) / 32 * 32 : (NC * PH * PWl + 15) / 16 * 16;
     const size_t one = use16 ? ((size_t)256 * 32 * c.m16 + (size_t)npixp * 32 * c.n16 + 1023) / 1024 * 1024
@@ -1300,21 +1342,25 @@ static bool wg_make_plan(const sos_wgrad_desc* d, const WgCtx& c, int mt, int nt
     return true;
 }
 
-// best pixel tile of the cost model for a channel tile (mt, ntb); false: no tile fits LDS
-static bool wg_best_tile(const sos_wgrad_desc* d, const WgCtx& c, int mt, int ntb, int occ, WgPlan* out) {
-    int fnc = -1, fth = -1, ftw = -1, fko = -1;
-    const char* force = getenv("SOS_WGRAD_TILE");  // experiments: "nc,lth,ltw,kord"
-    if (force) sscanf(force, "%d,%d,%d,%d", &fnc, &fth, &ftw, &fko);
-    bool any = false;
+// every legal plan of a channel tile (mt, ntb): the pixel tiles in their fixed enumeration order, priced
+static std::vector<WgPlan> wg_tiles(const sos_wgrad_desc* d, const WgCtx& c, int mt, int ntb, int occ) {
+    std::vector<WgPlan> out;
+    WgPlan pl;
     for (int lnc = 0; lnc <= 6; ++lnc)
         for (int lth = 0; lth + lnc <= 8; ++lth)
-            for (int kord = 0; kord < 2; ++kord) {
-                if (force && fnc > 0 && ((1 << lnc) != fnc || lth != fth || 8 - lnc - lth != ftw)) continue;
-                if (force && fko >= 0 && kord != fko) continue;
-                WgPlan pl;
-                if (!wg_make_plan(d, c, mt, ntb, lnc, lth, kord, occ, &pl)) continue;
-                if (!any || pl.cost < out->cost) { *out = pl; any = true; }
-            }
+            for (int kord = 0; kord < 2; ++kord)
+                if (wg_make_plan(d, c, mt, ntb, lnc, lth, kord, occ, &pl)) out.push_back(pl);
+    return out;
+}
+// the cheapest of them (the first of equals) among those SOS_WGRAD_TILE admits; false: none
+static bool wg_best_tile(const sos_wgrad_desc* d, const WgCtx& c, int mt, int ntb, int occ, WgPlan* out) {
+    const WgKnobs& k = c.kn;
+    bool any = false;
+    for (const WgPlan& pl : wg_tiles(d, c, mt, ntb, occ)) {
+        if (k.fnc > 0 && (pl.nc != k.fnc || pl.lth != k.fth || pl.ltw != k.ftw)) continue;
+        if (k.fko >= 0 && pl.kord != k.fko) continue;
+        if (!any || pl.cost < out->cost) { *out = pl; any = true; }
+    }
     return any;
 }
 
@@ -1325,28 +1371,25 @@ static int wg_simd_max(int pairs) {
     return std::max(std::max(simd[0], simd[1]), std::max(simd[2], simd[3]));
 }
 
-// The cost model's plan.
+// The cost model's plan (with SOS_WGRAD_MT / NTB / OCC / TILE: the forced one).
 static int wg_model_plan(const sos_wgrad_desc* d, const WgCtx& c, WgPlan* out) {
+    const WgKnobs& kn = c.kn;
     int ntb = WG_WAVES * WG_PAIRS / c.taps;         // (tap, n-tile) pairs per workgroup <= 32
     ntb = ntb >= 4 ? 4 : (ntb >= 2 ? 2 : 1);
     if (ntb > c.ntiles_n) ntb = c.ntiles_n >= 4 ? 4 : (c.ntiles_n >= 2 ? 2 : 1);
     int mgroups = (c.ntiles_m + 2) / 3;
     int mt = (c.ntiles_m + mgroups - 1) / mgroups;              // 1..3 m-tiles per workgroup, balanced
-    bool forced_ntb = false;
-    {   // experiments (tools/probe/wgrad_cfg_sweep.py): force the workgroup's channel tile
-        const char* e = getenv("SOS_WGRAD_MT");
-        if (e && atoi(e) >= 1 && atoi(e) <= 3) { mt = std::min(atoi(e), c.ntiles_m); }
-        e = getenv("SOS_WGRAD_NTB");
-        if (e && atoi(e) >= 1 && atoi(e) <= 4 && atoi(e) * c.taps <= WG_WAVES * WG_PAIRS) { ntb = std::min(atoi(e), c.ntiles_n); forced_ntb = true; }
-    }
+    // experiments (tools/probe/wgrad_cfg_sweep.py): force the workgroup's channel tile
+    if (kn.mt) mt = std::min(kn.mt, c.ntiles_m);
+    const bool forced_ntb = kn.ntb && kn.ntb * c.taps <= WG_WAVES * WG_PAIRS;
+    if (forced_ntb) ntb = std::min(kn.ntb, c.ntiles_n);
     // workgroups per CU: one (its own double-buffered DMA pipeline covers the fetch of the next tile) unless a tile is so
     // short that the fetch latency of a tile exceeds its MFMA time -- then several co-resident workgroups cover each other
     // (measured: the 96 -> 8 / 48 -> 4 1x1 heads, two MFMAs per k-step and workgroup: 0.456 -> 0.338 / 0.239 -> 0.185 ms with
     // two workgroups per CU; the thin 5x5 / 1x7 first layers, whose double buffers no longer fit then, get slower)
     // (round 4: only when the M side is the thin one -- 96 -> 8: 0.42 -> 0.32 ms, 48 -> 4: 0.22 -> 0.18 with two; a thin N side with
     // two m-tiles -- the first layers with their taps folded, 14 -> 48 -- is FASTER with one: 0.235 vs 0.285 ms)
-    int occ = c.is_flat && mt == 1 && ntb <= 2 ? 2 : 1;
-    { const char* e = getenv("SOS_WGRAD_OCC"); if (e && atoi(e) >= 1 && atoi(e) <= 4) occ = atoi(e); }
+    const int occ = kn.occ ? kn.occ : (c.is_flat && mt == 1 && ntb <= 2 ? 2 : 1);
     if (c.use16) { if (!wg_best_tile(d, c, mt, ntb, 1, out)) { sos_set_error("sos_conv2d_wgrad: patch does not fit LDS"); return SOS_ENOSPC; } return SOS_OK; }
     // Few-tap kernels (3x3, 7x1; round 4): the (tap, n-tile) pairs of NTB n-tiles go round robin over 8 waves, two waves per
     // SIMD, so NTB decides (a) how much of the last n-group is padding, (b) how evenly the pairs load the four SIMDs, (c) how
@@ -1357,7 +1400,7 @@ static int wg_model_plan(const sos_wgrad_desc* d, const WgCtx& c, WgPlan* out) {
     if (!forced_ntb && c.taps >= 5 && c.taps * 2 <= WG_WAVES * WG_PAIRS) {
         double best = 1e300;
         bool any = false;
-        for (int cn = 1; cn <= 4 && cn <= c.ntiles_n && cn * c.taps <= WG_WAVES * WG_PAIRS; ++cn) {
+        for (int cn = 1; cn <= WG_NTB_MAX; ++cn) {
             WgPlan pl;
             if (!wg_best_tile(d, c, mt, cn, 1, &pl)) continue;
             const int pairs = cn * c.taps, groups = (c.ntiles_n + cn - 1) / cn;
@@ -1378,8 +1421,7 @@ static int wg_model_plan(const sos_wgrad_desc* d, const WgCtx& c, WgPlan* out) {
 
 static int wg_choose_plan(const sos_wgrad_desc* d, const WgCtx& c, WgPlan* out) {
     const WgKey key = wg_key(d, c);
-    const bool forced = getenv("SOS_WGRAD_TILE") || getenv("SOS_WGRAD_MT") || getenv("SOS_WGRAD_NTB") || getenv("SOS_WGRAD_OCC");
-    if (!forced) {
+    if (!c.kn.forced) {
         std::lock_guard<std::mutex> lk(wg_mu());
         auto f = wg_table().find(key);
         if (f != wg_table().end()) { *out = f->second; return SOS_OK; }
@@ -1388,247 +1430,149 @@ static int wg_choose_plan(const sos_wgrad_desc* d, const WgCtx& c, WgPlan* out) 
     }
     const int rc = wg_model_plan(d, c, out);
     if (rc) return rc;
-    if (getenv("SOS_WGRAD_VERBOSE"))
+    if (c.kn.verbose)
         fprintf(stderr, "sos_conv2d_wgrad: %dx%d k%dx%d s%d d%dx%d M%d N%d %s-> MT=%d NTB=%d NC=%d TH=%d TW=%d order=%d dbuf=%d occ=%d lds=%d pitch=%d\n",
                 d->Hg, d->Wg, d->kh, d->kw, d->stride, d->dil_h, d->dil_w, d->M, d->N, c.use16 ? "(16x16x32) " : "", out->mt, out->ntb,
                 out->nc, 1 << out->lth, 1 << out->ltw, out->kord, out->db, out->occ, out->bufbytes, out->pw);
-    if (!forced) {
+    if (!c.kn.forced) {
         std::lock_guard<std::mutex> lk(wg_mu());
         wg_model_cache()[key] = *out;
     }
     return SOS_OK;
 }
 
-static int wg_launch(const sos_wgrad_desc* d, const WgCtx& c, const WgPlan& pl, hipStream_t s, const int what = 3) {
-    WgParams p;
+// A resolved launch: everything wg_run() needs besides the descriptor.  sos_conv2d_wgrad_partial launches the kernel,
+// sos_conv2d_wgrad_reduce folds its `ksplit` planes; each resolves the same descriptor to the same WgLaunch.
+struct WgLaunch {
+    const void* kernel;
+    const char* name;          // for the error message of a failed launch
+    dim3 grid;
+    unsigned threads;
+    size_t lds;
+    union { WgParams tiled; WgGemmParams gemm; WgThinParams thin; WgThinTapParams taps; };    // the kernel's one argument
+    int ksplit;                // partial planes: [ksplit][taps_all][Mp][Np]
+};
+
+static void wg_resolve_tiled(const WgRoute& r, const WgPlan& pl, WgLaunch* L) {
+    const sos_wgrad_desc* d = &r.d;
+    const WgCtx& c = r.cx;
+    WgParams& p = L->tiled;
     p.g = (const bf16_t*)d->g; p.x = (const bf16_t*)d->x; p.partial = d->partial;
     p.B = d->B; p.Hg = d->Hg; p.Wg = d->Wg; p.g_cs = d->g_cs; p.g_off = d->g_off;
     p.Hx = d->Hx; p.Wx = d->Wx; p.x_cs = d->x_cs; p.x_off = d->x_off;
-    p.M = d->M; p.N = d->N; p.Mp = (d->M + 31) / 32 * 32; p.Np = (d->N + 31) / 32 * 32;
+    p.M = d->M; p.N = d->N; p.Mp = wg_pad32(d->M); p.Np = wg_pad32(d->N);
     p.kw = d->kw; p.stride = d->stride; p.dh = d->dil_h; p.dw = d->dil_w;
     p.pad_t = d->pad_top; p.pad_l = d->pad_left; p.pad_mode = d->pad_mode;
     p.tT = c.temporal ? d->t_frames : 0; p.tcin = c.temporal ? d->t_cin : 0; p.tpad = c.temporal ? d->t_pad : 0;
     p.kh = c.khg; p.ntg = c.ntg; p.taps_all = c.taps_all;
-    const int taps = c.taps, taps_all = c.taps_all, mt = pl.mt, ntb = pl.ntb;
-    const bool use16 = c.use16;
-    const int mgroups = (c.ntiles_m + mt - 1) / mt;
     p.NC = pl.nc; p.logTH = pl.lth; p.logTW = pl.ltw; p.dbuf = pl.db; p.kord = pl.kord; p.bufbytes = pl.bufbytes; p.npixp = pl.npixp;
-    {
-        const int TH = 1 << p.logTH, TW = 1 << p.logTW;
-        p.tiles_h = (c.Hc + TH - 1) / TH; p.tiles_w = (c.Wc + TW - 1) / TW; p.ngw = (d->dil_w + p.NC - 1) / p.NC;
-        p.PH = (TH - 1) * d->stride + c.khg; p.PW = pl.pw;        // patch pitch: (TW - 1) stride + kw, + 1 when that keeps it odd
-        p.npix = p.NC * p.PH * p.PW;
-    }
-    const int occ = pl.occ;
-    const size_t lds = (size_t)p.bufbytes * (p.dbuf ? 2 : 1) + (size_t)(256 + p.npixp) * 8;
-    { const char* e = getenv("SOS_WGRAD_DBG"); p.dbg = e ? atoi(e) : 0; }
+    const int TH = 1 << p.logTH, TW = 1 << p.logTW;
+    p.tiles_h = (c.Hc + TH - 1) / TH; p.tiles_w = (c.Wc + TW - 1) / TW; p.ngw = (d->dil_w + p.NC - 1) / p.NC;
+    p.PH = (TH - 1) * d->stride + c.khg; p.PW = pl.pw;        // patch pitch: (TW - 1) stride + kw, + 1 when that keeps it odd
+    p.npix = p.NC * p.PH * p.PW;
+    p.dbg = c.kn.dbg;
     p.nsteps = d->B * d->dil_h * p.ngw * p.tiles_h * p.tiles_w;
+    p.ny = (c.ntiles_m + pl.mt - 1) / pl.mt; p.nz = (c.ntiles_n + pl.ntb - 1) / pl.ntb * p.ntg;
+    // automatic split: one workgroup per CU (pl.occ of them) over (pixel split, m-group, n-group), bounded by the workspace
+    const int cap = wg_max_split(d);
     int ksplit = d->ksplit;
-    if (ksplit <= 0) {
-        const int groups = use16 ? 1 : mgroups * ((c.ntiles_n + ntb - 1) / ntb) * p.ntg;
-        ksplit = occ * WG_NCU / groups;
-        if (ksplit < 1) ksplit = 1;
-        const int cap = wg_max_split(d);
-        if (ksplit > cap) ksplit = cap;
-    }
+    const int groups = c.use16 ? 1 : p.ny * p.nz;        // workgroups per split (the 16x16x32 kernel owns all of dW)
+    if (ksplit <= 0) ksplit = std::min(std::max(pl.occ * WG_NCU / groups, 1), cap);
     if (ksplit > p.nsteps) ksplit = p.nsteps;                            // never an empty split
-    p.ksplit = ksplit;
-    p.steps_per_split = (p.nsteps + ksplit - 1) / ksplit;
-    p.ny = mgroups; p.nz = (c.ntiles_n + ntb - 1) / ntb * p.ntg;
     p.xcdmap = 0;
-    if (!use16 && d->ksplit <= 0 && p.ny * p.nz > 1 && p.ny * p.nz <= 16 && !getenv("SOS_WGRAD_NOXCD")) {
+    if (d->ksplit <= 0 && groups > 1 && groups <= 16 && !c.kn.noxcd) {
         // one workgroup per CU: an XCD (32 CUs) takes floor(32 / groups) splits, all groups of a split on one XCD
-        const int per_xcd = occ * 32 / (p.ny * p.nz);
+        const int per_xcd = pl.occ * 32 / groups;
         int ks8 = 8 * per_xcd;
         if (ks8 > p.nsteps) ks8 = p.nsteps / 8 * 8;
-        const int cap = wg_max_split(d) / 8 * 8;
-        if (ks8 > cap) ks8 = cap;
+        if (ks8 > cap / 8 * 8) ks8 = cap / 8 * 8;
         if (ks8 >= 8 && ks8 * 100 >= ksplit * 93) {        // only if (almost) as many workgroups as one per CU remain
             ksplit = ks8;
-            p.ksplit = ksplit;
-            p.steps_per_split = (p.nsteps + ksplit - 1) / ksplit;
             p.xcdmap = 1;
         }
     }
-    dim3 grid((unsigned)(ksplit * p.ny * p.nz), 1, 1);                       // see the id mapping in wgrad_kernel
-    static sos_device_once attr_once;
-    if (use16) grid = dim3((unsigned)ksplit, 1, 1);
-#define SOS_WG_ATTR(MTV, NTBV) \
-    (void)hipFuncSetAttribute((const void*)wgrad_kernel<MTV, NTBV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#define SOS_WG_CASE(MTV, NTBV) \
-    if (mt == MTV && ntb == NTBV) hipLaunchKernelGGL((wgrad_kernel<MTV, NTBV>), grid, dim3(WG_THREADS), lds, s, p);
-    (void)sos_per_device_once(attr_once, [] {       // every instantiation may use the full 160 KB of LDS
-        SOS_WG_ATTR(1, 1) SOS_WG_ATTR(1, 2) SOS_WG_ATTR(1, 4) SOS_WG_ATTR(2, 1) SOS_WG_ATTR(2, 2) SOS_WG_ATTR(2, 4)
-        SOS_WG_ATTR(3, 1) SOS_WG_ATTR(3, 2) SOS_WG_ATTR(3, 4) SOS_WG_ATTR(1, 3) SOS_WG_ATTR(2, 3) SOS_WG_ATTR(3, 3)
-        (void)hipFuncSetAttribute((const void*)wgrad_kernel<3, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)wgrad_kernel<2, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)wgrad16_kernel<3, 3, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)wgrad16_kernel<3, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return (int)SOS_OK;
-    });
-    if (!(what & 1)) {
-        // reduce only
-    } else if (use16) {
-        if (taps == 25) hipLaunchKernelGGL((wgrad16_kernel<3, 3, 3>), grid, dim3(WG_THREADS), lds, s, p);
-        else hipLaunchKernelGGL((wgrad16_kernel<3, 3, 1>), grid, dim3(WG_THREADS), lds, s, p);
-    } else {
-        const bool bal = taps == 25 && ntb == 1 && mt >= 2 && !getenv("SOS_WGRAD_NOBAL");
-        if (bal && mt == 3) hipLaunchKernelGGL((wgrad_kernel<3, 1, true>), grid, dim3(WG_THREADS), lds, s, p);
-        else if (bal && mt == 2) hipLaunchKernelGGL((wgrad_kernel<2, 1, true>), grid, dim3(WG_THREADS), lds, s, p);
-        else {
-        SOS_WG_CASE(1, 1) SOS_WG_CASE(1, 2) SOS_WG_CASE(1, 4) SOS_WG_CASE(2, 1) SOS_WG_CASE(2, 2) SOS_WG_CASE(2, 4)
-        SOS_WG_CASE(3, 1) SOS_WG_CASE(3, 2) SOS_WG_CASE(3, 4) SOS_WG_CASE(1, 3) SOS_WG_CASE(2, 3) SOS_WG_CASE(3, 3)
+    p.ksplit = ksplit;
+    p.steps_per_split = (p.nsteps + ksplit - 1) / ksplit;
+    L->kernel = wg_tiled_kernel(c, pl.mt, pl.ntb); L->name = "sos_conv2d_wgrad";
+    L->grid = dim3((unsigned)(ksplit * groups), 1, 1);                       // see the id mapping in wgrad_kernel
+    L->threads = WG_THREADS;
+    L->lds = (size_t)p.bufbytes * (p.dbuf ? 2 : 1) + (size_t)(256 + p.npixp) * 8;
+    L->ksplit = ksplit;
+}
+
+// route (+ plan on the tiled route; null: the one wg_choose_plan() gives) -> launch.  Launches nothing; a launch without a kernel
+// instance is an error.
+static int wg_resolve(const WgRoute& r, const WgPlan* plan, WgLaunch* L) {
+    const sos_wgrad_desc* d = &r.d;
+    const WgCtx& c = r.cx;
+    // the GEMM and the streaming kernels: operands from their first channel, K pixels in all, 256 threads
+    auto operands = [&](auto& q, int K) {
+        q.g = (const bf16_t*)d->g + d->g_off; q.x = (const bf16_t*)d->x + d->x_off; q.partial = d->partial;
+        q.K = K; q.g_cs = d->g_cs; q.x_cs = d->x_cs; q.Mp = wg_pad32(d->M); q.Np = wg_pad32(d->N);
+    };
+    const int K = r.kind == WG_TILED ? 0 : d->B * d->Hg * d->Wg;      // (a flat descriptor: Wg)
+    L->threads = 256;
+    if (r.kind == WG_TILED) {
+        WgPlan chosen;
+        const int rc = plan ? (int)SOS_OK : wg_choose_plan(d, c, &chosen);
+        if (rc) return rc;
+        wg_resolve_tiled(r, plan ? *plan : chosen, L);
+    } else if (r.kind == WG_GEMM) {
+        WgGemmParams& q = L->gemm;
+        operands(q, K);
+        q.tiles_n = (q.Np + 127) / 128;
+        q.ntiles = ((q.Mp + 127) / 128) * q.tiles_n;
+        const int cap = wg_split_cap(d);
+        q.ksplit = c.kn.gemm_split && c.kn.gemm_split <= cap ? c.kn.gemm_split : wg_gemm_split(q.ntiles, q.K, (int64_t)q.Mp * q.Np * 4, cap);
+        q.kper = ((q.K + q.ksplit - 1) / q.ksplit + WGG_KT - 1) / WGG_KT * WGG_KT;
+        L->kernel = wg_kernel(WG_KGEMM, 0, 0, 0); L->name = "sos_conv2d_wgrad(gemm)";
+        L->grid = dim3((unsigned)(q.ntiles * q.ksplit)); L->lds = 2 * WGG_BUF; L->ksplit = q.ksplit;
+    } else {        // the streaming kernels: one workgroup per partial plane, its four waves share the plane's pixels
+        const int ksplit = wg_thin_split(d, c, K), kper = ((K + ksplit * 4 - 1) / (ksplit * 4) + 31) / 32 * 32;
+        int subs = c.m16 + c.n16;                       // 16-channel sub-images per stage
+        if (r.kind == WG_THIN) {
+            operands(L->thin, K);
+            L->thin.kper = kper;
+            L->kernel = wg_kernel(WG_KTHIN, c.m16, c.n16, 0); L->name = "sos_conv2d_wgrad(thin)";
+        } else {
+            WgThinTapParams& q = L->taps;
+            operands(q, K);
+            q.H = d->Hg; q.W = d->Wg; q.dil = d->dil_h; q.pad = d->pad_top; q.reflect = d->pad_mode == SOS_PAD_REFLECT; q.kper = kper;
+            L->kernel = wg_kernel(WG_KTAPS, 4, 5, 0); L->name = "sos_conv2d_wgrad(thin taps)";
+            subs = 4 + 5;
         }
+        L->grid = dim3((unsigned)ksplit); L->lds = (size_t)4 * WGT_NBUF * subs * 1024; L->ksplit = ksplit;
     }
-#undef SOS_WG_CASE
-#undef SOS_WG_ATTR
-    int rc = sos_check_launch("sos_conv2d_wgrad");
+    if (!L->kernel) { sos_set_error("sos_conv2d_wgrad: no kernel instance is built for this launch (route %d)", (int)r.kind); return SOS_EINVAL; }
+    return SOS_OK;
+}
+
+// what: 1 = the MFMA kernel (partial sums per pixel split), 2 = the deterministic reduce into dw, 3 = both.
+static int wg_run(const WgRoute& r, const WgLaunch& L, hipStream_t s, const int what) {
+    const sos_wgrad_desc* d = &r.d;
+    int rc = wg_set_attributes();
     if (rc) return rc;
+    if (what & 1) {
+        void* args[] = {(void*)&L.tiled};
+        (void)hipLaunchKernel(L.kernel, L.grid, dim3(L.threads), args, L.lds, s);
+        rc = sos_check_launch(L.name);
+        if (rc) return rc;
+    }
     if (!(what & 2)) return SOS_OK;
-    const long long total = (long long)d->M * d->N * taps_all;
-    long long gb = (total + 63) / 64;
-    if (gb > 8192) gb = 8192;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gb), dim3(256), 0, s, d->partial, ksplit, taps_all, d->M, d->N,
-                       p.Mp, p.Np, d->dw, d->accumulate, d->scale, d->scale_dev);
+    const long long total = (long long)d->M * d->N * r.cx.taps_all;
+    const long long gb = std::min((total + 63) / 64, 8192ll);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gb), dim3(256), 0, s, d->partial, L.ksplit, r.cx.taps_all, d->M, d->N,
+                       wg_pad32(d->M), wg_pad32(d->N), d->dw, d->accumulate, d->scale, d->scale_dev);
     return sos_check_launch("sos_conv2d_wgrad(reduce)");
 }
 
-extern "C" int64_t sos_wgrad_workspace_bytes(const sos_wgrad_desc* d) {
-    if (!d) return -1;
-    const int64_t Mp = (d->M + 31) / 32 * 32, Np = (d->N + 31) / 32 * 32;
-    return (int64_t)(d->ksplit > 0 ? d->ksplit : wg_max_split(d)) * d->kh * d->kw * Mp * Np * 4;
-}
-
-// what: 1 = the MFMA kernel (partial sums per pixel split), 2 = the deterministic reduce into dw, 3 = both (sos_conv2d_wgrad).
-// The two halves recompute the same launch plan from the descriptor, so they may run on different streams (ABI 8).
+// The two halves resolve the same launch from the descriptor, so they may run on different streams (ABI 8).
 static int wgrad_impl(const sos_wgrad_desc* d, sos_stream_t stream, const int what) {
-    if (!d || !d->g || !d->x || !d->partial || !d->dw) { sos_set_error("sos_conv2d_wgrad: null pointer"); return SOS_EINVAL; }
-    if (d->M < 1 || d->N < 1 || d->g_cs % 8 || d->x_cs % 8 || d->g_off % 8 || d->x_off % 8 || d->kh < 1 || d->kw < 1 ||
-        d->stride < 1 || d->dil_h < 1 || d->dil_w < 1 || (d->stride > 1 && (d->dil_h > 1 || d->dil_w > 1)) ||
-        d->B < 1) {
-        sos_set_error("sos_conv2d_wgrad: bad descriptor");
-        return SOS_EINVAL;
-    }
-    const bool temporal = d->t_taps > 1;
-    if (temporal && (d->t_frames < 1 || d->B % d->t_frames || d->t_cin < 128 || d->t_cin % 128 || d->N != d->t_taps * d->t_cin ||
-                     d->t_pad < 0 || d->t_pad >= d->t_taps || d->x_off + d->t_cin > d->x_cs)) {
-        sos_set_error("sos_conv2d_wgrad: bad temporal taps (B=%d frames=%d taps=%d cin=%d N=%d)", d->B, d->t_frames, d->t_taps,
-                      d->t_cin, d->N);
-        return SOS_EINVAL;
-    }
-    // 1x1 kernels (Linear layers, LSTM projections): the pixel arrays of G and X are congruent, so the batch
-    // is one long row -- full 256-pixel tiles instead of one ragged tile per (short) image.
-    sos_wgrad_desc flat = *d;
-    if (!temporal && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_top == 0 && d->pad_left == 0 && d->Hg == d->Hx && d->Wg == d->Wx) {
-        const uint64_t npx = (uint64_t)d->B * d->Hg * d->Wg;
-        if (npx * (uint64_t)d->g_cs * 2 < 0xfff00000ull && npx * (uint64_t)d->x_cs * 2 < 0xfff00000ull) {
-            flat.B = 1; flat.Hg = flat.Hx = 1; flat.Wg = flat.Wx = (int)npx;
-        }
-    }
-    const bool is_flat = !temporal && flat.B == 1 && flat.Hg == 1 && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_top == 0 &&
-                         d->pad_left == 0 && d->Hg == d->Hx && d->Wg == d->Wx;
-    d = &flat;
-    if (is_flat && d->M >= 128 && d->N >= 128 && !getenv("SOS_WGRAD_NO_GEMM")) {
-        WgGemmParams q;
-        q.g = (const bf16_t*)d->g + d->g_off; q.x = (const bf16_t*)d->x + d->x_off; q.partial = d->partial;
-        q.K = d->Wg; q.g_cs = d->g_cs; q.x_cs = d->x_cs;
-        q.Mp = (d->M + 31) / 32 * 32; q.Np = (d->N + 31) / 32 * 32;
-        q.tiles_n = (q.Np + 127) / 128;
-        q.ntiles = ((q.Mp + 127) / 128) * q.tiles_n;
-        const int cap = d->ksplit > 0 ? d->ksplit : wg_max_split(d);
-        q.ksplit = wg_gemm_split(q.ntiles, q.K, (int64_t)q.Mp * q.Np * 4, cap);
-        { const char* e = getenv("SOS_WGG_SPLIT"); if (e && atoi(e) >= 1 && atoi(e) <= cap) q.ksplit = atoi(e); }
-        q.kper = ((q.K + q.ksplit - 1) / q.ksplit + WGG_KT - 1) / WGG_KT * WGG_KT;
-        hipStream_t s = (hipStream_t)stream;
-        static sos_device_once gemm_once;
-        (void)sos_per_device_once(gemm_once, [] {
-            (void)hipFuncSetAttribute((const void*)wgrad_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WGG_BUF);
-            return (int)SOS_OK;
-        });
-        if (what & 1) {
-            hipLaunchKernelGGL(wgrad_gemm_kernel, dim3((unsigned)(q.ntiles * q.ksplit)), dim3(256), 2 * WGG_BUF, s, q);
-            int rc = sos_check_launch("sos_conv2d_wgrad(gemm)");
-            if (rc) return rc;
-        }
-        if (!(what & 2)) return SOS_OK;
-        const long long total = (long long)d->M * d->N;
-        long long gb = (total + 63) / 64;
-        if (gb > 8192) gb = 8192;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gb), dim3(256), 0, s, d->partial, q.ksplit, 1, d->M, d->N,
-                           q.Mp, q.Np, d->dw, d->accumulate, d->scale, d->scale_dev);
-        return sos_check_launch("sos_conv2d_wgrad(reduce)");
-    }
-    int m16 = 0, n16 = 0;
-    if (wg_thin_shape(d, is_flat, &m16, &n16)) {
-        WgThinParams q;
-        q.g = (const bf16_t*)d->g + d->g_off; q.x = (const bf16_t*)d->x + d->x_off; q.partial = d->partial;
-        q.K = d->Wg; q.g_cs = d->g_cs; q.x_cs = d->x_cs;
-        q.Mp = (d->M + 31) / 32 * 32; q.Np = (d->N + 31) / 32 * 32;
-        const int ksplit = wg_thin_split(d, m16 + n16);
-        q.kper = ((q.K + ksplit * 4 - 1) / (ksplit * 4) + 31) / 32 * 32;
-        const size_t lds = (size_t)4 * WGT_NBUF * (m16 + n16) * 1024;
-        hipStream_t s = (hipStream_t)stream;
-        static sos_device_once thin_once;
-#define SOS_WGT_ALL(F) F(1, 1) F(2, 1) F(3, 1) F(4, 1) F(6, 1) F(1, 2) F(1, 3) F(1, 4) F(1, 6)
-#define SOS_WGT_ATTR(A, B) (void)hipFuncSetAttribute((const void*)wgrad_thin_kernel<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#define SOS_WGT_CASE(A, B) if (m16 == A && n16 == B) hipLaunchKernelGGL((wgrad_thin_kernel<A, B>), dim3((unsigned)ksplit), dim3(256), lds, s, q);
-        (void)sos_per_device_once(thin_once, [] { SOS_WGT_ALL(SOS_WGT_ATTR) return (int)SOS_OK; });
-        if (what & 1) {
-            SOS_WGT_ALL(SOS_WGT_CASE)
-            int rc = sos_check_launch("sos_conv2d_wgrad(thin)");
-            if (rc) return rc;
-        }
-#undef SOS_WGT_CASE
-#undef SOS_WGT_ATTR
-#undef SOS_WGT_ALL
-        if (!(what & 2)) return SOS_OK;
-        const long long total = (long long)d->M * d->N;
-        long long gb = (total + 63) / 64;
-        if (gb > 8192) gb = 8192;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gb), dim3(256), 0, s, d->partial, ksplit, 1, d->M, d->N,
-                           q.Mp, q.Np, d->dw, d->accumulate, d->scale, d->scale_dev);
-        return sos_check_launch("sos_conv2d_wgrad(reduce)");
-    }
-    if (wg_thin_taps_shape(d, temporal)) {
-        WgThinTapParams q;
-        q.g = (const bf16_t*)d->g + d->g_off; q.x = (const bf16_t*)d->x + d->x_off; q.partial = d->partial;
-        q.K = d->B * d->Hg * d->Wg; q.H = d->Hg; q.W = d->Wg; q.g_cs = d->g_cs; q.x_cs = d->x_cs;
-        q.Mp = (d->M + 31) / 32 * 32; q.Np = (d->N + 31) / 32 * 32;
-        q.dil = d->dil_h; q.pad = d->pad_top; q.reflect = d->pad_mode == SOS_PAD_REFLECT;
-        sos_wgrad_desc one = *d;
-        one.Wg = q.K;                                   // (wg_thin_split looks at the pixel count only)
-        const int ksplit = wg_thin_split(&one, 4 + 5);
-        q.kper = ((q.K + ksplit * 4 - 1) / (ksplit * 4) + 31) / 32 * 32;
-        const size_t lds = (size_t)4 * WGT_NBUF * (4 + 5) * 1024;
-        hipStream_t s = (hipStream_t)stream;
-        static sos_device_once taps_once;
-        (void)sos_per_device_once(taps_once, [] {
-            (void)hipFuncSetAttribute((const void*)wgrad_thin_taps_kernel<4, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            return (int)SOS_OK;
-        });
-        if (what & 1) {
-            hipLaunchKernelGGL((wgrad_thin_taps_kernel<4, 5>), dim3((unsigned)ksplit), dim3(256), lds, s, q);
-            int rc = sos_check_launch("sos_conv2d_wgrad(thin taps)");
-            if (rc) return rc;
-        }
-        if (!(what & 2)) return SOS_OK;
-        const long long total = (long long)d->M * d->N * d->kh;
-        long long gb = (total + 63) / 64;
-        if (gb > 8192) gb = 8192;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gb), dim3(256), 0, s, d->partial, ksplit, d->kh, d->M, d->N,
-                           q.Mp, q.Np, d->dw, d->accumulate, d->scale, d->scale_dev);
-        return sos_check_launch("sos_conv2d_wgrad(reduce)");
-    }
-    const WgCtx cx = wg_ctx(d, temporal, is_flat);
-    if (cx.taps > WG_WAVES * WG_PAIRS) { sos_set_error("sos_conv2d_wgrad: kernel with %d taps per row not supported", cx.taps); return SOS_ENOSPC; }
-    if ((uint64_t)d->Hg * d->Wg * d->g_cs * 2 >= 0xffffff00ull || (uint64_t)d->Hx * d->Wx * d->x_cs * 2 >= 0xffffff00ull) {
-        sos_set_error("sos_conv2d_wgrad: one image of an operand exceeds 4 GB");
-        return SOS_ENOSPC;
-    }
-    WgPlan plan;
-    int rc = wg_choose_plan(d, cx, &plan);
-    if (rc) return rc;
-    return wg_launch(d, cx, plan, (hipStream_t)stream, what);
+    WgRoute r;
+    WgLaunch L;
+    int rc = wg_route(d, "sos_conv2d_wgrad", &r);
+    if (!rc) rc = wg_resolve(r, nullptr, &L);
+    return rc ? rc : wg_run(r, L, (hipStream_t)stream, what);
 }
 extern "C" int sos_conv2d_wgrad(const sos_wgrad_desc* d, sos_stream_t stream) { return wgrad_impl(d, stream, 3); }
 extern "C" int sos_conv2d_wgrad_partial(const sos_wgrad_desc* d, sos_stream_t stream) { return wgrad_impl(d, stream, 1); }
@@ -1638,47 +1582,33 @@ extern "C" int sos_conv2d_wgrad_reduce(const sos_wgrad_desc* d, sos_stream_t str
 // per CU) with the cost model's six cheapest pixel tiles each, in two stages like sos_conv2d_tune (all candidates over `iters`
 // launches; the five fastest and the cost model's pick again over 8x the launches, alternating twice; the model's pick is kept
 // unless the winner beats it by more than 2 %), and remembers the winner for later sos_conv2d_wgrad calls of that shape.
+// A descriptor sos_conv2d_wgrad would refuse is refused here with the same code; the three routes without a plan return SOS_OK
+// with *best_ms = -1.
 // Synchronises; overwrites d->dw and d->partial (pass accumulate = 0 and scratch buffers).  Call outside timed regions / captures.
-extern "C" int sos_wgrad_tune(const sos_wgrad_desc* d, int iters, float* best_ms, sos_stream_t stream) {
-    if (!d || !d->g || !d->x || !d->partial || !d->dw) { sos_set_error("sos_wgrad_tune: null pointer"); return SOS_EINVAL; }
-    if (d->accumulate) { sos_set_error("sos_wgrad_tune: needs accumulate = 0 (the launches would pile up in dw)"); return SOS_EINVAL; }
-    const bool temporal = d->t_taps > 1;
-    sos_wgrad_desc flat = *d;
-    if (!temporal && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_top == 0 && d->pad_left == 0 && d->Hg == d->Hx && d->Wg == d->Wx) {
-        const uint64_t npx = (uint64_t)d->B * d->Hg * d->Wg;
-        if (npx * (uint64_t)d->g_cs * 2 < 0xfff00000ull && npx * (uint64_t)d->x_cs * 2 < 0xfff00000ull) {
-            flat.B = 1; flat.Hg = flat.Hx = 1; flat.Wg = flat.Wx = (int)npx;
-        }
-    }
-    const bool is_flat = !temporal && flat.B == 1 && flat.Hg == 1 && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_top == 0 &&
-                         d->pad_left == 0 && d->Hg == d->Hx && d->Wg == d->Wx;
-    d = &flat;
+extern "C" int sos_wgrad_tune(const sos_wgrad_desc* desc, int iters, float* best_ms, sos_stream_t stream) {
+    WgRoute r;
+    int rc = wg_route(desc, "sos_wgrad_tune", &r);
+    if (rc) return rc;
+    if (desc->accumulate) { sos_set_error("sos_wgrad_tune: needs accumulate = 0 (the launches would pile up in dw)"); return SOS_EINVAL; }
     if (best_ms) *best_ms = -1.f;
-    if (is_flat && d->M >= 128 && d->N >= 128 && !getenv("SOS_WGRAD_NO_GEMM")) return SOS_OK;     // the GEMM path has no plan
-    { int a, b; if (wg_thin_shape(d, is_flat, &a, &b) || wg_thin_taps_shape(d, temporal)) return SOS_OK; }   // nor have the streaming paths
-    const WgCtx cx = wg_ctx(d, temporal, is_flat);
-    if (cx.taps > WG_WAVES * WG_PAIRS) return SOS_OK;
+    if (r.kind != WG_TILED) return SOS_OK;             // the GEMM and the streaming routes have no plan
+    const sos_wgrad_desc* d = &r.d;
+    const WgCtx& cx = r.cx;
     const WgKey key = wg_key(d, cx);
     {
         std::lock_guard<std::mutex> lk(wg_mu());
         if (wg_table().count(key)) return SOS_OK;
     }
     WgPlan model;
-    int rc = wg_model_plan(d, cx, &model);
+    rc = wg_model_plan(d, cx, &model);
     if (rc) return rc;
     std::vector<WgPlan> cands;
     cands.push_back(model);
-    const int mt_hi = cx.use16 ? 1 : std::min(3, cx.ntiles_m), ntb_hi = cx.use16 ? 1 : std::min(4, cx.ntiles_n);
-    for (int mt = 1; mt <= mt_hi; ++mt)
-        for (int ntb = 1; ntb <= ntb_hi && ntb * cx.taps <= WG_WAVES * WG_PAIRS; ++ntb)
+    // (the 16x16x32 kernel owns all of dW: one channel tile, the model's, and one workgroup per CU; twelve pixel tiles)
+    for (int mt = 1; mt <= (cx.use16 ? 1 : WG_MT_MAX); ++mt)
+        for (int ntb = 1; ntb <= (cx.use16 ? 1 : WG_NTB_MAX); ++ntb)
             for (int occ = 1; occ <= (cx.use16 ? 1 : 2); ++occ) {
-                std::vector<WgPlan> tiles;
-                for (int lnc = 0; lnc <= 6; ++lnc)
-                    for (int lth = 0; lth + lnc <= 8; ++lth)
-                        for (int kord = 0; kord < 2; ++kord) {
-                            WgPlan pl;
-                            if (wg_make_plan(d, cx, cx.use16 ? model.mt : mt, cx.use16 ? model.ntb : ntb, lnc, lth, kord, occ, &pl)) tiles.push_back(pl);
-                        }
+                std::vector<WgPlan> tiles = wg_tiles(d, cx, cx.use16 ? model.mt : mt, cx.use16 ? model.ntb : ntb, occ);
                 std::sort(tiles.begin(), tiles.end(), [](const WgPlan& a, const WgPlan& b) { return a.cost < b.cost; });
                 for (size_t t = 0; t < tiles.size() && t < (cx.use16 ? 12u : 6u); ++t) cands.push_back(tiles[t]);
             }
@@ -1687,12 +1617,14 @@ extern "C" int sos_wgrad_tune(const sos_wgrad_desc* d, int iters, float* best_ms
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { sos_set_error("sos_wgrad_tune: hipEventCreate failed"); return SOS_ELAUNCH; }
     auto time_plan = [&](const WgPlan& pl, const int reps, float* ms_out) {
-        int r = wg_launch(d, cx, pl, s);                         // warm-up
-        if (r) return r;
+        WgLaunch L;
+        int q = wg_resolve(r, &pl, &L);
+        if (!q) q = wg_run(r, L, s, 3);                          // warm-up
+        if (q) return q;
         (void)hipEventRecord(e0, s);
-        for (int k = 0; k < reps && !r; ++k) r = wg_launch(d, cx, pl, s);
+        for (int k = 0; k < reps && !q; ++k) q = wg_run(r, L, s, 3);
         (void)hipEventRecord(e1, s);
-        if (r || hipEventSynchronize(e1) != hipSuccess) return r ? r : (int)SOS_ELAUNCH;
+        if (q || hipEventSynchronize(e1) != hipSuccess) return q ? q : (int)SOS_ELAUNCH;
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
         *ms_out = ms / reps;
@@ -1723,7 +1655,7 @@ extern "C" int sos_wgrad_tune(const sos_wgrad_desc* d, int iters, float* best_ms
             for (size_t t = 0; t < fin.size(); ++t) { if (acc[t] < acc[bt]) bt = t; if (fin[t] == 0) t0 = t; }
             if (acc[bt] > 0.98f * acc[t0]) bt = t0;
             besti = fin[bt]; best = acc[bt];
-            if (getenv("SOS_CONV_TUNE_VERBOSE")) {
+            if (cx.kn.tune_verbose) {
                 const WgPlan& w = cands[besti];
                 fprintf(stderr, "wgrad tune %dx%d k%dx%d s%d d%dx%d M%d N%d B%d: %zu candidates, pick MT=%d NTB=%d NC=%d TH=%d TW=%d order=%d occ=%d dbuf=%d %.4f ms (model's MT=%d NTB=%d NC=%d TH=%d TW=%d order=%d occ=%d: %.4f ms)\n",
                         d->Hg, d->Wg, d->kh, d->kw, d->stride, d->dil_h, d->dil_w, d->M, d->N, d->B, cands.size(), w.mt, w.ntb, w.nc, 1 << w.lth,
@@ -1779,6 +1711,7 @@ extern "C" int sos_wgrad_tune_load(const char* path) {
         sos_set_error("sos_wgrad_tune_load: %s was written by another build (format %d)", path, fmt);
         return SOS_EINVAL;
     }
+    const WgKnobs kn = wg_knobs();
     int n = 0;
     for (;;) {
         WgKey k;
@@ -1791,13 +1724,9 @@ extern "C" int sos_wgrad_tune_load(const char* path) {
         d.Hg = k.v[0]; d.Wg = k.v[1]; d.kh = k.v[2]; d.kw = k.v[3]; d.stride = k.v[4]; d.dil_h = k.v[5]; d.dil_w = k.v[6];
         d.M = k.v[7]; d.N = k.v[8]; d.t_taps = k.v[10];
         if (d.Hg < 1 || d.Wg < 1 || d.kh < 1 || d.kw < 1 || d.stride < 1 || d.dil_h < 1 || d.dil_w < 1 || d.M < 1 || d.N < 1) continue;
-        const WgCtx cx = wg_ctx(&d, k.v[10] > 1, k.v[11] != 0);
-        if ((cx.use16 ? 1 : 0) != k.v[9] || cx.taps > WG_WAVES * WG_PAIRS) continue;
-        if (mt < 1 || mt > 3 || mt > cx.ntiles_m || ntb < 1 || ntb > 4 || ntb > cx.ntiles_n || ntb * cx.taps > WG_WAVES * WG_PAIRS ||
-            lnc < 0 || lnc > 6 || lth < 0 || kord < 0 || kord > 1 || occ < 1 || occ > 2)
-            continue;
+        const WgCtx cx = wg_ctx(&d, k.v[10] > 1, k.v[11] != 0, kn);
         WgPlan pl;
-        if (!wg_make_plan(&d, cx, mt, ntb, lnc, lth, kord, occ, &pl)) continue;
+        if ((cx.use16 ? 1 : 0) != k.v[9] || !wg_make_plan(&d, cx, mt, ntb, lnc, lth, kord, occ, &pl)) continue;
         std::lock_guard<std::mutex> lk(wg_mu());
         wg_table()[k] = pl;
         ++n;

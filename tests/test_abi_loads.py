@@ -102,6 +102,70 @@ def test_wgrad_table_load_rejects_foreign_and_illegal_entries(tmp_path):
     assert h.sos_wgrad_tune_load(engine.SHIPPED_WGRAD_TABLE.encode()) == len(lines)
 
 
+def test_wgrad_table_load_asks_the_plan_legality_function_for_every_bound(tmp_path):
+    """sos_wgrad_tune_load has no bounds of its own: an entry loads if and only if the one legality function (wg_make_plan) offers
+    that plan, so it admits what SOS_WGRAD_OCC admits -- up to four workgroups per CU where the buffers fit a quarter of the
+    LDS -- and nothing beyond."""
+    from sos_amd import _lib
+    h = _lib.lib()
+    flat = "1 2900000 1 1 1 1 1 24 96 0 0 1"        # a flattened 1x1 gradient, 24 x 96 channels: one m-tile, up to three n-tiles
+    t = tmp_path / "occ.txt"
+    t.write_text("sos_wgrad_tune 1 nkey 12\n"
+                 f"{flat} 1 1 0 0 0 3\n"             # three workgroups per CU: 16 KB + 16 KB + tables fit a third of the LDS
+                 f"{flat} 1 1 0 0 0 5\n"             # five: more than any caller can ask for
+                 f"{flat} 1 1 0 0 0 0\n"             # none
+                 f"{flat} 1 4 0 0 0 1\n"             # four n-tiles of a 96-channel side
+                 f"{flat} 2 1 0 0 0 1\n"             # two m-tiles of a 24-channel side
+                 f"{flat} 1 1 0 0 2 1\n"             # a third pixel order
+                 f"{flat} 1 1 7 0 0 1\n"             # 128 residue classes
+                 f"{flat} 1 1 0 -1 0 1\n")           # half a row
+    assert h.sos_wgrad_tune_load(str(t).encode()) == 1
+
+
+def _wgrad_tune_desc():
+    """A valid 3x3 descriptor over dummy (never dereferenced) pointers."""
+    import ctypes as C
+    from sos_amd import _lib as L
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p).value
+    d = L.WgradDesc()
+    d.g, d.x, d.partial, d.dw = p, p, p, p
+    d.B, d.Hg, d.Wg, d.g_cs, d.Hx, d.Wx, d.x_cs = 2, 20, 20, 64, 20, 20, 96
+    d.M, d.N, d.kh, d.kw, d.stride, d.dil_h, d.dil_w = 64, 96, 3, 3, 1, 1, 1
+    d.pad_top, d.pad_left, d.scale = 1, 1, 1.0
+    return d, buf
+
+
+@pytest.mark.parametrize("field,value,message", [
+    ("kw", 0, "bad descriptor"), ("M", 0, "bad descriptor"), ("stride+dil", 2, "bad descriptor"),
+    ("temporal", 3, "bad temporal taps"), ("dw", None, "null pointer"), ("kw", 33, "taps per row not supported")],
+    ids=["kw0", "M0", "stride2-dil2", "temporal", "null-dw", "33-taps-per-row"])
+def test_wgrad_tune_validates_like_the_launch(field, value, message):
+    """sos_wgrad_tune routes a descriptor exactly as sos_conv2d_wgrad does, so what the launch refuses the tuner refuses with the
+    same code and message -- before any plan arithmetic (kw = 0 and M = 0 used to reach integer divisions by zero) and without
+    touching the device (host only: the pointers are dummies, no GPU is needed)."""
+    import ctypes as C
+    from sos_amd import _lib as L
+    h = L.lib()
+    d, keep = _wgrad_tune_desc()
+    if field == "stride+dil":
+        d.stride, d.dil_h = value, value
+    elif field == "temporal":
+        d.t_taps, d.t_frames, d.t_cin = value, 2, 128          # N = 96 is not 3 x 128
+    else:
+        setattr(d, field, value)
+    best = C.c_float(7.0)
+    rc_tune = h.sos_wgrad_tune(C.byref(d), 1, C.byref(best), None)
+    msg_tune = h.sos_last_error().decode()
+    rc_launch = h.sos_conv2d_wgrad(C.byref(d), None)
+    msg_launch = h.sos_last_error().decode()
+    assert rc_tune == rc_launch and rc_tune < 0, (rc_tune, rc_launch)
+    assert rc_tune == (-28 if field == "kw" and value == 33 else -22)          # SOS_ENOSPC / SOS_EINVAL
+    assert message in msg_tune and message in msg_launch, (msg_tune, msg_launch)
+    assert msg_tune.startswith("sos_wgrad_tune:" if field == "dw" else "sos_conv2d_wgrad:")
+    assert best.value == 7.0                                    # refused: nothing was measured, nothing written
+
+
 def test_state_dict_keys_match_reference_layout():
     from sos_amd.detector import networks as dnet
     from sos_amd.denoiser import networks as jnet
