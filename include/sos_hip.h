@@ -486,6 +486,29 @@ int sos_metric_wss(const float* ref, const float* deg, int64_t n, int winlength,
                    const double* window, int n_fft, const float* crit_filter, double eps, float* out, sos_stream_t stream);
 int sos_metric_l1(const float* output, int64_t n_out, const float* target, int64_t n_t, double* result, sos_stream_t stream);
 
+/* ---- 8f-4  the measures above for a ragged batch of (clean, noisy) pairs in one launch sequence (csrc/metrics_batch.hip;
+ * sos_amd.metrics.evaluate_metrics_batch): no allocation, no host synchronisation, and every value of a clip depends on that
+ * clip's samples only.  clean, noisy, offsets, lengths, lengths_host: as sos_stoi_batch (clip b is clean[offsets[b] ..
+ * offsets[b] + lengths[b]); both buffers hold at least sum(lengths_host) samples).  winlength / skip / window as above,
+ * n_fft a power of two >= 2 winlength, P the LPC order of LLR (<= 16), crit_filter f32 [25][n_fft/2], eps the floor of the
+ * WSS band energies.  F_b = (long long)((double)n_b / skip - (double)winlength / skip), clamped at 0: the reference's frame
+ * count in f64, which is NOT (n_b - winlength) / skip in integers (22050 Hz, n = 21122: 123 against 124).
+ * sos_metric_batch_workspace_bytes: workspace size for these lengths (worst case: no sample removed), -1 on bad args.
+ * sos_metric_batch: `out` is one packed buffer of 64 nclips + 40 Ftot bytes, Ftot = sum of F_b over lengths_host, frame-indexed
+ * arrays in clip order (clip b at the sum of F_0 .. F_b-1):
+ *   f64 [nclips][8]  {sum c^2, sum (c-n)^2, max |c|, sum |n-c|, kept samples k, kept frames, frames, status}
+ *   f64 [Ftot][2]    frame energies {sum (w c)^2, sum (w c - w n)^2} of the full signals
+ *   f64 [Ftot][2]    the same of the signals without the samples |c| < float(max |c|) * 0.03f; clip b's first
+ *                    "kept frames" rows (the frame count of k, computed on the device) are written
+ *   f32 [Ftot]       LLR per frame        f32 [Ftot]  WSS per frame (the values of sos_metric_llr / sos_metric_wss, bit for bit)
+ * status = -1 (and zero frames): device lengths or offsets that overrun what lengths_host sized; the clip is not scored.
+ * SOS_EINVAL with a message when a frame's LDS, (2 winlength + 3 n_fft) * 4 bytes, exceeds 60 KB. */
+int64_t sos_metric_batch_workspace_bytes(const int64_t* lengths_host, int nclips, int winlength, int skip, int n_fft);
+int sos_metric_batch(const float* clean, const float* noisy, const int64_t* offsets, const int64_t* lengths,
+                     const int64_t* lengths_host, int nclips, int winlength, int skip, int n_fft, int P, const double* window,
+                     const float* crit_filter, double eps, void* workspace, int64_t workspace_bytes, void* out, int64_t out_bytes,
+                     sos_stream_t stream);
+
 /* ---- 8f-4  STOI / extended STOI (Taal et al. 2011; Jensen & Taal 2016) of a ragged batch, pystoi's
  * stoi(x, y, fs_sig, extended) contract (float64 restatement: tests/stoi_reference.py; csrc/stoi.hip).
  * x, y: f32 clean / processed clips concatenated; clip b is x[offsets[b] .. offsets[b] + lengths[b]) (int64 device tables;

@@ -131,6 +131,8 @@ SIGNATURES = {
     "sos_metric_llr": [_P, _P, _L, _I, _I, _L, _P, _I, _P, _P],
     "sos_metric_wss": [_P, _P, _L, _I, _I, _L, _P, _I, _P, _D, _P, _P],
     "sos_metric_l1": [_P, _L, _P, _L, _P, _P],
+    "sos_metric_batch_workspace_bytes": [_P, _I, _I, _I, _I],
+    "sos_metric_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _D, _P, _L, _P, _L, _P],
     "sos_stoi_workspace_bytes": [_P, _I, _I, _I],
     "sos_stoi_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _L, _P, _P],
     "sos_time_unstack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
@@ -152,7 +154,7 @@ def _load(path, want_dtype):
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in ("sos_wgrad_workspace_bytes", "sos_lstm_pack_bytes", "sos_conv2d_tile_count",
                                              "sos_stft_matrix_bytes", "sos_istft_matrix_bytes",
-                                             "sos_stoi_workspace_bytes") else C.c_int
+                                             "sos_stoi_workspace_bytes", "sos_metric_batch_workspace_bytes") else C.c_int
     if h.sos_abi_version() != EXPECTED_ABI:
         raise ImportError(f"{path} exports ABI version {h.sos_abi_version()}, this binding was written for {EXPECTED_ABI} "
                           "(the argument lists differ: rebuild the library, or drop the SOS_HIP_LIB / SOS_HIP_LIB_F16 override)")

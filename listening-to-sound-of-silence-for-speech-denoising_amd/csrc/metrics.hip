@@ -4,22 +4,7 @@
 // energies, LPC log-likelihood ratios, weighted spectral slope distances); the few-thousand-element finalisation
 // (log10 / clamp / mean / trimmed mean / composite formulas) is host code in sos_amd/metrics.py.
 // Frames: start = f * skip, `winlength` samples, window w[i] = 0.5 (1 - cos(2 pi (i+1) / (winlength+1))).
-#include "sos_common.h"
-
-#define MT 256
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = MT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
+#include "metrics_frame.h"           // MT, block_sum and the per-frame arithmetic shared with metrics_batch.hip
 
 // out[0] = sum ref^2, out[1] = sum (ref - deg)^2, out[2] = max |ref|   (single workgroup: evaluation sizes)
 __global__ __launch_bounds__(MT) void metric_totals_kernel(const float* __restrict__ ref, const float* __restrict__ deg,
@@ -47,12 +32,8 @@ __global__ __launch_bounds__(MT) void metric_frame_energy_kernel(const float* __
                                                                   double* __restrict__ out) {
     __shared__ double red[MT];
     const long long start = (long long)blockIdx.x * skip;
-    double a = 0, b = 0;
-    for (int i = threadIdx.x; i < winlength; i += MT) {
-        const double c = (double)ref[start + i] * window[i], p = (double)deg[start + i] * window[i];
-        a += c * c; b += (c - p) * (c - p);
-    }
-    const double sa = block_sum(a, red), sb = block_sum(b, red);
+    double sa, sb;
+    metric_frame_energy(ref + start, deg + start, winlength, window, red, sa, sb);
     if (threadIdx.x == 0) { out[2 * blockIdx.x] = sa; out[2 * blockIdx.x + 1] = sb; }
 }
 
@@ -83,9 +64,7 @@ __global__ __launch_bounds__(MT) void metric_compact_kernel(const float* __restr
     if (threadIdx.x == 0) *count = base;
 }
 
-// LLR of one frame per workgroup: autocorrelation lags 0..P of both windowed frames (f64), Levinson-Durbin (lane 0),
-// then -- like the reference, which casts R and the LPC vectors to float32 first -- the two quadratic forms in f32.
-#define LLR_MAXP 16
+// LLR of one frame per workgroup (metric_frame_llr)
 __global__ __launch_bounds__(MT) void metric_llr_kernel(const float* __restrict__ ref, const float* __restrict__ deg, int winlength,
                                                          int skip, const double* __restrict__ window, int P,
                                                          float* __restrict__ out) {
@@ -93,53 +72,10 @@ __global__ __launch_bounds__(MT) void metric_llr_kernel(const float* __restrict_
     __shared__ double red[MT];
     __shared__ double R[2][LLR_MAXP + 1];
     const long long start = (long long)blockIdx.x * skip;
-    for (int i = threadIdx.x; i < winlength; i += MT) {
-        fr[i] = (double)ref[start + i] * window[i];
-        fr[winlength + i] = (double)deg[start + i] * window[i];
-    }
-    __syncthreads();
-    for (int s = 0; s < 2; ++s)
-        for (int k = 0; k <= P; ++k) {
-            double a = 0;
-            for (int i = threadIdx.x; i < winlength - k; i += MT) a += fr[s * winlength + i] * fr[s * winlength + i + k];
-            const double v = block_sum(a, red);
-            if (threadIdx.x == 0) R[s][k] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float A[2][LLR_MAXP + 1];
-        for (int s = 0; s < 2; ++s) {
-            double a[LLR_MAXP], ap[LLR_MAXP], E = R[s][0];
-            for (int i = 0; i < P; ++i) a[i] = 1.0;
-            for (int i = 0; i < P; ++i) {
-                double sum = 0;
-                for (int j = 0; j < i; ++j) { ap[j] = a[j]; sum += a[j] * R[s][i - j]; }
-                const double rc = (R[s][i + 1] - sum) / E;
-                a[i] = rc;
-                for (int j = 0; j < i; ++j) a[j] = ap[j] - rc * ap[i - 1 - j];
-                E = (1.0 - rc * rc) * E;
-            }
-            A[s][0] = 1.f;
-            for (int i = 0; i < P; ++i) A[s][i + 1] = (float)(-a[i]);
-        }
-        float Rc[LLR_MAXP + 1];
-        for (int k = 0; k <= P; ++k) Rc[k] = (float)R[0][k];
-        float num = 0.f, den = 0.f;
-        for (int i = 0; i <= P; ++i) {                   // row vector . toeplitz(Rc), then . column vector
-            float tn = 0.f, td = 0.f;
-            for (int j = 0; j <= P; ++j) {
-                const float r = Rc[i > j ? i - j : j - i];
-                tn += A[1][j] * r; td += A[0][j] * r;
-            }
-            num += tn * A[1][i]; den += td * A[0][i];
-        }
-        out[blockIdx.x] = logf(num / den);
-    }
+    metric_frame_llr(ref + start, deg + start, winlength, window, P, fr, red, R, out + blockIdx.x);
 }
 
-// WSS of one frame per workgroup: |DFT|^2 of both windowed frames on bins 0..n_fft/2-1 (direct DFT, twiddles in LDS),
-// 25 critical-band energies -> dB -> slopes -> weighted distance (sequential part on lane 0).
-#define WSS_NCRIT 25
+// WSS of one frame per workgroup (metric_frame_wss)
 __global__ __launch_bounds__(MT) void metric_wss_kernel(const float* __restrict__ ref, const float* __restrict__ deg, int winlength,
                                                          int skip, const double* __restrict__ window, int n_fft,
                                                          const float* __restrict__ crit, double eps, float* __restrict__ out) {
@@ -151,68 +87,9 @@ __global__ __launch_bounds__(MT) void metric_wss_kernel(const float* __restrict_
     float* sp = ts + n_fft;
     __shared__ double red[MT];
     __shared__ double en[2][WSS_NCRIT];
-    const int half = n_fft / 2;
     const long long start = (long long)blockIdx.x * skip;
-    for (int i = threadIdx.x; i < winlength; i += MT) {
-        fc[i] = (float)((double)ref[start + i] * window[i]);
-        fp[i] = (float)((double)deg[start + i] * window[i]);
-    }
-    for (int i = threadIdx.x; i < n_fft; i += MT) {
-        double s, c;
-        sincos(-2.0 * 3.14159265358979323846 * (double)i / (double)n_fft, &s, &c);
-        tc[i] = (float)c; ts[i] = (float)s;
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < half; k += MT) {
-        float cr = 0.f, ci = 0.f, pr = 0.f, pi = 0.f;
-        int ph = 0;
-        for (int i = 0; i < winlength; ++i) {
-            const float c = tc[ph], s = ts[ph];
-            cr = fmaf(fc[i], c, cr); ci = fmaf(fc[i], s, ci);
-            pr = fmaf(fp[i], c, pr); pi = fmaf(fp[i], s, pi);
-            ph += k; if (ph >= n_fft) ph -= n_fft;
-        }
-        sp[k] = cr * cr + ci * ci;
-        sp[half + k] = pr * pr + pi * pi;
-    }
-    __syncthreads();
-    for (int s = 0; s < 2; ++s)
-        for (int b = 0; b < WSS_NCRIT; ++b) {
-            double a = 0;
-            for (int k = threadIdx.x; k < half; k += MT) a += (double)sp[s * half + k] * (double)crit[b * half + k];
-            const double v = block_sum(a, red);
-            if (threadIdx.x == 0) en[s][b] = 10.0 * log10(fmax(v, eps));
-        }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int NC = WSS_NCRIT;
-        double slope[2][WSS_NCRIT - 1], peak[2][WSS_NCRIT - 1], dbmax[2];
-        for (int s = 0; s < 2; ++s) {
-            dbmax[s] = en[s][0];
-            for (int b = 1; b < NC; ++b) dbmax[s] = fmax(dbmax[s], en[s][b]);
-            for (int b = 0; b < NC - 1; ++b) slope[s][b] = en[s][b + 1] - en[s][b];
-            for (int i = 0; i < NC - 1; ++i) {
-                int n = i;
-                if (slope[s][i] > 0) {
-                    while (n < NC - 1 && slope[s][n] > 0) ++n;
-                    peak[s][i] = en[s][n - 1];
-                } else {
-                    while (n >= 0 && slope[s][n] <= 0) --n;
-                    peak[s][i] = en[s][n + 1];
-                }
-            }
-        }
-        double num = 0, den = 0;
-        for (int b = 0; b < NC - 1; ++b) {
-            double W = 0;
-            for (int s = 0; s < 2; ++s)
-                W += (20.0 / (20.0 + dbmax[s] - en[s][b])) * (1.0 / (1.0 + peak[s][b] - en[s][b]));
-            W *= 0.5;
-            const double d = slope[0][b] - slope[1][b];
-            num += W * d * d; den += W;
-        }
-        out[blockIdx.x] = (float)(num / den);
-    }
+    metric_wss_twiddles(tc, ts, n_fft);
+    metric_frame_wss(ref + start, deg + start, winlength, window, n_fft, crit, eps, fc, fp, tc, ts, sp, red, en, out + blockIdx.x);
 }
 
 // mean | lerp(output)(steps) - target |, steps = linspace(0, n_out - 1, n_t)   (scipy interp1d + np.linspace)

@@ -12,7 +12,8 @@ envelopes and the segment correlations of a whole ragged batch in one launch seq
 Their float64 restatement is tests/stoi_reference.py; parity against pystoi itself is unpinned (not installed here).
 PESQ comes from a third-party package (pypesq) that is absent: `evaluate_metrics` / `CompositeEval` take it, and STOI, as
 arguments and return None for everything that depends on a missing one (`handoff.denoise_files(..., stoi_fn=stoi)`
-fills in STOI).  Signals: 1-D numpy arrays or GPU tensors.  No CPU fallback."""
+fills in STOI).  `evaluate_metrics_batch` scores a ragged batch of clips in one launch sequence (csrc/metrics_batch.hip) with the per-frame
+arithmetic of the one-clip kernels.  Signals: 1-D numpy arrays or GPU tensors.  No CPU fallback."""
 import ctypes as C
 import math
 import warnings
@@ -89,28 +90,28 @@ def metrics_L1(output, target):
 def metrics_ssnr(ref_wav, deg_wav, srate=16000, win_len=30, min_snr=-10, max_snr=35, eps=1e-10):
     ref, deg = _same_length(_dev(ref_wav), _dev(deg_wav))
     tot = _totals(ref, deg)
-    overall = 10 * np.log10(tot[0] / (tot[1] + eps))
-    return float(overall), _segmental(_frame_energies(ref, deg, srate), min_snr, max_snr, eps, eps)
+    overall = _overall_snr(tot, eps)
+    return overall, _segmental(_frame_energies(ref, deg, srate), min_snr, max_snr, eps, eps)
 
 
 def metrics_ssnr_shift(ref_wav, deg_wav, srate=16000, win_len=30, min_snr=-10, max_snr=35, eps=1e-10):
     ref, deg = _same_length(_dev(ref_wav), _dev(deg_wav))
     tot = _totals(ref, deg)
-    overall = 10 * np.log10(tot[0] / (tot[1] + eps))
-    return float(overall), _segmental(_frame_energies(ref, deg, srate), min_snr, max_snr, eps, 1.0)
+    overall = _overall_snr(tot, eps)
+    return overall, _segmental(_frame_energies(ref, deg, srate), min_snr, max_snr, eps, 1.0)
 
 
 def metrics_ssnr_exclude_silence(ref_wav, deg_wav, srate=16000, win_len=30, min_snr=-10, max_snr=35, eps=1e-10):
     ref, deg = _same_length(_dev(ref_wav), _dev(deg_wav))
     tot = _totals(ref, deg)
-    overall = 10 * np.log10(tot[0] / (tot[1] + eps))
+    overall = _overall_snr(tot, eps)
     nc, npz = torch.empty_like(ref), torch.empty_like(deg)
     cnt = torch.zeros(1, dtype=torch.int64, device=ref.device)
     thr = np.float32(np.float32(tot[2]) * np.float32(0.03))
     L.check(L.lib().sos_metric_compact(L.ptr(ref), L.ptr(deg), ref.numel(), float(thr), L.ptr(nc), L.ptr(npz), L.ptr(cnt),
                                        L.stream_ptr()), "sos_metric_compact")
     k = int(cnt.cpu()[0])
-    return float(overall), _segmental(_frame_energies(nc[:k].contiguous(), npz[:k].contiguous(), srate), min_snr, max_snr, eps, eps)
+    return overall, _segmental(_frame_energies(nc[:k].contiguous(), npz[:k].contiguous(), srate), min_snr, max_snr, eps, eps)
 
 
 def llr(ref_wav, deg_wav, srate):
@@ -153,17 +154,17 @@ def wss(ref_wav, deg_wav, srate, eps=1e-10):
     return [float(v) for v in out[:nf].cpu().numpy()]
 
 
-def CompositeEval(ref_wav, deg_wav, srate=16000, eps=1e-10, pesq_raw=None):
-    """(Csig, Cbak, Covl, pesq_raw, segSNR, overall_snr); the first four are None without a PESQ value
-    (the reference calls pypesq here, M2/metrics.py:377)."""
-    ref, deg = _dev(ref_wav), _dev(deg_wav)
-    n = min(ref.numel(), deg.numel())
-    ref, deg = ref[:n].contiguous(), deg[:n].contiguous()
-    wv = sorted(wss(ref, deg, srate, eps=eps))
+def _overall_snr(tot, eps):
+    return float(10 * np.log10(tot[0] / (tot[1] + eps)))
+
+
+def _composite(wss_frames, llr_frames, segSNR, overall_snr, pesq_raw):
+    """The reference's composite measures from the per-frame WSS (list of floats) and LLR (f32 array) values: the two
+    sorted 95 % trimmed means and the regressions of M2/metrics.py:377-402."""
+    wv = sorted(wss_frames)
     wss_dist = float(np.nanmean(wv[:int(round(len(wv) * 0.95))]))
-    lv = sorted(llr(ref, deg, srate))
+    lv = sorted(llr_frames)
     llr_mean = float(np.nanmean(lv[:round(len(lv) * 0.95)]))
-    overall_snr, segSNR = metrics_ssnr(ref, deg, srate=srate, min_snr=0, eps=eps)
     if pesq_raw is None:
         return None, None, None, None, segSNR, overall_snr
 
@@ -173,6 +174,18 @@ def CompositeEval(ref_wav, deg_wav, srate=16000, eps=1e-10, pesq_raw=None):
     Cbak = trim_mos(1.634 + 0.478 * pesq_raw - 0.007 * wss_dist + 0.063 * segSNR)
     Covl = trim_mos(1.594 + 0.805 * pesq_raw - 0.512 * llr_mean - 0.007 * wss_dist)
     return Csig, Cbak, Covl, pesq_raw, segSNR, overall_snr
+
+
+def CompositeEval(ref_wav, deg_wav, srate=16000, eps=1e-10, pesq_raw=None):
+    """(Csig, Cbak, Covl, pesq_raw, segSNR, overall_snr); the first four are None without a PESQ value
+    (the reference calls pypesq here, M2/metrics.py:377)."""
+    ref, deg = _dev(ref_wav), _dev(deg_wav)
+    n = min(ref.numel(), deg.numel())
+    ref, deg = ref[:n].contiguous(), deg[:n].contiguous()
+    wv = wss(ref, deg, srate, eps=eps)
+    lv = llr(ref, deg, srate)
+    overall_snr, segSNR = metrics_ssnr(ref, deg, srate=srate, min_snr=0, eps=eps)
+    return _composite(wv, lv, segSNR, overall_snr, pesq_raw)
 
 
 def evaluate_metrics(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None):
@@ -189,6 +202,104 @@ def evaluate_metrics(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None):
     m['ssnr_exsi'] = metrics_ssnr_exclude_silence(clean, noisy, srate=sr, eps=eps)[1]
     m['overall_snr'] = overall_snr
     return m
+
+
+_BATCH_MAX_CLIPS = 65535            # clips per launch sequence (the kernels' grid.y)
+_BATCH_HEAD = 8                     # f64 per clip at the front of sos_metric_batch's packed output (include/sos_hip.h)
+
+
+def _per_clip(values, nclips, name):
+    if values is None:
+        return [None] * nclips
+    values = list(values)
+    if len(values) != nclips:
+        raise ValueError(f"{len(values)} {name} values for {nclips} clips")
+    return values
+
+
+def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None, return_detail=False):
+    """evaluate_metrics of every pair (noisy[i], clean[i]) of 1-D signals (numpy arrays or GPU tensors; any lengths, each pair
+    equal): a list with one OrderedDict per clip, the same keys, order and meaning.  The whole batch goes up once, runs as
+    one launch sequence (csrc/metrics_batch.hip) and comes back in one copy; a clip's values depend on that clip's samples
+    only, so it gets the same bits alone, in any batch and in any order.  `pesq` / `stoi`: None or one value per clip (entries
+    may be None); stoi=True computes stoi_batch(clean, noisy, sr).  return_detail=True returns (results, detail) with, per
+    clip, the frame count, the kept-sample and kept-frame counts of the silence rule (computed on the device) and the
+    per-frame LLR, WSS and frame-energy arrays."""
+    noisy, clean = list(noisy), list(clean)
+    if len(noisy) != len(clean):
+        raise ValueError(f"{len(noisy)} noisy signals but {len(clean)} clean ones")
+    for i, (x, y) in enumerate(zip(noisy, clean)):
+        if tuple(np.shape(x)) != tuple(np.shape(y)):
+            raise ValueError(f"clip {i}: noisy and clean should have the same length, found {tuple(np.shape(x))} and "
+                             f"{tuple(np.shape(y))}")
+        if int(np.prod(np.shape(x))) == 0:
+            raise ValueError(f"clip {i} is empty")
+    nclips = len(clean)
+    pesq = _per_clip(pesq, nclips, "pesq")
+    stoi = stoi_batch(clean, noisy, sr) if stoi is True else _per_clip(stoi, nclips, "stoi")
+    results, detail = [], []
+    if nclips == 0:
+        return (results, detail) if return_detail else results
+    h = L.lib()
+    outs, plans, base = [], [], 0
+    for c0 in range(0, nclips, _BATCH_MAX_CLIPS):
+        c, n = _concat(clean[c0:c0 + _BATCH_MAX_CLIPS])
+        d, _ = _concat(noisy[c0:c0 + _BATCH_MAX_CLIPS])
+        lens = np.asarray(n, dtype=np.int64)
+        w, skip, _, win = _frame_setup(int(lens[0]), sr)
+        frames = np.asarray([max(int(v / skip - (w / skip)), 0) for v in n], dtype=np.int64)
+        n_fft = int(2 ** np.ceil(np.log(2 * w) / np.log(2)))
+        cf = _crit_filters(sr, n_fft, c.device)
+        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(c.device)      # offsets, lengths
+        lens_p = lens.ctypes.data_as(C.c_void_p)
+        nbytes = h.sos_metric_batch_workspace_bytes(lens_p, len(lens), w, skip, n_fft)
+        if nbytes < 0:
+            L.check(-22, "sos_metric_batch_workspace_bytes")
+        ftot = int(frames.sum())
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=c.device)
+        out = torch.empty(8 * _BATCH_HEAD * len(lens) + 40 * ftot, dtype=torch.uint8, device=c.device)
+        L.check(h.sos_metric_batch(L.ptr(c), L.ptr(d), L.ptr(tab[0]), L.ptr(tab[1]), lens_p, len(lens), w, skip, n_fft,
+                                   10 if sr < 10000 else 16, L.ptr(win), L.ptr(cf), float(eps), L.ptr(ws), ws.numel(),
+                                   L.ptr(out), out.numel(), L.stream_ptr()), "sos_metric_batch")
+        outs.append(out)
+        plans.append((base, lens, frames, ftot))
+        base += out.numel()
+    buf = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu().numpy()          # the one wait of the call
+    i = 0
+    for base, lens, frames, ftot in plans:
+        nb = len(lens)
+        head = np.frombuffer(buf, np.float64, _BATCH_HEAD * nb, base).reshape(nb, _BATCH_HEAD)
+        o = base + 8 * _BATCH_HEAD * nb
+        energy = np.frombuffer(buf, np.float64, 2 * ftot, o).reshape(ftot, 2)
+        energy_kept = np.frombuffer(buf, np.float64, 2 * ftot, o + 16 * ftot).reshape(ftot, 2)
+        llr_all = np.frombuffer(buf, np.float32, ftot, o + 32 * ftot)
+        wss_all = np.frombuffer(buf, np.float32, ftot, o + 36 * ftot)
+        f_off = np.cumsum(frames) - frames
+        for b in range(nb):
+            tot, nf, f0 = head[b], int(frames[b]), int(f_off[b])
+            if tot[7] < 0 or int(tot[6]) != nf:
+                raise RuntimeError("sos_metric_batch: device lengths disagree with the host's")
+            k, kf = int(tot[4]), int(tot[5])
+            en, ek = energy[f0:f0 + nf], energy_kept[f0:f0 + kf]
+            lv, wv = llr_all[f0:f0 + nf], wss_all[f0:f0 + nf]
+            overall_snr = _overall_snr(tot, eps)
+            ssnr = _segmental(en, 0, 35, eps, eps)
+            csig, cbak, covl, pesq_raw, ssnr, overall_snr = _composite([float(v) for v in wv], lv, ssnr, overall_snr, pesq[i])
+            m = OrderedDict()
+            m['l1'] = float(tot[3] / float(lens[b]))
+            m['stoi'] = stoi[i]
+            m['csig'], m['cbak'], m['covl'], m['pesq'] = csig, cbak, covl, pesq_raw
+            m['ssnr_regular'] = _segmental(en, -10, 35, eps, eps)
+            m['ssnr_shift'] = _segmental(en, -10, 35, eps, 1.0)
+            m['ssnr_clip'] = ssnr
+            m['ssnr_exsi'] = _segmental(ek, -10, 35, eps, eps)
+            m['overall_snr'] = overall_snr
+            results.append(m)
+            if return_detail:
+                detail.append(dict(frames=nf, kept_samples=k, kept_frames=kf, llr=lv.copy(), wss=wv.copy(), energy=en.copy(),
+                                   energy_kept=ek.copy()))
+            i += 1
+    return (results, detail) if return_detail else results
 
 
 # ---- STOI / extended STOI (pystoi's constants: 10 kHz, 256-sample frames at hop 128, 15 third-octave bands from 150 Hz,
