@@ -524,6 +524,34 @@ int sos_stoi_batch(const float* x, const float* y, const int64_t* offsets, const
                    int nclips, int p, int q, const double* taps, int ntaps, int extended, void* workspace, int64_t workspace_bytes,
                    double* out, sos_stream_t stream);
 
+/* ---- SI-SDR and the BSS-eval SDR of a ragged batch of (clean x, estimate y) pairs (csrc/sdr.hip; sos_amd.metrics.si_sdr_batch /
+ * sdr_batch; float64 restatement: tests/sdr_reference.py).  x, y, offsets, lengths, lengths_host: as sos_stoi_batch; both buffers
+ * hold at least sum(lengths_host) samples.  Every sum and the solve accumulate in f64 over fixed 4096-sample chunks in a fixed
+ * order, without atomics: a clip's values depend on that clip's samples only.  No allocation, no host synchronisation.
+ * sos_sdr_workspace_bytes: workspace size for these lengths, -1 on bad args; filter_length 0 sizes sos_sisdr_batch's workspace,
+ *   1 .. 512 sos_sdr_batch's: 256-byte-aligned arrays of 40 nclips + 8200 C bytes, C = sum of ceil(n_b / 4096) (every chunk
+ *   holds 512 lags of both correlations, whatever filter_length is).
+ * sos_sisdr_batch: oracle/frontend.py::si_sdr's terms, on mean-removed signals when zero_mean = 1: out f64 [nclips][4] =
+ *   {sum (alpha x)^2, sum (alpha x - y)^2, alpha = <y,x> / (<x,x> + 1e-30), samples}; alpha comes from sums over the mean-removed
+ *   samples themselves (the means from a pass before), the residual from a further pass with the device's alpha; SI-SDR = 10 log10((out[0] + 1e-30) / (out[1] + 1e-30)).
+ * sos_sdr_batch: r[k] = sum_t x[t] x[t+k], d[k] = sum_t x[t] y[t+k] for k < filter_length (1 .. 512), toeplitz(r) c = d by the
+ *   Levinson-Durbin recursion: out f64 [nclips][5] = {p = d.c, e = sum y^2, r[0], status, samples}; SDR = 10 log10(p / (e - p)).
+ *   status 0: solved; -2: r[0] <= 0 (an all-zero clean clip); -3: the prediction error stopped being positive (toeplitz(r) is
+ *   numerically singular); p is 0 then.  stages: SOS_SDR_CORRELATE | SOS_SDR_SOLVE runs the sequence; one of the two runs that
+ *   part alone (timing the two kernels apart): SOS_SDR_SOLVE then sums whatever the workspace holds, so it wants the same call
+ *   with SOS_SDR_CORRELATE before it.  Either part first rebuilds the per-clip extents from this call's offsets / lengths, so
+ *   no index it uses comes from the workspace's previous contents.
+ * In both outputs samples = -1 (and status -1): device offsets / lengths that leave what lengths_host sized; the clip is not
+ * scored.  SOS_EINVAL: null pointers, nclips outside 1 .. 65535, filter_length or stages out of range; SOS_ENOSPC: workspace
+ * smaller than sos_sdr_workspace_bytes says. */
+enum { SOS_SDR_CORRELATE = 1, SOS_SDR_SOLVE = 2 };
+int64_t sos_sdr_workspace_bytes(const int64_t* lengths_host, int nclips, int filter_length);
+int sos_sisdr_batch(const float* x, const float* y, const int64_t* offsets, const int64_t* lengths, const int64_t* lengths_host,
+                    int nclips, int zero_mean, void* workspace, int64_t workspace_bytes, double* out, sos_stream_t stream);
+int sos_sdr_batch(const float* x, const float* y, const int64_t* offsets, const int64_t* lengths, const int64_t* lengths_host,
+                  int nclips, int filter_length, int stages, void* workspace, int64_t workspace_bytes, double* out,
+                  sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

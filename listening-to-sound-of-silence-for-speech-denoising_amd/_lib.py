@@ -11,6 +11,7 @@ LIB_PATH_F16 = os.environ.get("SOS_HIP_LIB_F16", os.path.join(_HERE, "libsos_hip
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SIGMOID = 0, 1, 2, 3
 PAD_ZERO, PAD_REFLECT = 0, 1
 DT_BF16, DT_BF16X3, DT_F32 = 0, 1, 2
+SDR_CORRELATE, SDR_SOLVE = 1, 2            # SOS_SDR_* stages of sos_sdr_batch
 
 
 class ConvDesc(C.Structure):
@@ -135,6 +136,9 @@ SIGNATURES = {
     "sos_metric_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _D, _P, _L, _P, _L, _P],
     "sos_stoi_workspace_bytes": [_P, _I, _I, _I],
     "sos_stoi_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _L, _P, _P],
+    "sos_sdr_workspace_bytes": [_P, _I, _I],
+    "sos_sisdr_batch": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P, _P],
+    "sos_sdr_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P],
     "sos_time_unstack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
     "sos_spatial_mean_bwd": [_P, _L, _L, _I, _L, _I, _I, _I, _P, _I, _P],
 }
@@ -154,7 +158,8 @@ def _load(path, want_dtype):
         fn.argtypes = argtypes
         fn.restype = C.c_int64 if name in ("sos_wgrad_workspace_bytes", "sos_lstm_pack_bytes", "sos_conv2d_tile_count",
                                              "sos_stft_matrix_bytes", "sos_istft_matrix_bytes",
-                                             "sos_stoi_workspace_bytes", "sos_metric_batch_workspace_bytes") else C.c_int
+                                             "sos_stoi_workspace_bytes", "sos_metric_batch_workspace_bytes",
+                                             "sos_sdr_workspace_bytes") else C.c_int
     if h.sos_abi_version() != EXPECTED_ABI:
         raise ImportError(f"{path} exports ABI version {h.sos_abi_version()}, this binding was written for {EXPECTED_ABI} "
                           "(the argument lists differ: rebuild the library, or drop the SOS_HIP_LIB / SOS_HIP_LIB_F16 override)")

@@ -12,7 +12,11 @@ envelopes and the segment correlations of a whole ragged batch in one launch seq
 Their float64 restatement is tests/stoi_reference.py; parity against pystoi itself is unpinned (not installed here).
 PESQ comes from a third-party package (pypesq) that is absent: `evaluate_metrics` / `CompositeEval` take it, and STOI, as
 arguments and return None for everything that depends on a missing one (`handoff.denoise_files(..., stoi_fn=stoi)`
-fills in STOI).  `evaluate_metrics_batch` scores a ragged batch of clips in one launch sequence (csrc/metrics_batch.hip) with the per-frame
+fills in STOI).  SI-SDR (`si_sdr`, `si_sdr_batch`: the formula of the project's parity criterion, oracle/frontend.py::si_sdr) and
+the BSS-eval SDR (`sdr`, `sdr_batch`: mir_eval's bss_eval_sources with one source, a 512-tap distortion filter) of ragged batches
+run in HIP too (csrc/sdr.hip): float64 sums, lag correlations and Levinson-Durbin solve, one launch sequence per measure;
+float64 restatement tests/sdr_reference.py, parity against mir_eval itself unpinned (not installed here).
+`evaluate_metrics_batch` scores a ragged batch of clips in one launch sequence (csrc/metrics_batch.hip) with the per-frame
 arithmetic of the one-clip kernels.  Signals: 1-D numpy arrays or GPU tensors.  No CPU fallback."""
 import ctypes as C
 import math
@@ -217,14 +221,15 @@ def _per_clip(values, nclips, name):
     return values
 
 
-def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None, return_detail=False):
+def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None, return_detail=False, si_sdr=False, sdr=False):
     """evaluate_metrics of every pair (noisy[i], clean[i]) of 1-D signals (numpy arrays or GPU tensors; any lengths, each pair
     equal): a list with one OrderedDict per clip, the same keys, order and meaning.  The whole batch goes up once, runs as
     one launch sequence (csrc/metrics_batch.hip) and comes back in one copy; a clip's values depend on that clip's samples
     only, so it gets the same bits alone, in any batch and in any order.  `pesq` / `stoi`: None or one value per clip (entries
     may be None); stoi=True computes stoi_batch(clean, noisy, sr).  return_detail=True returns (results, detail) with, per
     clip, the frame count, the kept-sample and kept-frame counts of the silence rule (computed on the device) and the
-    per-frame LLR, WSS and frame-energy arrays."""
+    per-frame LLR, WSS and frame-energy arrays.  si_sdr=True / sdr=True append the keys 'si_sdr' / 'sdr' after 'overall_snr':
+    si_sdr_batch / sdr_batch of (clean[i], noisy[i]), their launch sequences enqueued before the call's one wait."""
     noisy, clean = list(noisy), list(clean)
     if len(noisy) != len(clean):
         raise ValueError(f"{len(noisy)} noisy signals but {len(clean)} clean ones")
@@ -262,12 +267,23 @@ def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=No
                                    10 if sr < 10000 else 16, L.ptr(win), L.ptr(cf), float(eps), L.ptr(ws), ws.numel(),
                                    L.ptr(out), out.numel(), L.stream_ptr()), "sos_metric_batch")
         outs.append(out)
-        plans.append((base, lens, frames, ftot))
-        base += out.numel()
+        extra, pos = [], base + out.numel()          # (key, byte offset in the one copy) of the optional measures
+        for key, on, fl in (("si_sdr", si_sdr, None), ("sdr", sdr, SDR_FILTER_LENGTH)):
+            if on:
+                outs.append(_sdr_enqueue(c, d, lens, tab, fl).view(torch.uint8).reshape(-1))
+                extra.append((key, pos))
+                pos += outs[-1].numel()
+        plans.append((base, lens, frames, ftot, extra))
+        base = pos
     buf = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu().numpy()          # the one wait of the call
     i = 0
-    for base, lens, frames, ftot in plans:
+    for base, lens, frames, ftot, extra in plans:
         nb = len(lens)
+        more = OrderedDict()
+        for key, o in extra:
+            w = _SDR_OUT[key]
+            rows = np.frombuffer(buf, np.float64, w * nb, o).reshape(nb, w)
+            more[key] = _si_sdr_finish(rows, lens) if key == "si_sdr" else _sdr_finish(rows, lens, i)[0]
         head = np.frombuffer(buf, np.float64, _BATCH_HEAD * nb, base).reshape(nb, _BATCH_HEAD)
         o = base + 8 * _BATCH_HEAD * nb
         energy = np.frombuffer(buf, np.float64, 2 * ftot, o).reshape(ftot, 2)
@@ -294,6 +310,8 @@ def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=No
             m['ssnr_clip'] = ssnr
             m['ssnr_exsi'] = _segmental(ek, -10, 35, eps, eps)
             m['overall_snr'] = overall_snr
+            for key, vals in more.items():
+                m[key] = vals[b]
             results.append(m)
             if return_detail:
                 detail.append(dict(frames=nf, kept_samples=k, kept_frames=kf, llr=lv.copy(), wss=wv.copy(), energy=en.copy(),
@@ -395,3 +413,122 @@ def stoi(x, y, fs_sig, extended=False):
     if tuple(np.shape(x)) != tuple(np.shape(y)):
         raise ValueError(f"x and y should have the same length, found {tuple(np.shape(x))} and {tuple(np.shape(y))}")
     return stoi_batch([x], [y], fs_sig, extended)[0]
+
+
+# ---- SI-SDR and the BSS-eval SDR (csrc/sdr.hip)
+SDR_FILTER_LENGTH = 512             # mir_eval's bss_eval_sources: taps of the allowed distortion filter; the kernels' maximum
+_SDR_MAX_CLIPS = 65535              # clips per launch sequence (the kernels' grid.y)
+_SDR_OUT = {"si_sdr": 4, "sdr": 5}  # f64 per clip of sos_sisdr_batch / sos_sdr_batch (include/sos_hip.h)
+
+
+def _sdr_enqueue(x, y, lens, tab, filter_length=None, zero_mean=False, stages=L.SDR_CORRELATE | L.SDR_SOLVE, ws=None):
+    """Enqueue sos_sisdr_batch (filter_length None) or sos_sdr_batch on the concatenated clips x (clean) and y (estimate) with
+    host lengths `lens` (int64 array) and the device table `tab` = [offsets, lengths]; no wait.  Returns the f64 [clips][4]
+    or [clips][5] device result (include/sos_hip.h).  `stages` / `ws`: one part of the SDR sequence on a workspace the caller
+    keeps (tools/sdr_bench.py times the correlation and the solve apart)."""
+    h = L.lib()
+    lens_p = lens.ctypes.data_as(C.c_void_p)
+    if ws is None:
+        nbytes = h.sos_sdr_workspace_bytes(lens_p, len(lens), 0 if filter_length is None else int(filter_length))
+        if nbytes < 0:
+            L.check(-22, "sos_sdr_workspace_bytes")
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+    if filter_length is None:
+        out = torch.empty((len(lens), _SDR_OUT["si_sdr"]), dtype=torch.float64, device=x.device)
+        L.check(h.sos_sisdr_batch(L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens_p, len(lens), int(bool(zero_mean)),
+                                  L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()), "sos_sisdr_batch")
+    else:
+        out = torch.empty((len(lens), _SDR_OUT["sdr"]), dtype=torch.float64, device=x.device)
+        L.check(h.sos_sdr_batch(L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens_p, len(lens), int(filter_length),
+                                int(stages), L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()), "sos_sdr_batch")
+    return out
+
+
+def _si_sdr_finish(rows, lens):
+    """Scores from sos_sisdr_batch's rows {sum (alpha x)^2, sum (alpha x - y)^2, alpha, samples}."""
+    if np.any(rows[:, 3] != lens):
+        raise RuntimeError("sos_sisdr_batch: device lengths disagree with the host's")
+    return [float(10.0 * np.log10((t + 1e-30) / (r + 1e-30))) for t, r in rows[:, :2]]
+
+
+def _sdr_finish(rows, lens, first_clip=0):
+    """(scores, detail) from sos_sdr_batch's rows {p, e, r[0], status, samples}: 10 log10(p / (e - p)) in float64; nan with a
+    RuntimeWarning where the clean clip is all zero or the recursion failed, inf where e - p <= 0."""
+    if np.any(rows[:, 4] != lens):
+        raise RuntimeError("sos_sdr_batch: device lengths disagree with the host's")
+    scores, detail = [], []
+    for b, (p, e, r0, status, _) in enumerate(rows):
+        detail.append(dict(p=float(p), e=float(e), r0=float(r0), status=int(status)))
+        if status < 0:
+            why = "the clean signal is all zero" if status == -2 else "the lag matrix of the clean signal is numerically singular"
+            warnings.warn(f"sdr: clip {first_clip + b}: {why}. Returning nan", RuntimeWarning)
+            scores.append(float("nan"))
+        elif e - p <= 0:
+            scores.append(float("inf"))
+        else:
+            with np.errstate(divide="ignore"):
+                scores.append(float(10.0 * np.log10(p / (e - p))))
+    return scores, detail
+
+
+def _sdr_pairs(clean, estimate):
+    clean, estimate = list(clean), list(estimate)
+    if len(clean) != len(estimate):
+        raise ValueError(f"{len(clean)} clean signals but {len(estimate)} estimates")
+    for i, (x, y) in enumerate(zip(clean, estimate)):
+        if tuple(np.shape(x)) != tuple(np.shape(y)):
+            raise ValueError(f"clip {i}: clean and estimate should have the same length, found {tuple(np.shape(x))} and "
+                             f"{tuple(np.shape(y))}")
+        if int(np.prod(np.shape(x))) == 0:
+            raise ValueError(f"clip {i} is empty")
+    return clean, estimate
+
+
+def _sdr_run(clean, estimate, key, filter_length=None, zero_mean=False):
+    """The f64 result rows and host lengths of the whole batch: one launch sequence per 65535 clips, one wait."""
+    outs, lens_all = [], []
+    for c0 in range(0, len(clean), _SDR_MAX_CLIPS):
+        x, n = _concat(clean[c0:c0 + _SDR_MAX_CLIPS])
+        y, _ = _concat(estimate[c0:c0 + _SDR_MAX_CLIPS])
+        lens = np.asarray(n, dtype=np.int64)
+        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(x.device)      # offsets, lengths
+        outs.append(_sdr_enqueue(x, y, lens, tab, filter_length, zero_mean))
+        lens_all.append(lens)
+    rows = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu().numpy() if outs else np.zeros((0, _SDR_OUT[key]))
+    return rows, np.concatenate(lens_all) if lens_all else np.zeros(0, np.int64)
+
+
+def si_sdr_batch(clean, estimate, zero_mean=False):
+    """Scale-invariant SDR in dB of every pair (clean[i], estimate[i]) of 1-D signals (numpy arrays or GPU tensors; any
+    lengths, each pair equal): oracle/frontend.py::si_sdr(est=estimate, ref=clean) with its 1e-30 terms, alpha =
+    <y,x> / (<x,x> + 1e-30), 10 log10((|alpha x|^2 + 1e-30) / (|alpha x - y|^2 + 1e-30)); zero_mean=True removes each
+    signal's mean first.  Float64 sums on the device, one launch sequence and one wait for the batch; a clip's value does not
+    depend on the other clips.  Returns the list of floats."""
+    clean, estimate = _sdr_pairs(clean, estimate)
+    return _si_sdr_finish(*_sdr_run(clean, estimate, "si_sdr", None, zero_mean))
+
+
+def si_sdr(clean, estimate, zero_mean=False):
+    """si_sdr_batch of one clip."""
+    return si_sdr_batch([clean], [estimate], zero_mean)[0]
+
+
+def sdr_batch(clean, estimate, filter_length=SDR_FILTER_LENGTH, return_detail=False):
+    """BSS-eval SDR in dB (Vincent et al. 2006; mir_eval.separation.bss_eval_sources with one source) of every pair
+    (clean[i], estimate[i]): the energy of the estimate's projection on the `filter_length` (1 .. 512) delayed copies of the
+    clean signal over the energy of the rest.  With r[k] = sum_t x[t] x[t+k], d[k] = sum_t x[t] y[t+k], toeplitz(r) c = d,
+    p = d.c and e = sum y^2 (all float64 on the device) it is 10 log10(p / (e - p)).  An all-zero clean clip (or a lag matrix
+    the recursion finds singular) scores nan with a RuntimeWarning naming the clip; an estimate inside the span up to rounding
+    (e - p <= 0) scores inf.  One launch sequence and one wait for the batch; a clip's value does not depend on the other clips.
+    Returns the list of floats, or (scores, detail) with per clip dict(p, e, r0, status) when return_detail=True."""
+    if isinstance(filter_length, bool) or int(filter_length) != filter_length or not 1 <= filter_length <= SDR_FILTER_LENGTH:
+        raise ValueError(f"filter_length must be an integer in 1 .. {SDR_FILTER_LENGTH}, got {filter_length!r}")
+    clean, estimate = _sdr_pairs(clean, estimate)
+    scores, detail = _sdr_finish(*_sdr_run(clean, estimate, "sdr", int(filter_length)))
+    return (scores, detail) if return_detail else scores
+
+
+def sdr(clean, estimate, filter_length=SDR_FILTER_LENGTH, return_detail=False):
+    """sdr_batch of one clip."""
+    res = sdr_batch([clean], [estimate], filter_length, return_detail)
+    return (res[0][0], res[1][0]) if return_detail else res[0]
