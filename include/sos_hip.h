@@ -445,6 +445,21 @@ int sos_pcm_to_mono_f32(const void* pcm, int format, int channels, int64_t n_fra
  * ceil(n_in * ratio)).  (nwin + 1) * 4 bytes must fit the 160 KB LDS. */
 int sos_resample_f32(const float* x, int64_t n_in, double ratio, const float* win, int nwin, int num_table,
                      float* out, int64_t n_out, sos_stream_t stream);
+/* sos_resample_f32 for a ragged batch of clips at one common ratio, in ONE launch whatever nclips is
+ * (csrc/wave_io.hip resample_batch_kernel: one workgroup per CU walks the (clip, SOS_RESAMPLE_CHUNK outputs) tiles).  x: the clips back to back in one f32 buffer; out: one
+ * buffer for all outputs, not pre-cleared.  table: int64 [6][nclips] on the device, table_host: the same values on the
+ * HOST (they are validated there before anything touches the device, and size the grid):
+ *   [0] input offset   [1] n_in   [2] output offset   [3] n_out   [4] n_valid = min((int64)(n_in * ratio), n_out)
+ *   [5] the clip's first tile = sum of ceil(n_out / SOS_RESAMPLE_CHUNK) over the clips before it
+ * Clips lie in increasing order of both offsets and do not overlap.  Clip c gets, bit for bit, what sos_resample_f32 writes
+ * for that clip alone -- in any batch and any order: every bound is the clip's own, no tap reads a neighbour, outputs
+ * n_valid .. n_out are written as zero.  A device entry that lies outside what table_host sized is skipped.
+ * SOS_EINVAL (sos_last_error() names the clip): null pointers, nclips outside 1 .. 65535, n_in < 1, n_valid < 1 or not the
+ * value above, ratio <= 0, (nwin + 1) * 4 bytes > 160 KB; SOS_ENOSPC: the time register of the longest clip needs more
+ * segments than the kernel argument holds. */
+#define SOS_RESAMPLE_CHUNK 4096
+int sos_resample_batch_f32(const float* x, const int64_t* table, const int64_t* table_host, int nclips, double ratio,
+                           const float* win, int nwin, int num_table, float* out, sos_stream_t stream);
 /* Host-only helper (no GPU work): the piecewise-linear description of resampy's running f64 time register
  * `time_register += 1/ratio` that sos_resample_f32 hands its kernel: time(t) = fma(t - k0[i], d[i], s0[i]) for
  * the last i with k0[i] <= t.  Returns the number of segments (<= capacity) or a negative error. */

@@ -62,6 +62,7 @@ class WgradDesc(C.Structure):
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 ADAM_CHUNK = 16384          # SOS_ADAM_CHUNK of include/sos_hip.h
 GUARD_FLOATS = 5            # SOS_GUARD_FLOATS
+RESAMPLE_CHUNK = 4096       # SOS_RESAMPLE_CHUNK
 EXPECTED_ABI = 10           # sos_abi_version() of the library these argument lists were written for
 
 # name -> argtypes, exactly the prototypes of include/sos_hip.h
@@ -123,6 +124,7 @@ SIGNATURES = {
     "sos_wgrad_tune_load": [C.c_char_p],
     "sos_pcm_to_mono_f32": [_P, _I, _I, _L, _P, _P],
     "sos_resample_f32": [_P, _L, _D, _P, _I, _I, _P, _L, _P],
+    "sos_resample_batch_f32": [_P, _P, _P, _I, _D, _P, _I, _I, _P, _P],
     "sos_resample_time_segments": [_D, _L, _P, _P, _P, _I],
     "sos_time_stack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
     "sos_spatial_mean": [_P, _L, _L, _I, _I, _I, _P, _L, _I, _I, _P],

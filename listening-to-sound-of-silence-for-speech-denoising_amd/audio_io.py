@@ -4,12 +4,15 @@
 
   load(path, sr=22050, mono=True, offset=0.0, duration=None, dtype=np.float32, res_type='kaiser_best') -> (y, sr)
   resample(y, orig_sr, target_sr, res_type='kaiser_best', fix=True, scale=False)
+  load_batch(paths, ...) / resample_batch(ys, ...): the same for a list of files / signals of any lengths, in a number
+      of launches and copies that does not grow with the list (`load_batch_device` / `resample_batch_device` stay in HBM)
   to_mono(y)
   write_wav(path, y, sr, norm=False)
 
 The RIFF container is parsed here on the host (bytes -> header fields + one frombuffer view, no per-sample
 Python); sample conversion, channel mix-down and the band-limited resampler are HIP kernels
 (csrc/wave_io.hip).  `load_device` keeps the result in HBM for the pipeline.  No CPU fallback."""
+import ctypes as C
 import os
 import struct
 
@@ -71,6 +74,46 @@ def resample_device(x, orig_sr, target_sr, res_type="kaiser_best", fix=True):
     L.check(L.lib().sos_resample_f32(L.ptr(x), n_in, ratio, L.ptr(win), win.numel(), num_table, L.ptr(out), n_out,
                                      L.stream_ptr()), "sos_resample_f32")
     return out
+
+
+_RESAMPLE_MAX_CLIPS = 65535         # clips per launch of sos_resample_batch_f32 (include/sos_hip.h)
+
+
+def resample_batch_device(clips, orig_sr, target_sr, res_type="kaiser_best", fix=True):
+    """resample_device of every clip of a list of 1-D f32 GPU tensors (any lengths) at one common ratio: a list of views
+    into one output buffer, clip i with ceil(n_i * ratio) samples (int(n_i * ratio) with fix=False) that are bit for bit
+    resample_device(clips[i]).  One torch.cat, one table upload and one launch (csrc/wave_io.hip) per 65535 clips."""
+    clips = list(clips)
+    L.require_cuda(*clips)
+    for x in clips:
+        if x.dim() != 1 or x.dtype != torch.float32:
+            raise ValueError("resample_batch_device expects 1-D float32 tensors")
+    if orig_sr == target_sr or not clips:
+        return clips
+    ratio = float(target_sr) / orig_sr
+    win, num_table = _filter_on(clips[0].device, ratio, res_type)
+    n_in = np.asarray([x.numel() for x in clips], dtype=np.int64)
+    n_res = np.asarray([int(int(n) * ratio) for n in n_in], dtype=np.int64)
+    for i, n in enumerate(n_res):
+        if n < 1:
+            raise ValueError("clip %d: Input signal length=%d is too small to resample from %s->%s"
+                             % (i, n_in[i], orig_sr, target_sr))
+    n_out = np.asarray([int(np.ceil(int(n) * ratio)) for n in n_in], dtype=np.int64) if fix else n_res
+    n_valid = np.minimum(n_res, n_out)
+    in_end, out_end = np.cumsum(n_in), np.cumsum(n_out)
+    x = torch.cat(clips)
+    out = torch.empty(int(out_end[-1]), dtype=torch.float32, device=x.device)
+    h = L.lib()
+    for c0 in range(0, len(clips), _RESAMPLE_MAX_CLIPS):
+        c1 = min(c0 + _RESAMPLE_MAX_CLIPS, len(clips))
+        i0, o0 = int(in_end[c0] - n_in[c0]), int(out_end[c0] - n_out[c0])
+        tiles = -(-n_out[c0:c1] // L.RESAMPLE_CHUNK)
+        tab = np.ascontiguousarray(np.stack([in_end[c0:c1] - n_in[c0:c1] - i0, n_in[c0:c1], out_end[c0:c1] - n_out[c0:c1] - o0,
+                                             n_out[c0:c1], n_valid[c0:c1], np.cumsum(tiles) - tiles]), dtype=np.int64)
+        tab_dev = torch.from_numpy(tab).to(x.device)
+        L.check(h.sos_resample_batch_f32(L.ptr(x[i0:]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, ratio, L.ptr(win),
+                                         win.numel(), num_table, L.ptr(out[o0:]), L.stream_ptr()), "sos_resample_batch_f32")
+    return [out[int(e - n):int(e)] for e, n in zip(out_end, n_out)]
 
 
 def pcm_to_mono_device(pcm, fmt):
@@ -158,6 +201,63 @@ def load_device(path, sr=22050, mono=True, offset=0.0, duration=None, res_type="
     return y, sr
 
 
+def load_batch_device(paths, sr=22050, mono=True, offset=0.0, duration=None, res_type="kaiser_best", device="cuda"):
+    """load_device of every file of a list: (ys, srs), one f32 GPU tensor and one rate per file, each bit for bit
+    load_device(path).  Every file is parsed on the host; files that share (sample format, channel count) go up in one
+    copy of their concatenated frames and through one sos_pcm_to_mono_f32 launch, files that share a native rate other
+    than `sr` through one sos_resample_batch_f32 launch: the number of launches and copies follows the number of distinct
+    formats and rates, not the number of files."""
+    if not mono:
+        raise NotImplementedError("load(mono=False): the reference only loads mono (M1/dataset.py:226)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("sos_amd.audio_io needs an MI355X: there is no CPU fallback")
+    paths = list(paths)
+    ys, rates, by_format = [None] * len(paths), [], {}
+    for i, path in enumerate(paths):
+        arr, kind, sr_native = read_wave(path)
+        if offset:
+            arr = arr[int(offset * sr_native):]
+        if duration is not None:
+            arr = arr[:int(duration * sr_native)]
+        rates.append(sr_native)
+        if arr.shape[0] == 0:
+            ys[i] = torch.zeros(0, dtype=torch.float32, device=device)
+        else:
+            by_format.setdefault((kind, arr.shape[1]), []).append((i, arr))
+    for (kind, _), group in by_format.items():
+        pcm = torch.from_numpy(np.concatenate([arr for _, arr in group])).to(device)
+        mono_all = pcm_to_mono_device(pcm, kind)          # per frame: the concatenation needs no table
+        pos = 0
+        for i, arr in group:
+            ys[i] = mono_all[pos:pos + arr.shape[0]]
+            pos += arr.shape[0]
+    if sr is None:
+        return ys, rates
+    by_rate = {}
+    for i, r in enumerate(rates):
+        if r != sr and ys[i].numel():
+            by_rate.setdefault(r, []).append(i)
+    for r, idx in by_rate.items():
+        for i, y in zip(idx, resample_batch_device([ys[i] for i in idx], r, sr, res_type)):
+            ys[i] = y
+    return ys, [sr] * len(paths)
+
+
+def load_batch(paths, sr=22050, mono=True, offset=0.0, duration=None, dtype=np.float32, res_type="kaiser_best"):
+    """load of every file of a list, through load_batch_device: (list of ndarrays, list of rates)."""
+    ys, srs = load_batch_device(paths, sr, mono, offset, duration, res_type)
+    return _download(ys, dtype), srs
+
+
+def _download(ys, dtype):
+    """The 1-D GPU tensors of a list as host arrays of `dtype`, through one copy of their concatenation."""
+    if not ys:
+        return []
+    flat = np.ascontiguousarray((torch.cat(ys) if len(ys) > 1 else ys[0]).cpu().numpy(), dtype=dtype)
+    ends = np.cumsum([y.numel() for y in ys])
+    return [flat[int(e) - y.numel():int(e)] for e, y in zip(ends, ys)]
+
+
 def load(path, sr=22050, mono=True, offset=0.0, duration=None, dtype=np.float32, res_type="kaiser_best"):
     """Drop-in for `librosa.load` (librosa 0.7.1 core/audio.py) on WAVE files: (y ndarray, sr)."""
     y, sr = load_device(path, sr, mono, offset, duration, res_type)
@@ -186,6 +286,26 @@ def resample(y, orig_sr, target_sr, res_type="kaiser_best", fix=True, scale=Fals
     if scale:
         out = out / np.sqrt(ratio)
     return np.ascontiguousarray(out, dtype=y.dtype if np.issubdtype(y.dtype, np.floating) else np.float32)
+
+
+def resample_batch(ys, orig_sr, target_sr, res_type="kaiser_best", fix=True, scale=False):
+    """resample of every signal of a list (1-D, any lengths): numpy in -> numpy out, one upload and one download for the
+    whole batch."""
+    ys = [np.asarray(y) for y in ys]
+    for y in ys:
+        if y.ndim != 1:
+            raise ValueError("resample expects a 1-D signal")
+    if orig_sr == target_sr or not ys:
+        return ys
+    ratio = float(target_sr) / orig_sr
+    ends = np.cumsum([len(y) for y in ys])
+    flat = torch.from_numpy(np.concatenate([np.asarray(y, dtype=np.float32) for y in ys])).cuda()
+    outs = _download(resample_batch_device([flat[int(e) - len(y):int(e)] for e, y in zip(ends, ys)], orig_sr, target_sr,
+                                           res_type, fix), np.float32)
+    if scale:
+        outs = [o / np.sqrt(ratio) for o in outs]
+    return [np.ascontiguousarray(o, dtype=y.dtype if np.issubdtype(y.dtype, np.floating) else np.float32)
+            for o, y in zip(outs, ys)]
 
 
 def wave_bytes(y, sr):

@@ -329,9 +329,59 @@ def get_data_from_first_model(first_model_json_path, sr=DATA_REQUIRED_SR, snr=No
     return data_list, info
 
 
+def _write_individual(data, info, sigs, gt_sigs, outputs, snr, save_individual_results):
+    """The WAVE files and stat.json of one file of denoise_files (M2/predict.py:515-560); fills the path keys of `info`."""
+    if not save_individual_results:
+        return
+    save_dir = os.path.join(os.path.abspath(outputs), convert_snr_to_suffix2(snr)[1:], str(data['id']))
+    ensure_dir(save_dir)
+    host = sigs.cpu().numpy()
+    for k, name in enumerate(('noisy_input', 'noise_intervals', 'predicted_full_noise', 'denoised_output')):
+        p = os.path.join(save_dir, name + '.wav')
+        audio_io.write_wav(p, host[k], data['sr'])
+        info[name] = p
+    if gt_sigs is not None:
+        gh = gt_sigs.cpu().numpy()
+        for k, name in enumerate(('ground_truth_full_noise', 'ground_truth_clean_input')):
+            p = os.path.join(save_dir, name + '.wav')
+            audio_io.write_wav(p, gh[k][:host.shape[1]], data['sr'])
+            info[name] = p
+    with open(os.path.join(save_dir, 'stat.json'), 'w') as fp:
+        json.dump(info, fp, **JSON_DUMP_PARAMS)
+
+
+def _batch_measures(work, pesq_fn, stoi_fn):
+    """The objective measures of all files with a known clean signal (denoise_files(batch_metrics=True)): outputs and clean
+    signals to 16 kHz in one resample_batch_device call per distinct rate (2 F clips), one evaluate_metrics_batch."""
+    if not work:
+        return
+    out16, clean16 = [None] * len(work), [None] * len(work)
+    by_rate = OrderedDict()
+    for i, (data, _, _, _) in enumerate(work):
+        by_rate.setdefault(data['sr'], []).append(i)
+    for sr, idx in by_rate.items():
+        clips = [work[i][2][3].contiguous() for i in idx] + [work[i][3][1].contiguous() for i in idx]
+        res = audio_io.resample_batch_device(clips, sr, 16000)
+        for k, i in enumerate(idx):
+            n = min(res[k].numel(), res[len(idx) + k].numel())       # evaluate_metrics compares the common prefix
+            out16[i], clean16[i] = res[k][:n], res[len(idx) + k][:n]
+    pesq, stoi = None, (True if stoi_fn is True else None)
+    if pesq_fn is not None or callable(stoi_fn):
+        flat = torch.cat(out16 + clean16).cpu().numpy()               # one download for the callables
+        ends = np.cumsum([t.numel() for t in out16 + clean16])
+        host = [flat[int(e) - t.numel():int(e)] for e, t in zip(ends, out16 + clean16)]
+        oh, ch = host[:len(work)], host[len(work):]
+        if pesq_fn is not None:
+            pesq = [pesq_fn(c, o, 16000) for c, o in zip(ch, oh)]
+        if callable(stoi_fn):
+            stoi = [stoi_fn(c, o, 16000) for c, o in zip(ch, oh)]
+    for (_, info, _, _), m in zip(work, metrics.evaluate_metrics_batch(out16, clean16, sr=16000, pesq=pesq, stoi=stoi)):
+        info.update(m)
+
+
 @torch.no_grad()
 def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_individual_results=True, save_stat=True,
-                  pesq_fn=None, stoi_fn=None):
+                  pesq_fn=None, stoi_fn=None, batch_metrics=False):
     """M2/predict.py:377-576 (`evaluate`): net(mixed, noise) -> (pred_noise, mask); mask applied to the mixed
     spectrogram; ISTFT of mixed / noise intervals / predicted noise / output written as
     <outputs>/<snr suffix>/<id>/*.wav + stat.json, and <outputs>/eval_results<suffixes>.json.  Items that carry a
@@ -339,12 +389,17 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
     16 kHz against the clean signal (:455-460) and the ground-truth WAVE files; `pesq_fn(clean, output, sr)` /
     `stoi_fn(clean, output, sr)` supply the two third-party scores (None entries otherwise) and the averages of the
     available measures go to `denoise_statistics`.  `stoi_fn=metrics.stoi` computes STOI in HIP (pypesq has no
-    counterpart here)."""
+    counterpart here).
+    batch_metrics=True: no file waits for the device inside the loop; afterwards the outputs and clean signals of all files
+    with a known clean signal go to 16 kHz in one audio_io.resample_batch_device call per distinct rate and through one
+    metrics.evaluate_metrics_batch, and the files are written after that.  `stoi_fn=True` then means STOI by
+    metrics.stoi_batch in the same launch sequence; a callable `stoi_fn` / `pesq_fn` is called per clip on host arrays
+    taken from one download of the resampled batch.  Same keys, order, types and files as the per-file path."""
     data_list, data_info = data_list_info
     data_info = OrderedDict(data_info)
     data_info['snr'] = snr
     net.eval()
-    stat = []
+    stat, work = [], []
     for data in data_list:
         pred_noise_stft, crm = net(data['mixed'], data['noise'])
         out_stft = transform.batch_fast_icRM_sigmoid(data['mixed'], crm)
@@ -360,28 +415,20 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
         gt_sigs = None
         if known:
             gt_sigs = transform.istft_batch(torch.cat([data['full_noise'], data['clean']], dim=0))
-            out16 = audio_io.resample_device(sigs[3].contiguous(), data['sr'], 16000)
-            clean16 = audio_io.resample_device(gt_sigs[1].contiguous(), data['sr'], 16000)
-            pesq = pesq_fn(clean16.cpu().numpy(), out16.cpu().numpy(), 16000) if pesq_fn is not None else None
-            stoi = stoi_fn(clean16.cpu().numpy(), out16.cpu().numpy(), 16000) if stoi_fn is not None else None
-            info.update(metrics.evaluate_metrics(out16, clean16, sr=16000, pesq=pesq, stoi=stoi))
-        if save_individual_results:
-            save_dir = os.path.join(os.path.abspath(outputs), convert_snr_to_suffix2(snr)[1:], str(data['id']))
-            ensure_dir(save_dir)
-            host = sigs.cpu().numpy()
-            for k, name in enumerate(('noisy_input', 'noise_intervals', 'predicted_full_noise', 'denoised_output')):
-                p = os.path.join(save_dir, name + '.wav')
-                audio_io.write_wav(p, host[k], data['sr'])
-                info[name] = p
-            if known:
-                gh = gt_sigs.cpu().numpy()
-                for k, name in enumerate(('ground_truth_full_noise', 'ground_truth_clean_input')):
-                    p = os.path.join(save_dir, name + '.wav')
-                    audio_io.write_wav(p, gh[k][:host.shape[1]], data['sr'])
-                    info[name] = p
-            with open(os.path.join(save_dir, 'stat.json'), 'w') as fp:
-                json.dump(info, fp, **JSON_DUMP_PARAMS)
+            if not batch_metrics:
+                out16 = audio_io.resample_device(sigs[3].contiguous(), data['sr'], 16000)
+                clean16 = audio_io.resample_device(gt_sigs[1].contiguous(), data['sr'], 16000)
+                pesq = pesq_fn(clean16.cpu().numpy(), out16.cpu().numpy(), 16000) if pesq_fn is not None else None
+                stoi = stoi_fn(clean16.cpu().numpy(), out16.cpu().numpy(), 16000) if stoi_fn is not None else None
+                info.update(metrics.evaluate_metrics(out16, clean16, sr=16000, pesq=pesq, stoi=stoi))
+        work.append((data, info, sigs, gt_sigs))
+        if not batch_metrics:
+            _write_individual(*work.pop(), outputs, snr, save_individual_results)
         stat.append(info)
+    if batch_metrics:
+        _batch_measures([w for w in work if w[3] is not None], pesq_fn, stoi_fn)
+        for w in work:
+            _write_individual(*w, outputs, snr, save_individual_results)
     if save_stat:
         if stat and 'l1' in stat[0]:
             keys = ('l1', 'stoi', 'csig', 'cbak', 'covl', 'pesq', 'ssnr_regular', 'ssnr_shift', 'ssnr_clip', 'ssnr_exsi', 'overall_snr')
