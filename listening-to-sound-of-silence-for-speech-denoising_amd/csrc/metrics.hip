@@ -4,7 +4,7 @@
 // energies, LPC log-likelihood ratios, weighted spectral slope distances); the few-thousand-element finalisation
 // (log10 / clamp / mean / trimmed mean / composite formulas) is host code in sos_amd/metrics.py.
 // Frames: start = f * skip, `winlength` samples, window w[i] = 0.5 (1 - cos(2 pi (i+1) / (winlength+1))).
-#include "metrics_frame.h"           // MT, block_sum and the per-frame arithmetic shared with metrics_batch.hip
+#include "metrics_frame.h"           // the per-frame arithmetic shared with metrics_batch.hip; MT and the block reductions
 
 // out[0] = sum ref^2, out[1] = sum (ref - deg)^2, out[2] = max |ref|   (single workgroup: evaluation sizes)
 __global__ __launch_bounds__(MT) void metric_totals_kernel(const float* __restrict__ ref, const float* __restrict__ deg,
@@ -16,14 +16,8 @@ __global__ __launch_bounds__(MT) void metric_totals_kernel(const float* __restri
         a += r * r; b += d * d;
         m = fmax(m, fabs(r));
     }
-    const double sa = block_sum(a, red), sb = block_sum(b, red);
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = MT / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[0] = sa; out[1] = sb; out[2] = red[0]; }
+    const double sa = block_sum(a, red), sb = block_sum(b, red), sm = block_max(m, red);
+    if (threadIdx.x == 0) { out[0] = sa; out[1] = sb; out[2] = sm; }
 }
 
 // one workgroup per frame: out[f][0] = sum (w c)^2, out[f][1] = sum (w c - w p)^2
@@ -48,15 +42,8 @@ __global__ __launch_bounds__(MT) void metric_compact_kernel(const float* __restr
     for (long long c0 = 0; c0 < n; c0 += MT) {
         const long long i = c0 + threadIdx.x;
         const int keep = (i < n && !(fabsf(clean[i]) < thr)) ? 1 : 0;
-        scan[threadIdx.x] = keep;
-        __syncthreads();
-        for (int s = 1; s < MT; s <<= 1) {
-            const int v = threadIdx.x >= s ? scan[threadIdx.x - s] : 0;
-            __syncthreads();
-            scan[threadIdx.x] += v;
-            __syncthreads();
-        }
-        if (keep) { const long long o = base + scan[threadIdx.x] - 1; oc[o] = clean[i]; op[o] = proc[i]; }
+        const int incl = block_scan_incl(keep, scan);
+        if (keep) { const long long o = base + incl - 1; oc[o] = clean[i]; op[o] = proc[i]; }
         __syncthreads();
         if (threadIdx.x == 0) base += scan[MT - 1];
         __syncthreads();

@@ -15,7 +15,6 @@
 // Every value a clip gets depends on that clip's samples only (chunking and summation order are functions of the clip's
 // length; no atomics, no cross-clip reductions), so a clip gets the same bits alone, in any batch and in any order.
 #include "metrics_frame.h"
-#include <algorithm>
 
 #define MB_CHUNK 4096                   // samples per workgroup of the sample-wide stages
 #define MB_PER_THREAD (MB_CHUNK / MT)
@@ -32,7 +31,8 @@ __host__ __device__ static inline int64_t mb_num_frames(int64_t n, int winlength
 __host__ __device__ static inline int64_t mb_num_chunks(int64_t n) { return (n + MB_CHUNK - 1) / MB_CHUNK; }
 
 // info[b] = {in_off, n, c_off, chunks, f_off, F, 0, 0, status}: chunk-indexed arrays start at c_off, frame-indexed ones at
-// f_off.  A clip whose extent would overrun what the host sized from its copy of the lengths gets status -1 and no work.
+// f_off.  A clip outside the s_cap samples the host summed (ragged_clip_inside), or whose chunks or frames would overrun what
+// the host sized from its copy of the lengths, gets status -1 and no work.
 __global__ void mb_plan_kernel(const int64_t* __restrict__ offsets, const int64_t* __restrict__ lengths, int nclips, int winlength,
                                int skip, int64_t s_cap, int64_t c_cap, int64_t f_cap, int64_t* __restrict__ info) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -41,7 +41,7 @@ __global__ void mb_plan_kernel(const int64_t* __restrict__ offsets, const int64_
         int64_t* ci = info + (int64_t)b * MB_INFO;
         const int64_t n = lengths[b] > 0 ? lengths[b] : 0, off = offsets[b];
         const int64_t chunks = mb_num_chunks(n), F = mb_num_frames(n, winlength, skip);
-        const bool ok = off >= 0 && off <= s_cap && n <= s_cap - off && c + chunks <= c_cap && f + F <= f_cap &&
+        const bool ok = ragged_clip_inside(off, n, s_cap) && c + chunks <= c_cap && f + F <= f_cap &&
                         (F == 0 || (F - 1) * skip + winlength <= n);
         ci[0] = ok ? off : 0;
         ci[1] = ok ? n : 0;
@@ -54,31 +54,6 @@ __global__ void mb_plan_kernel(const int64_t* __restrict__ offsets, const int64_
         ci[8] = ok ? 0 : -1;
         if (ok) { c += chunks; f += F; }
     }
-}
-
-__device__ static inline double block_max(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = MT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// inclusive scan of one int per thread over the workgroup (scan: int [MT]); returns this thread's inclusive value
-__device__ static inline int block_scan_incl(int v, int* scan) {
-    scan[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 1; s < MT; s <<= 1) {
-        const int u = (int)threadIdx.x >= s ? scan[threadIdx.x - s] : 0;
-        __syncthreads();
-        scan[threadIdx.x] += u;
-        __syncthreads();
-    }
-    return scan[threadIdx.x];
 }
 
 // grid (chunks of the longest clip, clips): part[c_off + chunk] = {sum c^2, sum (c-n)^2, max |c|, sum |n-c|} of the chunk
@@ -271,7 +246,6 @@ struct MbLayout {
     size_t info = 0, part = 0, cnt = 0, oc = 0, op = 0, bytes = 0;        // workspace
     size_t head = 0, energy = 0, energy_kept = 0, llr = 0, wss = 0, out_bytes = 0;   // packed output
 };
-size_t mb_align(size_t v) { return (v + 255) & ~(size_t)255; }
 MbLayout mb_layout(const int64_t* lengths, int nclips, int winlength, int skip) {
     MbLayout l;
     for (int b = 0; b < nclips; ++b) {
@@ -280,14 +254,14 @@ MbLayout mb_layout(const int64_t* lengths, int nclips, int winlength, int skip) 
         l.max_c = std::max(l.max_c, c);
         l.max_f = std::max(l.max_f, f);
     }
+    RaggedBump ws;
+    l.info = ws.take((size_t)nclips * MB_INFO * 8);
+    l.part = ws.take((size_t)l.c_total * 4 * 8);
+    l.cnt = ws.take((size_t)l.c_total * 8);
+    l.oc = ws.take((size_t)l.s_total * 4);
+    l.op = ws.take((size_t)l.s_total * 4);
+    l.bytes = ws.o;
     size_t o = 0;
-    l.info = o; o = mb_align(o + (size_t)nclips * MB_INFO * 8);
-    l.part = o; o = mb_align(o + (size_t)l.c_total * 4 * 8);
-    l.cnt = o;  o = mb_align(o + (size_t)l.c_total * 8);
-    l.oc = o;   o = mb_align(o + (size_t)l.s_total * 4);
-    l.op = o;   o = mb_align(o + (size_t)l.s_total * 4);
-    l.bytes = o;
-    o = 0;
     l.head = o;        o += (size_t)nclips * MB_HEAD * 8;
     l.energy = o;      o += (size_t)l.f_total * 2 * 8;
     l.energy_kept = o; o += (size_t)l.f_total * 2 * 8;
@@ -297,11 +271,9 @@ MbLayout mb_layout(const int64_t* lengths, int nclips, int winlength, int skip) 
     return l;
 }
 bool mb_args_ok(const int64_t* lengths, int nclips, int winlength, int skip, int n_fft) {
-    return lengths && nclips > 0 && nclips <= 65535 && winlength > 0 && skip > 0 && n_fft >= 2 * winlength &&
-           (n_fft & (n_fft - 1)) == 0;
+    return ragged_clips_ok(lengths, nclips) && winlength > 0 && skip > 0 && n_fft >= 2 * winlength && (n_fft & (n_fft - 1)) == 0;
 }
 size_t mb_frame_lds(int winlength, int n_fft) { return ((size_t)2 * winlength + 3 * (size_t)n_fft) * 4; }
-unsigned mb_grid(int64_t units) { return (unsigned)std::min<int64_t>(std::max<int64_t>(units, 1), 0x7fffffff); }
 }  // namespace
 
 extern "C" int64_t sos_metric_batch_workspace_bytes(const int64_t* lengths, int nclips, int winlength, int skip, int n_fft) {
@@ -346,8 +318,8 @@ extern "C" int sos_metric_batch(const float* clean, const float* noisy, const in
     float* llr = (float*)(ob + l.llr);
     float* wss = (float*)(ob + l.wss);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 chunk_grid(mb_grid(l.max_c), nclips);
-    const dim3 frame_grid(mb_grid((l.max_f + MB_FRAMES_PER_WG - 1) / MB_FRAMES_PER_WG), nclips);
+    const dim3 chunk_grid(ragged_grid(l.max_c, 1, 0x7fffffff), nclips);
+    const dim3 frame_grid(ragged_grid(l.max_f, MB_FRAMES_PER_WG, 0x7fffffff), nclips);
     int rc;
     hipLaunchKernelGGL(mb_plan_kernel, dim3(1), dim3(64), 0, s, offsets, lengths, nclips, winlength, skip, l.s_total, l.c_total,
                        l.f_total, info);

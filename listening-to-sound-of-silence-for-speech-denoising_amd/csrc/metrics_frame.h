@@ -4,24 +4,10 @@
 // of the round-1 kernels, so both callers return the same bits for the same frame.  LDS is handed in by the caller.
 // Frames: `winlength` samples under w[i] = 0.5 (1 - cos(2 pi (i+1) / (winlength+1))) (`window`, f64).
 #pragma once
-#include "sos_common.h"
+#include "ragged.h"                  // MT, block_sum / block_max / block_scan_incl
 
-#define MT 256
 #define LLR_MAXP 16
 #define WSS_NCRIT 25
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = MT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
 
 // sa = sum (w c)^2, sb = sum (w c - w p)^2 (on every thread); red: f64 [MT]
 __device__ __forceinline__ void metric_frame_energy(const float* __restrict__ ref, const float* __restrict__ deg, int winlength,

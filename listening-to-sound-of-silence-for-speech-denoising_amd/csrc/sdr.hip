@@ -14,8 +14,7 @@
 //   sdr_solve_kernel    per clip: partials summed in chunk order, Levinson-Durbin for a general right-hand side in LDS
 // A chunk is a fixed 4096 samples from the clip's start and every reduction has a fixed shape, so a clip's bits depend on that
 // clip's samples only: the same alone, in any batch and in any order.  No atomics.
-#include "sos_common.h"
-#include <algorithm>
+#include "ragged.h"
 
 #define SD 256
 #define SD_CHUNK 4096                   // samples per chunk
@@ -42,8 +41,8 @@ __device__ static inline double sdr_block_sum(double v, double* red4) {
     return ((red4[0] + red4[1]) + red4[2]) + red4[3];
 }
 
-// A clip whose samples would leave the buffers (total = what lengths_host summed to) or whose chunks would overrun the
-// workspace sized from lengths_host gets status -1 and no work.
+// A clip outside the `total` samples lengths_host summed to (ragged_clip_inside), an empty one, or one whose chunks would
+// overrun the workspace sized from lengths_host gets status -1 and no work.
 __global__ void sdr_plan_kernel(const int64_t* __restrict__ offsets, const int64_t* __restrict__ lengths, int nclips, int64_t total,
                                 int64_t chunk_cap, int64_t* __restrict__ info) {
     if (threadIdx.x != 0) return;
@@ -51,7 +50,7 @@ __global__ void sdr_plan_kernel(const int64_t* __restrict__ offsets, const int64
     for (int b = 0; b < nclips; ++b) {
         int64_t* ci = info + (int64_t)b * SD_INFO;
         const int64_t off = offsets[b], n = lengths[b];
-        const bool ok = n > 0 && off >= 0 && n <= total && off <= total - n && c + sdr_chunks(n) <= chunk_cap;
+        const bool ok = n > 0 && ragged_clip_inside(off, n, total) && c + sdr_chunks(n) <= chunk_cap;
         ci[0] = ok ? off : 0;
         ci[1] = ok ? n : 0;
         ci[2] = c;
@@ -293,7 +292,6 @@ struct SdrLayout {
     int64_t total = 0, chunks = 0, max_chunks = 0;
     size_t info = 0, mom = 0, stat = 0, res = 0, part = 0, ysq = 0, bytes = 0;
 };
-size_t sdr_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // filter_length 0: the SI-SDR sequence's arrays; 1 .. 512: the SDR sequence's
 SdrLayout sdr_layout(const int64_t* lengths, int nclips, int filter_length) {
     SdrLayout l;
@@ -303,25 +301,24 @@ SdrLayout sdr_layout(const int64_t* lengths, int nclips, int filter_length) {
         l.chunks += sdr_chunks(n);
         l.max_chunks = std::max(l.max_chunks, sdr_chunks(n));
     }
-    size_t o = 0;
-    l.info = o; o = sdr_align256(o + (size_t)nclips * SD_INFO * 8);
+    RaggedBump ws;
+    l.info = ws.take((size_t)nclips * SD_INFO * 8);
     if (filter_length == 0) {
-        l.mom = o;  o = sdr_align256(o + (size_t)l.chunks * SD_MOM * 8);
-        l.stat = o; o = sdr_align256(o + (size_t)nclips * SD_STAT * 8);
-        l.res = o;  o = sdr_align256(o + (size_t)l.chunks * 2 * 8);
+        l.mom = ws.take((size_t)l.chunks * SD_MOM * 8);
+        l.stat = ws.take((size_t)nclips * SD_STAT * 8);
+        l.res = ws.take((size_t)l.chunks * 2 * 8);
     } else {
-        l.part = o; o = sdr_align256(o + (size_t)l.chunks * 2 * SD_LMAX * 8);
-        l.ysq = o;  o = sdr_align256(o + (size_t)l.chunks * 8);
+        l.part = ws.take((size_t)l.chunks * 2 * SD_LMAX * 8);
+        l.ysq = ws.take((size_t)l.chunks * 8);
     }
-    l.bytes = o;
+    l.bytes = ws.o;
     return l;
 }
-unsigned sdr_grid_x(int64_t chunks) { return (unsigned)std::min<int64_t>(std::max<int64_t>(chunks, 1), SD_MAX_GRID); }
-bool sdr_lengths_ok(const int64_t* lengths, int nclips) { return lengths && nclips > 0 && nclips <= 65535; }
+unsigned sdr_grid_x(int64_t chunks) { return ragged_grid(chunks, 1, SD_MAX_GRID); }
 }  // namespace
 
 extern "C" int64_t sos_sdr_workspace_bytes(const int64_t* lengths_host, int nclips, int filter_length) {
-    if (!sdr_lengths_ok(lengths_host, nclips) || filter_length < 0 || filter_length > SD_LMAX) {
+    if (!ragged_clips_ok(lengths_host, nclips) || filter_length < 0 || filter_length > SD_LMAX) {
         sos_set_error("sos_sdr_workspace_bytes: bad args (1 .. 65535 clips, filter_length 0 .. %d)", SD_LMAX);
         return -1;
     }
@@ -332,7 +329,7 @@ extern "C" int sos_sisdr_batch(const float* x, const float* y, const int64_t* of
                                const int64_t* lengths_host, int nclips, int zero_mean, void* workspace, int64_t workspace_bytes,
                                double* out, sos_stream_t stream) {
     if (!x || !y || !offsets || !lengths || !workspace || !out) { sos_set_error("sos_sisdr_batch: null pointer"); return SOS_EINVAL; }
-    if (!sdr_lengths_ok(lengths_host, nclips) || (zero_mean != 0 && zero_mean != 1)) {
+    if (!ragged_clips_ok(lengths_host, nclips) || (zero_mean != 0 && zero_mean != 1)) {
         sos_set_error("sos_sisdr_batch: bad args (1 .. 65535 clips, zero_mean 0 or 1)");
         return SOS_EINVAL;
     }
@@ -371,7 +368,7 @@ extern "C" int sos_sdr_batch(const float* x, const float* y, const int64_t* offs
                              const int64_t* lengths_host, int nclips, int filter_length, int stages, void* workspace,
                              int64_t workspace_bytes, double* out, sos_stream_t stream) {
     if (!x || !y || !offsets || !lengths || !workspace || !out) { sos_set_error("sos_sdr_batch: null pointer"); return SOS_EINVAL; }
-    if (!sdr_lengths_ok(lengths_host, nclips) || filter_length < 1 || filter_length > SD_LMAX || stages < 1 || stages > 3) {
+    if (!ragged_clips_ok(lengths_host, nclips) || filter_length < 1 || filter_length > SD_LMAX || stages < 1 || stages > 3) {
         sos_set_error("sos_sdr_batch: bad args (1 .. 65535 clips, filter_length 1 .. %d, got %d; stages 1 .. 3)", SD_LMAX,
                       filter_length);
         return SOS_EINVAL;

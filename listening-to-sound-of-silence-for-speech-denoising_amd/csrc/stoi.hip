@@ -10,10 +10,9 @@
 //   stoi_sum_kernel       per clip: one fixed-order f64 sum over its segments -> out[b] = {sum, segments, kept_frames}
 // Every value a clip gets depends on that clip's samples only (no atomics, no cross-clip reductions), so a clip scores the
 // same bits alone, in any batch and in any order.
-#include "sos_common.h"
-#include <algorithm>
+#include "ragged.h"
 
-#define ST 256
+#define ST MT                           // 256 threads: the block reductions of ragged.h
 #define ST_FRAME 256
 #define ST_HOP 128
 #define ST_NFFT 512
@@ -43,33 +42,22 @@ __device__ static inline double half_wave_sum(double v) {           // over the 
     return v;
 }
 
-__device__ static inline double block_sum_d(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = ST / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // info[b] = {in_off, n, sig_off, n10, f_off, F, K = 0, status}: the signal the frames read starts at sig_off (the input
-// itself at 10 kHz, else the resampled copy), frame-indexed arrays at f_off.  A clip whose extent would overrun the
-// workspace sized from the host's lengths gets status -1 and no work.
+// itself at 10 kHz, else the resampled copy), frame-indexed arrays at f_off.  A clip outside the s_cap samples the host
+// summed (ragged_clip_inside), or whose extent would overrun the workspace sized from the host's lengths, gets status -1 and
+// no work.
 __global__ void stoi_plan_kernel(const int64_t* __restrict__ offsets, const int64_t* __restrict__ lengths, int nclips, int p, int q,
-                                 int64_t r_cap, int64_t f_cap, int64_t* __restrict__ info) {
+                                 int64_t s_cap, int64_t r_cap, int64_t f_cap, int64_t* __restrict__ info) {
     if (threadIdx.x != 0) return;
     int64_t r = 0, f = 0;
     for (int b = 0; b < nclips; ++b) {
         int64_t* ci = info + (int64_t)b * ST_INFO;
-        const int64_t n = lengths[b] > 0 ? lengths[b] : 0;
+        const int64_t n = lengths[b] > 0 ? lengths[b] : 0, off = offsets[b];
         const int64_t n10 = stoi_n10(n, p, q), F = stoi_nframes(n10);
-        const bool ok = (p == q || r + n10 <= r_cap) && f + F <= f_cap;
-        ci[0] = offsets[b];
+        const bool ok = ragged_clip_inside(off, n, s_cap) && (p == q || r + n10 <= r_cap) && f + F <= f_cap;
+        ci[0] = ok ? off : 0;
         ci[1] = ok ? n : 0;
-        ci[2] = p == q ? offsets[b] : r;
+        ci[2] = p == q ? ci[0] : r;
         ci[3] = ok ? n10 : 0;
         ci[4] = f;
         ci[5] = ok ? F : 0;
@@ -299,7 +287,7 @@ __global__ __launch_bounds__(ST) void stoi_sum_kernel(const int64_t* __restrict_
     const int64_t S = K - 1 - (ST_NSEG - 1) > 0 ? K - 1 - (ST_NSEG - 1) : 0;
     double a = 0;
     for (int64_t s = threadIdx.x; s < S; s += ST) a += segv[f_off + s];
-    const double tot = block_sum_d(a, red);
+    const double tot = block_sum(a, red);
     if (threadIdx.x == 0) {
         out[3 * blockIdx.x] = tot;
         out[3 * blockIdx.x + 1] = (double)S;
@@ -309,36 +297,33 @@ __global__ __launch_bounds__(ST) void stoi_sum_kernel(const int64_t* __restrict_
 
 namespace {
 struct StoiLayout {
-    int64_t r_total = 0, f_total = 0, max_n10 = 0, max_f = 0;
+    int64_t s_total = 0, r_total = 0, f_total = 0, max_n10 = 0, max_f = 0;
     size_t info = 0, rx = 0, ry = 0, energy = 0, kept = 0, tob = 0, segv = 0, bytes = 0;
 };
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 StoiLayout stoi_layout(const int64_t* lengths, int nclips, int p, int q) {
     StoiLayout l;
     for (int b = 0; b < nclips; ++b) {
-        const int64_t n10 = stoi_n10(lengths[b] > 0 ? lengths[b] : 0, p, q), F = stoi_nframes(n10);
+        const int64_t n = lengths[b] > 0 ? lengths[b] : 0, n10 = stoi_n10(n, p, q), F = stoi_nframes(n10);
+        l.s_total += n;
         l.r_total += p == q ? 0 : n10;
         l.f_total += F;
         l.max_n10 = std::max(l.max_n10, n10);
         l.max_f = std::max(l.max_f, F);
     }
-    size_t o = 0;
-    l.info = o;   o = align256(o + (size_t)nclips * ST_INFO * 8);
-    l.rx = o;     o = align256(o + (size_t)l.r_total * 4);
-    l.ry = o;     o = align256(o + (size_t)l.r_total * 4);
-    l.energy = o; o = align256(o + (size_t)l.f_total * 8);
-    l.kept = o;   o = align256(o + (size_t)l.f_total * 4);
-    l.tob = o;    o = align256(o + (size_t)l.f_total * 2 * ST_NBAND * 8);
-    l.segv = o;   o = align256(o + (size_t)l.f_total * 8);
-    l.bytes = o;
+    RaggedBump ws;
+    l.info = ws.take((size_t)nclips * ST_INFO * 8);
+    l.rx = ws.take((size_t)l.r_total * 4);
+    l.ry = ws.take((size_t)l.r_total * 4);
+    l.energy = ws.take((size_t)l.f_total * 8);
+    l.kept = ws.take((size_t)l.f_total * 4);
+    l.tob = ws.take((size_t)l.f_total * 2 * ST_NBAND * 8);
+    l.segv = ws.take((size_t)l.f_total * 8);
+    l.bytes = ws.o;
     return l;
 }
-unsigned grid_x(int64_t units, int per_block) {
-    const int64_t g = (units + per_block - 1) / per_block;
-    return (unsigned)std::min<int64_t>(std::max<int64_t>(g, 1), ST_MAX_GRID);
-}
+unsigned grid_x(int64_t units, int per_block) { return ragged_grid(units, per_block, ST_MAX_GRID); }
 bool stoi_args_ok(const int64_t* lengths, int nclips, int p, int q) {
-    return lengths && nclips > 0 && nclips <= 65535 && p > 0 && q > 0 && (int64_t)p * q <= (1 << 30);
+    return ragged_clips_ok(lengths, nclips) && p > 0 && q > 0 && (int64_t)p * q <= (1 << 30);
 }
 }  // namespace
 
@@ -370,7 +355,8 @@ extern "C" int sos_stoi_batch(const float* x, const float* y, const int64_t* off
     double* segv = (double*)(ws + l.segv);
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    hipLaunchKernelGGL(stoi_plan_kernel, dim3(1), dim3(64), 0, s, offsets, lengths, nclips, p, q, l.r_total, l.f_total, info);
+    hipLaunchKernelGGL(stoi_plan_kernel, dim3(1), dim3(64), 0, s, offsets, lengths, nclips, p, q, l.s_total, l.r_total,
+                       l.f_total, info);
     if ((rc = sos_check_launch("sos_stoi_batch: plan")) != SOS_OK) return rc;
     const float* sx = x;
     const float* sy = y;

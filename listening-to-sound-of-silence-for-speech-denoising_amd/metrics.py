@@ -21,7 +21,7 @@ arithmetic of the one-clip kernels.  Signals: 1-D numpy arrays or GPU tensors.  
 import ctypes as C
 import math
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -44,15 +44,27 @@ def _dev(x):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float32)).cuda()
 
 
+def _num_frames(n, winlength, skip):
+    """The reference's frame count, evaluated in f64 as it does (not (n - winlength) // skip), clamped at 0."""
+    return max(int(n / skip - (winlength / skip)), 0)
+
+
+def _wss_n_fft(winlength):
+    return int(2 ** np.ceil(np.log(2 * winlength) / np.log(2)))
+
+
+def _lpc_order(srate):
+    return 10 if srate < 10000 else 16
+
+
 def _frame_setup(n, srate, win_ms=30):
     winlength = int(np.round(win_ms * srate / 1000))
     skip = winlength // 4
-    num_frames = int(n / skip - (winlength / skip))
     key = ("win", winlength)
     if key not in _tables:
         time = np.linspace(1, winlength, winlength) / (winlength + 1)
         _tables[key] = torch.from_numpy(0.5 * (1 - np.cos(2 * np.pi * time))).cuda()
-    return winlength, skip, max(num_frames, 0), _tables[key]
+    return winlength, skip, _num_frames(n, winlength, skip), _tables[key]
 
 
 def _totals(ref, deg):
@@ -121,11 +133,10 @@ def metrics_ssnr_exclude_silence(ref_wav, deg_wav, srate=16000, win_len=30, min_
 def llr(ref_wav, deg_wav, srate):
     ref, deg = _same_length(_dev(ref_wav), _dev(deg_wav))
     w, s, nf, win = _frame_setup(ref.numel(), srate)
-    P = 10 if srate < 10000 else 16
     out = torch.empty(max(nf, 1), dtype=torch.float32, device=ref.device)
     if nf:
-        L.check(L.lib().sos_metric_llr(L.ptr(ref), L.ptr(deg), ref.numel(), w, s, nf, L.ptr(win), P, L.ptr(out), L.stream_ptr()),
-                "sos_metric_llr")
+        L.check(L.lib().sos_metric_llr(L.ptr(ref), L.ptr(deg), ref.numel(), w, s, nf, L.ptr(win), _lpc_order(srate), L.ptr(out),
+                                       L.stream_ptr()), "sos_metric_llr")
     return out[:nf].cpu().numpy()
 
 
@@ -149,7 +160,7 @@ def _crit_filters(srate, n_fft, device):
 def wss(ref_wav, deg_wav, srate, eps=1e-10):
     ref, deg = _same_length(_dev(ref_wav), _dev(deg_wav))
     w, s, nf, win = _frame_setup(ref.numel(), srate)
-    n_fft = int(2 ** np.ceil(np.log(2 * w) / np.log(2)))
+    n_fft = _wss_n_fft(w)
     out = torch.empty(max(nf, 1), dtype=torch.float32, device=ref.device)
     if nf:
         cf = _crit_filters(srate, n_fft, ref.device)
@@ -208,8 +219,60 @@ def evaluate_metrics(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None):
     return m
 
 
-_BATCH_MAX_CLIPS = 65535            # clips per launch sequence (the kernels' grid.y)
+# ---- ragged batches of clip pairs: the driver under evaluate_metrics_batch, stoi_batch, si_sdr_batch and sdr_batch
+_MAX_CLIPS = 65535                  # clips per launch sequence (the kernels' grid.y)
 _BATCH_HEAD = 8                     # f64 per clip at the front of sos_metric_batch's packed output (include/sos_hip.h)
+# One launch sequence's worth of pairs: the concatenated device buffers x / y, the host lengths `lens` (int64), the device
+# table `tab` = [offsets, lengths] and `lead` = (x, y, offsets, lengths, lengths_host, nclips), the arguments every
+# sos_*_batch entry point starts with.
+_Chunk = namedtuple("_Chunk", "x y lens tab lead")
+
+
+def _check_pairs(a, b, counted, named, allow_empty=False):
+    """The two lists of signals as lists, after the checks every batch entry point makes: as many of one as of the other, each
+    pair of one shape and (unless allow_empty) no empty clip.  counted / named: what the messages call the two sides."""
+    a, b = list(a), list(b)
+    if len(a) != len(b):
+        raise ValueError(f"{len(a)} {counted[0]} but {len(b)} {counted[1]}")
+    for i, (x, y) in enumerate(zip(a, b)):
+        if tuple(np.shape(x)) != tuple(np.shape(y)):
+            raise ValueError(f"clip {i}: {named[0]} and {named[1]} should have the same length, found {tuple(np.shape(x))} and "
+                             f"{tuple(np.shape(y))}")
+        if not allow_empty and int(np.prod(np.shape(x))) == 0:
+            raise ValueError(f"clip {i} is empty")
+    return a, b
+
+
+def _concat(signals):
+    """One f32 device buffer holding the signals back to back (plus a zero sentinel, so that it is never empty), and
+    their lengths.  numpy inputs go up in one copy; tensors must live on the GPU."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
+    if not any(torch.is_tensor(s) for s in signals):
+        flat = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
+        buf = np.concatenate(flat + [np.zeros(1, np.float32)])
+        return torch.from_numpy(buf).cuda(), [len(f) for f in flat]
+    ts = [_dev(s) for s in signals]
+    return torch.cat(ts + [torch.zeros(1, dtype=torch.float32, device=ts[0].device)]), [t.numel() for t in ts]
+
+
+def _chunks(a, b):
+    """The pairs (a[i], b[i]) as _Chunks of at most _MAX_CLIPS clips, each uploaded when it is asked for."""
+    for c0 in range(0, len(a), _MAX_CLIPS):
+        x, n = _concat(a[c0:c0 + _MAX_CLIPS])
+        y, _ = _concat(b[c0:c0 + _MAX_CLIPS])
+        lens = np.asarray(n, dtype=np.int64)
+        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(x.device)
+        lead = (L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens.ctypes.data_as(C.c_void_p), len(lens))
+        yield _Chunk(x, y, lens, tab, lead)
+
+
+def _workspace(sizer, ch, *params):
+    """The device workspace the library's function `sizer` (a sos_*_workspace_bytes) asks for the chunk's lengths."""
+    nbytes = getattr(L.lib(), sizer)(ch.lead[4], ch.lead[5], *params)
+    if nbytes < 0:
+        L.check(-22, sizer)
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=ch.x.device)
 
 
 def _per_clip(values, nclips, name):
@@ -230,47 +293,30 @@ def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=No
     clip, the frame count, the kept-sample and kept-frame counts of the silence rule (computed on the device) and the
     per-frame LLR, WSS and frame-energy arrays.  si_sdr=True / sdr=True append the keys 'si_sdr' / 'sdr' after 'overall_snr':
     si_sdr_batch / sdr_batch of (clean[i], noisy[i]), their launch sequences enqueued before the call's one wait."""
-    noisy, clean = list(noisy), list(clean)
-    if len(noisy) != len(clean):
-        raise ValueError(f"{len(noisy)} noisy signals but {len(clean)} clean ones")
-    for i, (x, y) in enumerate(zip(noisy, clean)):
-        if tuple(np.shape(x)) != tuple(np.shape(y)):
-            raise ValueError(f"clip {i}: noisy and clean should have the same length, found {tuple(np.shape(x))} and "
-                             f"{tuple(np.shape(y))}")
-        if int(np.prod(np.shape(x))) == 0:
-            raise ValueError(f"clip {i} is empty")
+    noisy, clean = _check_pairs(noisy, clean, ("noisy signals", "clean ones"), ("noisy", "clean"))
     nclips = len(clean)
     pesq = _per_clip(pesq, nclips, "pesq")
     stoi = stoi_batch(clean, noisy, sr) if stoi is True else _per_clip(stoi, nclips, "stoi")
     results, detail = [], []
     if nclips == 0:
         return (results, detail) if return_detail else results
-    h = L.lib()
     outs, plans, base = [], [], 0
-    for c0 in range(0, nclips, _BATCH_MAX_CLIPS):
-        c, n = _concat(clean[c0:c0 + _BATCH_MAX_CLIPS])
-        d, _ = _concat(noisy[c0:c0 + _BATCH_MAX_CLIPS])
-        lens = np.asarray(n, dtype=np.int64)
+    for ch in _chunks(clean, noisy):
+        lens = ch.lens
         w, skip, _, win = _frame_setup(int(lens[0]), sr)
-        frames = np.asarray([max(int(v / skip - (w / skip)), 0) for v in n], dtype=np.int64)
-        n_fft = int(2 ** np.ceil(np.log(2 * w) / np.log(2)))
-        cf = _crit_filters(sr, n_fft, c.device)
-        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(c.device)      # offsets, lengths
-        lens_p = lens.ctypes.data_as(C.c_void_p)
-        nbytes = h.sos_metric_batch_workspace_bytes(lens_p, len(lens), w, skip, n_fft)
-        if nbytes < 0:
-            L.check(-22, "sos_metric_batch_workspace_bytes")
+        frames = np.asarray([_num_frames(int(v), w, skip) for v in lens], dtype=np.int64)
+        n_fft = _wss_n_fft(w)
+        cf = _crit_filters(sr, n_fft, ch.x.device)
+        ws = _workspace("sos_metric_batch_workspace_bytes", ch, w, skip, n_fft)
         ftot = int(frames.sum())
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=c.device)
-        out = torch.empty(8 * _BATCH_HEAD * len(lens) + 40 * ftot, dtype=torch.uint8, device=c.device)
-        L.check(h.sos_metric_batch(L.ptr(c), L.ptr(d), L.ptr(tab[0]), L.ptr(tab[1]), lens_p, len(lens), w, skip, n_fft,
-                                   10 if sr < 10000 else 16, L.ptr(win), L.ptr(cf), float(eps), L.ptr(ws), ws.numel(),
-                                   L.ptr(out), out.numel(), L.stream_ptr()), "sos_metric_batch")
+        out = torch.empty(8 * _BATCH_HEAD * len(lens) + 40 * ftot, dtype=torch.uint8, device=ch.x.device)
+        L.check(L.lib().sos_metric_batch(*ch.lead, w, skip, n_fft, _lpc_order(sr), L.ptr(win), L.ptr(cf), float(eps), L.ptr(ws),
+                                         ws.numel(), L.ptr(out), out.numel(), L.stream_ptr()), "sos_metric_batch")
         outs.append(out)
         extra, pos = [], base + out.numel()          # (key, byte offset in the one copy) of the optional measures
         for key, on, fl in (("si_sdr", si_sdr, None), ("sdr", sdr, SDR_FILTER_LENGTH)):
             if on:
-                outs.append(_sdr_enqueue(c, d, lens, tab, fl).view(torch.uint8).reshape(-1))
+                outs.append(_sdr_enqueue(ch, fl).view(torch.uint8).reshape(-1))
                 extra.append((key, pos))
                 pos += outs[-1].numel()
         plans.append((base, lens, frames, ftot, extra))
@@ -324,7 +370,6 @@ def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=No
 # 30-frame segments, clipping at BETA = -15 dB, 40 dB dynamic range)
 STOI_FS = 10000
 STOI_NUMBAND = 15
-_STOI_MAX_CLIPS = 65535             # clips per launch sequence (the kernels' grid.y)
 
 
 def _stoi_ratio(fs_sig):
@@ -347,51 +392,24 @@ def _stoi_taps(p, q, device):
     return _tables[key]
 
 
-def _concat(signals):
-    """One f32 device buffer holding the signals back to back (plus a zero sentinel, so that it is never empty), and
-    their lengths.  numpy inputs go up in one copy; tensors must live on the GPU."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
-    if not any(torch.is_tensor(s) for s in signals):
-        flat = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
-        buf = np.concatenate(flat + [np.zeros(1, np.float32)])
-        return torch.from_numpy(buf).cuda(), [len(f) for f in flat]
-    ts = [_dev(s) for s in signals]
-    return torch.cat(ts + [torch.zeros(1, dtype=torch.float32, device=ts[0].device)]), [t.numel() for t in ts]
-
-
 def stoi_batch(clean, processed, fs_sig, extended=False, return_frames=False):
     """STOI (or, extended=True, ESTOI) of every pair (clean[i], processed[i]) of 1-D signals sampled at fs_sig; the
     clips may have any lengths, each pair equal.  One launch sequence for the whole batch and one synchronisation at the
     end; a clip's score does not depend on the other clips of the batch.  A clip with fewer than 30 STFT frames after
     silent-frame removal scores 1e-5 with a RuntimeWarning, as pystoi does.  Returns the list of scores, or
     (scores, kept-frame counts) with return_frames=True."""
-    clean, processed = list(clean), list(processed)
-    if len(clean) != len(processed):
-        raise ValueError(f"{len(clean)} clean signals but {len(processed)} processed ones")
-    for i, (x, y) in enumerate(zip(clean, processed)):
-        if tuple(np.shape(x)) != tuple(np.shape(y)):
-            raise ValueError(f"clip {i}: x and y should have the same length, found {tuple(np.shape(x))} and {tuple(np.shape(y))}")
+    clean, processed = _check_pairs(clean, processed, ("clean signals", "processed ones"), ("x", "y"), allow_empty=True)
     p, q = _stoi_ratio(fs_sig)
     scores, frames = [], []
     if not clean:
         return (scores, frames) if return_frames else scores
     outs = []
-    for c0 in range(0, len(clean), _STOI_MAX_CLIPS):
-        x, n = _concat(clean[c0:c0 + _STOI_MAX_CLIPS])
-        y, _ = _concat(processed[c0:c0 + _STOI_MAX_CLIPS])
-        lens = np.asarray(n, dtype=np.int64)
-        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(x.device)      # offsets, lengths
-        taps = _stoi_taps(p, q, x.device) if p != q else None
-        h = L.lib()
-        nbytes = h.sos_stoi_workspace_bytes(lens.ctypes.data_as(C.c_void_p), len(lens), p, q)
-        if nbytes < 0:
-            L.check(-22, "sos_stoi_workspace_bytes")
-        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=x.device)
-        out = torch.empty((len(lens), 3), dtype=torch.float64, device=x.device)
-        L.check(h.sos_stoi_batch(L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens.ctypes.data_as(C.c_void_p), len(lens),
-                                 p, q, L.ptr(taps), 0 if taps is None else taps.numel(), int(bool(extended)), L.ptr(ws),
-                                 ws.numel(), L.ptr(out), L.stream_ptr()), "sos_stoi_batch")
+    for ch in _chunks(clean, processed):
+        taps = _stoi_taps(p, q, ch.x.device) if p != q else None
+        ws = _workspace("sos_stoi_workspace_bytes", ch, p, q)
+        out = torch.empty((len(ch.lens), 3), dtype=torch.float64, device=ch.x.device)
+        L.check(L.lib().sos_stoi_batch(*ch.lead, p, q, L.ptr(taps), 0 if taps is None else taps.numel(), int(bool(extended)),
+                                       L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()), "sos_stoi_batch")
         outs.append(out)
     res = torch.cat(outs).cpu().numpy()
     for total, segments, kept in res:
@@ -417,30 +435,23 @@ def stoi(x, y, fs_sig, extended=False):
 
 # ---- SI-SDR and the BSS-eval SDR (csrc/sdr.hip)
 SDR_FILTER_LENGTH = 512             # mir_eval's bss_eval_sources: taps of the allowed distortion filter; the kernels' maximum
-_SDR_MAX_CLIPS = 65535              # clips per launch sequence (the kernels' grid.y)
 _SDR_OUT = {"si_sdr": 4, "sdr": 5}  # f64 per clip of sos_sisdr_batch / sos_sdr_batch (include/sos_hip.h)
 
 
-def _sdr_enqueue(x, y, lens, tab, filter_length=None, zero_mean=False, stages=L.SDR_CORRELATE | L.SDR_SOLVE, ws=None):
-    """Enqueue sos_sisdr_batch (filter_length None) or sos_sdr_batch on the concatenated clips x (clean) and y (estimate) with
-    host lengths `lens` (int64 array) and the device table `tab` = [offsets, lengths]; no wait.  Returns the f64 [clips][4]
-    or [clips][5] device result (include/sos_hip.h).  `stages` / `ws`: one part of the SDR sequence on a workspace the caller
-    keeps (tools/sdr_bench.py times the correlation and the solve apart)."""
-    h = L.lib()
-    lens_p = lens.ctypes.data_as(C.c_void_p)
+def _sdr_enqueue(ch, filter_length=None, zero_mean=False, stages=L.SDR_CORRELATE | L.SDR_SOLVE, ws=None):
+    """Enqueue sos_sisdr_batch (filter_length None) or sos_sdr_batch on the _Chunk `ch` of (clean, estimate) pairs; no wait.
+    Returns the f64 [clips][4] or [clips][5] device result (include/sos_hip.h).  `stages` / `ws`: one part of the SDR sequence on
+    a workspace the caller keeps (tools/sdr_bench.py times the correlation and the solve apart)."""
+    h, si = L.lib(), filter_length is None
     if ws is None:
-        nbytes = h.sos_sdr_workspace_bytes(lens_p, len(lens), 0 if filter_length is None else int(filter_length))
-        if nbytes < 0:
-            L.check(-22, "sos_sdr_workspace_bytes")
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
-    if filter_length is None:
-        out = torch.empty((len(lens), _SDR_OUT["si_sdr"]), dtype=torch.float64, device=x.device)
-        L.check(h.sos_sisdr_batch(L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens_p, len(lens), int(bool(zero_mean)),
-                                  L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()), "sos_sisdr_batch")
+        ws = _workspace("sos_sdr_workspace_bytes", ch, 0 if si else int(filter_length))
+    out = torch.empty((len(ch.lens), _SDR_OUT["si_sdr" if si else "sdr"]), dtype=torch.float64, device=ch.x.device)
+    if si:
+        L.check(h.sos_sisdr_batch(*ch.lead, int(bool(zero_mean)), L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()),
+                "sos_sisdr_batch")
     else:
-        out = torch.empty((len(lens), _SDR_OUT["sdr"]), dtype=torch.float64, device=x.device)
-        L.check(h.sos_sdr_batch(L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens_p, len(lens), int(filter_length),
-                                int(stages), L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()), "sos_sdr_batch")
+        L.check(h.sos_sdr_batch(*ch.lead, int(filter_length), int(stages), L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()),
+                "sos_sdr_batch")
     return out
 
 
@@ -471,29 +482,13 @@ def _sdr_finish(rows, lens, first_clip=0):
     return scores, detail
 
 
-def _sdr_pairs(clean, estimate):
-    clean, estimate = list(clean), list(estimate)
-    if len(clean) != len(estimate):
-        raise ValueError(f"{len(clean)} clean signals but {len(estimate)} estimates")
-    for i, (x, y) in enumerate(zip(clean, estimate)):
-        if tuple(np.shape(x)) != tuple(np.shape(y)):
-            raise ValueError(f"clip {i}: clean and estimate should have the same length, found {tuple(np.shape(x))} and "
-                             f"{tuple(np.shape(y))}")
-        if int(np.prod(np.shape(x))) == 0:
-            raise ValueError(f"clip {i} is empty")
-    return clean, estimate
-
-
 def _sdr_run(clean, estimate, key, filter_length=None, zero_mean=False):
-    """The f64 result rows and host lengths of the whole batch: one launch sequence per 65535 clips, one wait."""
+    """The f64 result rows and host lengths of the whole batch: the pairs checked, one launch sequence per 65535 clips, one wait."""
+    clean, estimate = _check_pairs(clean, estimate, ("clean signals", "estimates"), ("clean", "estimate"))
     outs, lens_all = [], []
-    for c0 in range(0, len(clean), _SDR_MAX_CLIPS):
-        x, n = _concat(clean[c0:c0 + _SDR_MAX_CLIPS])
-        y, _ = _concat(estimate[c0:c0 + _SDR_MAX_CLIPS])
-        lens = np.asarray(n, dtype=np.int64)
-        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(x.device)      # offsets, lengths
-        outs.append(_sdr_enqueue(x, y, lens, tab, filter_length, zero_mean))
-        lens_all.append(lens)
+    for ch in _chunks(clean, estimate):
+        outs.append(_sdr_enqueue(ch, filter_length, zero_mean))
+        lens_all.append(ch.lens)
     rows = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu().numpy() if outs else np.zeros((0, _SDR_OUT[key]))
     return rows, np.concatenate(lens_all) if lens_all else np.zeros(0, np.int64)
 
@@ -504,7 +499,6 @@ def si_sdr_batch(clean, estimate, zero_mean=False):
     <y,x> / (<x,x> + 1e-30), 10 log10((|alpha x|^2 + 1e-30) / (|alpha x - y|^2 + 1e-30)); zero_mean=True removes each
     signal's mean first.  Float64 sums on the device, one launch sequence and one wait for the batch; a clip's value does not
     depend on the other clips.  Returns the list of floats."""
-    clean, estimate = _sdr_pairs(clean, estimate)
     return _si_sdr_finish(*_sdr_run(clean, estimate, "si_sdr", None, zero_mean))
 
 
@@ -523,7 +517,6 @@ def sdr_batch(clean, estimate, filter_length=SDR_FILTER_LENGTH, return_detail=Fa
     Returns the list of floats, or (scores, detail) with per clip dict(p, e, r0, status) when return_detail=True."""
     if isinstance(filter_length, bool) or int(filter_length) != filter_length or not 1 <= filter_length <= SDR_FILTER_LENGTH:
         raise ValueError(f"filter_length must be an integer in 1 .. {SDR_FILTER_LENGTH}, got {filter_length!r}")
-    clean, estimate = _sdr_pairs(clean, estimate)
     scores, detail = _sdr_finish(*_sdr_run(clean, estimate, "sdr", int(filter_length)))
     return (scores, detail) if return_detail else scores
 

@@ -166,6 +166,39 @@ def test_wgrad_tune_validates_like_the_launch(field, value, message):
     assert best.value == 7.0                                    # refused: nothing was measured, nothing written
 
 
+# lengths list -> (sdr filter_length 0, 512; stoi (p, q) = (1, 1), (5, 8); metric batch at 8 kHz (240, 60, 512), at 16 kHz (480, 120, 1024))
+RAGGED_WORKSPACE_BYTES = {
+    "one_sample": (1024, 8704, 256, 768, 1280, 1280),
+    "one_chunk": (1024, 8704, 8448, 25856, 33536, 33536),
+    "three": (2048, 353024, 333056, 1029120, 1315584, 1315584),
+    "mixed_300": (212736, 48859648, 48235008, 149080832, 190613760, 190613760),
+}
+
+
+def test_ragged_workspace_sizes_are_the_recorded_ones():
+    """sos_sdr_workspace_bytes, sos_stoi_workspace_bytes and sos_metric_batch_workspace_bytes (host only) lay their arrays out
+    with one shared helper (csrc/ragged.h).  The expected byte counts are literals: the same calls were made against the library
+    of the commit before the shared header, on a CPU, and every offset and total was to stay that number."""
+    import ctypes as C
+    import numpy as np
+    from sos_amd import _lib
+    h = _lib.lib()
+    lists = {"one_sample": [1], "one_chunk": [4096], "three": [4097, 1, 160000],
+             "mixed_300": [int(v) for v in np.random.default_rng(11).integers(1, 160001, size=300)]}
+    assert set(lists) == set(RAGGED_WORKSPACE_BYTES)
+    for name, ls in lists.items():
+        a = np.asarray(ls, dtype=np.int64)
+        p, n = a.ctypes.data_as(C.c_void_p), len(a)
+        got = (h.sos_sdr_workspace_bytes(p, n, 0), h.sos_sdr_workspace_bytes(p, n, 512),
+               h.sos_stoi_workspace_bytes(p, n, 1, 1), h.sos_stoi_workspace_bytes(p, n, 5, 8),
+               h.sos_metric_batch_workspace_bytes(p, n, 240, 60, 512), h.sos_metric_batch_workspace_bytes(p, n, 480, 120, 1024))
+        assert got == RAGGED_WORKSPACE_BYTES[name], (name, got)
+    for bad_p, bad_n in ((p, 0), (p, 65536), (None, 3)):
+        assert h.sos_sdr_workspace_bytes(bad_p, bad_n, 512) == -1
+        assert h.sos_stoi_workspace_bytes(bad_p, bad_n, 5, 8) == -1
+        assert h.sos_metric_batch_workspace_bytes(bad_p, bad_n, 480, 120, 1024) == -1
+
+
 def test_state_dict_keys_match_reference_layout():
     from sos_amd.detector import networks as dnet
     from sos_amd.denoiser import networks as jnet

@@ -127,11 +127,37 @@ def test_chunks_of_a_large_batch_give_the_same_bits(ragged, monkeypatch):
     """More clips than one launch sequence takes (65535) go in chunks; exercised with a chunk size of 5."""
     from sos_amd import metrics as M
     clean, noisy, results, detail = ragged
-    monkeypatch.setattr(M, "_BATCH_MAX_CLIPS", 5)
+    monkeypatch.setattr(M, "_MAX_CLIPS", 5)
     rc, dc = M.evaluate_metrics_batch(noisy[:12], clean[:12], sr=SR, pesq=[2.7] * 12, return_detail=True)
     for i in range(12):
         _same_result(rc[i], results[i])
         _same_detail(dc[i], detail[i])
+
+
+def test_device_table_entries_outside_the_hosts_lengths_are_not_followed():
+    """sos_metric_batch called directly: the kernels take offsets and lengths from the device table, and a clip that leaves the
+    samples the host's lengths sum to gets status -1 and no work (csrc/ragged.h); the clip before it is scored.  The overrun by
+    one sample lies inside the allocation."""
+    import ctypes as C
+    import torch
+    from sos_amd import _lib as L
+    from sos_amd import metrics as M
+    h = L.lib()
+    lens = np.asarray([5000, 9000], dtype=np.int64)
+    lp = lens.ctypes.data_as(C.c_void_p)
+    buf = torch.zeros(14001, device="cuda")
+    tab = torch.tensor([[0, 5000], [5000, 9001]], dtype=torch.int64, device="cuda")         # the second clip overruns
+    w, skip, f0, win = M._frame_setup(5000, SR)
+    n_fft = 1024
+    assert (w, skip, f0, M._frame_setup(9000, SR)[2]) == (480, 120, 37, 71)
+    cf = M._crit_filters(SR, n_fft, buf.device)
+    need = h.sos_metric_batch_workspace_bytes(lp, 2, w, skip, n_fft)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    out = torch.zeros(8 * 8 * 2 + 40 * (37 + 71), dtype=torch.uint8, device="cuda")
+    assert h.sos_metric_batch(L.ptr(buf), L.ptr(buf), L.ptr(tab[0]), L.ptr(tab[1]), lp, 2, w, skip, n_fft, 16, L.ptr(win), L.ptr(cf),
+                              1e-20, L.ptr(ws), need, L.ptr(out), out.numel(), L.stream_ptr()) == 0
+    head = np.frombuffer(out.cpu().numpy(), np.float64, 16).reshape(2, 8)
+    assert head[0][7] == 0 and head[0][6] == 37 and head[1][7] == -1, head
 
 
 def test_frame_count_is_the_references_f64_expression():

@@ -245,6 +245,20 @@ def test_device_lengths_that_disagree_with_the_host_are_refused():
     assert o[0, 4] == 5000 and o[1, 4] == -1 and o[1, 3] == -1
 
 
+def test_chunks_of_a_large_batch_give_the_same_bits(monkeypatch):
+    """More clips than one launch sequence takes (65535) go in chunks; exercised with 7 clips in chunks of 3."""
+    from sos_amd import metrics
+    pairs = [closed_form_pair(400 + 2 * i, 5000 + 900 * i, 16000, 0.1) for i in range(7)]
+    xs, ys = [p[0] for p in pairs], [p[1] for p in pairs]
+    want = metrics.sdr_batch(xs, ys, filter_length=64)
+    want_si = {zm: metrics.si_sdr_batch(xs, ys, zm) for zm in (False, True)}
+    assert all(np.isfinite(v) for v in want + want_si[False] + want_si[True])
+    monkeypatch.setattr(metrics, "_MAX_CLIPS", 3)
+    assert metrics.sdr_batch(xs, ys, filter_length=64) == want
+    for zm in (False, True):
+        assert metrics.si_sdr_batch(xs, ys, zm) == want_si[zm]
+
+
 def test_gpu_tensors_give_the_numpy_result():
     from sos_amd import metrics
     x, y = closed_form_pair(71, 48000, 16000, 0.1)

@@ -81,6 +81,45 @@ def test_clip_silent_but_for_a_burst_is_scored_on_the_burst(extended):
     assert kept == [want["kept_frames"]] and abs(got[0] - want["score"]) < TOL
 
 
+@pytest.mark.parametrize("extended", [False, True])
+def test_chunks_of_a_large_batch_give_the_same_bits(extended, monkeypatch):
+    """More clips than one launch sequence takes (65535) go in chunks; exercised with 7 clips in chunks of 3.  Every clip keeps
+    at least 30 frames (tests/stoi_reference.py: 42, 42, 42, 43, 49, 54 and 60), so every one is really scored."""
+    from sos_amd import metrics
+    fs = 10000
+    pairs = [R.closed_form_pair(300 + 2 * i, 8000 + 700 * i, fs, 0.1) for i in range(7)]
+    xs, ys = [p[0] for p in pairs], [p[1] for p in pairs]
+    want, want_kept = metrics.stoi_batch(xs, ys, fs, extended, return_frames=True)
+    assert all(k >= 30 for k in want_kept), want_kept
+    monkeypatch.setattr(metrics, "_MAX_CLIPS", 3)
+    got, kept = metrics.stoi_batch(xs, ys, fs, extended, return_frames=True)
+    assert got == want and kept == want_kept
+
+
+def test_device_table_entries_outside_the_hosts_lengths_are_not_followed():
+    """The kernels take offsets and lengths from the device table; a clip that leaves the samples the host's lengths sum to gets
+    status -1 and is not read.  At 10 kHz (p == q) 9000 and 9001 samples make the same 69 frames, so only the bounds rule
+    (csrc/ragged.h) can refuse the clip; at 16 kHz the longer resampled copy refuses it as well.  The overrun by one sample lies
+    inside the allocation."""
+    import ctypes as C
+    from sos_amd import _lib as L
+    from sos_amd import metrics
+    h = L.lib()
+    lens = np.asarray([5000, 9000], dtype=np.int64)
+    lp = lens.ctypes.data_as(C.c_void_p)
+    buf = torch.zeros(14001, device="cuda")
+    tab = torch.tensor([[0, 5000], [5000, 9001]], dtype=torch.int64, device="cuda")         # the second clip overruns
+    for p, q in ((1, 1), (5, 8)):
+        taps = metrics._stoi_taps(p, q, buf.device) if p != q else None
+        need = h.sos_stoi_workspace_bytes(lp, 2, p, q)
+        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        out = torch.zeros((2, 3), dtype=torch.float64, device="cuda")
+        assert h.sos_stoi_batch(L.ptr(buf), L.ptr(buf), L.ptr(tab[0]), L.ptr(tab[1]), lp, 2, p, q, L.ptr(taps),
+                                0 if taps is None else taps.numel(), 0, L.ptr(ws), need, L.ptr(out), L.stream_ptr()) == 0
+        o = out.cpu().numpy()
+        assert o[0, 2] >= 0 and o[1, 2] == -1, (p, q, o)
+
+
 def test_bad_inputs_raise():
     from sos_amd import metrics
     x, y = R.closed_form_pair(61, 30000, 10000, 0.1)

@@ -55,14 +55,10 @@ def main():
     ms_sd = _timed(lambda: metrics.sdr_batch(xs, ys, fl), args.iters)
 
     # the SDR sequence's two parts on one workspace
-    x, n = metrics._concat(xs)
-    y, _ = metrics._concat(ys)
-    hl = np.asarray(n, dtype=np.int64)
-    tab = torch.from_numpy(np.stack([np.cumsum(hl) - hl, hl])).to(x.device)
-    nbytes = L.lib().sos_sdr_workspace_bytes(hl.ctypes.data, len(hl), fl)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
-    ms_corr = _timed(lambda: metrics._sdr_enqueue(x, y, hl, tab, fl, stages=L.SDR_CORRELATE, ws=ws), args.iters)
-    ms_solve = _timed(lambda: metrics._sdr_enqueue(x, y, hl, tab, fl, stages=L.SDR_SOLVE, ws=ws), args.iters)
+    ch = next(metrics._chunks(xs, ys))
+    ws = metrics._workspace("sos_sdr_workspace_bytes", ch, fl)
+    ms_corr = _timed(lambda: metrics._sdr_enqueue(ch, fl, stages=L.SDR_CORRELATE, ws=ws), args.iters)
+    ms_solve = _timed(lambda: metrics._sdr_enqueue(ch, fl, stages=L.SDR_SOLVE, ws=ws), args.iters)
     fma = 2.0 * 512 * float(lens.sum())                        # f64 FMAs of the correlation kernel (it always runs 512 lags)
 
     t0 = time.perf_counter()
@@ -78,7 +74,7 @@ def main():
     print(f"sdr_batch    {ms_sd:8.3f} ms per call ({args.clips / (ms_sd / 1e3):9.0f} clips/s); CPU f64 reference "
           f"{cpu_sd * 1e3:8.2f} ms per clip; max |GPU - reference| over {args.oracle_clips} clips {err_sd:.1e} dB")
     print(f"  plan + sdr_corr_kernel {ms_corr:8.3f} ms ({2 * fma / (ms_corr / 1e3) / 1e12:6.2f} TFLOP/s f64, workspace "
-          f"{nbytes / 1e6:.1f} MB); sdr_solve_kernel {ms_solve:8.3f} ms")
+          f"{ws.numel() / 1e6:.1f} MB); sdr_solve_kernel {ms_solve:8.3f} ms")
 
 
 if __name__ == "__main__":
