@@ -567,6 +567,28 @@ int sos_sdr_batch(const float* x, const float* y, const int64_t* offsets, const 
                   int nclips, int filter_length, int stages, void* workspace, int64_t workspace_bytes, double* out,
                   sos_stream_t stream);
 
+/* ---- ragged groups of clips: staging for the networks and unpacking of results (csrc/ragged_io.hip).  One launch each,
+ * whatever the number of clips; no allocation, no host synchronisation.
+ * sos_ragged_stage_f32: x = the clips back to back in one f32 buffer.  table: int64 [nclips][4] on the device,
+ *   {sample offset, samples, bit offset, frames} per clip; table_host: the same values on the HOST (validated there, and they
+ *   size the buffers: x and mask hold sum(samples) floats, bits holds sum(frames) bytes).  bits: the clips' frame decisions back
+ *   to back (1 = non-silent); ratios / ratios_host: one double per clip on the device / the host, samples per frame
+ *   (sr / framerate, > 1).  Writes wave [nclips][stride] = the clip, zero from its end to the stride; masked [nclips][stride] =
+ *   clip * mask, zero-filled alike; mask = 1 on silent samples, back to back at the clip's sample offset.  A clip's mask is bit
+ *   for bit what sos_bits_to_mask gives that clip alone at its ratio (csrc/mask_rule.h is the one statement of the rule), in
+ *   any group and any order.  bits = NULL: only wave is written (ratios, masked, mask are not touched and may be NULL).
+ * sos_ragged_unpack_f32: rows f32 [n_rows][stride]; table / table_host: int64 [nentries][3] = {row, valid samples, output
+ *   offset}; out holds sum(valid) floats; out[offset .. offset + valid) = rows[row][0 .. valid).  Rows may repeat or be left
+ *   out, entries may come in any order.
+ * SOS_EINVAL (sos_last_error() names the entry): null pointers, nclips / nentries outside 1 .. 65535, stride < 1, samples or
+ * valid > stride, a row outside n_rows, a ratio <= 1, or an entry that lies outside the samples / frames summed from the host
+ * table.  The kernels follow the DEVICE table and skip an entry that fails the same bounds rule. */
+int sos_ragged_stage_f32(const float* x, const int64_t* table, const int64_t* table_host, int nclips, const uint8_t* bits,
+                         const double* ratios, const double* ratios_host, int64_t stride, float* wave, float* masked,
+                         float* mask, sos_stream_t stream);
+int sos_ragged_unpack_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
+                          int nentries, float* out, sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,8 @@ SIGNATURES = {
     "sos_sdr_workspace_bytes": [_P, _I, _I],
     "sos_sisdr_batch": [_P, _P, _P, _P, _P, _I, _I, _P, _L, _P, _P],
     "sos_sdr_batch": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P],
+    "sos_ragged_stage_f32": [_P, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P, _P],
+    "sos_ragged_unpack_f32": [_P, _L, _L, _P, _P, _I, _P, _P],
     "sos_time_unstack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
     "sos_spatial_mean_bwd": [_P, _L, _L, _I, _L, _I, _I, _I, _P, _I, _P],
 }

@@ -7,6 +7,7 @@
 //   batch_fast_icRM_sigmoid M1/transform.py:156-169   fast_cRM_sigmoid :130-138
 //   convert_bitstreammask_to_audiomask M2/tools.py:340-362
 #include "sos_common.h"
+#include "mask_rule.h"
 #include <stdlib.h>
 
 // ------------------------------------------------------------------- complex ratio mask ops
@@ -186,20 +187,8 @@ extern "C" int sos_power_law_f32(const float* x, int64_t n, float power, float* 
 }
 
 // --------------------------------------------------------------------- bits -> sample mask
-// Pre-flip mask value of sample j: 1 if j lies in [int(i*r), int((i+1)*r - 1)) of a silent
-// frame i (bit 0), else 0.  All index arithmetic in IEEE double with explicit (un-fused)
-// multiply/add so it reproduces Python's float64 evaluation bit for bit.
-__device__ __forceinline__ int premask(const uint8_t* bits, int64_t n_frames, double ratio, int64_t j) {
-    int64_t i0 = (int64_t)((double)j / ratio);
-    for (int64_t i = i0 - 1; i <= i0 + 1; ++i) {
-        if (i < 0 || i >= n_frames) continue;
-        const int64_t lo = (int64_t)__dmul_rn((double)i, ratio);
-        const int64_t hi = (int64_t)__dadd_rn(__dmul_rn((double)(i + 1), ratio), -1.0);
-        if (j >= lo && j < hi) return bits[i] == 0 ? 1 : 0;
-    }
-    return 0;
-}
-
+// The rule itself (premask, the flip of original runs shorter than five samples, the ratio >= 16 fast path) is mask_sample of
+// mask_rule.h, shared with ragged_io.hip.
 __global__ void bits_to_mask_kernel(const uint8_t* __restrict__ bits, int64_t n_frames, double ratio,
                                     int64_t n_samples, float* __restrict__ mask, const float* __restrict__ sig,
                                     float* __restrict__ masked, const int* __restrict__ fr_tab,
@@ -209,57 +198,7 @@ __global__ void bits_to_mask_kernel(const uint8_t* __restrict__ bits, int64_t n_
     const int64_t pitch_s = n_samples, pitch_f = n_frames;       // ragged batch: row pitches stay the batch maxima
     if (fr_tab) { n_frames = fr_tab[b]; n_samples = ns_tab[b]; }
     if (j >= n_samples) return;
-    const uint8_t* bb = bits + b * pitch_f;
-    if (ratio >= 16.0) {
-        // Frames are longer than the 9-sample neighbourhood: j - 4 .. j + 4 can only lie in the frames i0 - 1 .. i0 + 1 of
-        // sample j, whose [lo, hi) are computed ONCE (same un-fused double arithmetic as premask, so the values are the
-        // same bit for bit); the per-neighbour double division + three interval evaluations made this kernel ALU bound
-        // (37 us for 64 clips against ~5 us of HBM time).
-        const int64_t i0 = (int64_t)((double)j / ratio);
-        int64_t lo[3], hi[3];
-        int val[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int64_t i = i0 - 1 + q;
-            const bool ok = i >= 0 && i < n_frames;
-            lo[q] = ok ? (int64_t)__dmul_rn((double)i, ratio) : 0;
-            hi[q] = ok ? (int64_t)__dadd_rn(__dmul_rn((double)(i + 1), ratio), -1.0) : 0;      // empty interval when !ok
-            val[q] = ok && bb[i] == 0 ? 1 : 0;
-        }
-        auto pm = [&](const int64_t jj) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                if (jj >= lo[q] && jj < hi[q]) return val[q];
-            return 0;
-        };
-        const int v = pm(j);
-        int len = 1;
-        for (int d = 1; d <= 4 && j - d >= 0; ++d) {
-            if (pm(j - d) != v) break;
-            ++len;
-        }
-        for (int d = 1; d <= 4 && j + d < n_samples && len < 5; ++d) {
-            if (pm(j + d) != v) break;
-            ++len;
-        }
-        const float m = (float)(len < 5 ? 1 - v : v);
-        mask[b * pitch_s + j] = m;
-        if (masked) masked[b * pitch_s + j] = sig[b * pitch_s + j] * m;
-        return;
-    }
-    const int v = premask(bb, n_frames, ratio, j);
-    // length of the ORIGINAL run containing j (capped): the reference flips every run shorter
-    // than 5 samples in one pass over the original runs (groupby never sees its own writes).
-    int len = 1;
-    for (int d = 1; d <= 4 && j - d >= 0; ++d) {
-        if (premask(bb, n_frames, ratio, j - d) != v) break;
-        ++len;
-    }
-    for (int d = 1; d <= 4 && j + d < n_samples && len < 5; ++d) {
-        if (premask(bb, n_frames, ratio, j + d) != v) break;
-        ++len;
-    }
-    const float m = (float)(len < 5 ? 1 - v : v);
+    const float m = mask_sample(bits + b * pitch_f, n_frames, ratio, n_samples, j);
     mask[b * pitch_s + j] = m;
     if (masked) masked[b * pitch_s + j] = sig[b * pitch_s + j] * m;
 }

@@ -132,7 +132,42 @@ def add_noise_to_audio(audio, noise, snr, start_pos=0, norm=0.5):
     return add_signals(np.asarray(audio), [crop], snr=snr, norm=norm)
 
 
-def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noise_files=None, snr=None, seed=0):
+def _detect_item(data_id, f, bits_full, i1, label, pred, conf):
+    """One `data` entry of eval_results.json (M1/predict.py:150-175) from a file's host arrays of decisions and confidences."""
+    pred_label = [str(int(b)) for b in pred]
+    return OrderedDict([
+        ('id', data_id), ('path', f['path']), ('full_bit_stream', bits_full), ('num_frames', f['num_frames']),
+        ('framerate', f['framerate']), ('audio_sample_rate', f['audio_sample_rate']),
+        ('audio_samples', f['audio_samples']), ('duration', f['duration']), ('frame_start_idx', i1),
+        ('label', label), ('pred_label', pred_label), ('match', label == pred_label),
+        ('confidence', [str(c) for c in conf])])
+
+
+@torch.no_grad()
+def _detect_groups(net, pending, max_batch, max_columns):
+    """detect_files(batch_files=True): the (id, file, bit stream, first frame, label, 14 kHz signal) entries through the
+    detector in ragged groups; the stat entries in file order.  The decisions are taken from the one array that comes down per
+    group: sos_threshold_bits' confidence s, whose bit is s >= threshold in f32 -- the same comparison on the host."""
+    from . import engine as E
+    from . import pipeline
+    clips = [p[5].contiguous() for p in pending]
+    items = [None] * len(pending)
+    for part in pipeline._ragged_groups(clips, max_batch, max_columns):
+        wave, ns = pipeline.stage_group([clips[i] for i in part])
+        nv = [len(pending[i][4]) for i in part]
+        rag = E.Ragged([1 + n // transform.HOP_LENGTH for n in ns], wave.device, n_vframes=nv, n_samples=ns)
+        S = transform.stft_batch(wave, clip_samples=rag.tab(ns))
+        logits = net(s=S, v_num_frames=max(nv), rag=rag)
+        _, conf = tools.threshold_bits(logits, SIGMOID_THRESHOLD)
+        conf = conf.cpu().numpy()
+        for k, i in enumerate(part):
+            c = conf[k, :nv[k]]
+            items[i] = _detect_item(*pending[i][:5], (c >= np.float32(SIGMOID_THRESHOLD)).astype(np.uint8), c)
+    return items
+
+
+def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noise_files=None, snr=None, seed=0,
+                 batch_files=False, max_batch=64, max_columns=65536):
     """Whole-file silent-interval detection of every file of a dataset JSON (`evaluate`, M1/predict.py:38-233 with
     the prediction-phase items of M1/tools.py:297-332 and M1/dataset.py:226-252): one item per file, the whole
     recording at 14 kHz -> STFT -> net(s, v_num_frames=len(bits)) -> sigmoid -> >= 0.5.  Returns the stat dict and
@@ -141,7 +176,12 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     labelled silent intervals, a crop of a noise file is mixed in at `snr` dB (peak 0.5) before detection, and the
     crop + its bookkeeping go to <outputs>/noise_snr<snr>/ (M1/predict.py:82-104) for create_data_from_prediction.
     The reference draws noise file and crop from Python's `random` stream; here a seeded numpy generator does
-    (the draws themselves are not reproducible across the two)."""
+    (the draws themselves are not reproducible across the two).
+    batch_files=True: every recording comes from one audio_io.load_batch_device call and detection runs in ragged groups
+    (files sorted by length, cut into groups of <= max_batch files and <= max_columns spectrogram columns like
+    pipeline.denoise_ragged's): one staging launch, one STFT, one detector call with per-file geometry, one thresholding launch
+    and one download per group.  The clean-recordings branch keeps its per-file draws and mixing in file order (a seeded run
+    draws the same crops).  Same JSON as the per-file form: schema, key order, file order, sort."""
     with open(dataset_json, 'r') as fp:
         ds = json.load(fp)
     net.eval()
@@ -152,11 +192,18 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     suffix = convert_snr_to_suffix2(snr) if clean_audio else ''
     rng = np.random.default_rng(seed)
     noise_entries = OrderedDict()
+    loaded, pending = None, []
+    if batch_files and ds['files']:
+        loaded, _ = audio_io.load_batch_device([_resolve(f['audio_path'], ds.get('dataset_path'), data_root) for f in ds['files']],
+                                               sr=DATA_REQUIRED_SR)
     for data_id, f in enumerate(ds['files']):
         bits_full = f[BITSTREAM_JSON_LABEL]
         i1, i2 = _trim_unknown(bits_full)
         label = [str(int(b)) for b in bits_full[i1:i2]]
-        snd, _ = audio_io.load_device(_resolve(f['audio_path'], ds.get('dataset_path'), data_root), sr=DATA_REQUIRED_SR)
+        if batch_files:
+            snd = loaded[data_id]
+        else:
+            snd, _ = audio_io.load_device(_resolve(f['audio_path'], ds.get('dataset_path'), data_root), sr=DATA_REQUIRED_SR)
         if clean_audio:
             gt = torch.tensor([int(b) for b in label], dtype=torch.uint8, device=snd.device).reshape(1, -1)
             gmask = tools.bits_to_mask_batch(gt, float(DATA_REQUIRED_SR) / f['framerate'], snd.numel())
@@ -174,16 +221,15 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
             audio_io.write_wav(os.path.join(noise_dir, noise_name), crop.astype(np.float32), DATA_REQUIRED_SR)
             noise_entries[base] = OrderedDict([('audio', base.split('.mp4')[0].split('.wav')[0] + '.wav'),
                                                ('noise', noise_name), ('snr', snr)])
+        if batch_files:
+            pending.append((data_id, f, bits_full, i1, label, snd))
+            continue
         S = transform.stft_batch(snd.reshape(1, -1))
         logits = net(s=S, v_num_frames=len(label))
         pred, conf = tools.threshold_bits(logits, SIGMOID_THRESHOLD)
-        pred_label = [str(int(b)) for b in pred[0].cpu().numpy()]
-        stat.append(OrderedDict([
-            ('id', data_id), ('path', f['path']), ('full_bit_stream', bits_full), ('num_frames', f['num_frames']),
-            ('framerate', f['framerate']), ('audio_sample_rate', f['audio_sample_rate']),
-            ('audio_samples', f['audio_samples']), ('duration', f['duration']), ('frame_start_idx', i1),
-            ('label', label), ('pred_label', pred_label), ('match', label == pred_label),
-            ('confidence', [str(c) for c in conf[0].cpu().numpy()])]))
+        stat.append(_detect_item(data_id, f, bits_full, i1, label, pred[0].cpu().numpy(), conf[0].cpu().numpy()))
+    if pending:
+        stat = _detect_groups(net, pending, max_batch, max_columns)
     stat_dict = OrderedDict([
         ('data_total_frames', CLIP_FRAMES), ('data_center_frames', SILENT_CONSECUTIVE_FRAMES),
         ('sigmoid_threshold', SIGMOID_THRESHOLD), ('snr', snr if clean_audio else None),
@@ -273,6 +319,17 @@ def create_data_from_prediction(input_json, output_json=None, suffix="", noise_s
 
 
 # ------------------------------------------------------------------------------------------- JSON -> model 2
+def _parse_bits(bitstream):
+    """M2/predict.py:232-252: '0' / '1' (a '2' is tolerated as non-silent) -> 0 / 1 values; anything else is an error."""
+    vals = []
+    for bit in bitstream:
+        if bit not in '012':
+            print('Invalid bit?')
+            raise RuntimeError
+        vals.append(0 if bit == '0' else 1)
+    return vals
+
+
 def get_data_from_first_model(first_model_json_path, sr=DATA_REQUIRED_SR, snr=None, n_fft=510, hop_length=158,
                               win_length=400, unknown_clean_signal=True):
     """M2/predict.py:255-374: per file of pred_data.json load `mixed_audio`, turn `recovered_prediction` into the
@@ -289,13 +346,7 @@ def get_data_from_first_model(first_model_json_path, sr=DATA_REQUIRED_SR, snr=No
         mixed_audio_path = os.path.join(get_parent_dir(first_model_json_path), data['mixed_audio'])
         mixed_sig, _ = audio_io.load_device(mixed_audio_path, sr=sr)
         bitstream = data[BIT_STREAM_LABEL]
-        vals = []
-        for bit in bitstream:                      # M2/predict.py:232-252: '0' / '1' (a '2' is tolerated as non-silent)
-            if bit not in '012':
-                print('Invalid bit?')
-                raise RuntimeError
-            vals.append(0 if bit == '0' else 1)
-        bits = torch.tensor(vals, dtype=torch.uint8, device=mixed_sig.device).reshape(1, -1)
+        bits = torch.tensor(_parse_bits(bitstream), dtype=torch.uint8, device=mixed_sig.device).reshape(1, -1)
         mask, noise_sig = tools.bits_to_mask_batch(bits, float(sr) / data['framerate'], mixed_sig.numel(),
                                                    mixed_sig.reshape(1, -1))
         item = OrderedDict([('id', os.path.splitext(os.path.basename(data['path']))[0]), ('path', data['path'])])
@@ -333,18 +384,21 @@ def _write_individual(data, info, sigs, gt_sigs, outputs, snr, save_individual_r
     """The WAVE files and stat.json of one file of denoise_files (M2/predict.py:515-560); fills the path keys of `info`."""
     if not save_individual_results:
         return
+    _write_individual_host(data, info, sigs.cpu().numpy(), None if gt_sigs is None else gt_sigs.cpu().numpy(), outputs, snr)
+
+
+def _write_individual_host(data, info, host, gh, outputs, snr):
+    """_write_individual on host arrays: host (4, n) = the four signals, gh (2, >= n) = the ground-truth ones or None."""
     save_dir = os.path.join(os.path.abspath(outputs), convert_snr_to_suffix2(snr)[1:], str(data['id']))
     ensure_dir(save_dir)
-    host = sigs.cpu().numpy()
     for k, name in enumerate(('noisy_input', 'noise_intervals', 'predicted_full_noise', 'denoised_output')):
         p = os.path.join(save_dir, name + '.wav')
         audio_io.write_wav(p, host[k], data['sr'])
         info[name] = p
-    if gt_sigs is not None:
-        gh = gt_sigs.cpu().numpy()
+    if gh is not None:
         for k, name in enumerate(('ground_truth_full_noise', 'ground_truth_clean_input')):
             p = os.path.join(save_dir, name + '.wav')
-            audio_io.write_wav(p, gh[k][:host.shape[1]], data['sr'])
+            audio_io.write_wav(p, gh[k][:len(host[0])], data['sr'])
             info[name] = p
     with open(os.path.join(save_dir, 'stat.json'), 'w') as fp:
         json.dump(info, fp, **JSON_DUMP_PARAMS)
@@ -377,6 +431,21 @@ def _batch_measures(work, pesq_fn, stoi_fn):
             stoi = [stoi_fn(c, o, 16000) for c, o in zip(ch, oh)]
     for (_, info, _, _), m in zip(work, metrics.evaluate_metrics_batch(out16, clean16, sr=16000, pesq=pesq, stoi=stoi)):
         info.update(m)
+
+
+def _write_eval_results(data_info, stat, outputs, threshold, snr):
+    """eval_results<suffixes>.json of denoise_files (M2/predict.py:562-576): the averages of the available measures and the files."""
+    if stat and 'l1' in stat[0]:
+        keys = ('l1', 'stoi', 'csig', 'cbak', 'covl', 'pesq', 'ssnr_regular', 'ssnr_shift', 'ssnr_clip', 'ssnr_exsi', 'overall_snr')
+        data_info['denoise_statistics'] = OrderedDict(
+            ('avg_' + k, (sum(it[k] for it in stat) / len(stat)) if all(it[k] is not None for it in stat) else None)
+            for k in keys)
+    data_info['files'] = stat
+    ensure_dir(os.path.abspath(outputs))
+    path = os.path.join(os.path.abspath(outputs), 'eval_results' + convert_threshold_to_suffix(threshold) +
+                        convert_snr_to_suffix2(snr) + '.json')
+    with open(path, 'w') as fp:
+        json.dump(data_info, fp, **JSON_DUMP_PARAMS)
 
 
 @torch.no_grad()
@@ -430,15 +499,124 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
         for w in work:
             _write_individual(*w, outputs, snr, save_individual_results)
     if save_stat:
-        if stat and 'l1' in stat[0]:
-            keys = ('l1', 'stoi', 'csig', 'cbak', 'covl', 'pesq', 'ssnr_regular', 'ssnr_shift', 'ssnr_clip', 'ssnr_exsi', 'overall_snr')
-            data_info['denoise_statistics'] = OrderedDict(
-                ('avg_' + k, (sum(it[k] for it in stat) / len(stat)) if all(it[k] is not None for it in stat) else None)
-                for k in keys)
-        data_info['files'] = stat
-        ensure_dir(os.path.abspath(outputs))
-        path = os.path.join(os.path.abspath(outputs), 'eval_results' + convert_threshold_to_suffix(threshold) +
-                            convert_snr_to_suffix2(snr) + '.json')
-        with open(path, 'w') as fp:
-            json.dump(data_info, fp, **JSON_DUMP_PARAMS)
+        _write_eval_results(data_info, stat, outputs, threshold, snr)
+    return stat
+
+
+@torch.no_grad()
+def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR, snr=None, threshold="", unknown_clean_signal=True,
+                        save_individual_results=True, save_stat=True, pesq_fn=None, stoi_fn=None, max_batch=64, max_columns=65536):
+    """get_data_from_first_model + denoise_files(batch_metrics=True) over the files of pred_data.json in ragged groups instead
+    of one file at a time: the same WAVE files, stat.json, eval_results<suffixes>.json and returned `stat` list (in the JSON's
+    file order), with the number of launches, copies and host waits following the number of GROUPS, not of files.
+      - one audio_io.load_batch_device over every `mixed_audio` (and `clean_audio`, `full_noise` with
+        unknown_clean_signal=False); the bit strings are parsed on the host and go up in one copy;
+      - files sorted by length and cut into groups of <= max_batch files and <= max_columns spectrogram columns
+        (pipeline._ragged_groups); a group is staged by ONE sos_ragged_stage_f32 launch -- padded recordings, noise intervals
+        from `recovered_prediction` at the file's own sr / framerate, and with known clean signals the ground-truth mask of the
+        clean recording in the same launch (clean * (1 - mask) is then wave - masked of its row: M2/predict.py:321) -- and runs
+        as pipeline.denoise_ragged(bits=..., fps=framerates, return_all=True) runs it; the STFT -> ISTFT round trip of
+        `full_noise` and the silenced clean signal are further rows of the group;
+      - the four (six) signals of every file of a group come down in one copy (sos_ragged_unpack_f32);
+      - the measures of all files go through _batch_measures (stoi_fn=True: STOI in the same launch sequence).
+    A file with fewer than pipeline.MIN_FRAMES STFT frames raises ValueError naming it before any group is staged or run."""
+    from . import engine as E
+    from . import pipeline
+    with open(first_model_json_path, 'r') as fp:
+        obj = json.load(fp)
+    base = get_parent_dir(first_model_json_path)
+    files = obj['files']
+    known = not unknown_clean_signal
+    F = len(files)
+    data_info = OrderedDict([(k, obj[k]) for k in ('dataset_path', 'num_videos', 'data_total_frames', 'data_center_frames',
+                                                   'sigmoid_threshold')])
+    data_info['snr'] = snr
+    net.eval()
+    mixed_paths = [os.path.join(base, d['mixed_audio']) for d in files]
+    clean_paths = [os.path.join(base, d['clean_audio']) for d in files] if known else []
+    noise_paths = [os.path.join(base, d['full_noise']) for d in files] if known else []
+    rec_bits = [np.asarray(_parse_bits(d[BIT_STREAM_LABEL]), dtype=np.uint8) for d in files]
+    gt_bits = [np.asarray([0 if b == '0' else 1 for b in d[GT_BIT_STREAM_LABEL]], dtype=np.uint8) for d in files] if known else []
+    ratios = [float(sr) / d['framerate'] for d in files]
+    stat, work = [], []
+    if F:
+        ys, _ = audio_io.load_batch_device(mixed_paths + clean_paths + noise_paths, sr=sr)
+        mixed, clean, noise = ys[:F], ys[F:2 * F], ys[2 * F:]
+        hop = transform.HOP_LENGTH
+        for i, y in enumerate(mixed):
+            if 1 + y.numel() // hop < pipeline.MIN_FRAMES:
+                raise ValueError("%s: %d samples at %d Hz are fewer than the %d STFT frames (%d samples) the denoiser needs"
+                                 % (mixed_paths[i], y.numel(), sr, pipeline.MIN_FRAMES, pipeline.MIN_FRAMES * hop))
+        device = mixed[0].device
+        all_bits = torch.from_numpy(np.concatenate(rec_bits + gt_bits)).to(device)       # every bit string: one copy
+        ends = np.cumsum([len(b) for b in rec_bits + gt_bits])
+        d_bits = [all_bits[int(e) - len(b):int(e)] for e, b in zip(ends, rec_bits + gt_bits)]
+        work = [None] * F
+    for part in (pipeline._ragged_groups(mixed, max_batch, max_columns) if F else []):
+        B = len(part)
+        rows = [mixed[i] for i in part]
+        bits_g = [d_bits[i] for i in part]
+        nb = [len(rec_bits[i]) for i in part]
+        rat = [ratios[i] for i in part]
+        if known:                                    # rows B .. 2B: full_noise (packed only), rows 2B .. 3B: clean + ground-truth bits
+            rows += [noise[i] for i in part] + [clean[i] for i in part]
+            bits_g += [d_bits[F + i] for i in part]
+            nb += [0] * B + [len(gt_bits[i]) for i in part]
+            rat = rat * 3
+        (wave, masked, _), ns = pipeline.stage_group(rows, torch.cat(bits_g), nb, rat)
+        n_long = max(ns[:B])
+        rag = pipeline._group_geometry(ns[:B], device, sr, pipeline.FPS, nv=nb[:B])
+        sigs = pipeline._denoise_group_staged(net, wave[:B, :n_long], masked[:B, :n_long], rag, signals=True)
+        n_out = [hop * (t - 1) for t in rag.T]
+        table = [(q * B + k, n_out[k], 0) for k in range(B) for q in range(4)]
+        gt = None
+        if known:
+            wave[2 * B:].sub_(masked[2 * B:])        # silent intervals of the clean signal truly silent (M2/predict.py:321)
+            Tg = [1 + n // hop for n in ns[B:]]
+            grag = E.Ragged(Tg, device, n_samples=ns[B:])
+            gt = transform.istft_batch(transform.stft_batch(wave[B:], clip_samples=grag.tab(ns[B:])), clip_frames=grag.level(0))
+            n_gt = [hop * (t - 1) for t in Tg]
+        host = None
+        if save_individual_results:                  # the signals of the whole group: one unpack launch, one download
+            if known:                                # ground-truth rows follow the group's 4 B rows, cropped like _write_individual
+                if gt.shape[1] != sigs.shape[1]:
+                    wide = torch.zeros((6 * B, max(gt.shape[1], sigs.shape[1])), dtype=torch.float32, device=device)
+                    wide[:4 * B, :sigs.shape[1]] = sigs
+                    wide[4 * B:, :gt.shape[1]] = gt
+                    both = wide
+                else:
+                    both = torch.cat([sigs, gt], dim=0)
+                table = [row for k in range(B) for row in
+                         ([(q * B + k, n_out[k], 0) for q in range(4)] +
+                          [((4 + q) * B + k, min(n_gt[q * B + k], n_out[k]), 0) for q in range(2)])]
+            else:
+                both = sigs
+            tab = np.asarray(table, dtype=np.int64)
+            tab[:, 2] = np.cumsum(tab[:, 1]) - tab[:, 1]
+            host = tools.ragged_unpack(both, tab).cpu().numpy()
+        per = 6 if known else 4
+        for k, i in enumerate(part):
+            d = files[i]
+            data = dict(id=os.path.splitext(os.path.basename(d['path']))[0], sr=sr)
+            info = OrderedDict([('id', str(data['id'])), ('path', str(d['path']))])
+            if known:
+                info['clean_audio_path'] = clean_paths[i]
+            info['mixed_audio_path'] = mixed_paths[i]
+            if known:
+                info['full_noise_path'] = noise_paths[i]
+            info.update([('bitstream', d[BIT_STREAM_LABEL]), ('sr', sr), ('snr', obj['snr'])])
+            sig_i = [sigs[q * B + k, :n_out[k]] for q in range(4)]
+            gt_i = [gt[q * B + k, :n_gt[q * B + k]] for q in range(2)] if known else None
+            host_i = None
+            if host is not None:
+                e = [(int(tab[per * k + q, 2]), int(tab[per * k + q, 1])) for q in range(per)]
+                host_i = [host[o:o + n] for o, n in e]
+            work[i] = (data, info, sig_i, gt_i, host_i)
+    stat = [w[1] for w in work]
+    _batch_measures([w[:4] for w in work if w[3] is not None], pesq_fn, stoi_fn)
+    for data, info, _, _, host_i in work:
+        if host_i is not None:
+            _write_individual_host(data, info, host_i[:4], host_i[4:] if known else None, outputs, snr)
+    if save_stat:
+        _write_eval_results(data_info, stat, outputs, threshold, snr)
     return stat

@@ -130,11 +130,12 @@ def denoise(detector, denoiser, mixed, sr=SR, fps=FPS, bits=None, return_all=Fal
     return out
 
 
-def _group_geometry(ns, device, sr, fps):
-    """Per-clip frame / video-frame counts of a ragged group and their device tables (engine.Ragged)."""
+def _group_geometry(ns, device, sr, fps, nv=None):
+    """Per-clip frame / video-frame counts of a ragged group and their device tables (engine.Ragged).  nv: the clips' own
+    numbers of frame decisions where they are given (the `bits` override) instead of following from sr and fps."""
     from . import engine as E
     T = [1 + n // transform.HOP_LENGTH for n in ns]
-    nv = [n_video_frames(n, sr, fps) for n in ns]
+    nv = [n_video_frames(n, sr, fps) for n in ns] if nv is None else [int(v) for v in nv]
     if min(T) < MIN_FRAMES:
         # the U-Net's dilation-16 block reflects 16 columns at a quarter of the resolution: nn.ReflectionPad2d raises for a
         # shorter input (M2/networks.py:105,181), and so does the single-clip path (sos_conv2d_fwd's descriptor check)
@@ -194,18 +195,102 @@ def _ragged_groups(clips, max_batch, max_columns):
     return groups
 
 
+def stage_group(clips, bits=None, n_bits=None, ratios=None):
+    """Clips of one group (1-D f32 GPU tensors) -> the padded buffer(s) of the launch sequence in ONE launch
+    (tools.ragged_stage): (wave (B, longest), ns) without `bits`; with `bits` -- the clips' frame decisions back to back on the
+    GPU, `n_bits` of them per clip, `ratios` samples per frame per clip -- ((wave, masked, mask), ns), mask back to back in clip
+    order."""
+    import numpy as np
+    ns = [int(c.numel()) for c in clips]
+    flat = torch.cat(clips) if len(clips) > 1 else clips[0].contiguous()
+    nb = [0] * len(ns) if n_bits is None else [int(v) for v in n_bits]
+    ends, bends = np.cumsum(ns), np.cumsum(nb)
+    table = np.stack([ends - ns, ns, bends - nb, nb], axis=1)
+    return tools.ragged_stage(flat, table, max(ns), bits, ratios), ns
+
+
+def _denoise_group_staged(denoiser, wave, masked, rag, signals=False):
+    """The denoiser's launch sequence of one ragged group whose noise intervals are already cut out (`masked`): what
+    _denoise_group_padded runs after its detector.  Returns the padded output (B, hop * (max T - 1)); signals=True: the padded
+    ISTFTs (4 B, hop * (max T - 1)) of the mixed, the noise-interval, the predicted-noise and the output spectrograms, B rows
+    each in that order -- the four signals the hand-off writes (M2/predict.py:515-560)."""
+    t_ns = rag.tab(rag.n_samples)
+    S_mixed = transform.stft_batch(wave, clip_samples=t_ns)
+    S_noise = transform.stft_batch(masked, clip_samples=t_ns)
+    n_pred, crm = denoiser(S_mixed, S_noise, rag=rag)
+    S_out = transform.batch_fast_icRM_sigmoid(S_mixed, crm)
+    if not signals:
+        return transform.istft_batch(S_out, clip_frames=rag.level(0))
+    return transform.istft_batch(torch.cat([S_mixed, S_noise, n_pred, S_out], dim=0), clip_frames=rag.tab(rag.T * 4))
+
+
+def _clip_ratios(n, sr, fps):
+    """sr / fps per clip: fps a scalar or one value per clip."""
+    try:
+        fps = [float(f) for f in fps]
+    except TypeError:
+        fps = [float(fps)] * n
+    if len(fps) != n:
+        raise ValueError("fps must be a scalar or one value per clip")
+    return [float(sr) / f for f in fps]
+
+
+def _denoise_ragged_bits(denoiser, clips, bits, sr, fps, max_batch, max_columns, return_all):
+    """denoise_ragged with the first model's decisions given (`bits`): no detector; every group is staged by
+    sos_ragged_stage_f32 in one launch (padded clips, noise intervals, sample masks at each clip's own sr / fps)."""
+    import numpy as np
+    if len(bits) != len(clips):
+        raise ValueError("bits must hold one array of frame decisions per clip")
+    ratios = _clip_ratios(len(clips), sr, fps)
+    for b in bits:
+        if b.ndim != 1 or (b.dtype != torch.uint8 if torch.is_tensor(b) else b.dtype != np.uint8):
+            raise ValueError("bits must be 1-D uint8 arrays or GPU tensors (1 = non-silent)")
+    outs, extra = [None] * len(clips), [None] * len(clips)
+    hop = transform.HOP_LENGTH
+    for part in _ragged_groups(clips, max_batch, max_columns):
+        group = [clips[i].contiguous().float() for i in part]
+        device = group[0].device
+        nb = [int(bits[i].shape[0]) for i in part]
+        rag = _group_geometry([int(c.numel()) for c in group], device, sr, FPS, nv=nb)      # refuses short clips before any launch
+        if all(torch.is_tensor(bits[i]) for i in part):
+            d_bits = torch.cat([bits[i].to(device) for i in part])
+        else:                                                                                # host arrays: one upload per group
+            d_bits = torch.from_numpy(np.concatenate([bits[i].cpu().numpy() if torch.is_tensor(bits[i]) else bits[i] for i in part])).to(device)
+        (wave, masked, mask), ns = stage_group(group, d_bits, nb, [ratios[i] for i in part])
+        y = _denoise_group_staged(denoiser, wave, masked, rag, signals=return_all)
+        B, pos, bpos = len(part), 0, 0
+        for k, i in enumerate(part):
+            n_out = hop * (rag.T[k] - 1)
+            outs[i] = y[(3 * B if return_all else 0) + k, :n_out]
+            if return_all:
+                extra[i] = dict(bits=d_bits[bpos:bpos + nb[k]], mask=mask[pos:pos + ns[k]], noisy_input=y[k, :n_out],
+                                noise_intervals=y[B + k, :n_out], predicted_full_noise=y[2 * B + k, :n_out])
+            pos += ns[k]
+            bpos += nb[k]
+    return (outs, extra) if return_all else outs
+
+
 @torch.no_grad()
-def denoise_ragged(detector, denoiser, clips, sr=SR, fps=FPS, max_batch=256, max_columns=65536, return_all=False):
+def denoise_ragged(detector, denoiser, clips, sr=SR, fps=FPS, max_batch=256, max_columns=65536, return_all=False, bits=None):
     """Variable-length inference (BASELINE configs[3]): `clips` = list of 1-D f32 GPU tensors of ANY lengths.
     The reference denoises one file at a time at its own length (M2/predict.py:377-447: no padding, so reflect
     padding, frame count and video-frame count follow the clip).  Here clips of different lengths share launches:
     they are sorted by length (the BiLSTM kernel steps 16 clips in lockstep, so neighbours should be similar) and cut
     into groups of <= max_batch clips and <= max_columns (clips x frames of the longest) spectrogram columns -- the
     memory budget of a launch sequence, ~0.5 MB of live activations per column -- and every group runs as ONE batch
-    with per-clip geometry (_denoise_group).  Outputs come back in input order, each hop*(T-1) samples long."""
+    with per-clip geometry (_denoise_group).  Outputs come back in input order, each hop*(T-1) samples long.
+    `bits` (one 1-D uint8 array or GPU tensor per clip, 1 = non-silent) overrides the detector as in denoise() -- M2/predict.py's
+    `recovered_prediction` input; `detector` may then be None -- and `fps` may be one value per clip (the files of a data set
+    carry their own `framerate`).  Grouping, the MIN_FRAMES refusal and the output order are the same; return_all then yields
+    per clip its `bits`, the sample `mask` and the ISTFTs `noisy_input`, `noise_intervals`, `predicted_full_noise` of the mixed,
+    the noise-interval and the predicted-noise spectrograms (with the output: the four signals the hand-off writes)."""
     for c in clips:
         if c.dim() != 1:
             raise ValueError("denoise_ragged expects 1-D waveforms")
+    if bits is None and not isinstance(fps, (int, float)):
+        raise ValueError("one fps per clip needs the clips' frame decisions (bits=): the detector's groups share one rate")
+    if bits is not None:
+        return _denoise_ragged_bits(denoiser, clips, bits, sr, fps, max_batch, max_columns, return_all)
     outs, extra = [None] * len(clips), [None] * len(clips)
     for part in _ragged_groups(clips, max_batch, max_columns):
         ys, info = _denoise_group(detector, denoiser, [clips[i].contiguous().float() for i in part], sr, fps)

@@ -27,6 +27,62 @@ def bits_to_mask_batch(bits, ratio, n_samples, sig=None, clip_frames=None, clip_
     return (mask, masked) if sig is not None else mask
 
 
+def _host_table(rows, cols):
+    tab = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, cols))
+    if tab.shape[0] < 1:
+        raise ValueError("an empty table")
+    return tab
+
+
+def _upload(host, device):
+    from .engine import upload
+    return upload(host, torch.int64 if host.dtype == np.int64 else torch.float64, device)
+
+
+def ragged_stage(flat, table, stride, bits=None, ratios=None):
+    """A ragged group staged for the networks in one launch (sos_ragged_stage_f32).  flat: the clips back to back, f32 GPU
+    tensor; table: host rows {sample offset, samples, bit offset, frames}, one per clip; bits: the clips' frame decisions back
+    to back (uint8 GPU tensor, 1 = non-silent); ratios: samples per frame, one float per clip.
+    -> (wave (B, stride), masked (B, stride), mask back to back like `flat`): the clip zero-filled to the stride, clip * mask
+    likewise, and the sample mask (1 = silent), each clip's bit for bit bits_to_mask_batch of that clip alone at its ratio.
+    Without `bits` only `wave` is computed and returned."""
+    L.require_cuda(flat, bits)
+    tab = _host_table(table, 4)
+    B = tab.shape[0]
+    if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("flat must be a contiguous 1-D float32 tensor")
+    if flat.numel() < int(tab[:, 1].sum()):
+        raise ValueError("the table names more samples than `flat` holds")
+    wave = torch.empty((B, int(stride)), dtype=torch.float32, device=flat.device)
+    d_tab = _upload(tab, flat.device)
+    masked = mask = rat = d_rat = None
+    if bits is not None:
+        if bits.dim() != 1 or bits.dtype != torch.uint8 or not bits.is_contiguous() or bits.numel() < int(tab[:, 3].sum()):
+            raise ValueError("bits must be a contiguous 1-D uint8 tensor holding every frame of the table")
+        rat = np.array(np.broadcast_to(np.asarray(ratios, dtype=np.float64), (B,)))      # a writable copy
+        d_rat = _upload(rat, flat.device)
+        masked, mask = torch.empty_like(wave), torch.empty_like(flat)
+    L.check(L.lib().sos_ragged_stage_f32(L.ptr(flat), L.ptr(d_tab), tab.ctypes.data, B, L.ptr(bits), L.ptr(d_rat),
+                                         rat.ctypes.data if rat is not None else None, int(stride), L.ptr(wave), L.ptr(masked),
+                                         L.ptr(mask), L.stream_ptr()), "sos_ragged_stage_f32")
+    return (wave, masked, mask) if bits is not None else wave
+
+
+def ragged_unpack(rows, table):
+    """Padded rows f32 (R, stride) on the GPU + host table rows {row, valid samples, output offset} -> one 1-D f32 GPU tensor
+    of sum(valid) samples, out[offset : offset + valid] = rows[row, :valid], in one launch (sos_ragged_unpack_f32): what a
+    single download of a group's results needs."""
+    L.require_cuda(rows)
+    tab = _host_table(table, 3)
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
+    out = torch.empty(int(tab[:, 1].sum()), dtype=torch.float32, device=rows.device)
+    d_tab = _upload(tab, rows.device)
+    L.check(L.lib().sos_ragged_unpack_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data,
+                                          tab.shape[0], L.ptr(out), L.stream_ptr()), "sos_ragged_unpack_f32")
+    return out
+
+
 def convert_bitstreammask_to_audiomask(ref_audio_signal, frames_to_audiosample_ratio, bitstream):
     """M2/tools.py:340-362 (string bits) / M1/tools.py:770-792 (int bits): same arguments, same
     RuntimeError on an invalid bit, same dtype as `ref_audio_signal`."""

@@ -1,0 +1,125 @@
+"""File-chain benchmark (run on the GPU box): N synthetic recordings of 1 .. 10 s (seeded lengths, 14 kHz f32 WAVE, a quarter
+of them at framerate 25) in a temporary directory, through both stages of the on-disk hand-off in the per-file form and in the
+ragged-group form, in 'mixed' precision:
+  stage 1   handoff.detect_files(...)                                           vs  detect_files(batch_files=True)
+  stage 2   handoff.get_data_from_first_model + denoise_files(batch_metrics=True)  vs  handoff.denoise_first_model
+(real-recording branch: unknown clean signal, WAVE files and JSONs written).  Both forms are warmed once, then alternate,
+--repeats times each; per stage and form the median wall time from an idle device to an idle device (file reads and writes
+included), the spread of the repeats, files/s and the number of host waits -- device-to-host downloads (Tensor.cpu calls),
+each of which blocks the host until the stream has drained -- are printed."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import sos_amd  # noqa: E402
+from oracle import nets as onet  # noqa: E402
+from sos_amd import audio_io, handoff  # noqa: E402
+from sos_amd.common import MyConfig  # noqa: E402
+from sos_amd.denoiser import networks as jnet  # noqa: E402
+from sos_amd.detector import networks as dnet  # noqa: E402
+
+WAITS = [0]
+
+
+def _count_downloads():
+    orig = torch.Tensor.cpu
+
+    def cpu(self, *a, **k):
+        if self.is_cuda:
+            WAITS[0] += 1
+        return orig(self, *a, **k)
+    torch.Tensor.cpu = cpu
+
+
+def once(fn):
+    """(wall seconds, host waits) of one call, from an idle device to an idle device."""
+    torch.cuda.synchronize()
+    WAITS[0] = 0
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, WAITS[0]
+
+
+def make_dataset(root, n_files, seed):
+    rng = np.random.default_rng(seed)
+    files = []
+    for i in range(n_files):
+        n = int(rng.integers(14000, 10 * 14000 + 1))
+        secs, fr = n / 14000, (25 if i % 4 == 3 else 30)
+        t = np.arange(n) / 14000
+        sig = 0.3 * (np.sin(2 * np.pi * 0.7 * t + i) > -0.2) * np.sin(2 * np.pi * 220 * t) + 0.05 * rng.standard_normal(n)
+        name = "rec_%03d" % i
+        os.makedirs(os.path.join(root, name))
+        audio_io.write_wav(os.path.join(root, name, name + ".wav"), sig.astype(np.float32), 14000)
+        nfr = int(round(secs * fr))
+        path = "/bench/ds/%s/%s.wav" % (name, name)
+        files.append(dict(path=path, framerate=fr, audio_sample_rate=14000, audio_samples=n, duration=secs, num_frames=nfr,
+                          bit_stream="1" * nfr, audio_path=path))
+    with open(os.path.join(root, "dataset.json"), "w") as fp:
+        json.dump(dict(dataset_path="/bench/ds", num_videos=n_files, files=files), fp)
+    return os.path.join(root, "dataset.json"), sum(f["duration"] for f in files)
+
+
+def report(stage, name, n_files, runs):
+    ts, waits = [r[0] for r in runs], [r[1] for r in runs]
+    med = float(np.median(ts))
+    print(f"  {stage} {name:9s}: {med * 1e3:9.1f} ms (min {min(ts) * 1e3:.1f}, max {max(ts) * 1e3:.1f})   {n_files / med:8.1f} files/s   "
+          f"host waits {int(np.median(waits))}")
+    return med
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--max-batch", type=int, default=64)
+    args = ap.parse_args()
+    print(torch.cuda.get_device_name(0))
+    det = dnet.get_network()
+    det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+    jm = jnet.get_network(MyConfig())
+    jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+    det, jm = det.cuda().eval(), jm.cuda().eval()
+    _count_downloads()
+    sos_amd.set_precision("mixed")
+    with tempfile.TemporaryDirectory() as tmp:
+        root = os.path.join(tmp, "ds")
+        os.makedirs(root)
+        dj, secs = make_dataset(root, args.files, args.seed)
+        out = lambda name: os.path.join(tmp, name)                                        # noqa: E731
+        s1_file = lambda: handoff.detect_files(det, dj, out("m1_file"), data_root=root)   # noqa: E731
+        s1_batch = lambda: handoff.detect_files(det, dj, out("m1_batch"), data_root=root, batch_files=True,   # noqa: E731
+                                                max_batch=args.max_batch)
+        s1_file(), s1_batch()                                                             # warm-up of both forms
+        pred = handoff.create_data_from_prediction(os.path.join(out("m1_file"), "eval_results.json"), data_root=root)
+        s2_file = lambda: handoff.denoise_files(jm, handoff.get_data_from_first_model(pred, sr=14000), out("m2_file"),   # noqa: E731
+                                                batch_metrics=True)
+        s2_batch = lambda: handoff.denoise_first_model(jm, pred, out("m2_batch"), sr=14000, max_batch=args.max_batch)    # noqa: E731
+        s2_file(), s2_batch()
+        runs = {k: [] for k in ("s1_file", "s1_batch", "s2_file", "s2_batch")}
+        for _ in range(args.repeats):                                                     # the forms alternate
+            runs["s1_file"].append(once(s1_file))
+            runs["s1_batch"].append(once(s1_batch))
+            runs["s2_file"].append(once(s2_file))
+            runs["s2_batch"].append(once(s2_batch))
+        print(f"{args.files} files, {secs:.0f} s of audio, 'mixed' precision, {args.repeats} alternating repeats (median, min, max)")
+        m = {k: report("stage 1 (detect) " if k[1] == "1" else "stage 2 (denoise)", "per file" if k.endswith("file") else "batched",
+                       args.files, v) for k, v in runs.items()}
+        for name, a, b in (("stage 1", "s1_file", "s1_batch"), ("stage 2", "s2_file", "s2_batch")):
+            print(f"  {name}: per file / batched = {m[a] / m[b]:.2f}")
+        tf, tb = m["s1_file"] + m["s2_file"], m["s1_batch"] + m["s2_batch"]
+        print(f"  both stages: per file {args.files / tf:.1f} files/s, batched {args.files / tb:.1f} files/s, ratio {tf / tb:.2f}")
+    sos_amd.set_precision("bf16")
+
+
+if __name__ == "__main__":
+    main()
