@@ -589,6 +589,34 @@ int sos_ragged_stage_f32(const float* x, const int64_t* table, const int64_t* ta
 int sos_ragged_unpack_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
                           int nentries, float* out, sos_stream_t stream);
 
+/* ---- silent-interval labels of clean speech for a ragged batch of clips (csrc/silence_label.hip; sos_amd.labels; float64
+ * restatement: tests/silence_reference.py; parity with the reference's preprocessing/get_bitstream_better is unpinned).
+ * x = the clips back to back in one f32 buffer.  table / table_host: int64 [nclips][4] on the device / the HOST, {sample offset,
+ * samples, frame offset, frames} per clip -- the four columns of sos_ragged_stage_f32's table, so one table serves both calls
+ * and `bits` goes into that call as it is.  params / params_host: f64 [nclips][5] on the device / the host, {ratio = samples per
+ * frame (sr / framerate, > 1), rel = 10^(-threshold_db / 10), floor, min_silent, min_speech (frames, >= 1; 1 disables the pass)}.
+ * Frame i of a clip of n samples is [int(i ratio), min(int((i+1) ratio), n)), the products rounded once in double; `frames`
+ * must tile the clip: int((frames-1) ratio) < n <= int(frames ratio) (ceil(n / ratio) up to the rounding of the products).
+ *   E[i] = mean of x^2 over frame i, f64, a fixed order that depends on the frame's own samples only (no atomics);
+ *   quiet[i] = E[i] <= T, T = max(rel max_i E[i], floor);
+ *   pass 1: a run of non-quiet frames shorter than min_speech with quiet frames on both sides turns quiet;
+ *   pass 2: of the runs as pass 1 left them, a quiet run shorter than min_silent turns non-quiet, wherever it lies.
+ * Writes bits [sum frames] (1 = non-silent, sos_bits_to_mask's convention) and energy f64 [sum frames] at the clips' frame
+ * offsets, and out f64 [nclips][6] = {max E, T, silent frames, silent runs, frames, status}.  A clip's bits and energies are the
+ * same alone, in any batch and in any order.  frames = -1 and status = -1: the DEVICE table or parameters leave what the host's
+ * sized (the bounds rule of the other ragged kernels, and the tiling rule above); nothing is read or written for that clip.
+ * Two launches, no allocation, no host synchronisation.
+ * sos_silence_label_workspace_bytes: 256-byte-aligned int32 arrays of sum(frames) and sum(frames) + nclips entries; -1 on
+ *   a null table or nclips outside 1 .. 65535.
+ * SOS_EINVAL (sos_last_error() names the clip), before any launch: null pointers, nclips outside 1 .. 65535, a clip without
+ * samples or frames, an entry outside the samples / frames summed from the host table, ratio <= 1, a minimum run length < 1, a
+ * negative rel or floor, a frame count under which the last frame would be empty or samples would be left over; SOS_ENOSPC: a
+ * workspace smaller than sos_silence_label_workspace_bytes says. */
+int64_t sos_silence_label_workspace_bytes(const int64_t* table_host, int nclips);
+int sos_silence_label_batch(const float* x, const int64_t* table, const int64_t* table_host, int nclips, const double* params,
+                            const double* params_host, void* workspace, int64_t workspace_bytes, uint8_t* bits, double* energy,
+                            double* out, sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
