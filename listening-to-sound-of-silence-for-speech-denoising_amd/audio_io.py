@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import ragged
 
 # resampy 0.2.2 `kaiser_best`: 64 zero crossings, 2**9 table points per crossing, Kaiser beta, roll-off
 KAISER_BEST = dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596)
@@ -76,9 +77,6 @@ def resample_device(x, orig_sr, target_sr, res_type="kaiser_best", fix=True):
     return out
 
 
-_RESAMPLE_MAX_CLIPS = 65535         # clips per launch of sos_resample_batch_f32 (include/sos_hip.h)
-
-
 def resample_batch_device(clips, orig_sr, target_sr, res_type="kaiser_best", fix=True):
     """resample_device of every clip of a list of 1-D f32 GPU tensors (any lengths) at one common ratio: a list of views
     into one output buffer, clip i with ceil(n_i * ratio) samples (int(n_i * ratio) with fix=False) that are bit for bit
@@ -100,20 +98,20 @@ def resample_batch_device(clips, orig_sr, target_sr, res_type="kaiser_best", fix
                              % (i, n_in[i], orig_sr, target_sr))
     n_out = np.asarray([int(np.ceil(int(n) * ratio)) for n in n_in], dtype=np.int64) if fix else n_res
     n_valid = np.minimum(n_res, n_out)
-    in_end, out_end = np.cumsum(n_in), np.cumsum(n_out)
+    in_off, out_off = ragged.offsets(n_in), ragged.offsets(n_out)
     x = torch.cat(clips)
-    out = torch.empty(int(out_end[-1]), dtype=torch.float32, device=x.device)
+    out = torch.empty(int(n_out.sum()), dtype=torch.float32, device=x.device)
     h = L.lib()
-    for c0 in range(0, len(clips), _RESAMPLE_MAX_CLIPS):
-        c1 = min(c0 + _RESAMPLE_MAX_CLIPS, len(clips))
-        i0, o0 = int(in_end[c0] - n_in[c0]), int(out_end[c0] - n_out[c0])
+    for c0 in range(0, len(clips), ragged.MAX_CLIPS):
+        c1 = min(c0 + ragged.MAX_CLIPS, len(clips))
+        i0, o0 = int(in_off[c0]), int(out_off[c0])
         tiles = -(-n_out[c0:c1] // L.RESAMPLE_CHUNK)
-        tab = np.ascontiguousarray(np.stack([in_end[c0:c1] - n_in[c0:c1] - i0, n_in[c0:c1], out_end[c0:c1] - n_out[c0:c1] - o0,
-                                             n_out[c0:c1], n_valid[c0:c1], np.cumsum(tiles) - tiles]), dtype=np.int64)
+        tab = np.ascontiguousarray(np.stack([in_off[c0:c1] - i0, n_in[c0:c1], out_off[c0:c1] - o0, n_out[c0:c1], n_valid[c0:c1],
+                                             ragged.offsets(tiles)]), dtype=np.int64)
         tab_dev = torch.from_numpy(tab).to(x.device)
         L.check(h.sos_resample_batch_f32(L.ptr(x[i0:]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, ratio, L.ptr(win),
                                          win.numel(), num_table, L.ptr(out[o0:]), L.stream_ptr()), "sos_resample_batch_f32")
-    return [out[int(e - n):int(e)] for e, n in zip(out_end, n_out)]
+    return ragged.split(out, n_out)
 
 
 def pcm_to_mono_device(pcm, fmt):
@@ -227,10 +225,8 @@ def load_batch_device(paths, sr=22050, mono=True, offset=0.0, duration=None, res
     for (kind, _), group in by_format.items():
         pcm = torch.from_numpy(np.concatenate([arr for _, arr in group])).to(device)
         mono_all = pcm_to_mono_device(pcm, kind)          # per frame: the concatenation needs no table
-        pos = 0
-        for i, arr in group:
-            ys[i] = mono_all[pos:pos + arr.shape[0]]
-            pos += arr.shape[0]
+        for (i, _), y in zip(group, ragged.split(mono_all, [arr.shape[0] for _, arr in group])):
+            ys[i] = y
     if sr is None:
         return ys, rates
     by_rate = {}
@@ -246,16 +242,7 @@ def load_batch_device(paths, sr=22050, mono=True, offset=0.0, duration=None, res
 def load_batch(paths, sr=22050, mono=True, offset=0.0, duration=None, dtype=np.float32, res_type="kaiser_best"):
     """load of every file of a list, through load_batch_device: (list of ndarrays, list of rates)."""
     ys, srs = load_batch_device(paths, sr, mono, offset, duration, res_type)
-    return _download(ys, dtype), srs
-
-
-def _download(ys, dtype):
-    """The 1-D GPU tensors of a list as host arrays of `dtype`, through one copy of their concatenation."""
-    if not ys:
-        return []
-    flat = np.ascontiguousarray((torch.cat(ys) if len(ys) > 1 else ys[0]).cpu().numpy(), dtype=dtype)
-    ends = np.cumsum([y.numel() for y in ys])
-    return [flat[int(e) - y.numel():int(e)] for e, y in zip(ends, ys)]
+    return ragged.download(ys, dtype), srs
 
 
 def load(path, sr=22050, mono=True, offset=0.0, duration=None, dtype=np.float32, res_type="kaiser_best"):
@@ -298,10 +285,9 @@ def resample_batch(ys, orig_sr, target_sr, res_type="kaiser_best", fix=True, sca
     if orig_sr == target_sr or not ys:
         return ys
     ratio = float(target_sr) / orig_sr
-    ends = np.cumsum([len(y) for y in ys])
     flat = torch.from_numpy(np.concatenate([np.asarray(y, dtype=np.float32) for y in ys])).cuda()
-    outs = _download(resample_batch_device([flat[int(e) - len(y):int(e)] for e, y in zip(ends, ys)], orig_sr, target_sr,
-                                           res_type, fix), np.float32)
+    outs = ragged.download(resample_batch_device(ragged.split(flat, [len(y) for y in ys]), orig_sr, target_sr, res_type, fix),
+                           np.float32)
     if scale:
         outs = [o / np.sqrt(ratio) for o in outs]
     return [np.ascontiguousarray(o, dtype=y.dtype if np.issubdtype(y.dtype, np.floating) else np.float32)

@@ -4,6 +4,17 @@
 #pragma once
 #include "sos_common.h"
 
+// The frame edge, int(i * ratio) as Python's float64 evaluates it: ONE rounded multiply (the host is compiled with
+// -ffp-contract=on: the volatile product keeps it out of an fma).  The mask rule below and silence_label.hip both use it.
+__host__ __device__ __forceinline__ int64_t frame_edge(int64_t i, double ratio) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (int64_t)__dmul_rn((double)i, ratio);
+#else
+    volatile double p = (double)i * ratio;
+    return (int64_t)p;
+#endif
+}
+
 // Pre-flip mask value of sample j: 1 if j lies in [int(i*r), int((i+1)*r - 1)) of a silent
 // frame i (bit 0), else 0.  All index arithmetic in IEEE double with explicit (un-fused)
 // multiply/add so it reproduces Python's float64 evaluation bit for bit.
@@ -11,7 +22,7 @@ __device__ __forceinline__ int premask(const uint8_t* bits, int64_t n_frames, do
     int64_t i0 = (int64_t)((double)j / ratio);
     for (int64_t i = i0 - 1; i <= i0 + 1; ++i) {
         if (i < 0 || i >= n_frames) continue;
-        const int64_t lo = (int64_t)__dmul_rn((double)i, ratio);
+        const int64_t lo = frame_edge(i, ratio);
         const int64_t hi = (int64_t)__dadd_rn(__dmul_rn((double)(i + 1), ratio), -1.0);
         if (j >= lo && j < hi) return bits[i] == 0 ? 1 : 0;
     }
@@ -34,7 +45,7 @@ __device__ __forceinline__ float mask_sample(const uint8_t* __restrict__ bits, i
         for (int q = 0; q < 3; ++q) {
             const int64_t i = i0 - 1 + q;
             const bool ok = i >= 0 && i < n_frames;
-            lo[q] = ok ? (int64_t)__dmul_rn((double)i, ratio) : 0;
+            lo[q] = ok ? frame_edge(i, ratio) : 0;
             hi[q] = ok ? (int64_t)__dadd_rn(__dmul_rn((double)(i + 1), ratio), -1.0) : 0;      // empty interval when !ok
             val[q] = ok && bits[i] == 0 ? 1 : 0;
         }

@@ -1,7 +1,8 @@
-// ragged.h -- what the three ragged-batch measures (metrics_batch.hip, stoi.hip, sdr.hip) share: the clip-count check, the
-// workspace layout arithmetic, the clamped grid, the bounds rule of their plan kernels and the 256-thread LDS reductions.
-// A batch is two concatenated signals plus a device table [offsets, lengths]; the host sizes every array from its own copy
-// of the lengths (lengths_host), the kernels follow the device table.
+// ragged.h -- what every ragged-batch entry point shares (metrics_batch.hip, stoi.hip, sdr.hip, ragged_io.hip,
+// silence_label.hip, wave_io.hip): the clip-count check, the clip row, the bounds rule on both sides of the launch, the host's
+// sums over a table, the workspace layout arithmetic, the clamped grid and the 256-thread LDS reductions.
+// A batch is clips back to back in one buffer plus a table of where each lies, in two copies: the host sizes every array
+// from its own (table_host / lengths_host) and refuses a bad entry before any launch; the kernels follow the DEVICE table.
 #pragma once
 #include "sos_common.h"
 #include <algorithm>
@@ -30,11 +31,43 @@ static inline unsigned ragged_grid(int64_t units, int per_block, int64_t cap) {
     return (unsigned)std::min<int64_t>(std::max<int64_t>((units + per_block - 1) / per_block, 1), cap);
 }
 
-// The bounds rule of every plan kernel: a clip [off, off + n) of the device table is followed only if it lies inside the
-// `total` samples the host summed from lengths_host (what both signals are known to hold); otherwise the clip gets status
-// -1, extents 0 and no work.  No overflowing add.
+// The bounds rule: a clip [off, off + n) of the device table is followed only if it lies inside the `total` elements the
+// host summed from its own table (what the buffers are known to hold); otherwise the clip gets no work (and, where the
+// kernel reports one, status -1).  No overflowing add.
 __host__ __device__ static inline bool ragged_clip_inside(int64_t off, int64_t n, int64_t total) {
     return off >= 0 && n >= 0 && n <= total && off <= total - n;
+}
+
+// The clip row of sos_ragged_stage_f32 and sos_silence_label_batch: int64 [nclips][4]
+#define RAGGED_CLIP_COLS 4
+struct RaggedClip { int64_t off, n, foff, frames; };      // sample offset, samples, frame offset, frames
+__host__ __device__ static inline RaggedClip ragged_clip(const int64_t* table, int64_t b) {
+    const int64_t* te = table + b * RAGGED_CLIP_COLS;
+    return {te[0], te[1], te[2], te[3]};
+}
+// the device rule for such a row: both extents lie inside (total samples, total frames)
+__host__ __device__ static inline bool ragged_row_inside(const RaggedClip& c, int64_t total, int64_t total_frames) {
+    return ragged_clip_inside(c.off, c.n, total) && ragged_clip_inside(c.foff, c.frames, total_frames);
+}
+
+// Host: adds column `col` of a row-major table [nrows][cols] to `s` from row `first` on, every entry within [lo, hi] and the
+// sum within INT64_MAX / 8 (bytes of f64 stay inside int64); returns nrows, or the first entry it cannot accept.
+struct RaggedSum { int64_t total = 0, longest = 0; };
+static inline int ragged_sum_column(const int64_t* table, int nrows, int cols, int col, int64_t lo, int64_t hi, RaggedSum* s,
+                                    int first = 0) {
+    for (int r = first; r < nrows; ++r) {
+        const int64_t v = table[(int64_t)r * cols + col];
+        if (v < lo || v > hi || v > INT64_MAX / 8 - s->total) return r;
+        s->total += v;
+        s->longest = std::max(s->longest, v);
+    }
+    return nrows;
+}
+// Host: nrows, or the index of the first entry whose [table[off_col], + table[len_col]) leaves the `total` elements
+static inline int ragged_first_outside(const int64_t* table, int nrows, int cols, int off_col, int len_col, int64_t total) {
+    for (int r = 0; r < nrows; ++r)
+        if (!ragged_clip_inside(table[(int64_t)r * cols + off_col], table[(int64_t)r * cols + len_col], total)) return r;
+    return nrows;
 }
 
 // Reductions over the MT threads of a workgroup through LDS (red: f64 [MT], scan: int [MT]), fixed trees.  block_sum and

@@ -8,29 +8,48 @@
 // inside the clip; scalar accesses otherwise (the two sides of an unaligned clip cannot both be aligned).
 // The mask is mask_sample of mask_rule.h, the rule of sos_bits_to_mask: a clip's bits are those of
 // sos_bits_to_mask(bits, 1, frames, ratio, samples) for that clip alone, in any group and any order.
-// Bounds: the host refuses a table entry outside the samples / frames it summed from table_host (SOS_EINVAL); the kernels
-// follow the DEVICE table and skip an entry that fails the same rule (ragged_clip_inside), so nothing outside the buffers
-// the host sized is read or written.
+// Bounds: the rule of ragged.h -- the host refuses a table entry outside the samples / frames it summed from table_host
+// (SOS_EINVAL), the kernels skip an entry of the DEVICE table that fails the same rule.
 #include "ragged.h"
 #include "mask_rule.h"
 
 #define RIO_THREADS 256
 #define RIO_MAX_GRID 1024               // workgroups along a row (they stride over what the grid does not cover)
-#define RIO_STAGE_COLS 4                // int64 per clip: sample offset, samples, bit offset, frames
 #define RIO_UNPACK_COLS 3               // int64 per entry: row, valid samples, output offset
 
 typedef float rio_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bool rio_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }      // a null pointer counts
+
+// v = p[j0 .. j0 + 4): one 16-byte load if `vec` (p + j0 aligned, all four inside), else the samples below `end` one by one
+__device__ __forceinline__ void rio_load4(const float* p, int64_t j0, int64_t end, bool vec, float (&v)[4]) {
+    if (vec) {
+        const rio_f32x4 q = *(const rio_f32x4*)(p + j0);
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k < end) v[k] = p[j0 + k];
+    }
+}
+// p[j0 .. j0 + 4) = v, likewise
+__device__ __forceinline__ void rio_store4(float* p, int64_t j0, int64_t end, bool vec, const float (&v)[4]) {
+    if (vec) {
+        *(rio_f32x4*)(p + j0) = rio_f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k < end) p[j0 + k] = v[k];
+    }
+}
 
 __global__ __launch_bounds__(RIO_THREADS) void ragged_stage_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ table, int64_t total, const uint8_t* __restrict__ bits,
     int64_t total_bits, const double* __restrict__ ratios, int64_t stride, float* __restrict__ wave, float* __restrict__ masked,
     float* __restrict__ mask) {
     const int64_t b = blockIdx.y;
-    const int64_t* te = table + b * RIO_STAGE_COLS;
-    const int64_t off = te[0], n = te[1], boff = te[2], nfr = te[3];
-    if (!ragged_clip_inside(off, n, total) || n > stride) return;
-    if (bits && !ragged_clip_inside(boff, nfr, total_bits)) return;
+    const RaggedClip c = ragged_clip(table, b);
+    const int64_t off = c.off, n = c.n, boff = c.foff, nfr = c.frames;
+    if (n > stride || !(bits ? ragged_row_inside(c, total, total_bits) : ragged_clip_inside(off, n, total))) return;
     const double ratio = bits ? ratios[b] : 0.0;
     if (bits && !(ratio > 1.0)) return;
     const float* xc = x + off;
@@ -43,37 +62,19 @@ __global__ __launch_bounds__(RIO_THREADS) void ragged_stage_kernel(
     for (int64_t j0 = ((int64_t)blockIdx.x * RIO_THREADS + threadIdx.x) * 4; j0 < stride; j0 += (int64_t)gridDim.x * RIO_THREADS * 4) {
         const bool full = j0 + 4 <= n;                       // all four samples inside the clip
         float v[4] = {0.f, 0.f, 0.f, 0.f}, m[4] = {0.f, 0.f, 0.f, 0.f};
-        if (full && clip_vec) {
-            const rio_f32x4 q = *(const rio_f32x4*)(xc + j0);
-            v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (j0 + k < n) v[k] = xc[j0 + k];
-        }
+        rio_load4(xc, j0, n, full && clip_vec, v);
         if (bits) {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (j0 + k < n) m[k] = mask_sample(bc, nfr, ratio, n, j0 + k);
-            if (full && clip_vec) {
-                *(rio_f32x4*)(mc + j0) = rio_f32x4{m[0], m[1], m[2], m[3]};
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (j0 + k < n) mc[j0 + k] = m[k];
-            }
+            rio_store4(mc, j0, n, full && clip_vec, m);
         }
-        // the rows: zero from the clip's end to the stride (v and m are 0 there)
-        if (row_vec) {                                       // j0 + 4 <= stride: the stride is a multiple of four
-            *(rio_f32x4*)(wrow + j0) = rio_f32x4{v[0], v[1], v[2], v[3]};
-            if (bits) *(rio_f32x4*)(mrow + j0) = rio_f32x4{v[0] * m[0], v[1] * m[1], v[2] * m[2], v[3] * m[3]};
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (j0 + k < stride) {
-                    wrow[j0 + k] = v[k];
-                    if (bits) mrow[j0 + k] = v[k] * m[k];
-                }
+        // the rows: zero from the clip's end to the stride (v and m are 0 there); row_vec: the stride is a multiple of four,
+        // so j0 + 4 <= stride
+        rio_store4(wrow, j0, stride, row_vec, v);
+        if (bits) {
+            const float vm[4] = {v[0] * m[0], v[1] * m[1], v[2] * m[2], v[3] * m[3]};
+            rio_store4(mrow, j0, stride, row_vec, vm);
         }
     }
 }
@@ -90,21 +91,8 @@ __global__ __launch_bounds__(RIO_THREADS) void ragged_unpack_kernel(const float*
     for (int64_t j0 = ((int64_t)blockIdx.x * RIO_THREADS + threadIdx.x) * 4; j0 < n; j0 += (int64_t)gridDim.x * RIO_THREADS * 4) {
         const bool full = j0 + 4 <= n;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (full && row_vec) {
-            const rio_f32x4 q = *(const rio_f32x4*)(src + j0);
-            v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (j0 + k < n) v[k] = src[j0 + k];
-        }
-        if (full && out_vec) {
-            *(rio_f32x4*)(dst + j0) = rio_f32x4{v[0], v[1], v[2], v[3]};
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (j0 + k < n) dst[j0 + k] = v[k];
-        }
+        rio_load4(src, j0, n, full && row_vec, v);
+        rio_store4(dst, j0, n, full && out_vec, v);
     }
 }
 
@@ -120,33 +108,32 @@ extern "C" int sos_ragged_stage_f32(const float* x, const int64_t* table, const 
         sos_set_error("sos_ragged_stage_f32: frame decisions need ratios, ratios_host, masked and mask");
         return SOS_EINVAL;
     }
-    int64_t total = 0, total_bits = 0;
-    for (int b = 0; b < nclips; ++b) {
-        const int64_t n = table_host[b * RIO_STAGE_COLS + 1], nfr = table_host[b * RIO_STAGE_COLS + 3];
-        if (n < 0 || n > stride || nfr < 0 || n > INT64_MAX / 8 - total || nfr > INT64_MAX / 8 - total_bits) {
-            sos_set_error("sos_ragged_stage_f32: clip %d has %lld samples (stride %lld) and %lld frames", b, (long long)n,
-                          (long long)stride, (long long)nfr);
-            return SOS_EINVAL;
-        }
-        total += n;
-        total_bits += nfr;
+    RaggedSum ns, nf;
+    int bad = std::min(ragged_sum_column(table_host, nclips, RAGGED_CLIP_COLS, 1, 0, stride, &ns),
+                       ragged_sum_column(table_host, nclips, RAGGED_CLIP_COLS, 3, 0, INT64_MAX, &nf));
+    if (bad < nclips) {
+        const RaggedClip c = ragged_clip(table_host, bad);
+        sos_set_error("sos_ragged_stage_f32: clip %d has %lld samples (stride %lld) and %lld frames", bad, (long long)c.n,
+                      (long long)stride, (long long)c.frames);
+        return SOS_EINVAL;
     }
-    for (int b = 0; b < nclips; ++b) {
-        const int64_t* te = table_host + b * RIO_STAGE_COLS;
-        if (!ragged_clip_inside(te[0], te[1], total) || (bits && !ragged_clip_inside(te[2], te[3], total_bits))) {
-            sos_set_error("sos_ragged_stage_f32: clip %d (samples %lld + %lld, frames %lld + %lld) lies outside the %lld samples / "
-                          "%lld frames of the table", b, (long long)te[0], (long long)te[1], (long long)te[2], (long long)te[3],
-                          (long long)total, (long long)total_bits);
-            return SOS_EINVAL;
-        }
-        if (bits && !(ratios_host[b] > 1.0)) {
+    bad = ragged_first_outside(table_host, nclips, RAGGED_CLIP_COLS, 0, 1, ns.total);
+    if (bits) bad = std::min(bad, ragged_first_outside(table_host, nclips, RAGGED_CLIP_COLS, 2, 3, nf.total));
+    for (int b = 0; bits && b < bad; ++b)                    // the clips before the first that lies outside
+        if (!(ratios_host[b] > 1.0)) {
             sos_set_error("sos_ragged_stage_f32: clip %d has ratio %g (samples per frame must exceed 1)", b, ratios_host[b]);
             return SOS_EINVAL;
         }
+    if (bad < nclips) {
+        const RaggedClip c = ragged_clip(table_host, bad);
+        sos_set_error("sos_ragged_stage_f32: clip %d (samples %lld + %lld, frames %lld + %lld) lies outside the %lld samples / "
+                      "%lld frames of the table", bad, (long long)c.off, (long long)c.n, (long long)c.foff, (long long)c.frames,
+                      (long long)ns.total, (long long)nf.total);
+        return SOS_EINVAL;
     }
     const dim3 grid(ragged_grid((stride + 3) / 4, RIO_THREADS, RIO_MAX_GRID), (unsigned)nclips);
-    hipLaunchKernelGGL(ragged_stage_kernel, grid, dim3(RIO_THREADS), 0, (hipStream_t)stream, x, table, total, bits, total_bits, ratios,
-                       stride, wave, masked, mask);
+    hipLaunchKernelGGL(ragged_stage_kernel, grid, dim3(RIO_THREADS), 0, (hipStream_t)stream, x, table, ns.total, bits, nf.total,
+                       ratios, stride, wave, masked, mask);
     return sos_check_launch("sos_ragged_stage_f32");
 }
 
@@ -158,26 +145,25 @@ extern "C" int sos_ragged_unpack_f32(const float* rows, int64_t n_rows, int64_t 
                       (long long)stride);
         return SOS_EINVAL;
     }
-    int64_t total = 0, longest = 0;
-    for (int e = 0; e < nentries; ++e) {
-        const int64_t row = table_host[e * RIO_UNPACK_COLS], n = table_host[e * RIO_UNPACK_COLS + 1];
-        if (row < 0 || row >= n_rows || n < 0 || n > stride || n > INT64_MAX / 8 - total) {
-            sos_set_error("sos_ragged_unpack_f32: entry %d takes %lld samples of row %lld (%lld rows of %lld)", e, (long long)n,
-                          (long long)row, (long long)n_rows, (long long)stride);
-            return SOS_EINVAL;
-        }
-        total += n;
-        longest = std::max(longest, n);
+    RaggedSum ns;
+    int bad = ragged_sum_column(table_host, nentries, RIO_UNPACK_COLS, 1, 0, stride, &ns);
+    for (int e = 0; e < bad; ++e)                            // the entries before it name a row there is
+        if (table_host[e * RIO_UNPACK_COLS] < 0 || table_host[e * RIO_UNPACK_COLS] >= n_rows) bad = e;
+    if (bad < nentries) {
+        const int64_t* te = table_host + bad * RIO_UNPACK_COLS;
+        sos_set_error("sos_ragged_unpack_f32: entry %d takes %lld samples of row %lld (%lld rows of %lld)", bad, (long long)te[1],
+                      (long long)te[0], (long long)n_rows, (long long)stride);
+        return SOS_EINVAL;
     }
-    for (int e = 0; e < nentries; ++e) {
-        const int64_t* te = table_host + e * RIO_UNPACK_COLS;
-        if (!ragged_clip_inside(te[2], te[1], total)) {
-            sos_set_error("sos_ragged_unpack_f32: entry %d (output %lld + %lld) lies outside the %lld samples of the table", e,
-                          (long long)te[2], (long long)te[1], (long long)total);
-            return SOS_EINVAL;
-        }
+    bad = ragged_first_outside(table_host, nentries, RIO_UNPACK_COLS, 2, 1, ns.total);
+    if (bad < nentries) {
+        const int64_t* te = table_host + bad * RIO_UNPACK_COLS;
+        sos_set_error("sos_ragged_unpack_f32: entry %d (output %lld + %lld) lies outside the %lld samples of the table", bad,
+                      (long long)te[2], (long long)te[1], (long long)ns.total);
+        return SOS_EINVAL;
     }
-    const dim3 grid(ragged_grid((longest + 3) / 4, RIO_THREADS, RIO_MAX_GRID), (unsigned)nentries);
-    hipLaunchKernelGGL(ragged_unpack_kernel, grid, dim3(RIO_THREADS), 0, (hipStream_t)stream, rows, n_rows, stride, table, total, out);
+    const dim3 grid(ragged_grid((ns.longest + 3) / 4, RIO_THREADS, RIO_MAX_GRID), (unsigned)nentries);
+    hipLaunchKernelGGL(ragged_unpack_kernel, grid, dim3(RIO_THREADS), 0, (hipStream_t)stream, rows, n_rows, stride, table, ns.total,
+                       out);
     return sos_check_launch("sos_ragged_unpack_f32");
 }

@@ -13,14 +13,14 @@
 //                          frame's run number and every run's first frame into the workspace) and a rule over the runs as
 //                          they were when the pass began: 1. a non-quiet run shorter than min_speech with a quiet run on both
 //                          sides turns quiet, 2. a quiet run shorter than min_silent turns non-quiet.
-// bits (1 = non-silent, the convention of sos_bits_to_mask) and E lie back to back at the frame offsets of the table, which
-// has the four columns of sos_ragged_stage_f32's.  No atomics; a clip's bits depend on that clip's samples only.
-// Bounds: the host refuses a table entry outside the samples / frames it summed from table_host; the kernels follow the
-// DEVICE table and parameters and give a clip that fails the same rules (ragged_clip_inside, sl_frames_fit) status -1 and no
-// work, and every frame's sample range is clamped to its clip.
+// bits (1 = non-silent, the convention of sos_bits_to_mask) and E lie back to back at the frame offsets of the table, the
+// clip rows of ragged.h (sos_ragged_stage_f32 takes the same).  No atomics; a clip's bits depend on that clip's samples only.
+// Bounds: the rule of ragged.h -- the host refuses a table entry outside the samples / frames it summed from table_host; the
+// kernels follow the DEVICE table and parameters and give a clip that fails the same rules (ragged_row_inside, sl_frames_fit)
+// status -1 and no work; every frame's sample range is clamped to its clip.  Frame edges: frame_edge of mask_rule.h, the mask's.
 #include "ragged.h"
+#include "mask_rule.h"
 
-#define SL_COLS 4                       // int64 per clip: sample offset, samples, frame offset, frames
 #define SL_PARAMS 5                     // f64 per clip: ratio, rel, floor, min_silent, min_speech
 #define SL_OUT 6                        // f64 per clip: max E, T, silent frames, silent runs, frames, status
 #define SL_WAVES (MT / 64)              // frames a workgroup of the energy kernel works on at a time
@@ -31,21 +31,11 @@
 typedef float sl_f32x4 __attribute__((ext_vector_type(4)));
 typedef sl_f32x4 sl_f32x4_u __attribute__((aligned(4)));             // four consecutive samples at any sample address
 
-// i * ratio as Python's float64 evaluates it: one rounded multiply (csrc/mask_rule.h states the same rule)
-__host__ __device__ static inline int64_t sl_edge(int64_t i, double ratio) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return (int64_t)__dmul_rn((double)i, ratio);
-#else
-    volatile double p = (double)i * ratio;
-    return (int64_t)p;
-#endif
-}
-
 __host__ __device__ static inline bool sl_ratio_ok(double ratio) { return ratio > 1.0 && ratio <= SL_MAX_RATIO; }
 
 // `frames` frames of `ratio` samples tile a clip of n samples: none is empty and no sample is left over
 __host__ __device__ static inline bool sl_frames_fit(int64_t n, int64_t frames, double ratio) {
-    return n >= 1 && frames >= 1 && frames <= SL_MAX_FRAMES && sl_edge(frames - 1, ratio) < n && n <= sl_edge(frames, ratio);
+    return n >= 1 && frames >= 1 && frames <= SL_MAX_FRAMES && frame_edge(frames - 1, ratio) < n && n <= frame_edge(frames, ratio);
 }
 
 __host__ __device__ static inline bool sl_params_ok(const double* p) {
@@ -53,25 +43,24 @@ __host__ __device__ static inline bool sl_params_ok(const double* p) {
 }
 
 // what both kernels ask of a clip of the device table before they touch anything
-__device__ static inline bool sl_clip_ok(const int64_t* te, const double* p, int64_t total, int64_t total_frames) {
-    return ragged_clip_inside(te[0], te[1], total) && ragged_clip_inside(te[2], te[3], total_frames) && sl_params_ok(p) &&
-           sl_frames_fit(te[1], te[3], p[0]);
+__device__ static inline bool sl_clip_ok(const RaggedClip& c, const double* p, int64_t total, int64_t total_frames) {
+    return ragged_row_inside(c, total, total_frames) && sl_params_ok(p) && sl_frames_fit(c.n, c.frames, p[0]);
 }
 
 __global__ __launch_bounds__(MT) void silence_energy_kernel(const float* __restrict__ x, const int64_t* __restrict__ table,
                                                             const double* __restrict__ params, int64_t total, int64_t total_frames,
                                                             double* __restrict__ energy) {
-    const int64_t* te = table + (int64_t)blockIdx.y * SL_COLS;
+    const RaggedClip c = ragged_clip(table, blockIdx.y);
     const double* p = params + (int64_t)blockIdx.y * SL_PARAMS;
-    if (!sl_clip_ok(te, p, total, total_frames)) return;
-    const int64_t n = te[1], frames = te[3];
+    if (!sl_clip_ok(c, p, total, total_frames)) return;
+    const int64_t n = c.n, frames = c.frames;
     const double ratio = p[0];
-    const float* xc = x + te[0];
-    double* ec = energy + te[2];
+    const float* xc = x + c.off;
+    double* ec = energy + c.foff;
     const int lane = threadIdx.x & 63;
     for (int64_t f = (int64_t)blockIdx.x * SL_WAVES + (threadIdx.x >> 6); f < frames; f += (int64_t)gridDim.x * SL_WAVES) {
         // clamped to the clip, whatever the ratio: 0 <= lo <= hi <= n
-        const int64_t lo = min(max(sl_edge(f, ratio), (int64_t)0), n), hi = min(max(sl_edge(f + 1, ratio), lo), n);
+        const int64_t lo = min(max(frame_edge(f, ratio), (int64_t)0), n), hi = min(max(frame_edge(f + 1, ratio), lo), n);
         const int64_t len = hi - lo, groups = len >> 2;
         const float* xf = xc + lo;
         double acc = 0.0;
@@ -129,18 +118,18 @@ __global__ __launch_bounds__(MT) void silence_label_kernel(const int64_t* __rest
                                                            uint8_t* __restrict__ bits, double* __restrict__ out) {
     __shared__ double red[MT];
     __shared__ int scan[MT];
-    const int64_t* te = table + (int64_t)blockIdx.x * SL_COLS;
+    const RaggedClip c = ragged_clip(table, blockIdx.x);
     const double* p = params + (int64_t)blockIdx.x * SL_PARAMS;
     double* o = out + (int64_t)blockIdx.x * SL_OUT;
-    if (!sl_clip_ok(te, p, total, total_frames)) {
+    if (!sl_clip_ok(c, p, total, total_frames)) {
         if (threadIdx.x == 0) { o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; o[3] = 0.0; o[4] = -1.0; o[5] = -1.0; }
         return;
     }
-    const int frames = (int)te[3];
-    const double* ec = energy + te[2];
-    uint8_t* bc = bits + te[2];
-    int* rid = rid_all + te[2];
-    int* rs = rs_all + te[2] + blockIdx.x;                               // frames + 1 entries per clip
+    const int frames = (int)c.frames;
+    const double* ec = energy + c.foff;
+    uint8_t* bc = bits + c.foff;
+    int* rid = rid_all + c.foff;
+    int* rs = rs_all + c.foff + blockIdx.x;                              // frames + 1 entries per clip
     const double rel = p[1], floor_ = p[2], min_silent = p[3], min_speech = p[4];
     double m = 0.0;                                                      // energies are >= 0
     for (int i = threadIdx.x; i < frames; i += MT) m = fmax(m, ec[i]);
@@ -170,36 +159,18 @@ __global__ __launch_bounds__(MT) void silence_label_kernel(const int64_t* __rest
     if (threadIdx.x == 0) { o[0] = emax; o[1] = T; o[2] = s0; o[3] = s1; o[4] = (double)frames; o[5] = 0.0; }
 }
 
-namespace {
-struct SlLayout {
-    int64_t total = 0, total_frames = 0, max_frames = 0;
-    size_t rid = 0, rs = 0, bytes = 0;
-};
-// totals from the host table (entries that cannot be summed count as 0: the launch refuses them by name)
-SlLayout sl_layout(const int64_t* table_host, int nclips) {
-    SlLayout l;
-    for (int b = 0; b < nclips; ++b) {
-        const int64_t n = table_host[b * SL_COLS + 1], f = table_host[b * SL_COLS + 3];
-        if (n > 0 && n <= INT64_MAX / 8 - l.total) l.total += n;
-        if (f > 0 && f <= SL_MAX_FRAMES && f <= INT64_MAX / 8 - l.total_frames) {
-            l.total_frames += f;
-            l.max_frames = std::max(l.max_frames, f);
-        }
-    }
-    RaggedBump ws;
-    l.rid = ws.take((size_t)l.total_frames * 4);
-    l.rs = ws.take(((size_t)l.total_frames + (size_t)nclips) * 4);
-    l.bytes = ws.o;
-    return l;
-}
-}  // namespace
+// the workspace: a run number per frame at 0, then frames + 1 run starts per clip at sl_rs, each array to 256 bytes
+static size_t sl_rs(int64_t frames) { return align256((size_t)frames * 4); }
+static size_t sl_bytes(int64_t frames, int nclips) { return sl_rs(frames) + align256(((size_t)frames + (size_t)nclips) * 4); }
 
 extern "C" int64_t sos_silence_label_workspace_bytes(const int64_t* table_host, int nclips) {
     if (!ragged_clips_ok(table_host, nclips)) {
         sos_set_error("sos_silence_label_workspace_bytes: bad args (1 .. 65535 clips, got %d)", nclips);
         return -1;
     }
-    return (int64_t)sl_layout(table_host, nclips).bytes;
+    RaggedSum nf;                                                        // a clip the launch would refuse by name counts as 0
+    for (int b = 0; b < nclips; ++b) b = ragged_sum_column(table_host, nclips, RAGGED_CLIP_COLS, 3, 1, SL_MAX_FRAMES, &nf, b);
+    return (int64_t)sl_bytes(nf.total, nclips);
 }
 
 extern "C" int sos_silence_label_batch(const float* x, const int64_t* table, const int64_t* table_host, int nclips,
@@ -213,24 +184,24 @@ extern "C" int sos_silence_label_batch(const float* x, const int64_t* table, con
         sos_set_error("sos_silence_label_batch: bad args (1 .. 65535 clips, got %d)", nclips);
         return SOS_EINVAL;
     }
-    int64_t total = 0, total_frames = 0;
-    for (int b = 0; b < nclips; ++b) {
-        const int64_t n = table_host[b * SL_COLS + 1], f = table_host[b * SL_COLS + 3];
-        if (n < 1 || f < 1 || f > SL_MAX_FRAMES || n > INT64_MAX / 8 - total || f > INT64_MAX / 8 - total_frames) {
-            sos_set_error("sos_silence_label_batch: clip %d has %lld samples and %lld frames (at least 1 of each)", b, (long long)n,
-                          (long long)f);
-            return SOS_EINVAL;
-        }
-        total += n;
-        total_frames += f;
+    RaggedSum ns, nf;
+    int bad = std::min(ragged_sum_column(table_host, nclips, RAGGED_CLIP_COLS, 1, 1, INT64_MAX, &ns),
+                       ragged_sum_column(table_host, nclips, RAGGED_CLIP_COLS, 3, 1, SL_MAX_FRAMES, &nf));
+    if (bad < nclips) {
+        const RaggedClip c = ragged_clip(table_host, bad);
+        sos_set_error("sos_silence_label_batch: clip %d has %lld samples and %lld frames (at least 1 of each)", bad, (long long)c.n,
+                      (long long)c.frames);
+        return SOS_EINVAL;
     }
+    bad = std::min(ragged_first_outside(table_host, nclips, RAGGED_CLIP_COLS, 0, 1, ns.total),
+                   ragged_first_outside(table_host, nclips, RAGGED_CLIP_COLS, 2, 3, nf.total));
     for (int b = 0; b < nclips; ++b) {
-        const int64_t* te = table_host + b * SL_COLS;
+        const RaggedClip c = ragged_clip(table_host, b);
         const double* p = params_host + b * SL_PARAMS;
-        if (!ragged_clip_inside(te[0], te[1], total) || !ragged_clip_inside(te[2], te[3], total_frames)) {
+        if (b == bad) {
             sos_set_error("sos_silence_label_batch: clip %d (samples %lld + %lld, frames %lld + %lld) lies outside the %lld samples / "
-                          "%lld frames of the table", b, (long long)te[0], (long long)te[1], (long long)te[2], (long long)te[3],
-                          (long long)total, (long long)total_frames);
+                          "%lld frames of the table", b, (long long)c.off, (long long)c.n, (long long)c.foff, (long long)c.frames,
+                          (long long)ns.total, (long long)nf.total);
             return SOS_EINVAL;
         }
         if (!sl_ratio_ok(p[0])) {
@@ -247,25 +218,25 @@ extern "C" int sos_silence_label_batch(const float* x, const int64_t* table, con
                           p[2]);
             return SOS_EINVAL;
         }
-        if (!sl_frames_fit(te[1], te[3], p[0])) {
+        if (!sl_frames_fit(c.n, c.frames, p[0])) {
             sos_set_error("sos_silence_label_batch: clip %d: %lld frames of %g samples do not tile %lld samples (%s)", b,
-                          (long long)te[3], p[0], (long long)te[1],
-                          sl_edge(te[3] - 1, p[0]) >= te[1] ? "the last frame would be empty" : "samples would be left over");
+                          (long long)c.frames, p[0], (long long)c.n,
+                          frame_edge(c.frames - 1, p[0]) >= c.n ? "the last frame would be empty" : "samples would be left over");
             return SOS_EINVAL;
         }
     }
-    const SlLayout l = sl_layout(table_host, nclips);
-    if (workspace_bytes < (int64_t)l.bytes) {
-        sos_set_error("sos_silence_label_batch: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)l.bytes);
+    const int64_t need = (int64_t)sl_bytes(nf.total, nclips);
+    if (workspace_bytes < need) {
+        sos_set_error("sos_silence_label_batch: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
         return SOS_ENOSPC;
     }
     char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    hipLaunchKernelGGL(silence_energy_kernel, dim3(ragged_grid(l.max_frames, SL_WAVES, SL_MAX_GRID), (unsigned)nclips), dim3(MT), 0, s,
-                       x, table, params, total, total_frames, energy);
+    hipLaunchKernelGGL(silence_energy_kernel, dim3(ragged_grid(nf.longest, SL_WAVES, SL_MAX_GRID), (unsigned)nclips), dim3(MT), 0, s,
+                       x, table, params, ns.total, nf.total, energy);
     if ((rc = sos_check_launch("sos_silence_label_batch: energies")) != SOS_OK) return rc;
-    hipLaunchKernelGGL(silence_label_kernel, dim3((unsigned)nclips), dim3(MT), 0, s, table, params, total, total_frames,
-                       (const double*)energy, (int*)(ws + l.rid), (int*)(ws + l.rs), bits, out);
+    hipLaunchKernelGGL(silence_label_kernel, dim3((unsigned)nclips), dim3(MT), 0, s, table, params, ns.total, nf.total,
+                       (const double*)energy, (int*)ws, (int*)(ws + sl_rs(nf.total)), bits, out);
     return sos_check_launch("sos_silence_label_batch: labels");
 }

@@ -11,7 +11,7 @@
 // resample_kernel: one output sample per thread; the filter half-window (32 769 + 1 floats = 128 KB) lives
 // in LDS, so the ~2 x 202 taps of an output at 44.1 -> 14 kHz cost one ds_read2_b32 (w[o], w[o+1]) and one
 // L1-resident input read each.  A workgroup walks RS_PER_WG consecutive outputs to amortise the table load.
-#include "sos_common.h"
+#include "ragged.h"
 #include <stdlib.h>
 
 #define RS_THREADS 256
@@ -188,9 +188,8 @@ __global__ __launch_bounds__(THREADS) void resample_batch_kernel(const float* __
         const int64_t in_off = tab[lo], n_in = tab[nclips + lo], out_off = tab[2 * (int64_t)nclips + lo];
         const int64_t n_out = tab[3 * (int64_t)nclips + lo], n_valid = tab[4 * (int64_t)nclips + lo];
         const int64_t t0 = (tile - tile0[lo]) * RS_PER_WG;
-        if (in_off < 0 || n_in < 1 || n_in > total_in || in_off > total_in - n_in || out_off < 0 || n_out < 1 ||
-            n_out > total_out || out_off > total_out - n_out || n_valid < 0 || n_valid > n_out || n_valid > max_valid ||
-            t0 < 0 || t0 >= n_out)
+        if (!ragged_clip_inside(in_off, n_in, total_in) || n_in < 1 || !ragged_clip_inside(out_off, n_out, total_out) ||
+            n_out < 1 || n_valid < 0 || n_valid > n_out || n_valid > max_valid || t0 < 0 || t0 >= n_out)
             continue;
         const float* xc = x + in_off;
         float* oc = out + out_off;
@@ -255,7 +254,7 @@ static int rs_launch_batch(unsigned grid, size_t lds, hipStream_t st, const floa
 extern "C" int sos_resample_batch_f32(const float* x, const int64_t* table, const int64_t* table_host, int nclips, double ratio,
                                       const float* win, int nwin, int num_table, float* out, sos_stream_t stream) {
     if (!x || !table || !table_host || !win || !out) { sos_set_error("sos_resample_batch_f32: null pointer"); return SOS_EINVAL; }
-    if (nclips < 1 || nclips > 65535 || !(ratio > 0.0) || nwin < 2 || num_table < 1 ||
+    if (nclips < 1 || nclips > RAGGED_MAX_CLIPS || !(ratio > 0.0) || nwin < 2 || num_table < 1 ||
         (size_t)(nwin + 1) * sizeof(float) > 160 * 1024) {
         sos_set_error("sos_resample_batch_f32: bad args (1 .. 65535 clips, got %d; ratio=%g, nwin=%d: (nwin + 1) * 4 bytes must "
                       "fit the 160 KB LDS)", nclips, ratio, nwin);

@@ -24,7 +24,7 @@ from operator import itemgetter
 import numpy as np
 import torch
 
-from . import audio_io, metrics, tools, transform
+from . import audio_io, metrics, ragged, tools, transform
 from .tools import add_signals
 
 JSON_DUMP_PARAMS = dict(indent=4, sort_keys=False, ensure_ascii=False, separators=(',', ':'))   # M1/tools.py:36
@@ -421,9 +421,7 @@ def _batch_measures(work, pesq_fn, stoi_fn):
             out16[i], clean16[i] = res[k][:n], res[len(idx) + k][:n]
     pesq, stoi = None, (True if stoi_fn is True else None)
     if pesq_fn is not None or callable(stoi_fn):
-        flat = torch.cat(out16 + clean16).cpu().numpy()               # one download for the callables
-        ends = np.cumsum([t.numel() for t in out16 + clean16])
-        host = [flat[int(e) - t.numel():int(e)] for e, t in zip(ends, out16 + clean16)]
+        host = ragged.download(out16 + clean16)                       # one download for the callables
         oh, ch = host[:len(work)], host[len(work):]
         if pesq_fn is not None:
             pesq = [pesq_fn(c, o, 16000) for c, o in zip(ch, oh)]
@@ -549,8 +547,7 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
                                  % (mixed_paths[i], y.numel(), sr, pipeline.MIN_FRAMES, pipeline.MIN_FRAMES * hop))
         device = mixed[0].device
         all_bits = torch.from_numpy(np.concatenate(rec_bits + gt_bits)).to(device)       # every bit string: one copy
-        ends = np.cumsum([len(b) for b in rec_bits + gt_bits])
-        d_bits = [all_bits[int(e) - len(b):int(e)] for e, b in zip(ends, rec_bits + gt_bits)]
+        d_bits = ragged.split(all_bits, [len(b) for b in rec_bits + gt_bits])
         work = [None] * F
     for part in (pipeline._ragged_groups(mixed, max_batch, max_columns) if F else []):
         B = len(part)
@@ -592,8 +589,8 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
             else:
                 both = sigs
             tab = np.asarray(table, dtype=np.int64)
-            tab[:, 2] = np.cumsum(tab[:, 1]) - tab[:, 1]
-            host = tools.ragged_unpack(both, tab).cpu().numpy()
+            tab[:, 2] = ragged.offsets(tab[:, 1])
+            host = ragged.split(tools.ragged_unpack(both, tab).cpu().numpy(), tab[:, 1])
         per = 6 if known else 4
         for k, i in enumerate(part):
             d = files[i]
@@ -607,10 +604,7 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
             info.update([('bitstream', d[BIT_STREAM_LABEL]), ('sr', sr), ('snr', obj['snr'])])
             sig_i = [sigs[q * B + k, :n_out[k]] for q in range(4)]
             gt_i = [gt[q * B + k, :n_gt[q * B + k]] for q in range(2)] if known else None
-            host_i = None
-            if host is not None:
-                e = [(int(tab[per * k + q, 2]), int(tab[per * k + q, 1])) for q in range(per)]
-                host_i = [host[o:o + n] for o, n in e]
+            host_i = host[per * k:per * (k + 1)] if host is not None else None
             work[i] = (data, info, sig_i, gt_i, host_i)
     stat = [w[1] for w in work]
     _batch_measures([w[:4] for w in work if w[3] is not None], pesq_fn, stoi_fn)

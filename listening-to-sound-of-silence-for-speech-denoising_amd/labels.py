@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import metrics
+from . import ragged
 
 _OUT = 6                            # f64 per clip of sos_silence_label_batch: max E, T, silent frames, silent runs, frames, status
 DEFAULT_MAX_BYTES = 1 << 30         # label_files: f32 samples per group of files
@@ -52,23 +52,14 @@ def frame_count(n, sr, fps):
     return F
 
 
-def _per_clip(value, nclips, name):
-    v = np.asarray(value, dtype=np.float64)
-    if v.ndim > 1 or (v.ndim == 1 and len(v) != nclips):
-        raise ValueError(f"{name}: one value or one per clip ({nclips}), got shape {v.shape}")
-    return np.array(np.broadcast_to(v, (nclips,)))
-
-
 def _plan(lens, sr, fps, threshold_db, min_silence, min_speech, floor, first_clip=0):
     """Host table int64 [B][4] and parameters f64 [B][5] of sos_silence_label_batch for clips of `lens` samples."""
-    B = len(lens)
-    tab, par = np.zeros((B, 4), dtype=np.int64), np.zeros((B, 5), dtype=np.float64)
+    par, frames = np.zeros((len(lens), 5), dtype=np.float64), []
     rel = float(10.0 ** (-float(threshold_db) / 10.0))
     if not rel >= 0.0 or not float(floor) >= 0.0:
         raise ValueError(f"threshold_db {threshold_db!r} / floor {floor!r}: the threshold must not be negative")
     if min_silence < 0 or min_speech < 0:
         raise ValueError("min_silence and min_speech are non-negative seconds")
-    s_off = f_off = 0
     for b, n in enumerate(lens):
         n, s, f = int(n), float(sr[b]), float(fps[b])
         if n < 1:
@@ -76,13 +67,9 @@ def _plan(lens, sr, fps, threshold_db, min_silence, min_speech, floor, first_cli
         if not (s > 0 and f > 0) or not s / f > 1.0:
             raise ValueError(f"clip {first_clip + b}: sample rate {s!r} and frame rate {f!r} must be positive with more than one "
                              "sample per frame")
-        ratio = s / f
-        F = frame_count(n, s, f)
-        tab[b] = (s_off, n, f_off, F)
-        par[b] = (ratio, rel, float(floor), max(1, int(round(min_silence * f))), max(1, int(round(min_speech * f))))
-        s_off += n
-        f_off += F
-    return tab, par
+        frames.append(frame_count(n, s, f))
+        par[b] = (s / f, rel, float(floor), max(1, int(round(min_silence * f))), max(1, int(round(min_speech * f))))
+    return ragged.clip_table(lens, frames), par
 
 
 _Staged = namedtuple("_Staged", "flat tab par d_tab d_par ws bits energy summary")
@@ -95,7 +82,7 @@ def _stage(clips, sr, fps, threshold_db, min_silence, min_speech, floor, first_c
     for i, c in enumerate(clips):
         if int(np.prod(np.shape(c))) == 0:
             raise ValueError(f"clip {first_clip + i} is empty")
-    flat, lens = metrics._concat(clips)
+    flat, lens = ragged.concat(clips)
     tab, par = _plan(lens, sr, fps, threshold_db, min_silence, min_speech, floor, first_clip)
     B, dev = len(lens), flat.device
     nbytes = L.lib().sos_silence_label_workspace_bytes(tab.ctypes.data, B)
@@ -131,10 +118,10 @@ def silence_bits_batch_device(clips, sr, fps=30.0, threshold_db=40.0, min_silenc
     nothing waited for, so `summary` has not been checked).  `tools.ragged_stage(lb.flat, lb.table, stride, lb.bits, lb.ratios)`
     stages the labelled clips for the networks."""
     clips = list(clips)
-    if not 1 <= len(clips) <= metrics._MAX_CLIPS:
-        raise ValueError(f"1 .. {metrics._MAX_CLIPS} clips per launch sequence, got {len(clips)}")
-    return _enqueue(clips, _per_clip(sr, len(clips), "sr"), _per_clip(fps, len(clips), "fps"), threshold_db, min_silence,
-                    min_speech, floor)
+    if not 1 <= len(clips) <= ragged.MAX_CLIPS:
+        raise ValueError(f"1 .. {ragged.MAX_CLIPS} clips per launch sequence, got {len(clips)}")
+    return _enqueue(clips, ragged.per_clip(sr, len(clips), "sr"), ragged.per_clip(fps, len(clips), "fps"), threshold_db,
+                    min_silence, min_speech, floor)
 
 
 def silence_bits_batch(clips, sr, fps=30.0, threshold_db=40.0, min_silence=0.1, min_speech=0.0, floor=0.0, return_detail=False):
@@ -146,10 +133,10 @@ def silence_bits_batch(clips, sr, fps=30.0, threshold_db=40.0, min_silence=0.1, 
     sr / fps <= 1 raises ValueError naming the clip."""
     clips = list(clips)
     B = len(clips)
-    sr, fps = _per_clip(sr, B, "sr"), _per_clip(fps, B, "fps")
+    sr, fps = ragged.per_clip(sr, B, "sr"), ragged.per_clip(fps, B, "fps")
     done = []
-    for c0 in range(0, B, metrics._MAX_CLIPS):
-        c1 = min(B, c0 + metrics._MAX_CLIPS)
+    for c0 in range(0, B, ragged.MAX_CLIPS):
+        c1 = min(B, c0 + ragged.MAX_CLIPS)
         done.append(_enqueue(clips[c0:c1], sr[c0:c1], fps[c0:c1], threshold_db, min_silence, min_speech, floor, c0))
     bits, detail = [], []
     if not done:
@@ -212,7 +199,7 @@ def _file_groups(paths, max_bytes):
     groups, cur, size = [], [], 0
     for i, p in enumerate(paths):
         nb = _wave_sample_bytes(p)
-        if cur and (size + nb > max_bytes or len(cur) >= metrics._MAX_CLIPS):
+        if cur and (size + nb > max_bytes or len(cur) >= ragged.MAX_CLIPS):
             groups.append(cur)
             cur, size = [], 0
         cur.append(i)

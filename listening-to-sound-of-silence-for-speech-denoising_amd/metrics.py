@@ -27,21 +27,14 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import ragged
+from .ragged import device_f32 as _dev
 
 CENT_FREQ = [50., 120, 190, 260, 330, 400, 470, 540, 617.372, 703.378, 798.717, 904.128, 1020.38, 1148.30, 1288.72, 1442.54,
              1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17, 3597.63]
 BANDWIDTH = [70., 70, 70, 70, 70, 70, 70, 77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423, 153.823, 168.154,
              183.457, 199.776, 217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136]
 _tables = {}
-
-
-def _dev(x):
-    if not torch.cuda.is_available():
-        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
-    if torch.is_tensor(x):
-        L.require_cuda(x)
-        return x.detach().reshape(-1).float().contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float32)).cuda()
 
 
 def _num_frames(n, winlength, skip):
@@ -220,7 +213,6 @@ def evaluate_metrics(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=None):
 
 
 # ---- ragged batches of clip pairs: the driver under evaluate_metrics_batch, stoi_batch, si_sdr_batch and sdr_batch
-_MAX_CLIPS = 65535                  # clips per launch sequence (the kernels' grid.y)
 _BATCH_HEAD = 8                     # f64 per clip at the front of sos_metric_batch's packed output (include/sos_hip.h)
 # One launch sequence's worth of pairs: the concatenated device buffers x / y, the host lengths `lens` (int64), the device
 # table `tab` = [offsets, lengths] and `lead` = (x, y, offsets, lengths, lengths_host, nclips), the arguments every
@@ -243,26 +235,13 @@ def _check_pairs(a, b, counted, named, allow_empty=False):
     return a, b
 
 
-def _concat(signals):
-    """One f32 device buffer holding the signals back to back (plus a zero sentinel, so that it is never empty), and
-    their lengths.  numpy inputs go up in one copy; tensors must live on the GPU."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
-    if not any(torch.is_tensor(s) for s in signals):
-        flat = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
-        buf = np.concatenate(flat + [np.zeros(1, np.float32)])
-        return torch.from_numpy(buf).cuda(), [len(f) for f in flat]
-    ts = [_dev(s) for s in signals]
-    return torch.cat(ts + [torch.zeros(1, dtype=torch.float32, device=ts[0].device)]), [t.numel() for t in ts]
-
-
 def _chunks(a, b):
-    """The pairs (a[i], b[i]) as _Chunks of at most _MAX_CLIPS clips, each uploaded when it is asked for."""
-    for c0 in range(0, len(a), _MAX_CLIPS):
-        x, n = _concat(a[c0:c0 + _MAX_CLIPS])
-        y, _ = _concat(b[c0:c0 + _MAX_CLIPS])
+    """The pairs (a[i], b[i]) as _Chunks of at most ragged.MAX_CLIPS clips, each uploaded when it is asked for."""
+    for c0 in range(0, len(a), ragged.MAX_CLIPS):
+        x, n = ragged.concat(a[c0:c0 + ragged.MAX_CLIPS])
+        y, _ = ragged.concat(b[c0:c0 + ragged.MAX_CLIPS])
         lens = np.asarray(n, dtype=np.int64)
-        tab = torch.from_numpy(np.stack([np.cumsum(lens) - lens, lens])).to(x.device)
+        tab = torch.from_numpy(np.stack([ragged.offsets(lens), lens])).to(x.device)
         lead = (L.ptr(x), L.ptr(y), L.ptr(tab[0]), L.ptr(tab[1]), lens.ctypes.data_as(C.c_void_p), len(lens))
         yield _Chunk(x, y, lens, tab, lead)
 
@@ -336,7 +315,7 @@ def evaluate_metrics_batch(noisy, clean, sr=16000, eps=1e-20, pesq=None, stoi=No
         energy_kept = np.frombuffer(buf, np.float64, 2 * ftot, o + 16 * ftot).reshape(ftot, 2)
         llr_all = np.frombuffer(buf, np.float32, ftot, o + 32 * ftot)
         wss_all = np.frombuffer(buf, np.float32, ftot, o + 36 * ftot)
-        f_off = np.cumsum(frames) - frames
+        f_off = ragged.offsets(frames)
         for b in range(nb):
             tot, nf, f0 = head[b], int(frames[b]), int(f_off[b])
             if tot[7] < 0 or int(tot[6]) != nf:

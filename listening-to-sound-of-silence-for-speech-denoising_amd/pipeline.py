@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import get_mode, get_precision, precision_scope
+from . import ragged
 from . import tools
 from . import transform
 
@@ -200,13 +201,9 @@ def stage_group(clips, bits=None, n_bits=None, ratios=None):
     (tools.ragged_stage): (wave (B, longest), ns) without `bits`; with `bits` -- the clips' frame decisions back to back on the
     GPU, `n_bits` of them per clip, `ratios` samples per frame per clip -- ((wave, masked, mask), ns), mask back to back in clip
     order."""
-    import numpy as np
     ns = [int(c.numel()) for c in clips]
     flat = torch.cat(clips) if len(clips) > 1 else clips[0].contiguous()
-    nb = [0] * len(ns) if n_bits is None else [int(v) for v in n_bits]
-    ends, bends = np.cumsum(ns), np.cumsum(nb)
-    table = np.stack([ends - ns, ns, bends - nb, nb], axis=1)
-    return tools.ragged_stage(flat, table, max(ns), bits, ratios), ns
+    return tools.ragged_stage(flat, ragged.clip_table(ns, n_bits), max(ns), bits, ratios), ns
 
 
 def _denoise_group_staged(denoiser, wave, masked, rag, signals=False):
@@ -224,24 +221,13 @@ def _denoise_group_staged(denoiser, wave, masked, rag, signals=False):
     return transform.istft_batch(torch.cat([S_mixed, S_noise, n_pred, S_out], dim=0), clip_frames=rag.tab(rag.T * 4))
 
 
-def _clip_ratios(n, sr, fps):
-    """sr / fps per clip: fps a scalar or one value per clip."""
-    try:
-        fps = [float(f) for f in fps]
-    except TypeError:
-        fps = [float(fps)] * n
-    if len(fps) != n:
-        raise ValueError("fps must be a scalar or one value per clip")
-    return [float(sr) / f for f in fps]
-
-
 def _denoise_ragged_bits(denoiser, clips, bits, sr, fps, max_batch, max_columns, return_all):
     """denoise_ragged with the first model's decisions given (`bits`): no detector; every group is staged by
     sos_ragged_stage_f32 in one launch (padded clips, noise intervals, sample masks at each clip's own sr / fps)."""
     import numpy as np
     if len(bits) != len(clips):
         raise ValueError("bits must hold one array of frame decisions per clip")
-    ratios = _clip_ratios(len(clips), sr, fps)
+    ratios = [float(sr) / float(f) for f in ragged.per_clip(fps, len(clips), "fps")]      # fps: a scalar or one per clip
     for b in bits:
         if b.ndim != 1 or (b.dtype != torch.uint8 if torch.is_tensor(b) else b.dtype != np.uint8):
             raise ValueError("bits must be 1-D uint8 arrays or GPU tensors (1 = non-silent)")
@@ -258,15 +244,14 @@ def _denoise_ragged_bits(denoiser, clips, bits, sr, fps, max_batch, max_columns,
             d_bits = torch.from_numpy(np.concatenate([bits[i].cpu().numpy() if torch.is_tensor(bits[i]) else bits[i] for i in part])).to(device)
         (wave, masked, mask), ns = stage_group(group, d_bits, nb, [ratios[i] for i in part])
         y = _denoise_group_staged(denoiser, wave, masked, rag, signals=return_all)
-        B, pos, bpos = len(part), 0, 0
+        B = len(part)
+        bit_views, mask_views = (ragged.split(d_bits, nb), ragged.split(mask, ns)) if return_all else (None, None)
         for k, i in enumerate(part):
             n_out = hop * (rag.T[k] - 1)
             outs[i] = y[(3 * B if return_all else 0) + k, :n_out]
             if return_all:
-                extra[i] = dict(bits=d_bits[bpos:bpos + nb[k]], mask=mask[pos:pos + ns[k]], noisy_input=y[k, :n_out],
+                extra[i] = dict(bits=bit_views[k], mask=mask_views[k], noisy_input=y[k, :n_out],
                                 noise_intervals=y[B + k, :n_out], predicted_full_noise=y[2 * B + k, :n_out])
-            pos += ns[k]
-            bpos += nb[k]
     return (outs, extra) if return_all else outs
 
 

@@ -1,0 +1,65 @@
+"""The ragged layer of the package (csrc/ragged.h is its other half): clips of any lengths back to back in one buffer plus a
+table of where each lies.  Package-internal; nothing here touches the GPU at import."""
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MAX_CLIPS = 65535                   # clips per launch sequence (the kernels' grid.y); every chunking loop reads it when called
+
+
+def offsets(lens):
+    """Where each of consecutive spans of `lens` elements starts: int64 cumsum(lens) - lens."""
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    return np.cumsum(lens, dtype=np.int64) - lens
+
+
+def clip_table(ns, nb=None):
+    """Host int64 [B][4] rows {sample offset, samples, frame offset, frames} of clips of ns samples and nb (default 0) frames."""
+    tab = np.zeros((len(ns), 4), dtype=np.int64)
+    tab[:, 1] = ns
+    if nb is not None:
+        tab[:, 3] = nb
+    np.cumsum(tab[:-1, 1::2], axis=0, out=tab[1:, 0::2])              # both offset columns: one call (one-clip tables are hot)
+    return tab
+
+
+def per_clip(value, nclips, name):
+    """A scalar or one value per clip -> a writable f64 array of `nclips` values."""
+    v = np.asarray(value, dtype=np.float64)
+    if v.ndim > 1 or (v.ndim == 1 and len(v) != nclips):
+        raise ValueError(f"{name}: one value or one per clip ({nclips}), got shape {v.shape}")
+    return np.array(np.broadcast_to(v, (nclips,)))
+
+
+def device_f32(x):
+    """A signal (numpy array or GPU tensor) as a contiguous 1-D f32 GPU tensor."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
+    if torch.is_tensor(x):
+        L.require_cuda(x)
+        return x.detach().reshape(-1).float().contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float32)).cuda()
+
+
+def concat(signals):
+    """One f32 device buffer holding the signals back to back (plus a zero sentinel, so that it is never empty), and
+    their lengths.  numpy inputs go up in one copy; tensors must live on the GPU."""
+    if not any(torch.is_tensor(s) for s in signals):
+        flat = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
+        return device_f32(np.concatenate(flat + [np.zeros(1, np.float32)])), [len(f) for f in flat]
+    ts = [device_f32(s) for s in signals]
+    return torch.cat(ts + [torch.zeros(1, dtype=torch.float32, device=ts[0].device)]), [t.numel() for t in ts]
+
+
+def split(flat, lens):
+    """Views of consecutive spans of `lens` elements of a 1-D tensor or array."""
+    return [flat[o:o + n] for o, n in zip(offsets(lens).tolist(), np.asarray(lens, dtype=np.int64).reshape(-1).tolist())]
+
+
+def download(tensors, dtype=None):
+    """The 1-D GPU tensors of a list as host arrays (of `dtype`, if given), through one copy of their concatenation."""
+    if not tensors:
+        return []
+    flat = np.ascontiguousarray((torch.cat(tensors) if len(tensors) > 1 else tensors[0]).cpu().numpy(), dtype=dtype)
+    return split(flat, [t.numel() for t in tensors])

@@ -3,6 +3,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import ragged
 
 
 def bits_to_mask_batch(bits, ratio, n_samples, sig=None, clip_frames=None, clip_samples=None):
@@ -59,7 +60,7 @@ def ragged_stage(flat, table, stride, bits=None, ratios=None):
     if bits is not None:
         if bits.dim() != 1 or bits.dtype != torch.uint8 or not bits.is_contiguous() or bits.numel() < int(tab[:, 3].sum()):
             raise ValueError("bits must be a contiguous 1-D uint8 tensor holding every frame of the table")
-        rat = np.array(np.broadcast_to(np.asarray(ratios, dtype=np.float64), (B,)))      # a writable copy
+        rat = ragged.per_clip(ratios, B, "ratios")
         d_rat = _upload(rat, flat.device)
         masked, mask = torch.empty_like(wave), torch.empty_like(flat)
     L.check(L.lib().sos_ragged_stage_f32(L.ptr(flat), L.ptr(d_tab), tab.ctypes.data, B, L.ptr(bits), L.ptr(d_rat),

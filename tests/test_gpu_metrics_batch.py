@@ -127,7 +127,7 @@ def test_chunks_of_a_large_batch_give_the_same_bits(ragged, monkeypatch):
     """More clips than one launch sequence takes (65535) go in chunks; exercised with a chunk size of 5."""
     from sos_amd import metrics as M
     clean, noisy, results, detail = ragged
-    monkeypatch.setattr(M, "_MAX_CLIPS", 5)
+    monkeypatch.setattr("sos_amd.ragged.MAX_CLIPS", 5)
     rc, dc = M.evaluate_metrics_batch(noisy[:12], clean[:12], sr=SR, pesq=[2.7] * 12, return_detail=True)
     for i in range(12):
         _same_result(rc[i], results[i])

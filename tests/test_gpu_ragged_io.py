@@ -157,3 +157,75 @@ def test_bits_to_mask_still_is_the_integer_rule(ratio):
         want = ofe.convert_bitstreammask_to_audiomask(np.zeros(n, np.float32), ratio, [int(b) for b in bits])
         got = tools.bits_to_mask_batch(torch.from_numpy(bits.astype(np.uint8)[None]).cuda(), ratio, n)[0].cpu().numpy()
         assert np.array_equal(got, want)
+
+
+SPARE = 16                                                # elements past what the table sums to, in every buffer
+
+
+def _spared(a, fill=0):
+    """`a` on the GPU with SPARE further elements behind it: an entry that is wrongly followed one element past the totals still
+    touches allocated memory only, and shows up as a wrong value."""
+    a = np.asarray(a).reshape(-1)
+    return torch.from_numpy(np.concatenate([a, np.full(SPARE, fill, a.dtype)])).cuda()
+
+
+def test_stage_kernel_skips_a_device_entry_outside_the_totals(reference):
+    """The device rule of ragged_stage_kernel: the host table is correct, the DEVICE table differs in one entry of clip 1.  The
+    call succeeds, clip 1's rows and mask span are left as they were, every other clip is what the unaltered call gives."""
+    from sos_amd import _lib as L
+    clips, bits, ratios, _ = reference
+    ns, nb = [len(c) for c in clips], [len(b) for b in bits]
+    B, stride, total, total_bits = len(ns), 11200, sum(ns), sum(nb)
+    tab, rat = _table(ns, nb), np.asarray(ratios, dtype=np.float64)
+    flat, d_bits, d_rat = _spared(np.concatenate(clips)), _spared(np.concatenate(bits)), torch.from_numpy(rat).cuda()
+
+    def run(d_tab):
+        wave = torch.full((B * stride + SPARE,), SENTINEL, device="cuda")
+        masked, mask = torch.full_like(wave, SENTINEL), torch.full((total + SPARE,), SENTINEL, device="cuda")
+        rc = L.lib().sos_ragged_stage_f32(L.ptr(flat), L.ptr(d_tab), tab.ctypes.data, B, L.ptr(d_bits), L.ptr(d_rat), rat.ctypes.data,
+                                          stride, L.ptr(wave), L.ptr(masked), L.ptr(mask), L.stream_ptr())
+        return rc, wave.cpu().numpy(), masked.cpu().numpy(), mask.cpu().numpy()
+
+    rc, *base = run(torch.from_numpy(tab).cuda())
+    assert rc == 0 and not any((a[:-SPARE] == SENTINEL).all() for a in base)
+    o1, n1 = int(tab[1, 0]), ns[1]
+    for what, col, value in (("sample offset", 0, total - n1 + 1), ("samples", 1, stride + 1), ("frame offset", 2, total_bits - nb[1] + 1)):
+        d_tab = torch.from_numpy(tab).cuda()
+        d_tab[1, col] = value
+        rc, *got = run(d_tab)
+        assert rc == 0, what
+        for g, b, name in zip(got, base, ("wave", "masked", "mask")):
+            lo, hi = (o1, o1 + n1) if name == "mask" else (stride, 2 * stride)          # clip 1's span / row
+            assert (g[lo:hi] == SENTINEL).all(), (what, name)
+            assert _same_bits(g[:lo], b[:lo]) and _same_bits(g[hi:], b[hi:]), (what, name)
+            assert (g[-SPARE:] == SENTINEL).all(), (what, name)
+
+
+def test_unpack_kernel_skips_a_device_entry_outside_the_totals(reference):
+    """The same for ragged_unpack_kernel: a row that does not exist, an output span one sample past the total."""
+    from sos_amd import _lib as L
+    clips, _, _, _ = reference
+    ns = [len(c) for c in clips]
+    B, stride, total = len(ns), 11200, sum(ns)
+    rows = np.zeros((B + 1, stride), np.float32)          # a spare row: "row = n_rows", wrongly followed, reads it
+    for r, c in enumerate(clips):
+        rows[r, :len(c)] = c
+    d_rows = _spared(rows)
+    offs = np.cumsum(ns) - ns
+    tab = np.ascontiguousarray(np.stack([np.arange(B), ns, offs], axis=1).astype(np.int64))
+
+    def run(d_tab):
+        out = torch.full((total + SPARE,), SENTINEL, device="cuda")
+        rc = L.lib().sos_ragged_unpack_f32(L.ptr(d_rows), B, stride, L.ptr(d_tab), tab.ctypes.data, B, L.ptr(out), L.stream_ptr())
+        return rc, out.cpu().numpy()
+
+    rc, base = run(torch.from_numpy(tab).cuda())
+    assert rc == 0 and _same_bits(base[:total], np.concatenate(clips))
+    lo, hi = int(offs[1]), int(offs[1]) + ns[1]
+    for what, col, value in (("row", 0, B), ("output offset", 2, total - ns[1] + 1)):
+        d_tab = torch.from_numpy(tab).cuda()
+        d_tab[1, col] = value
+        rc, got = run(d_tab)
+        assert rc == 0, what
+        assert (got[lo:hi] == SENTINEL).all() and (got[-SPARE:] == SENTINEL).all(), what
+        assert _same_bits(got[:lo], base[:lo]) and _same_bits(got[hi:total], base[hi:total]), what

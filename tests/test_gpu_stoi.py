@@ -91,7 +91,7 @@ def test_chunks_of_a_large_batch_give_the_same_bits(extended, monkeypatch):
     xs, ys = [p[0] for p in pairs], [p[1] for p in pairs]
     want, want_kept = metrics.stoi_batch(xs, ys, fs, extended, return_frames=True)
     assert all(k >= 30 for k in want_kept), want_kept
-    monkeypatch.setattr(metrics, "_MAX_CLIPS", 3)
+    monkeypatch.setattr("sos_amd.ragged.MAX_CLIPS", 3)
     got, kept = metrics.stoi_batch(xs, ys, fs, extended, return_frames=True)
     assert got == want and kept == want_kept
 

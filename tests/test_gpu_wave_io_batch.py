@@ -88,10 +88,48 @@ def test_many_short_clips_and_the_clip_cap(monkeypatch):
     assert len(got) == 301
     for i, (g, o) in enumerate(zip(got, one)):
         assert torch.equal(g, o), f"clip {i} (n={dev[i].numel()})"
-    monkeypatch.setattr(audio_io, "_RESAMPLE_MAX_CLIPS", 7)
+    monkeypatch.setattr("sos_amd.ragged.MAX_CLIPS", 7)
     cut = audio_io.resample_batch_device(dev, 14000, 16000)
     for i, (g, o) in enumerate(zip(cut, one)):
         assert torch.equal(g, o), f"clip {i} (n={dev[i].numel()}) with 7 clips per launch"
+
+
+def test_kernel_skips_a_device_entry_outside_the_totals():
+    """The device rule of resample_batch_kernel: the host table is correct, the DEVICE table differs in one entry of clip 1 (its
+    input one sample past the total; more resampled outputs than outputs).  Every buffer has 16 spare elements, so an entry that
+    is wrongly followed touches allocated memory only.  The call succeeds, clip 1's outputs stay as they were and every other
+    clip gets the bits of the unaltered call."""
+    import ctypes as C
+    from sos_amd import _lib as L
+    from sos_amd import audio_io
+    spare, sentinel, ratio = 16, -77.0, 16000 / 14000
+    n_in = np.asarray([7, 130, 2, 300], dtype=np.int64)
+    n_out = np.asarray([int(np.ceil(int(n) * ratio)) for n in n_in], dtype=np.int64)
+    n_valid = np.minimum(np.asarray([int(int(n) * ratio) for n in n_in], dtype=np.int64), n_out)
+    tiles = -(-n_out // L.RESAMPLE_CHUNK)
+    tab = np.ascontiguousarray(np.stack([np.cumsum(n_in) - n_in, n_in, np.cumsum(n_out) - n_out, n_out, n_valid,
+                                         np.cumsum(tiles) - tiles]), dtype=np.int64)
+    total_in, total_out = int(n_in.sum()), int(n_out.sum())
+    x = torch.from_numpy(np.random.default_rng(5).standard_normal(total_in + spare).astype(np.float32)).cuda()
+    win, num_table = audio_io._filter_on(x.device, ratio, "kaiser_best")
+
+    def run(d_tab):
+        out = torch.full((total_out + spare,), sentinel, device="cuda")
+        rc = L.lib().sos_resample_batch_f32(L.ptr(x), L.ptr(d_tab), tab.ctypes.data_as(C.c_void_p), len(n_in), ratio, L.ptr(win),
+                                            win.numel(), num_table, L.ptr(out), L.stream_ptr())
+        return rc, out.cpu().numpy()
+
+    rc, base = run(torch.from_numpy(tab).cuda())
+    assert rc == 0 and not (base[:total_out] == sentinel).any() and (base[total_out:] == sentinel).all()
+    lo, hi = int(tab[2, 1]), int(tab[2, 1] + n_out[1])
+    for what, row, value in (("input offset", 0, total_in - int(n_in[1]) + 1), ("n_valid", 4, int(n_out[1]) + 1)):
+        d_tab = torch.from_numpy(tab).cuda()
+        d_tab[row, 1] = value
+        rc, got = run(d_tab)
+        assert rc == 0, what
+        assert (got[lo:hi] == sentinel).all() and (got[total_out:] == sentinel).all(), what
+        assert np.array_equal(got[:lo].view(np.uint32), base[:lo].view(np.uint32)), what
+        assert np.array_equal(got[hi:total_out].view(np.uint32), base[hi:total_out].view(np.uint32)), what
 
 
 def test_errors_and_trivial_cases():
