@@ -617,6 +617,37 @@ int sos_silence_label_batch(const float* x, const int64_t* table, const int64_t*
                             const double* params_host, void* workspace, int64_t workspace_bytes, uint8_t* bits, double* energy,
                             double* out, sos_stream_t stream);
 
+/* ---- noisy speech out of clean speech for a ragged batch of clips (csrc/ragged_mix.hip; sos_amd.tools.add_signals_ragged;
+ * float64 restatement: tests/mix_reference.py): add_signals with one noise (M2/tools.py:217-276) around the silencing and the
+ * zero-filled noise crop of the hand-off.  clips = the clips back to back in one f32 buffer.  table / table_host: int64
+ * [nclips][4] on the device / the HOST, the rows of sos_ragged_stage_f32 {sample offset, samples, frame offset, frames}.
+ * noise: f32 buffer of noise_total samples; noise_table / noise_table_host: int64 [nclips][2] = {noff, nz}: clip b is mixed with
+ * noise[noff .. noff + nz), zero from nz to the clip's end (nz <= samples; nz = 0: a silent noise).  Crops of different clips may
+ * overlap or coincide.  params / params_host: f64 [nclips][2] = {snr in dB, ratio = samples per frame (> 1), or 0 = the clip has
+ * no frame decisions}; bits: the frame decisions back to back at the frame offsets (1 = non-silent), NULL if every ratio is 0.
+ *   s = clip * (1 - mask) under the mask rule of sos_bits_to_mask (csrc/mask_rule.h), or the clip itself at ratio 0;
+ *   Es = sum s^2, Ez = sum z^2 in f64; gain = 1 if Es == 0 or Ez == 0, else sqrt(Es / 10^(snr / 10)) / sqrt(Ez);
+ *   m = s + gain z; peak = max |m|; inv = norm / peak if norm != 0 and peak != 0, else 1;
+ *   mixed = m inv, clean = s inv, noise_out = gain z inv: f32, each back to back at the clips' sample offsets (sum(samples)
+ *   floats each; they must not overlap `clips`).
+ * out: f64 [nclips][6] = {Es, Ez, gain, peak, inv, status}; gain and inv are applied as f32 factors and reported as those f32
+ * values.  A clip's outputs and its row have the same bits alone, in any batch, at any offset and in any order: sums and maxima
+ * over chunks of SOS_MIX_CHUNK samples counted from the clip's first sample, fixed trees, no atomics.  status = -1: the DEVICE
+ * tables or parameters leave what the host's sized (the bounds rule of the other ragged kernels); nothing is read or written for
+ * that clip but its row.  Four launches whatever the number of clips, no allocation, no host synchronisation.
+ * sos_ragged_mix_workspace_bytes: 256-byte-aligned arrays of nclips int64 and 3 f64 per chunk; -1 on a null table or nclips
+ *   outside 1 .. 65535.
+ * SOS_EINVAL (sos_last_error() names the clip), before any launch: null pointers, nclips outside 1 .. 65535, a clip without
+ * samples, more than 2^40 samples in all, an entry outside the samples / frames summed from the host table, a non-finite snr or
+ * norm, a ratio that is neither 0 nor > 1, a ratio without bits, a crop outside [0, noise_total) or longer than its clip;
+ * SOS_ENOSPC: a workspace smaller than sos_ragged_mix_workspace_bytes says. */
+#define SOS_MIX_CHUNK 4096
+int64_t sos_ragged_mix_workspace_bytes(const int64_t* table_host, int nclips);
+int sos_ragged_mix_f32(const float* clips, const int64_t* table, const int64_t* table_host, int nclips, const float* noise,
+                       int64_t noise_total, const int64_t* noise_table, const int64_t* noise_table_host, const uint8_t* bits,
+                       const double* params, const double* params_host, double norm, void* workspace, int64_t workspace_bytes,
+                       float* mixed, float* clean, float* noise_out, double* out, sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

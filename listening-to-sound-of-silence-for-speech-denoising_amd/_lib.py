@@ -63,6 +63,7 @@ _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 ADAM_CHUNK = 16384          # SOS_ADAM_CHUNK of include/sos_hip.h
 GUARD_FLOATS = 5            # SOS_GUARD_FLOATS
 RESAMPLE_CHUNK = 4096       # SOS_RESAMPLE_CHUNK
+MIX_CHUNK = 4096            # SOS_MIX_CHUNK
 EXPECTED_ABI = 10           # sos_abi_version() of the library these argument lists were written for
 
 # name -> argtypes, exactly the prototypes of include/sos_hip.h
@@ -145,6 +146,8 @@ SIGNATURES = {
     "sos_ragged_unpack_f32": [_P, _L, _L, _P, _P, _I, _P, _P],
     "sos_silence_label_workspace_bytes": [_P, _I],
     "sos_silence_label_batch": [_P, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P, _P],
+    "sos_ragged_mix_workspace_bytes": [_P, _I],
+    "sos_ragged_mix_f32": [_P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P, _D, _P, _L, _P, _P, _P, _P, _P],
     "sos_time_unstack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
     "sos_spatial_mean_bwd": [_P, _L, _L, _I, _L, _I, _I, _I, _P, _I, _P],
 }
@@ -165,7 +168,8 @@ def _load(path, want_dtype):
         fn.restype = C.c_int64 if name in ("sos_wgrad_workspace_bytes", "sos_lstm_pack_bytes", "sos_conv2d_tile_count",
                                              "sos_stft_matrix_bytes", "sos_istft_matrix_bytes",
                                              "sos_stoi_workspace_bytes", "sos_metric_batch_workspace_bytes",
-                                             "sos_sdr_workspace_bytes", "sos_silence_label_workspace_bytes") else C.c_int
+                                             "sos_sdr_workspace_bytes", "sos_silence_label_workspace_bytes",
+                                             "sos_ragged_mix_workspace_bytes") else C.c_int
     if h.sos_abi_version() != EXPECTED_ABI:
         raise ImportError(f"{path} exports ABI version {h.sos_abi_version()}, this binding was written for {EXPECTED_ABI} "
                           "(the argument lists differ: rebuild the library, or drop the SOS_HIP_LIB / SOS_HIP_LIB_F16 override)")

@@ -1,6 +1,7 @@
 // ragged.h -- what every ragged-batch entry point shares (metrics_batch.hip, stoi.hip, sdr.hip, ragged_io.hip,
-// silence_label.hip, wave_io.hip): the clip-count check, the clip row, the bounds rule on both sides of the launch, the host's
-// sums over a table, the workspace layout arithmetic, the clamped grid and the 256-thread LDS reductions.
+// silence_label.hip, ragged_mix.hip, wave_io.hip): the clip-count check, the clip row, the bounds rule on both sides of the launch,
+// the host's sums over a table, the workspace layout arithmetic, the clamped grid, the 256-thread LDS reductions and the
+// four-sample accesses of clips that start on any sample.
 // A batch is clips back to back in one buffer plus a table of where each lies, in two copies: the host sizes every array
 // from its own (table_host / lengths_host) and refuses a bad entry before any launch; the kernels follow the DEVICE table.
 #pragma once
@@ -109,4 +110,31 @@ __device__ static inline int block_scan_incl(int v, int* scan) {
         __syncthreads();
     }
     return scan[threadIdx.x];
+}
+
+// Four consecutive samples of a clip that may start on any sample (ragged_io.hip, ragged_mix.hip): one 16-byte access where the
+// address allows it, sample by sample otherwise.  Which of the two is taken changes no value.
+typedef float ragged_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bool ragged_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }      // a null pointer counts
+
+// v = p[j0 .. j0 + 4): one 16-byte load if `vec` (p + j0 aligned, all four inside), else the samples below `end` one by one
+__device__ __forceinline__ void ragged_load4(const float* p, int64_t j0, int64_t end, bool vec, float (&v)[4]) {
+    if (vec) {
+        const ragged_f32x4 q = *(const ragged_f32x4*)(p + j0);
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k < end) v[k] = p[j0 + k];
+    }
+}
+// p[j0 .. j0 + 4) = v, likewise
+__device__ __forceinline__ void ragged_store4(float* p, int64_t j0, int64_t end, bool vec, const float (&v)[4]) {
+    if (vec) {
+        *(ragged_f32x4*)(p + j0) = ragged_f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k < end) p[j0 + k] = v[k];
+    }
 }

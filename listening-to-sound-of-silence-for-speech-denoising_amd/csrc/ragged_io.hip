@@ -17,31 +17,6 @@
 #define RIO_MAX_GRID 1024               // workgroups along a row (they stride over what the grid does not cover)
 #define RIO_UNPACK_COLS 3               // int64 per entry: row, valid samples, output offset
 
-typedef float rio_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bool rio_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }      // a null pointer counts
-
-// v = p[j0 .. j0 + 4): one 16-byte load if `vec` (p + j0 aligned, all four inside), else the samples below `end` one by one
-__device__ __forceinline__ void rio_load4(const float* p, int64_t j0, int64_t end, bool vec, float (&v)[4]) {
-    if (vec) {
-        const rio_f32x4 q = *(const rio_f32x4*)(p + j0);
-        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (j0 + k < end) v[k] = p[j0 + k];
-    }
-}
-// p[j0 .. j0 + 4) = v, likewise
-__device__ __forceinline__ void rio_store4(float* p, int64_t j0, int64_t end, bool vec, const float (&v)[4]) {
-    if (vec) {
-        *(rio_f32x4*)(p + j0) = rio_f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (j0 + k < end) p[j0 + k] = v[k];
-    }
-}
-
 __global__ __launch_bounds__(RIO_THREADS) void ragged_stage_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ table, int64_t total, const uint8_t* __restrict__ bits,
     int64_t total_bits, const double* __restrict__ ratios, int64_t stride, float* __restrict__ wave, float* __restrict__ masked,
@@ -57,24 +32,24 @@ __global__ __launch_bounds__(RIO_THREADS) void ragged_stage_kernel(
     float* wrow = wave + b * stride;
     float* mrow = bits ? masked + b * stride : nullptr;
     float* mc = bits ? mask + off : nullptr;
-    const bool row_vec = (stride & 3) == 0 && rio_aligned16(wave) && rio_aligned16(masked);
-    const bool clip_vec = rio_aligned16(xc) && rio_aligned16(mc);
+    const bool row_vec = (stride & 3) == 0 && ragged_aligned16(wave) && ragged_aligned16(masked);
+    const bool clip_vec = ragged_aligned16(xc) && ragged_aligned16(mc);
     for (int64_t j0 = ((int64_t)blockIdx.x * RIO_THREADS + threadIdx.x) * 4; j0 < stride; j0 += (int64_t)gridDim.x * RIO_THREADS * 4) {
         const bool full = j0 + 4 <= n;                       // all four samples inside the clip
         float v[4] = {0.f, 0.f, 0.f, 0.f}, m[4] = {0.f, 0.f, 0.f, 0.f};
-        rio_load4(xc, j0, n, full && clip_vec, v);
+        ragged_load4(xc, j0, n, full && clip_vec, v);
         if (bits) {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (j0 + k < n) m[k] = mask_sample(bc, nfr, ratio, n, j0 + k);
-            rio_store4(mc, j0, n, full && clip_vec, m);
+            ragged_store4(mc, j0, n, full && clip_vec, m);
         }
         // the rows: zero from the clip's end to the stride (v and m are 0 there); row_vec: the stride is a multiple of four,
         // so j0 + 4 <= stride
-        rio_store4(wrow, j0, stride, row_vec, v);
+        ragged_store4(wrow, j0, stride, row_vec, v);
         if (bits) {
             const float vm[4] = {v[0] * m[0], v[1] * m[1], v[2] * m[2], v[3] * m[3]};
-            rio_store4(mrow, j0, stride, row_vec, vm);
+            ragged_store4(mrow, j0, stride, row_vec, vm);
         }
     }
 }
@@ -87,12 +62,12 @@ __global__ __launch_bounds__(RIO_THREADS) void ragged_unpack_kernel(const float*
     if (row < 0 || row >= n_rows || n > stride || !ragged_clip_inside(off, n, total)) return;
     const float* src = rows + row * stride;
     float* dst = out + off;
-    const bool row_vec = (stride & 3) == 0 && rio_aligned16(rows), out_vec = rio_aligned16(dst);
+    const bool row_vec = (stride & 3) == 0 && ragged_aligned16(rows), out_vec = ragged_aligned16(dst);
     for (int64_t j0 = ((int64_t)blockIdx.x * RIO_THREADS + threadIdx.x) * 4; j0 < n; j0 += (int64_t)gridDim.x * RIO_THREADS * 4) {
         const bool full = j0 + 4 <= n;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        rio_load4(src, j0, n, full && row_vec, v);
-        rio_store4(dst, j0, n, full && out_vec, v);
+        ragged_load4(src, j0, n, full && row_vec, v);
+        ragged_store4(dst, j0, n, full && out_vec, v);
     }
 }
 

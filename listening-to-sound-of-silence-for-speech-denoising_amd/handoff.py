@@ -166,8 +166,25 @@ def _detect_groups(net, pending, max_batch, max_columns):
     return items
 
 
+def _mix_pending(pending, mixes, noises, snr, max_bytes):
+    """detect_files(batch_mix=True): the recordings of `pending` silenced on their labelled silent intervals and mixed with
+    their noise crops on the device, one tools.add_signals_ragged call per group of files of at most max_bytes of samples.
+    mixes: per file (noise index, first noise sample, valid samples); noises: the decoded noise files by index."""
+    used = sorted({m[0] for m in mixes})
+    slot = {k: j for j, k in enumerate(used)}
+    out = []
+    for group in ragged.byte_groups([4 * p[5].numel() for p in pending], max_bytes):
+        bits = [np.asarray([int(b) for b in pending[i][4]], dtype=np.uint8) if pending[i][4] else None for i in group]
+        ratios = [float(DATA_REQUIRED_SR) / pending[i][1]['framerate'] if b is not None else None for i, b in zip(group, bits)]
+        mixed, _, _ = tools.add_signals_ragged([pending[i][5] for i in group], [noises[k] for k in used], snr,
+                                               noise_index=[slot[mixes[i][0]] for i in group], starts=[mixes[i][1] for i in group],
+                                               counts=[mixes[i][2] for i in group], bits=bits, ratios=ratios, norm=0.5)
+        out += [pending[i][:5] + (m,) for i, m in zip(group, mixed)]
+    return out
+
+
 def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noise_files=None, snr=None, seed=0,
-                 batch_files=False, max_batch=64, max_columns=65536):
+                 batch_files=False, max_batch=64, max_columns=65536, batch_mix=False, max_mix_bytes=1 << 30):
     """Whole-file silent-interval detection of every file of a dataset JSON (`evaluate`, M1/predict.py:38-233 with
     the prediction-phase items of M1/tools.py:297-332 and M1/dataset.py:226-252): one item per file, the whole
     recording at 14 kHz -> STFT -> net(s, v_num_frames=len(bits)) -> sigmoid -> >= 0.5.  Returns the stat dict and
@@ -181,18 +198,26 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     (files sorted by length, cut into groups of <= max_batch files and <= max_columns spectrogram columns like
     pipeline.denoise_ragged's): one staging launch, one STFT, one detector call with per-file geometry, one thresholding launch
     and one download per group.  The clean-recordings branch keeps its per-file draws and mixing in file order (a seeded run
-    draws the same crops).  Same JSON as the per-file form: schema, key order, file order, sort."""
+    draws the same crops).  Same JSON as the per-file form: schema, key order, file order, sort.
+    batch_mix=True (with noise_files and batch_files=True; ValueError otherwise): the draws stay per file in file order -- the
+    same seeded generator, so the same noise files and JSON in noise<suffix>/ byte for byte -- but every distinct noise file is
+    decoded once and the recordings are silenced and mixed on the device by one tools.add_signals_ragged call per group of
+    files (groups of at most max_mix_bytes of samples); recordings and mixes never visit the host.  The mixes may differ
+    from the per-file kernel's in the last bit."""
     with open(dataset_json, 'r') as fp:
         ds = json.load(fp)
     net.eval()
     stat = []
     clean_audio = noise_files is not None
+    if batch_mix and not (batch_files and clean_audio):
+        raise ValueError("batch_mix=True applies to noise_files given with batch_files=True")
     if clean_audio and snr is None:
         raise ValueError("the clean-recordings branch needs an snr")
     suffix = convert_snr_to_suffix2(snr) if clean_audio else ''
     rng = np.random.default_rng(seed)
     noise_entries = OrderedDict()
     loaded, pending = None, []
+    decoded, mixes = {}, []                                     # batch_mix: noise files by index, per-file crops
     if batch_files and ds['files']:
         loaded, _ = audio_io.load_batch_device([_resolve(f['audio_path'], ds.get('dataset_path'), data_root) for f in ds['files']],
                                                sr=DATA_REQUIRED_SR)
@@ -204,6 +229,25 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
             snd = loaded[data_id]
         else:
             snd, _ = audio_io.load_device(_resolve(f['audio_path'], ds.get('dataset_path'), data_root), sr=DATA_REQUIRED_SR)
+        if batch_mix:
+            k = int(rng.integers(len(noise_files)))
+            if k not in decoded:
+                decoded[k] = audio_io.load(noise_files[k], sr=DATA_REQUIRED_SR)[0]
+            noise = decoded[k]
+            need = int(np.ceil(f['duration'])) * DATA_REQUIRED_SR
+            start = int(rng.integers(0, max(len(noise) - need, 0) + 1))
+            crop = noise[start:start + need]                        # M1/dataset.py:141-142
+            start_pos = int(i1 / f['framerate'] * DATA_REQUIRED_SR)
+            mixes.append((k, start + start_pos, max(len(crop) - start_pos, 0)))
+            base = os.path.basename(f['path'])
+            noise_name = base.split('.mp4')[0].split('.wav')[0] + '_noise.wav'
+            noise_dir = os.path.join(os.path.abspath(outputs), 'noise' + suffix)
+            ensure_dir(noise_dir)
+            audio_io.write_wav(os.path.join(noise_dir, noise_name), crop.astype(np.float32), DATA_REQUIRED_SR)
+            noise_entries[base] = OrderedDict([('audio', base.split('.mp4')[0].split('.wav')[0] + '.wav'),
+                                               ('noise', noise_name), ('snr', snr)])
+            pending.append((data_id, f, bits_full, i1, label, snd))     # mixed after the loop, in groups
+            continue
         if clean_audio:
             gt = torch.tensor([int(b) for b in label], dtype=torch.uint8, device=snd.device).reshape(1, -1)
             gmask = tools.bits_to_mask_batch(gt, float(DATA_REQUIRED_SR) / f['framerate'], snd.numel())
@@ -228,6 +272,8 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
         logits = net(s=S, v_num_frames=len(label))
         pred, conf = tools.threshold_bits(logits, SIGMOID_THRESHOLD)
         stat.append(_detect_item(data_id, f, bits_full, i1, label, pred[0].cpu().numpy(), conf[0].cpu().numpy()))
+    if pending and batch_mix:
+        pending = _mix_pending(pending, mixes, decoded, snr, max_mix_bytes)
     if pending:
         stat = _detect_groups(net, pending, max_batch, max_columns)
     stat_dict = OrderedDict([
@@ -246,14 +292,52 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     return stat_dict
 
 
+def _write_recovered_batch(jobs, clean_audio, noise_dir, nsuffix, max_bytes):
+    """create_data_from_prediction(batch_files=True): the WAVE files of `jobs` = (item, recording path, save_dir, name), per
+    group of files one audio_io.load_batch_device for the recordings (and one for the stored noise crops, one
+    tools.add_signals_ragged call) and one download."""
+    from .labels import _file_groups
+    noise_files = None
+    if clean_audio and jobs:
+        with open(os.path.join(noise_dir, nsuffix[1:] + '.json'), 'r') as fpn:
+            noise_files = json.load(fpn)['files']
+    for group in _file_groups([j[1] for j in jobs], max_bytes):
+        part = [jobs[i] for i in group]
+        snds, _ = audio_io.load_batch_device([j[1] for j in part], sr=DATA_REQUIRED_SR)
+        if clean_audio:
+            entries = [noise_files[os.path.basename(j[0]['path'])] for j in part]
+            noises, _ = audio_io.load_batch_device([os.path.join(noise_dir, e['noise']) for e in entries], sr=DATA_REQUIRED_SR)
+            mixed, clean, full_noise = tools.add_signals_ragged(snds, noises, [e['snr'] for e in entries], starts=0, norm=0.5)
+            host = ragged.download(mixed + clean + full_noise, np.float32)
+        else:
+            host = ragged.download(snds, np.float32)
+        B = len(part)
+        for k, (item, _, save_dir, filename) in enumerate(part):
+            mixed_path = os.path.join(save_dir, filename + '_mixed.wav')
+            rel = lambda q: os.path.join(os.path.basename(save_dir), os.path.basename(q))     # noqa: E731
+            audio_io.write_wav(mixed_path, host[k], DATA_REQUIRED_SR)
+            if clean_audio:
+                clean_path = os.path.join(save_dir, filename + '_clean.wav')
+                full_noise_path = os.path.join(save_dir, filename + '_full_noise.wav')
+                audio_io.write_wav(clean_path, host[B + k], DATA_REQUIRED_SR)
+                audio_io.write_wav(full_noise_path, host[2 * B + k], DATA_REQUIRED_SR)
+                item['mixed_audio'], item['clean_audio'], item['full_noise'] = rel(mixed_path), rel(clean_path), rel(full_noise_path)
+                item['audio_path'] = clean_path
+            else:
+                item['mixed_audio'] = rel(mixed_path)
+
+
 def create_data_from_prediction(input_json, output_json=None, suffix="", noise_snr=None, save_results=True,
-                                data_root=None, clean_audio=False):
+                                data_root=None, clean_audio=False, batch_files=False, max_bytes=1 << 30):
     """eval_results.json -> pred_data.json (`create_data_from_prediction_newtarget_bceloss_no_voting`,
     M1/create_data_from_pred.py:38-271): per file the ground-truth, predicted and `recovered_prediction` bit
     streams; with save_results the 14 kHz signal is written to recovered<suffix>/<name>_mixed.wav next to the JSON and
     referenced as `mixed_audio`.  clean_audio=True (:158-190): the recording is mixed with the noise crop that
     detect_files stored (noise<nsuffix>/<nsuffix[1:]>.json) at its SNR, and `<name>_mixed / _clean / _full_noise.wav`
-    are written and referenced (`mixed_audio`, `clean_audio`, `full_noise`, `audio_path`)."""
+    are written and referenced (`mixed_audio`, `clean_audio`, `full_noise`, `audio_path`).
+    batch_files=True (with save_results): the recordings come from one audio_io.load_batch_device call per group of files of at
+    most max_bytes of samples; with clean_audio so do the stored noise crops, one tools.add_signals_ragged call mixes the group
+    and its three signals per file come down in one copy.  The same WAVE files per item and the same JSON."""
     suffix = suffix or ""
     if output_json is None:
         output_json = os.path.join(get_parent_dir(input_json), 'pred_data.json')
@@ -274,7 +358,7 @@ def create_data_from_prediction(input_json, output_json=None, suffix="", noise_s
             ('ground_truth_bit_stream', ''.join(str(int(b)) for it in g for b in it['label'])),
             ('predicted_bit_stream', ''.join(str(int(b)) for it in g for b in it['pred_label'])),
             ('recovered_prediction', None), ('overlay_original', None), ('overlay_predicted', None)]))
-    ds_path, labels, pred_labels = '', [], []
+    ds_path, labels, pred_labels, jobs = '', [], [], []
     # the JSON carries the authors' absolute paths: `data_root` stands in for their common directory
     src_root = os.path.commonpath([os.path.dirname(g['path']) for g in groups]) if groups else ''
     for item in groups:
@@ -288,6 +372,9 @@ def create_data_from_prediction(input_json, output_json=None, suffix="", noise_s
             ensure_dir(save_dir)
             parts = item['path'].split('.mp4')
             wav_path = parts[0] if len(parts) == 1 else parts[0] + '.wav'
+            if batch_files:
+                jobs.append((item, _resolve(wav_path, src_root, data_root), save_dir, os.path.basename(wav_path).split('.wav')[0]))
+                continue
             snd, _ = audio_io.load(_resolve(wav_path, src_root, data_root), sr=DATA_REQUIRED_SR)
             filename = os.path.basename(wav_path).split('.wav')[0]
             mixed_path = os.path.join(save_dir, filename + '_mixed.wav')
@@ -309,6 +396,8 @@ def create_data_from_prediction(input_json, output_json=None, suffix="", noise_s
             else:
                 audio_io.write_wav(mixed_path, snd, DATA_REQUIRED_SR)
                 item['mixed_audio'] = rel(mixed_path)
+    if jobs:
+        _write_recovered_batch(jobs, clean_audio, os.path.join(get_parent_dir(output_json), 'noise' + nsuffix), nsuffix, max_bytes)
     hierarchy = OrderedDict([
         ('dataset_path', ds_path), ('num_videos', len(groups)), ('data_total_frames', obj['data_total_frames']),
         ('data_center_frames', obj['data_center_frames']), ('sigmoid_threshold', obj['sigmoid_threshold']),

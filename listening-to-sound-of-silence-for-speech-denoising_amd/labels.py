@@ -196,17 +196,7 @@ def _wave_sample_bytes(path):
 
 def _file_groups(paths, max_bytes):
     """Consecutive files in groups of at most max_bytes of f32 samples (a file larger than that is a group of its own)."""
-    groups, cur, size = [], [], 0
-    for i, p in enumerate(paths):
-        nb = _wave_sample_bytes(p)
-        if cur and (size + nb > max_bytes or len(cur) >= ragged.MAX_CLIPS):
-            groups.append(cur)
-            cur, size = [], 0
-        cur.append(i)
-        size += nb
-    if cur:
-        groups.append(cur)
-    return groups
+    return ragged.byte_groups([_wave_sample_bytes(p) for p in paths], max_bytes)
 
 
 def _plain(v):

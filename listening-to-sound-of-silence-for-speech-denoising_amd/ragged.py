@@ -57,6 +57,21 @@ def split(flat, lens):
     return [flat[o:o + n] for o, n in zip(offsets(lens).tolist(), np.asarray(lens, dtype=np.int64).reshape(-1).tolist())]
 
 
+def byte_groups(sizes, max_bytes):
+    """Consecutive indices 0 .. len(sizes) in groups of at most max_bytes (an entry larger than that is a group of its own) and
+    at most MAX_CLIPS entries."""
+    groups, cur, size = [], [], 0
+    for i, nb in enumerate(sizes):
+        if cur and (size + nb > max_bytes or len(cur) >= MAX_CLIPS):
+            groups.append(cur)
+            cur, size = [], 0
+        cur.append(i)
+        size += nb
+    if cur:
+        groups.append(cur)
+    return groups
+
+
 def download(tensors, dtype=None):
     """The 1-D GPU tensors of a list as host arrays (of `dtype`, if given), through one copy of their concatenation."""
     if not tensors:

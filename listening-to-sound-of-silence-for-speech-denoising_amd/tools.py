@@ -1,4 +1,6 @@
 """Mirror of the on-path pieces of the reference `tools.py` (M2/tools.py:217-303,340-362)."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -147,6 +149,155 @@ def add_signals(signal, noises, snr, norm=0.5):
     m, s, nz = add_signals_batch(sig, torch.from_numpy(stack).cuda()[None], float(snr), norm)
     dt = np.asarray(signal).dtype if np.issubdtype(np.asarray(signal).dtype, np.floating) else np.float32
     return m[0].cpu().numpy().astype(dt), s[0].cpu().numpy().astype(dt), [x.cpu().numpy().astype(dt) for x in nz[0]]
+
+
+_MIX_OUT = 6                        # f64 per clip of sos_ragged_mix_f32: Es, Ez, gain, peak, inv, status
+
+
+def _mix_1d(x, name, i, dtype_ok, what):
+    """The length of entry i of a list of 1-D arrays / tensors, or ValueError."""
+    dt, shape = (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else (np.asarray(x).dtype, np.shape(x))
+    if len(shape) != 1 or not dtype_ok(dt):
+        raise ValueError(f"{name}[{i}]: a 1-D {what} array or tensor, got shape {shape} of {dt}")
+    return int(shape[0])
+
+
+def _mix_float(dt):
+    return dt.is_floating_point if isinstance(dt, torch.dtype) else np.issubdtype(dt, np.floating)
+
+
+def _mix_plan(signals, noises, snr, noise_index, starts, counts, bits, ratios, norm):
+    """The host side of add_signals_ragged, checked before anything goes up: per-clip lengths, crops {noise, start, valid
+    samples}, parameters {snr, ratio or 0} and frame counts."""
+    B = len(signals)
+    lens = [_mix_1d(s, "signals", i, _mix_float, "floating-point") for i, s in enumerate(signals)]
+    for i, n in enumerate(lens):
+        if n < 1:
+            raise ValueError(f"signals[{i}] is empty")
+    nlens = [_mix_1d(z, "noises", i, _mix_float, "floating-point") for i, z in enumerate(noises)]
+    if B and not nlens:
+        raise ValueError("no noise recordings")
+    if noise_index is None:
+        if len(noises) != B:
+            raise ValueError(f"noise_index=None pairs clip i with noise i: {B} clips, {len(noises)} noises")
+        noise_index = range(B)
+    index = np.asarray(list(noise_index), dtype=np.int64).reshape(-1)
+    if len(index) != B:
+        raise ValueError(f"noise_index: one entry per clip ({B}), got {len(index)}")
+    if B and (index.min() < 0 or index.max() >= len(noises)):
+        raise ValueError(f"noise_index names a recording outside the {len(noises)} noises")
+    start = ragged.per_clip(starts, B, "starts")
+    count = ragged.per_clip(lens if counts is None else counts, B, "counts")
+    if np.any(start < 0) or np.any(count < 0) or np.any(start != np.floor(start)) or np.any(count != np.floor(count)):
+        raise ValueError("starts and counts are non-negative whole numbers of samples")
+    par = np.zeros((B, 2), dtype=np.float64)
+    par[:, 0] = ragged.per_clip(snr, B, "snr")
+    if not np.all(np.isfinite(par[:, 0])):
+        raise ValueError("snr must be finite")
+    if not np.isfinite(float(norm or 0.0)):
+        raise ValueError("norm must be finite")
+    nb = [0] * B
+    if bits is not None:
+        if len(bits) != B:
+            raise ValueError(f"bits: one entry (or None) per clip ({B}), got {len(bits)}")
+        if isinstance(ratios, (list, tuple)):                            # (a None entry goes with a None entry of bits)
+            ratios = [0.0 if r is None else r for r in ratios]
+        rat = ragged.per_clip(0.0 if ratios is None else ratios, B, "ratios")
+        for i, b in enumerate(bits):
+            if b is None:
+                continue
+            nb[i] = _mix_1d(b, "bits", i, lambda dt: dt in (torch.uint8, np.dtype(np.uint8)), "uint8")
+            if nb[i] < 1:
+                raise ValueError(f"bits[{i}] is empty")
+            if not (rat[i] > 1.0 and np.isfinite(rat[i])):
+                raise ValueError(f"ratios[{i}] = {rat[i]!r}: a clip with frame decisions needs more than one sample per frame")
+            par[i, 1] = rat[i]
+    crop = np.zeros((B, 3), dtype=np.int64)
+    crop[:, 0], crop[:, 1] = index, start
+    avail = np.asarray(nlens, dtype=np.int64)[index] - crop[:, 1] if B else crop[:, 1]
+    crop[:, 2] = np.clip(np.minimum(np.minimum(count, lens), avail), 0, None)
+    crop[crop[:, 2] == 0, 1] = 0                                         # an empty crop starts anywhere: keep it inside
+    return lens, nlens, crop, par, nb
+
+
+_MixStaged = namedtuple("_MixStaged", "flat lens tab d_tab d_noise noise_total ntab d_ntab d_bits par d_par norm ws mixed clean noise out")
+
+
+def _mix_stage(signals, d_noise, noise_total, ntab, par, bits, nb, norm):
+    """One launch sequence's worth of clips (at most ragged.MAX_CLIPS) on the device: the concatenated samples, the tables and
+    parameters (host and device), the frame decisions, the workspace and the result buffers."""
+    flat, lens = ragged.concat(signals)
+    dev, B = flat.device, len(lens)
+    tab = ragged.clip_table(lens, nb)
+    d_bits = None
+    if any(nb):
+        some = [b for b in bits if b is not None]
+        if any(torch.is_tensor(b) for b in some):
+            d_bits = torch.cat([b.to(dev) if torch.is_tensor(b) else torch.from_numpy(np.ascontiguousarray(b)).to(dev) for b in some])
+        else:
+            d_bits = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.uint8) for b in some])).to(dev)
+    nbytes = L.lib().sos_ragged_mix_workspace_bytes(tab.ctypes.data, B)
+    if nbytes < 0:
+        L.check(-22, "sos_ragged_mix_workspace_bytes")
+    total = int(tab[:, 1].sum())
+    mixed, clean, noise = (torch.empty(total, dtype=torch.float32, device=dev) for _ in range(3))
+    return _MixStaged(flat, lens, tab, _upload(tab, dev), d_noise, noise_total, ntab, _upload(ntab, dev), d_bits, par,
+                      _upload(par, dev), float(norm or 0.0), torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev),
+                      mixed, clean, noise, torch.empty((B, _MIX_OUT), dtype=torch.float64, device=dev))
+
+
+def _mix_launch(st):
+    """Enqueue sos_ragged_mix_f32 on staged clips; no wait."""
+    L.check(L.lib().sos_ragged_mix_f32(L.ptr(st.flat), L.ptr(st.d_tab), st.tab.ctypes.data, len(st.tab), L.ptr(st.d_noise),
+                                       st.noise_total, L.ptr(st.d_ntab), st.ntab.ctypes.data, L.ptr(st.d_bits), L.ptr(st.d_par),
+                                       st.par.ctypes.data, st.norm, L.ptr(st.ws), st.ws.numel(), L.ptr(st.mixed), L.ptr(st.clean),
+                                       L.ptr(st.noise), L.ptr(st.out), L.stream_ptr()), "sos_ragged_mix_f32")
+    return st
+
+
+def add_signals_ragged(signals, noises, snr, noise_index=None, starts=0, counts=None, bits=None, ratios=None, norm=0.5,
+                       return_detail=False):
+    """`add_signals` with one noise (M2/tools.py:217-276) for clips of any lengths in one launch sequence
+    (sos_ragged_mix_f32; float64 restatement: tests/mix_reference.py).  signals: a list of 1-D clips, numpy arrays or GPU
+    tensors; noises: a list of 1-D noise recordings, uploaded once per call; noise_index[i] names the recording of clip i
+    (default i: as many noises as clips).  Clip i is mixed with noise[start : start + count] (starts / counts: a scalar or one
+    value per clip; counts defaults to the clip's length), clipped to the recording and to the clip's length and zero-filled
+    beyond -- the crop of handoff.add_noise_to_audio.  snr: dB, a scalar or one value per clip.  bits / ratios: per-clip uint8
+    frame decisions (1 = non-silent) and samples per frame as pipeline.denoise_ragged(bits=) takes them; the clip is silenced
+    on its silent intervals (bits_to_mask_batch's mask) before mixing; a None entry leaves the clip as it is.  norm: the peak
+    of the mix (None / 0: no normalisation).
+    -> (mixed, clean, noise): three lists of 1-D f32 GPU tensors in input order, views into three flat buffers (per
+    ragged.MAX_CLIPS clips), so ragged.download brings a whole batch down in one copy.  return_detail=True adds a list of
+    dict(signal_energy, noise_energy, gain, peak, inv).  A clip's results are the same bits alone, in any batch and in any
+    order.  One wait per call (the status rows).  Argument errors are ValueErrors raised before anything is uploaded."""
+    signals, noises = list(signals), list(noises)
+    bits = None if bits is None else list(bits)
+    lens, nlens, crop, par, nb = _mix_plan(signals, noises, snr, noise_index, starts, counts, bits, ratios, norm)
+    B = len(signals)
+    mixed, clean, noise, detail = [], [], [], []
+    if not B:
+        return (mixed, clean, noise, detail) if return_detail else (mixed, clean, noise)
+    d_noise, _ = ragged.concat(noises)
+    ntab = np.ascontiguousarray(np.stack([ragged.offsets(nlens)[crop[:, 0]] + crop[:, 1], crop[:, 2]], axis=1))
+    done = []
+    for c0 in range(0, B, ragged.MAX_CLIPS):
+        c1 = min(B, c0 + ragged.MAX_CLIPS)
+        done.append(_mix_launch(_mix_stage(signals[c0:c1], d_noise, int(sum(nlens)), np.ascontiguousarray(ntab[c0:c1]),
+                                           np.ascontiguousarray(par[c0:c1]), None if bits is None else bits[c0:c1], nb[c0:c1],
+                                           norm)))
+    rows = torch.cat([st.out for st in done]).cpu().numpy()              # the one wait of the call
+    bad = np.flatnonzero(rows[:, 5] < 0)
+    if len(bad):
+        raise RuntimeError(f"sos_ragged_mix_f32: clip {int(bad[0])}: the device tables disagree with the host's")
+    for st in done:
+        mixed += ragged.split(st.mixed, st.lens)
+        clean += ragged.split(st.clean, st.lens)
+        noise += ragged.split(st.noise, st.lens)
+    if not return_detail:
+        return mixed, clean, noise
+    detail = [dict(signal_energy=float(r[0]), noise_energy=float(r[1]), gain=float(r[2]), peak=float(r[3]), inv=float(r[4]))
+              for r in rows]
+    return mixed, clean, noise, detail
 
 
 def trim_unknown_frames(bits):
