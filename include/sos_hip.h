@@ -648,6 +648,33 @@ int sos_ragged_mix_f32(const float* clips, const int64_t* table, const int64_t* 
                        const double* params, const double* params_host, double norm, void* workspace, int64_t workspace_bytes,
                        float* mixed, float* clean, float* noise_out, double* out, sos_stream_t stream);
 
+/* ---- long recordings as ragged batches of overlapping windows (csrc/ragged_window.hip; sos_amd.pipeline.denoise_long; float64
+ * restatement of the plan and the stitch: tests/window_reference.py).  One launch each, whatever the number of windows; no
+ * allocation, no host synchronisation.  table / table_host: int64 [nwin][10] on the device / the HOST, the rows of
+ * pipeline.window_plan: {recording, source offset, samples, output offset, core start, core end, window start, row, previous
+ * window, next window}.  Core start, core end and window start count samples of the window's own recording; the output offset
+ * is where the window's first output sample lies in `out`; previous / next are table indices of the neighbouring windows of the
+ * same recording, -1 at its ends.
+ * sos_window_stage_f32: x holds `total` floats; rows [nwin][stride]: rows[w][0 .. samples) = x[source offset ..), zero from
+ *   there to the stride.  Windows may overlap and may start on any sample.  Reads only {source offset, samples}, so one table
+ *   stages several buffers through different source offsets.
+ * sos_window_stitch_f32: rows f32 [n_rows][stride], window w in row `row`, its sample i being sample window start + i of its
+ *   recording; out holds the recordings' outputs back to back, sum(core end - core start) floats: the cores must tile them.
+ *   Window w is the one writer of its core.  A sample p of it that lies within `context` samples of a core boundary b shared
+ *   with a neighbour is blended over the zone [b - context, b + context): w = (p - (b - context) + 0.5) / (2 context),
+ *   out = (1 - w) earlier window + w later window, in f32; every other sample is copied bit for bit; context = 0 is a plain
+ *   cut.  No atomics, fixed arithmetic: a recording's output has the same bits alone, in any batch, at any offset and with the
+ *   table in any order.
+ * SOS_EINVAL (sos_last_error() names the window), before any launch: null pointers, nwin outside 1 .. 65535, stride < 1,
+ * samples > stride, a row outside n_rows, context < 0 or above 2^22, a context not less than a window it blends or more than
+ * the core holds (twice with two neighbours), a core outside its window, a neighbour that is no window of the same recording
+ * or does not cover the overlap, an entry outside `total` or outside the summed output length.  The kernels follow the DEVICE
+ * table and skip an entry that fails the same tests. */
+int sos_window_stage_f32(const float* x, int64_t total, const int64_t* table, const int64_t* table_host, int nwin, int64_t stride,
+                         float* rows, sos_stream_t stream);
+int sos_window_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
+                          int nwin, int64_t context, float* out, sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 // ragged.h -- what every ragged-batch entry point shares (metrics_batch.hip, stoi.hip, sdr.hip, ragged_io.hip,
-// silence_label.hip, ragged_mix.hip, wave_io.hip): the clip-count check, the clip row, the bounds rule on both sides of the launch,
-// the host's sums over a table, the workspace layout arithmetic, the clamped grid, the 256-thread LDS reductions and the
-// four-sample accesses of clips that start on any sample.
+// silence_label.hip, ragged_mix.hip, wave_io.hip, ragged_window.hip): the clip-count check, the clip row, the bounds rule on
+// both sides of the launch, the host's sums over a table, the workspace layout arithmetic, the clamped grid, the 256-thread LDS
+// reductions and the four-sample accesses of clips that start on any sample.
 // A batch is clips back to back in one buffer plus a table of where each lies, in two copies: the host sizes every array
 // from its own (table_host / lengths_host) and refuses a bad entry before any launch; the kernels follow the DEVICE table.
 #pragma once
@@ -112,8 +112,8 @@ __device__ static inline int block_scan_incl(int v, int* scan) {
     return scan[threadIdx.x];
 }
 
-// Four consecutive samples of a clip that may start on any sample (ragged_io.hip, ragged_mix.hip): one 16-byte access where the
-// address allows it, sample by sample otherwise.  Which of the two is taken changes no value.
+// Four consecutive samples of a clip that may start on any sample (ragged_io.hip, ragged_mix.hip, ragged_window.hip): one
+// 16-byte access where the address allows it, sample by sample otherwise.  Which of the two is taken changes no value.
 typedef float ragged_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bool ragged_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }      // a null pointer counts
 

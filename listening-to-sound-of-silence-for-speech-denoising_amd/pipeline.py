@@ -186,10 +186,15 @@ def _denoise_group(detector, denoiser, clips, sr, fps):
 def _ragged_groups(clips, max_batch, max_columns):
     """Clips sorted by length (longest first) and cut into groups of <= max_batch clips and <= max_columns
     (clips x frames of the group's longest) spectrogram columns: lists of indices into `clips`."""
-    order = sorted(range(len(clips)), key=lambda i: -int(clips[i].numel()))
+    return _length_groups([int(c.numel()) for c in clips], max_batch, max_columns)
+
+
+def _length_groups(ns, max_batch, max_columns):
+    """_ragged_groups of clips (or of windows, denoise_long) given by their lengths `ns` in samples."""
+    order = sorted(range(len(ns)), key=lambda i: -ns[i])
     groups, j = [], 0
     while j < len(order):
-        t_long = 1 + int(clips[order[j]].numel()) // transform.HOP_LENGTH
+        t_long = 1 + ns[order[j]] // transform.HOP_LENGTH
         nb = max(1, min(max_batch, max_columns // t_long, len(order) - j))
         groups.append(order[j:j + nb])
         j += nb
@@ -284,6 +289,150 @@ def denoise_ragged(detector, denoiser, clips, sr=SR, fps=FPS, max_batch=256, max
             if return_all:
                 extra[i] = dict(logits=info["logits"][k, :info["rag"].n_vframes[k]], bits=info["bits"][k, :info["rag"].n_vframes[k]])
     return (outs, extra) if return_all else outs
+
+
+def _hops(samples):
+    """`samples` rounded up to a multiple of the STFT hop."""
+    hop = transform.HOP_LENGTH
+    return -(-int(samples) // hop) * hop
+
+
+def window_plan(ns, core, context):
+    """Recordings of `ns` samples cut into overlapping windows (host only; float64 restatement: tests/window_reference.py).
+    core, context: samples, rounded up to multiples of the hop; core >= 2 context (only neighbouring windows overlap) and
+    core + context >= MIN_FRAMES hops (every window is a clip the networks accept).  A recording of n samples has the output
+    length n_out = hop * (n // hop) and K = max(1, n_out // core) windows.  Window k owns the core [k core, (k + 1) core) of the
+    output -- the last one up to n_out, so between core and 2 core samples; a recording shorter than 2 core is one window -- and
+    reads the source samples [max(k core - context, 0), (k + 1) core + context), the last one up to n: it keeps the n % hop
+    tail, so its reflect padding sees the real end.  Every window starts on a multiple of the hop and all but the last are
+    multiples of the hop long, so a window's denoised row covers exactly [start, start + hop * (samples // hop)) of the output.
+    -> host int64 (windows, 10), the rows of sos_window_stage_f32 / sos_window_stitch_f32 in recording order:
+    {recording, source offset in the back-to-back buffer, samples, output offset of the window's start in the back-to-back
+    outputs, core start, core end, window start, row of the window's result (its index here), previous window, next window
+    (indices here, -1 at a recording's ends)}.
+    ValueError: the argument rules above, or a recording with fewer than MIN_FRAMES STFT frames (named)."""
+    import numpy as np
+    hop = transform.HOP_LENGTH
+    if core < 0 or context < 0:
+        raise ValueError(f"window_plan: core and context are non-negative sample counts, got {core} and {context}")
+    core, context = _hops(core), _hops(context)
+    if core < 2 * context:
+        raise ValueError(f"window_plan: core ({core} samples) must be at least twice the context ({context}): only neighbouring "
+                         "windows may overlap")
+    if core + context < MIN_FRAMES * hop:
+        raise ValueError(f"window_plan: core + context ({core + context} samples) must be at least {MIN_FRAMES} hops "
+                         f"({MIN_FRAMES * hop} samples)")
+    ns = [int(n) for n in ns]
+    src, dst = ragged.offsets(ns).tolist(), ragged.offsets([hop * (n // hop) for n in ns]).tolist()
+    rows = []
+    for r, n in enumerate(ns):
+        if 1 + n // hop < MIN_FRAMES:
+            raise ValueError(f"recording {r}: clips need at least {MIN_FRAMES} STFT frames ({MIN_FRAMES * hop} samples); got {n} samples")
+        n_out = hop * (n // hop)
+        K, first = max(1, n_out // core), len(rows)
+        for k in range(K):
+            last = k == K - 1
+            cs, ce = k * core, n_out if last else (k + 1) * core
+            start, end = max(cs - context, 0), n if last else ce + context
+            rows.append((r, src[r] + start, end - start, dst[r] + start, cs, ce, start, first + k, first + k - 1 if k else -1,
+                         -1 if last else first + k + 1))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, tools.WINDOW_COLS)
+
+
+@torch.no_grad()
+def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0, context_seconds=2.0, max_batch=256,
+                 max_columns=65536, bits=None, return_all=False):
+    """Recordings of ANY length, minutes and hours included: `clips` = list of 1-D f32 GPU waveforms, short and long mixed.
+    denoise_ragged runs a recording as one clip, which ends at sos_conv2d_fwd's 4 GB image (about 16 minutes at 14 kHz), needs
+    ~0.5 MB of activations per STFT column and steps both BiLSTMs serially through the whole file.  Here every recording is cut
+    into overlapping windows (window_plan: cores of `window_seconds`, `context_seconds` more on each inner side; a recording
+    shorter than two cores is one window, i.e. exactly denoise_ragged's clip), the windows of ALL recordings run as ordinary
+    ragged clips -- sorted by length and grouped by max_batch / max_columns like denoise_ragged's clips, one
+    sos_window_stage_f32 launch per group out of the one concatenated buffer -- and their outputs are cross-faded over the
+    2 context samples around every core boundary (sos_window_stitch_f32).  Activation memory follows max_columns (a group of
+    windows), not the file: a file below that budget runs as one group and saves nothing, so lower max_columns to save memory
+    (EXPERIMENTS.md 3.14: a quarter of the default costs no time on a 10-minute file, one window per group does).
+    Each window is a clip in its own right: its own reflect padding, detector pass, frame count n_video_frames(samples, sr,
+    fps) and BiLSTM passes.  The context is what is paid so that a core does not see these artificial edges at full weight: the
+    result APPROXIMATES the whole-file result and is not equal to it (EXPERIMENTS.md has the distance on random-weight networks).
+    Windows of one recording fall into different groups, and a boundary needs both rows: every group's output rows are kept
+    (one buffer of windows x longest window, 4 bytes per output sample and overlap) and stitched ONCE after the last group, in
+    one launch.  Nothing goes to the host between the groups.
+    `bits` (one 1-D uint8 array or GPU tensor per recording, 1 = non-silent; `fps` a scalar or one value per recording;
+    `detector` may be None): the first model's decisions as in denoise_ragged.  The noise-interval signal of each recording is
+    made once at full length with the mask rule (tools.ragged_stage: padded rows, recordings x longest recording) and windowed
+    by the same stage kernel, so a sample's mask does not depend on the window it lands in.
+    Outputs come back in input order, each hop * (n // hop) samples long, views into one buffer.  return_all adds per recording
+    dict(plan=its window_plan rows (row = the order the windows ran in), windows=[dict(logits, bits) per window]), or with
+    `bits` dict(plan, bits, mask=the sample mask at full length).
+    ValueError before any launch: window_plan's (a recording below MIN_FRAMES frames is named), more than 65535 windows."""
+    import numpy as np
+    clips = list(clips)
+    for c in clips:
+        if c.dim() != 1:
+            raise ValueError("denoise_long expects 1-D waveforms")
+    if bits is None and not isinstance(fps, (int, float)):
+        raise ValueError("one fps per recording needs the recordings' frame decisions (bits=): the detector's groups share one rate")
+    if bits is not None and len(bits) != len(clips):
+        raise ValueError("bits must hold one array of frame decisions per recording")
+    if not clips:
+        return ([], []) if return_all else []
+    hop = transform.HOP_LENGTH
+    context = _hops(round(context_seconds * sr))
+    ns = [int(c.numel()) for c in clips]
+    plan = window_plan(ns, round(window_seconds * sr), context)
+    W = len(plan)
+    if W > ragged.MAX_CLIPS:
+        raise ValueError(f"denoise_long: {W} windows in one call (at most {ragged.MAX_CLIPS}): longer windows, or fewer recordings")
+    flat, _ = ragged.concat(clips)
+    device = flat.device
+    ms = plan[:, 2].tolist()
+    if bits is not None:
+        rates = ragged.per_clip(fps, len(clips), "fps")                                  # fps: a scalar or one per recording
+        for b in bits:
+            if b.ndim != 1 or (b.dtype != torch.uint8 if torch.is_tensor(b) else b.dtype != np.uint8):
+                raise ValueError("bits must be 1-D uint8 arrays or GPU tensors (1 = non-silent)")
+        nb = [int(b.shape[0]) for b in bits]
+        if all(torch.is_tensor(b) for b in bits):
+            d_bits = torch.cat([b.to(device) for b in bits])
+        else:                                                                            # host arrays: one upload
+            d_bits = torch.from_numpy(np.concatenate([b.cpu().numpy() if torch.is_tensor(b) else b for b in bits])).to(device)
+        _, noise_rows, mask = tools.ragged_stage(flat, ragged.clip_table(ns, nb), max(ns), d_bits, [float(sr) / float(f) for f in rates])
+        noise_src = plan.copy()                                                          # the same windows of the padded rows
+        noise_src[:, 1] = plan[:, 0] * max(ns) + plan[:, 6]
+        fps_w = rates[plan[:, 0]]
+    kept = torch.empty((W, hop * (max(ms) // hop)), dtype=torch.float32, device=device)
+    seen, done = [None] * W, 0
+    for part in _length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
+        m = [ms[i] for i in part]
+        sub = np.ascontiguousarray(plan[part])
+        wave = tools.window_stage(flat, sub, max(m))
+        if bits is None:
+            rag = _group_geometry(m, device, sr, fps)
+            y, logits, wbits = _denoise_group_padded(detector, denoiser, wave, rag, sr, fps)
+            if return_all:
+                for k, i in enumerate(part):
+                    seen[i] = dict(logits=logits[k, :rag.n_vframes[k]], bits=wbits[k, :rag.n_vframes[k]])
+        else:
+            rag = _group_geometry(m, device, sr, FPS, nv=[max(1, n_video_frames(ms[i], sr, fps_w[i])) for i in part])
+            y = _denoise_group_staged(denoiser, wave, tools.window_stage(noise_rows.view(-1), np.ascontiguousarray(noise_src[part]), max(m)), rag)
+        kept[done:done + len(part), :y.shape[1]] = y
+        plan[part, 7] = np.arange(done, done + len(part))
+        done += len(part)
+    rows = plan.copy()
+    rows[:, 2] = hop * (plan[:, 2] // hop)                                               # what a window's row holds
+    outs = ragged.split(tools.window_stitch(kept, rows, context), [hop * (n // hop) for n in ns])
+    if not return_all:
+        return outs
+    first = np.searchsorted(plan[:, 0], np.arange(len(clips) + 1))
+    extra = [dict(plan=plan[first[r]:first[r + 1]]) for r in range(len(clips))]
+    if bits is None:
+        for r, e in enumerate(extra):
+            e["windows"] = seen[first[r]:first[r + 1]]
+    else:
+        for e, b, m in zip(extra, ragged.split(d_bits, nb), ragged.split(mask, ns)):
+            e["bits"], e["mask"] = b, m
+    return outs, extra
 
 
 class PipelinedDenoiser:

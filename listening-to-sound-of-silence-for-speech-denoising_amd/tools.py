@@ -86,6 +86,40 @@ def ragged_unpack(rows, table):
     return out
 
 
+WINDOW_COLS = 10                    # int64 per window of pipeline.window_plan (csrc/ragged_window.hip: RW_COLS)
+
+
+def window_stage(x, table, stride):
+    """Windows of a buffer as zero-filled rows in one launch (sos_window_stage_f32).  x: contiguous 1-D f32 GPU tensor; table:
+    host rows of pipeline.window_plan, of which {source offset, samples} are read; windows may overlap and start on any sample.
+    -> rows (windows, stride): rows[w, :samples] = x[source offset : source offset + samples], zero beyond."""
+    L.require_cuda(x)
+    tab = _host_table(table, WINDOW_COLS)
+    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous 1-D float32 tensor")
+    rows = torch.empty((tab.shape[0], int(stride)), dtype=torch.float32, device=x.device)
+    d_tab = _upload(tab, x.device)
+    L.check(L.lib().sos_window_stage_f32(L.ptr(x), x.numel(), L.ptr(d_tab), tab.ctypes.data, tab.shape[0], int(stride),
+                                         L.ptr(rows), L.stream_ptr()), "sos_window_stage_f32")
+    return rows
+
+
+def window_stitch(rows, table, context):
+    """The rows of overlapping windows cross-faded into their recordings' outputs in one launch (sos_window_stitch_f32).  rows:
+    contiguous f32 (R, stride) GPU tensor; table: host rows of pipeline.window_plan, whose cores tile the outputs; context: half
+    the width of the blend around an inner core boundary, in samples (0: a plain cut).
+    -> one 1-D f32 GPU tensor, the recordings' outputs back to back (sum of the cores' lengths)."""
+    L.require_cuda(rows)
+    tab = _host_table(table, WINDOW_COLS)
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
+    out = torch.empty(max(int((tab[:, 5] - tab[:, 4]).sum()), 0), dtype=torch.float32, device=rows.device)
+    d_tab = _upload(tab, rows.device)
+    L.check(L.lib().sos_window_stitch_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
+                                          int(context), L.ptr(out), L.stream_ptr()), "sos_window_stitch_f32")
+    return out
+
+
 def convert_bitstreammask_to_audiomask(ref_audio_signal, frames_to_audiosample_ratio, bitstream):
     """M2/tools.py:340-362 (string bits) / M1/tools.py:770-792 (int bits): same arguments, same
     RuntimeError on an invalid bit, same dtype as `ref_audio_signal`."""

@@ -1,0 +1,144 @@
+"""Long-recording benchmark (run on the GPU box): one synthetic recording (default 10 minutes at 14 kHz, dataset.synth_batch
+pieces back to back) denoised whole by pipeline.denoise_ragged([clip]) and in overlapping windows by pipeline.denoise_long at
+several window lengths, in fp16, timed with HIP events around whole calls, peak memory from the allocator; the two window
+kernels alone (sos_window_stage_f32, sos_window_stitch_f32) on the recording's 30 s plan, as a rate over the bytes they move,
+next to a float4 copy (torch's copy kernel) of the same number of bytes.  --distance: how far the windowed result is from the
+whole-file result on a 60 s recording with the closed-form test networks in bf16x3 -- a characterisation of random-weight
+networks, nothing is asserted on it.  One line per configuration."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import sos_amd  # noqa: E402
+from oracle import nets as onet  # noqa: E402
+from sos_amd import _lib as L  # noqa: E402
+from sos_amd import pipeline, tools, transform  # noqa: E402
+
+SR = 14000
+
+
+def _wave(seed, n):
+    from sos_amd.dataset import synth_batch
+    parts = synth_batch(seed, (n + 27999) // 28000)["mixed"]
+    return torch.from_numpy(np.ascontiguousarray(np.concatenate(list(parts))[:n])).cuda()
+
+
+def _nets():
+    from sos_amd.common import MyConfig
+    from sos_amd.denoiser import networks as jnet
+    from sos_amd.detector import networks as dnet
+    det = dnet.get_network()
+    det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+    jm = jnet.get_network(MyConfig())
+    jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+    return det.cuda().eval(), jm.cuda().eval()
+
+
+def _timed(fn, iters):
+    """(ms per call, peak bytes allocated during the timed calls) after one warm-up call."""
+    fn()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters, torch.cuda.max_memory_allocated()
+
+
+def speed(args, det, jm):
+    n = int(args.seconds * SR)
+    clip = _wave(800, n)
+    sos_amd.set_precision(args.precision)
+    try:
+        if not args.skip_whole:
+            ms, peak = _timed(lambda: pipeline.denoise_ragged(det, jm, [clip]), args.iters)
+            print(f"{args.seconds:g} s at {SR} Hz, {args.precision}: whole file, denoise_ragged([clip])      {ms:9.1f} ms per call "
+                  f"({args.seconds / (ms / 1e3):7.1f} x real time), peak {peak / 2**30:6.2f} GiB")
+        for win, cols in [(w, 65536) for w in args.windows] + [(30.0, c) for c in args.max_columns]:
+            plan = pipeline.window_plan([n], round(win * SR), round(args.context * SR))
+            groups = len(pipeline._length_groups(plan[:, 2].tolist(), 256, cols))
+            ms, peak = _timed(lambda: pipeline.denoise_long(det, jm, [clip], window_seconds=win, context_seconds=args.context,
+                                                            max_columns=cols), args.iters)
+            print(f"{args.seconds:g} s at {SR} Hz, {args.precision}: denoise_long, {win:g} s windows + {args.context:g} s context "
+                  f"({len(plan):3d} windows, max_columns {cols}: {groups} groups) {ms:9.1f} ms per call "
+                  f"({args.seconds / (ms / 1e3):7.1f} x real time), peak {peak / 2**30:6.2f} GiB")
+    finally:
+        sos_amd.set_precision("bf16")
+    # the two kernels alone, on resident buffers
+    hop = transform.HOP_LENGTH
+    context = pipeline._hops(round(args.context * SR))
+    plan = np.ascontiguousarray(pipeline.window_plan([n], round(30.0 * SR), context))
+    stride = int(plan[:, 2].max())
+    rows = tools.window_stage(clip, plan, stride)
+    held = plan.copy()
+    held[:, 2] = hop * (plan[:, 2] // hop)                      # what a window's row holds
+    out = tools.window_stitch(rows, held, context)
+    d_plan, d_held = torch.from_numpy(plan).cuda(), torch.from_numpy(held).cuda()
+    lib = L.lib()
+    ms_stage, _ = _timed(lambda: L.check(lib.sos_window_stage_f32(L.ptr(clip), clip.numel(), L.ptr(d_plan), plan.ctypes.data, len(plan),
+                                                                  stride, L.ptr(rows), L.stream_ptr())), 200)
+    ms_stitch, _ = _timed(lambda: L.check(lib.sos_window_stitch_f32(L.ptr(rows), len(plan), stride, L.ptr(d_held), held.ctypes.data,
+                                                                    len(plan), context, L.ptr(out), L.stream_ptr())), 200)
+    n_out = int((plan[:, 5] - plan[:, 4]).sum())
+    for name, ms, floats_in, floats_out in (("sos_window_stage_f32", ms_stage, int(plan[:, 2].sum()), rows.numel()),
+                                            ("sos_window_stitch_f32", ms_stitch, n_out + 2 * context * (len(plan) - 1), n_out)):
+        src, dst = torch.empty((floats_in + floats_out) // 2, device="cuda"), torch.empty((floats_in + floats_out) // 2, device="cuda")
+        ms_copy, _ = _timed(lambda: dst.copy_(src), 200)
+        nbytes = 4.0 * (floats_in + floats_out)
+        print(f"{name} ({len(plan)} windows of 30 s + {args.context:g} s, resident buffers): {ms * 1e3:8.1f} us, "
+              f"{nbytes / 1e6:.1f} MB at {nbytes / (ms / 1e3) / 1e12:.3f} TB/s; a float4 copy of the same bytes {ms_copy * 1e3:8.1f} us "
+              f"({nbytes / (ms_copy / 1e3) / 1e12:.3f} TB/s)")
+
+
+def distance(args, det, jm):
+    n = 60 * SR
+    clip = _wave(810, n)
+    sos_amd.set_precision("bf16x3")
+    try:
+        whole = pipeline.denoise_ragged(det, jm, [clip])[0]
+        scale = float(whole.abs().max())
+        for win in args.distance_windows:
+            for ctx in (0.0, 1.0, 2.0):
+                got, extra = pipeline.denoise_long(det, jm, [clip], window_seconds=win, context_seconds=ctx, return_all=True)
+                cores = [float((got[0][cs:ce] - whole[cs:ce]).abs().max()) / scale for cs, ce in extra[0]["plan"][:, 4:6].tolist()]
+                rms = float(((got[0] - whole) ** 2).mean().sqrt() / (whole ** 2).mean().sqrt())
+                print(f"60 s, bf16x3, closed-form networks: {win:g} s windows, context {ctx:g} s ({len(cores)} windows): max relative "
+                      f"error over the cores {max(cores):.3e} (per core " + " ".join(f"{c:.1e}" for c in cores) + f"), rms relative {rms:.3e}")
+    finally:
+        sos_amd.set_precision("bf16")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=600.0)
+    ap.add_argument("--windows", type=float, nargs="*", default=[10.0, 30.0, 60.0])
+    ap.add_argument("--max-columns", type=int, nargs="*", default=[16384, 4096],
+                    help="further runs at 30 s windows with these column budgets per group (the default budget is 65536)")
+    ap.add_argument("--context", type=float, default=2.0)
+    ap.add_argument("--precision", default="fp16")
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--skip-whole", action="store_true", help="do not time the whole-file call")
+    ap.add_argument("--distance", action="store_true", help="also report the distance from the whole-file result (60 s, bf16x3)")
+    ap.add_argument("--distance-windows", type=float, nargs="*", default=[10.0, 30.0])
+    ap.add_argument("--no-speed", action="store_true")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("long_bench needs an MI355X: nothing is measured without one")
+    det, jm = _nets()
+    with torch.no_grad():
+        if not args.no_speed:
+            speed(args, det, jm)
+        if args.distance:
+            distance(args, det, jm)
+
+
+if __name__ == "__main__":
+    main()
