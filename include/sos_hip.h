@@ -675,6 +675,42 @@ int sos_window_stage_f32(const float* x, int64_t total, const int64_t* table, co
 int sos_window_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
                           int nwin, int64_t context, float* out, sos_stream_t stream);
 
+/* ---- one decision stream per recording, and windows masked by it (csrc/ragged_window.hip; sos_amd.pipeline.detect_long and the
+ * `bits=` path of denoise_long; float64 restatement of the frame stitch: tests/frames_reference.py).  One launch each.
+ * sos_window_frames_stitch_f32: rows f32 [n_rows][stride] hold the windows' frame logits, window w (an entry of the plan table
+ *   above, of which {core start, core end, window start, row} are read) in row `row` with frames[w] logits (frames /
+ *   frames_host: int64 [nwin], 1 .. stride).  recs / recs_host: int64 [nrec][4] = {frame offset in `out`, frames F, first
+ *   window, windows K}: the windows first .. first + K - 1 of the table are the recording's, in order; ratios / ratios_host:
+ *   f64 [nrec], rho = samples per frame, in (0, 2^30]; F <= 2^31.  out: the recordings' F logits each, sum(F) floats.  Frame i
+ *   of a recording has the centre p = (i + 0.5) rho (float64, one rounded multiply) and the owner k = min(floor(p) / core,
+ *   K - 1); window q gives for it its frame j_q = clamp(floor((i + 0.5) - start_q / rho), 0, frames_q - 1) (one rounded divide,
+ *   one rounded subtract).  out[i] = rows[k][j_k], a bit-for-bit copy, except with context > 0 in the zones
+ *     k > 0     and p <  core start_k + context: w = (p - (core start_k - context)) / (2 context), out = (1 - w) rows[k-1][j_{k-1}] + w rows[k][j_k]
+ *     k < K - 1 and p >= core end_k - context:   w = (p - (core end_k - context)) / (2 context),   out = (1 - w) rows[k][j_k] + w rows[k+1][j_{k+1}]
+ *   with w computed in float64, rounded once to f32, and the blend in f32.  core >= 2 context keeps the zones apart.  One
+ *   writer per output frame, no atomics: the same bits alone, in any batch, at any offset, with the rows in any order.
+ * sos_window_stage_masked_f32: x = the recordings back to back, bits = their frame decisions back to back (1 = non-silent),
+ *   clips / clips_host + ratios / ratios_host: the recordings' table {sample offset, samples, bit offset, frames} and samples
+ *   per frame (> 1) as sos_ragged_stage_f32 takes them; table / table_host: the plan table, of which {recording, source offset,
+ *   samples, window start} are read (source offset = the recording's sample offset + window start).  wave, masked f32
+ *   [nwin][stride]: wave[w][j] = x[source offset + j], masked[w][j] = wave[w][j] * mask, mask = the value sos_ragged_stage_f32 /
+ *   sos_bits_to_mask give sample window start + j of the WHOLE recording (its frames, its ratio, its last sample for the
+ *   short-run flip); both zero from the window's samples to the stride.  Rows equal slices of sos_ragged_stage_f32's
+ *   full-length wave / masked bit for bit; nothing of full length is written.
+ * SOS_EINVAL before any launch (sos_last_error() names the window or the recording): null pointers, nwin / nrec outside
+ * 1 .. 65535, stride < 1, core < 1, context < 0 or above 2^22, core < 2 context, a recording outside the summed frames /
+ * samples / the table's windows, a ratio outside its range, a window with a row outside n_rows, frames outside 1 .. stride,
+ * samples > stride, or samples outside its recording.  The kernels follow the DEVICE tables and skip an entry that fails
+ * the same tests. */
+int sos_window_frames_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
+                                 const int64_t* frames, const int64_t* frames_host, int nwin, const int64_t* recs,
+                                 const int64_t* recs_host, const double* ratios, const double* ratios_host, int nrec, int64_t core,
+                                 int64_t context, float* out, sos_stream_t stream);
+int sos_window_stage_masked_f32(const float* x, const uint8_t* bits, const int64_t* clips, const int64_t* clips_host,
+                                const double* ratios, const double* ratios_host, int nrec, const int64_t* table,
+                                const int64_t* table_host, int nwin, int64_t stride, float* wave, float* masked,
+                                sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,15 +12,32 @@
 // Pure streaming, shaped like ragged_io.hip: a thread handles four consecutive samples, one 16-byte access where the address
 // allows it and scalar accesses otherwise; which of the two is taken changes no value, so a recording's output has the same bits
 // alone, in any batch, at any offset and with the table in any order.
+// Two more for the detector half of the chain and the `bits=` path (pipeline.detect_long / denoise_long):
+//   window_frames_stitch_kernel   one row of frame logits per window -> ONE logit stream per recording.  The windows' frame grids
+//                          do not line up with the recording's (a frame is rho = sr / fps samples, windows start on samples), so
+//                          frame i of the recording is placed by its centre p = (i + 0.5) rho: the window whose core holds p owns
+//                          it and gives the frame of its own grid that holds p, j = clamp(floor((i + 0.5) - start / rho), 0,
+//                          frames - 1); within `context` samples of an inner core boundary the two neighbours' frames are blended
+//                          with w = (p - (b - context)) / (2 context) (float64, rounded once to f32; blend in f32).  float64
+//                          restatement: tests/frames_reference.py.  One thread and one writer per output frame.
+//   window_stage_masked_kernel    window_stage_kernel plus the mask rule (mask_rule.h) in the RECORDING's coordinates: the windows'
+//                          wave rows and their masked rows x * mask, mask = mask_sample(bits of the recording, its frames, its
+//                          ratio, its samples, window start + j): slices of what sos_ragged_stage_f32 makes at full length, bit
+//                          for bit, with nothing of full length written.
 // Bounds: the rule of ragged.h -- the host refuses a table entry that leaves what it sized from table_host (SOS_EINVAL), the
-// kernels skip an entry of the DEVICE table that fails the same test (window_stage_ok / window_stitch_why below).
+// kernels skip an entry of the DEVICE table that fails the same test (window_stage_ok / window_stitch_why / frames_rec_ok /
+// frames_win_ok / window_masked_ok below).
 #include "ragged.h"
+#include "mask_rule.h"
 
 #define RW_THREADS 256
 #define RW_MAX_GRID 1024                // workgroups along a row (they stride over what the grid does not cover)
 #define RW_STITCH_QUADS 4               // quads per thread the stitch grid is sized for
 #define RW_COLS 10                      // int64 per window, the row of pipeline.window_plan
 #define RW_MAX_CONTEXT ((int64_t)1 << 22)   // 2 context + 0.5 is exact in f32
+#define RW_REC_COLS 4                   // int64 per recording of the frame stitch: frame offset in the output, frames, first window, windows
+#define RW_MAX_FRAMES ((int64_t)1 << 31)    // frames of a recording and
+#define RW_MAX_RATIO 1073741824.0           // samples per frame (2^30): a frame centre (i + 0.5) rho stays inside int64
 
 // One window.  rec: the recording (not read here); off: first source sample in the staged buffer; n: samples; out: where the
 // window's first output sample lies in the stitched buffer; cs, ce, start: core start, core end and the window's first sample
@@ -219,4 +236,218 @@ extern "C" int sos_window_stitch_f32(const float* rows, int64_t n_rows, int64_t 
     hipLaunchKernelGGL(window_stitch_kernel, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, rows, n_rows, stride, table,
                        (int64_t)nwin, context, total_out, out);
     return sos_check_launch("sos_window_stitch_f32");
+}
+
+// ---- one logit stream per recording out of the windows' frame logits
+
+struct FrameRec { int64_t foff, F, first, K; };            // frame offset in the output, frames, first window (table index), windows
+__host__ __device__ static inline FrameRec frame_rec(const int64_t* recs, int64_t r) {
+    const int64_t* te = recs + r * RW_REC_COLS;
+    return {te[0], te[1], te[2], te[3]};
+}
+// a recording can be followed: its frames lie inside the summed output, its windows inside the table, its ratio places every
+// frame centre inside int64 (a NaN fails rho > 0)
+__host__ __device__ static inline bool frames_rec_ok(const FrameRec& r, double rho, int64_t nwin, int64_t total_frames) {
+    return ragged_clip_inside(r.foff, r.F, total_frames) && r.F <= RW_MAX_FRAMES && r.first >= 0 && r.K >= 1 && r.K <= nwin &&
+           r.first <= nwin - r.K && rho > 0.0 && rho <= RW_MAX_RATIO;
+}
+// a window can be read: its row exists and holds its `frames` logits
+__host__ __device__ static inline bool frames_win_ok(const WindowRow& e, int64_t frames, int64_t n_rows, int64_t stride) {
+    return e.row >= 0 && e.row < n_rows && frames >= 1 && frames <= stride && window_small(e.start) && window_small(e.cs) &&
+           window_small(e.ce) && e.cs <= e.ce;
+}
+
+// Frame of a window (first sample `start` of the recording, `frames` frames) that holds the centre of the recording's frame
+// i, c = i + 0.5: clamp(floor(c - start / rho), 0, frames - 1).  One rounded divide, one rounded subtract (un-fused).
+__device__ __forceinline__ int64_t frame_in_window(double c, int64_t start, double rho, int64_t frames) {
+    const double j = floor(__dadd_rn(c, -__ddiv_rn((double)start, rho)));
+    return j < 0.0 ? 0 : j > (double)(frames - 1) ? frames - 1 : (int64_t)j;
+}
+
+__global__ __launch_bounds__(RW_THREADS) void window_frames_stitch_kernel(
+    const float* __restrict__ rows, int64_t n_rows, int64_t stride, const int64_t* __restrict__ table,
+    const int64_t* __restrict__ frames, int64_t nwin, const int64_t* __restrict__ recs, const double* __restrict__ ratios,
+    int64_t core, int64_t context, int64_t total_frames, float* __restrict__ out) {
+    const int64_t r = blockIdx.y;
+    const FrameRec rec = frame_rec(recs, r);
+    const double rho = ratios[r];
+    if (core < 1 || !frames_rec_ok(rec, rho, nwin, total_frames)) return;
+    float* dst = out + rec.foff;
+    const double span = (double)(2 * context);
+    for (int64_t i = (int64_t)blockIdx.x * RW_THREADS + threadIdx.x; i < rec.F; i += (int64_t)gridDim.x * RW_THREADS) {
+        const double c = (double)i + 0.5;                       // exact
+        const double p = __dmul_rn(c, rho);                     // the frame's centre, in samples of the recording
+        const int64_t own = (int64_t)p / core, k = own < rec.K - 1 ? own : rec.K - 1;      // frames past the last core belong to the last window
+        const int64_t w = rec.first + k;
+        const WindowRow e = window_row(table, w);
+        const int64_t fe = frames[w];
+        if (!frames_win_ok(e, fe, n_rows, stride)) continue;
+        float v = rows[e.row * stride + frame_in_window(c, e.start, rho, fe)];
+        if (context > 0) {
+            // core >= 2 context: at most one of the two zones holds p
+            const int side = k > 0 && p < (double)(e.cs + context) ? -1 : k < rec.K - 1 && p >= (double)(e.ce - context) ? 1 : 0;
+            if (side) {
+                const WindowRow q = window_row(table, w + side);
+                const int64_t fq = frames[w + side];
+                if (!frames_win_ok(q, fq, n_rows, stride)) continue;
+                const float u = rows[q.row * stride + frame_in_window(c, q.start, rho, fq)];
+                const double b = (double)((side < 0 ? e.cs : e.ce) - context);
+                const float wt = (float)__ddiv_rn(__dadd_rn(p, -b), span);   // float64, rounded once
+                v = side < 0 ? (1.f - wt) * u + wt * v : (1.f - wt) * v + wt * u;
+            }
+        }
+        dst[i] = v;
+    }
+}
+
+extern "C" int sos_window_frames_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table,
+                                            const int64_t* table_host, const int64_t* frames, const int64_t* frames_host, int nwin,
+                                            const int64_t* recs, const int64_t* recs_host, const double* ratios,
+                                            const double* ratios_host, int nrec, int64_t core, int64_t context, float* out,
+                                            sos_stream_t stream) {
+    const char* who = "sos_window_frames_stitch_f32";
+    if (!window_args_ok(who, rows, out, table, table_host, nwin, stride)) return SOS_EINVAL;
+    if (!frames || !frames_host || !recs || !recs_host || !ratios || !ratios_host) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
+    if (nrec < 1 || nrec > RAGGED_MAX_CLIPS || n_rows < 1 || n_rows > INT64_MAX / 8 / stride || core < 1 || context < 0 ||
+        context > RW_MAX_CONTEXT || core < 2 * context) {
+        sos_set_error("%s: bad args (1 .. 65535 recordings, got %d; %lld rows of %lld; core %lld >= 1 and >= twice the context "
+                      "%lld, 0 .. %lld)", who, nrec, (long long)n_rows, (long long)stride, (long long)core, (long long)context,
+                      (long long)RW_MAX_CONTEXT);
+        return SOS_EINVAL;
+    }
+    RaggedSum nf;
+    int bad = ragged_sum_column(recs_host, nrec, RW_REC_COLS, 1, 0, RW_MAX_FRAMES, &nf);
+    if (bad < nrec) {
+        sos_set_error("%s: recording %d has %lld frames (0 .. %lld)", who, bad, (long long)frame_rec(recs_host, bad).F,
+                      (long long)RW_MAX_FRAMES);
+        return SOS_EINVAL;
+    }
+    for (int r = 0; r < nrec; ++r) {
+        const FrameRec rec = frame_rec(recs_host, r);
+        if (!frames_rec_ok(rec, ratios_host[r], nwin, nf.total)) {
+            sos_set_error("%s: recording %d (frames %lld + %lld of %lld, windows %lld + %lld of %d, %g samples per frame) lies "
+                          "outside the output or the table, or has a ratio outside (0, 2^30]", who, r, (long long)rec.foff,
+                          (long long)rec.F, (long long)nf.total, (long long)rec.first, (long long)rec.K, nwin, ratios_host[r]);
+            return SOS_EINVAL;
+        }
+        for (int64_t w = rec.first; w < rec.first + rec.K; ++w) {
+            const WindowRow e = window_row(table_host, w);
+            if (!frames_win_ok(e, frames_host[w], n_rows, stride)) {
+                sos_set_error("%s: window %lld of recording %d names a row outside the rows, or frames outside the stride (row "
+                              "%lld of %lld, frames %lld, stride %lld, start %lld, core %lld .. %lld)", who, (long long)w, r,
+                              (long long)e.row, (long long)n_rows, (long long)frames_host[w], (long long)stride,
+                              (long long)e.start, (long long)e.cs, (long long)e.ce);
+                return SOS_EINVAL;
+            }
+        }
+    }
+    const dim3 grid(ragged_grid(nf.longest, RW_THREADS, RW_MAX_GRID), (unsigned)nrec);
+    hipLaunchKernelGGL(window_frames_stitch_kernel, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, rows, n_rows, stride, table,
+                       frames, (int64_t)nwin, recs, ratios, core, context, nf.total, out);
+    return sos_check_launch(who);
+}
+
+// ---- windows staged with the recording's mask
+
+// window e of recording c (a row of the clip table): inside the stride, inside its recording, and its source offset is that
+// recording's sample `start`
+__host__ __device__ static inline bool window_masked_ok(const WindowRow& e, const RaggedClip& c, int64_t stride) {
+    return e.n >= 0 && e.n <= stride && e.start >= 0 && e.n <= c.n && e.start <= c.n - e.n && e.off >= e.start && e.off - e.start == c.off;
+}
+
+__global__ __launch_bounds__(RW_THREADS) void window_stage_masked_kernel(
+    const float* __restrict__ x, int64_t total, const uint8_t* __restrict__ bits, int64_t total_bits,
+    const int64_t* __restrict__ clips, const double* __restrict__ ratios, int64_t nrec, const int64_t* __restrict__ table,
+    int64_t stride, float* __restrict__ wave, float* __restrict__ masked) {
+    const int64_t w = blockIdx.y;
+    const WindowRow e = window_row(table, w);
+    if (e.rec < 0 || e.rec >= nrec) return;
+    const RaggedClip c = ragged_clip(clips, e.rec);
+    const double ratio = ratios[e.rec];
+    if (!ragged_row_inside(c, total, total_bits) || !(ratio > 1.0) || !window_masked_ok(e, c, stride)) return;
+    const float* src = x + c.off + e.start;
+    const uint8_t* bc = bits + c.foff;
+    float* wrow = wave + w * stride;
+    float* mrow = masked + w * stride;
+    const int64_t n = e.n, g = e.start;                         // sample j of the window is sample g + j of the recording
+    const bool row_vec = (stride & 3) == 0 && ragged_aligned16(wave) && ragged_aligned16(masked), src_vec = ragged_aligned16(src);
+    for (int64_t j0 = ((int64_t)blockIdx.x * RW_THREADS + threadIdx.x) * 4; j0 < stride; j0 += (int64_t)gridDim.x * RW_THREADS * 4) {
+        const bool full = j0 + 4 <= n;
+        float v[4] = {0.f, 0.f, 0.f, 0.f}, m[4] = {0.f, 0.f, 0.f, 0.f};      // zero from the window's end to the stride
+        ragged_load4(src, j0, n, full && src_vec, v);
+        bool one = false;
+        if (full) {
+            // A quad whose samples all have their four left neighbours in the same frame interval [lo, hi) of mask_rule.h: each
+            // lies in an original run of five or more equal values, which is never flipped, so all four take the frame's value --
+            // what mask_sample returns for each of them, from one interval instead of four times three (5.5 % of the kernel's
+            // time on 30 s windows at 30 fps, EXPERIMENTS.md 3.15).
+            const int64_t i = (int64_t)((double)(g + j0) / ratio);
+            if (i < c.frames) {
+                const int64_t lo = frame_edge(i, ratio), hi = (int64_t)__dadd_rn(__dmul_rn((double)(i + 1), ratio), -1.0);
+                if (g + j0 >= lo + 4 && g + j0 + 3 < hi) {
+                    m[0] = m[1] = m[2] = m[3] = bc[i] == 0 ? 1.f : 0.f;
+                    one = true;
+                }
+            }
+        }
+        if (!one) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (j0 + k < n) m[k] = mask_sample(bc, c.frames, ratio, c.n, g + j0 + k);
+        }
+        ragged_store4(wrow, j0, stride, row_vec, v);            // row_vec: the stride is a multiple of four, so j0 + 4 <= stride
+        const float vm[4] = {v[0] * m[0], v[1] * m[1], v[2] * m[2], v[3] * m[3]};
+        ragged_store4(mrow, j0, stride, row_vec, vm);
+    }
+}
+
+extern "C" int sos_window_stage_masked_f32(const float* x, const uint8_t* bits, const int64_t* clips, const int64_t* clips_host,
+                                           const double* ratios, const double* ratios_host, int nrec, const int64_t* table,
+                                           const int64_t* table_host, int nwin, int64_t stride, float* wave, float* masked,
+                                           sos_stream_t stream) {
+    const char* who = "sos_window_stage_masked_f32";
+    if (!window_args_ok(who, x, wave, table, table_host, nwin, stride)) return SOS_EINVAL;
+    if (!bits || !clips || !clips_host || !ratios || !ratios_host || !masked) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
+    if (nrec < 1 || nrec > RAGGED_MAX_CLIPS) {
+        sos_set_error("%s: bad args (1 .. 65535 recordings, got %d)", who, nrec);
+        return SOS_EINVAL;
+    }
+    RaggedSum ns, nf;
+    int bad = std::min(ragged_sum_column(clips_host, nrec, RAGGED_CLIP_COLS, 1, 0, INT64_MAX / 8, &ns),
+                       ragged_sum_column(clips_host, nrec, RAGGED_CLIP_COLS, 3, 0, INT64_MAX / 8, &nf));
+    if (bad < nrec) {
+        const RaggedClip c = ragged_clip(clips_host, bad);
+        sos_set_error("%s: recording %d has %lld samples and %lld frames", who, bad, (long long)c.n, (long long)c.frames);
+        return SOS_EINVAL;
+    }
+    for (int r = 0; r < nrec; ++r) {
+        const RaggedClip c = ragged_clip(clips_host, r);
+        if (!ragged_row_inside(c, ns.total, nf.total)) {
+            sos_set_error("%s: recording %d (samples %lld + %lld, frames %lld + %lld) lies outside the %lld samples / %lld frames "
+                          "of the table", who, r, (long long)c.off, (long long)c.n, (long long)c.foff, (long long)c.frames,
+                          (long long)ns.total, (long long)nf.total);
+            return SOS_EINVAL;
+        }
+        if (!(ratios_host[r] > 1.0)) {
+            sos_set_error("%s: recording %d has ratio %g (samples per frame must exceed 1)", who, r, ratios_host[r]);
+            return SOS_EINVAL;
+        }
+    }
+    for (int w = 0; w < nwin; ++w) {
+        const WindowRow e = window_row(table_host, w);
+        if (e.n > stride) {
+            sos_set_error("%s: window %d has %lld samples (stride %lld)", who, w, (long long)e.n, (long long)stride);
+            return SOS_EINVAL;
+        }
+        if (e.rec < 0 || e.rec >= nrec || !window_masked_ok(e, ragged_clip(clips_host, e.rec), stride)) {
+            sos_set_error("%s: window %d (recording %lld of %d, source offset %lld, start %lld, samples %lld) lies outside its "
+                          "recording, or its source offset is not its start in that recording", who, w, (long long)e.rec, nrec,
+                          (long long)e.off, (long long)e.start, (long long)e.n);
+            return SOS_EINVAL;
+        }
+    }
+    const dim3 grid(ragged_grid((stride + 3) / 4, RW_THREADS, RW_MAX_GRID), (unsigned)nwin);
+    hipLaunchKernelGGL(window_stage_masked_kernel, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, x, ns.total, bits, nf.total,
+                       clips, ratios, (int64_t)nrec, table, stride, wave, masked);
+    return sos_check_launch(who);
 }

@@ -166,6 +166,20 @@ def _detect_groups(net, pending, max_batch, max_columns):
     return items
 
 
+@torch.no_grad()
+def _detect_windows(net, pending, window_seconds, context_seconds, max_batch, max_columns):
+    """detect_files(window_seconds=...): the entries of _detect_groups through pipeline.detect_long -- the recordings in
+    overlapping windows, ONE stitched logit stream per file at the file's own framerate and label length -- and the same one
+    thresholding launch and download of confidences for all of them."""
+    from . import pipeline
+    pairs = pipeline.detect_long(net, [p[5].contiguous() for p in pending], sr=DATA_REQUIRED_SR, fps=[p[1]['framerate'] for p in pending],
+                                 window_seconds=window_seconds, context_seconds=context_seconds, max_batch=max_batch,
+                                 max_columns=max_columns, n_frames=[len(p[4]) for p in pending])
+    _, conf = tools.threshold_bits(torch.cat([lg for lg, _ in pairs]), SIGMOID_THRESHOLD)
+    conf = ragged.split(conf.cpu().numpy(), [len(p[4]) for p in pending])
+    return [_detect_item(*p[:5], (c >= np.float32(SIGMOID_THRESHOLD)).astype(np.uint8), c) for p, c in zip(pending, conf)]
+
+
 def _mix_pending(pending, mixes, noises, snr, max_bytes):
     """detect_files(batch_mix=True): the recordings of `pending` silenced on their labelled silent intervals and mixed with
     their noise crops on the device, one tools.add_signals_ragged call per group of files of at most max_bytes of samples.
@@ -184,7 +198,8 @@ def _mix_pending(pending, mixes, noises, snr, max_bytes):
 
 
 def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noise_files=None, snr=None, seed=0,
-                 batch_files=False, max_batch=64, max_columns=65536, batch_mix=False, max_mix_bytes=1 << 30):
+                 batch_files=False, max_batch=64, max_columns=65536, batch_mix=False, max_mix_bytes=1 << 30,
+                 window_seconds=None, context_seconds=2.0):
     """Whole-file silent-interval detection of every file of a dataset JSON (`evaluate`, M1/predict.py:38-233 with
     the prediction-phase items of M1/tools.py:297-332 and M1/dataset.py:226-252): one item per file, the whole
     recording at 14 kHz -> STFT -> net(s, v_num_frames=len(bits)) -> sigmoid -> >= 0.5.  Returns the stat dict and
@@ -203,7 +218,14 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     same seeded generator, so the same noise files and JSON in noise<suffix>/ byte for byte -- but every distinct noise file is
     decoded once and the recordings are silenced and mixed on the device by one tools.add_signals_ragged call per group of
     files (groups of at most max_mix_bytes of samples); recordings and mixes never visit the host.  The mixes may differ
-    from the per-file kernel's in the last bit."""
+    from the per-file kernel's in the last bit.
+    window_seconds (with batch_files=True; ValueError otherwise): recordings of any length.  The recordings (after the optional
+    mixing) go through pipeline.detect_long in overlapping windows of `window_seconds` cores and `context_seconds` more on each
+    inner side, at each file's own `framerate` and with as many decisions as its label holds; `confidence` and `pred_label`
+    come from the stitched logits.  Memory follows max_columns, not the longest file, and the 4 GB image limit of a whole-file
+    detector pass is gone.  A file shorter than two cores is one window: the same JSON as batch_files=True alone."""
+    if window_seconds is not None and not batch_files:
+        raise ValueError("window_seconds applies to batch_files=True")
     with open(dataset_json, 'r') as fp:
         ds = json.load(fp)
     net.eval()
@@ -275,7 +297,8 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     if pending and batch_mix:
         pending = _mix_pending(pending, mixes, decoded, snr, max_mix_bytes)
     if pending:
-        stat = _detect_groups(net, pending, max_batch, max_columns)
+        stat = (_detect_groups(net, pending, max_batch, max_columns) if window_seconds is None else
+                _detect_windows(net, pending, window_seconds, context_seconds, max_batch, max_columns))
     stat_dict = OrderedDict([
         ('data_total_frames', CLIP_FRAMES), ('data_center_frames', SILENT_CONSECUTIVE_FRAMES),
         ('sigmoid_threshold', SIGMOID_THRESHOLD), ('snr', snr if clean_audio else None),

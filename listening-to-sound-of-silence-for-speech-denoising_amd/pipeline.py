@@ -339,9 +339,103 @@ def window_plan(ns, core, context):
     return np.asarray(rows, dtype=np.int64).reshape(-1, tools.WINDOW_COLS)
 
 
+def _long_plan(who, clips, sr, window_seconds, context_seconds):
+    """What detect_long and denoise_long share before their first launch: (core, context, ns, plan) of 1-D `clips`."""
+    for c in clips:
+        if c.dim() != 1:
+            raise ValueError(f"{who} expects 1-D waveforms")
+    core, context = _hops(round(window_seconds * sr)), _hops(round(context_seconds * sr))
+    ns = [int(c.numel()) for c in clips]
+    plan = window_plan(ns, core, context)
+    if len(plan) > ragged.MAX_CLIPS:
+        raise ValueError(f"{who}: {len(plan)} windows in one call (at most {ragged.MAX_CLIPS}): longer windows, or fewer recordings")
+    return core, context, ns, plan
+
+
+def _window_frames(plan, sr, rates, frames):
+    """Frame decisions per window of a plan: F_k = max(1, n_video_frames(samples_k, sr, fps of its recording)); a recording of
+    ONE window is that clip itself and carries the recording's own count (`frames`, one per recording)."""
+    first = _first_windows(plan, len(frames))
+    wf = [max(1, n_video_frames(int(m), sr, rates[int(r)])) for r, m in zip(plan[:, 0], plan[:, 2])]
+    for r, F in enumerate(frames):
+        if first[r + 1] - first[r] == 1:
+            wf[first[r]] = max(1, int(F))
+    return wf
+
+
+def _first_windows(plan, n_recordings):
+    """Index of each recording's first window in a plan (and the number of windows at the end)."""
+    import numpy as np
+    return np.searchsorted(plan[:, 0], np.arange(n_recordings + 1))
+
+
+def _stitch_frames(kept, plan, wf, frames, sr, rates, core, context):
+    """The windows' logits (`kept`: one row per window, plan[:, 7] says which) -> (logits, bits) of the recordings back to back:
+    one sos_window_frames_stitch_f32 launch and one thresholding launch."""
+    import numpy as np
+    first = _first_windows(plan, len(frames))
+    recs = np.stack([ragged.offsets(frames), np.asarray(frames, dtype=np.int64), first[:-1], np.diff(first)], axis=1)
+    logits = tools.window_frames_stitch(kept, plan, wf, recs, [float(sr) / float(f) for f in rates], core, context)
+    return logits, tools.threshold_bits(logits, SIGMOID_THRESHOLD)[0]
+
+
+def _recording_frames(n_frames, ns, sr, rates):
+    if n_frames is None:
+        return [n_video_frames(n, sr, f) for n, f in zip(ns, rates)]
+    if len(n_frames) != len(ns) or min(int(F) for F in n_frames) < 0:
+        raise ValueError("n_frames must hold one non-negative number of frame decisions per recording")
+    return [int(F) for F in n_frames]
+
+
+@torch.no_grad()
+def detect_long(detector, clips, sr=SR, fps=FPS, window_seconds=30.0, context_seconds=2.0, max_batch=256, max_columns=65536,
+                n_frames=None, return_all=False):
+    """The detector half of denoise_long: ONE stream of frame decisions per recording of any length.  `clips` are cut, staged
+    and grouped exactly as denoise_long does it (window_plan, one sos_window_stage_f32 launch, one STFT and one detect() call
+    with per-window frame counts per group); every group's logits are kept in one (windows, most frames of a window) buffer,
+    and after the last group ONE sos_window_frames_stitch_f32 launch places every frame of a recording by its centre -- the
+    window whose core holds it gives the frame of its own grid that holds it, blended with the neighbour's within
+    `context_seconds` of an inner core boundary (the rule: csrc/ragged_window.hip; float64: tests/frames_reference.py) -- and
+    one tools.threshold_bits launch decides.  Nothing goes to the host between the groups.
+    fps: a scalar or one value per recording.  n_frames: the recordings' numbers of decisions (a file's label is not always
+    n_video_frames(samples, sr, fps) long); default n_video_frames.  A recording shorter than two cores is one window with
+    exactly these frames: denoise_ragged's clip, logits and bits bit for bit.
+    -> [(logits f32 (F,), bits uint8 (F,)) per recording], views of one buffer each, in input order; return_all adds per
+    recording dict(plan=its window_plan rows (row = the order the windows ran in), windows=[logits per window]).
+    ValueError before any launch as denoise_long."""
+    import numpy as np
+    clips = list(clips)
+    if not clips:
+        return ([], []) if return_all else []
+    core, context, ns, plan = _long_plan("detect_long", clips, sr, window_seconds, context_seconds)
+    rates = ragged.per_clip(fps, len(clips), "fps")
+    frames = _recording_frames(n_frames, ns, sr, rates)
+    wf = _window_frames(plan, sr, rates, frames)
+    flat, _ = ragged.concat(clips)
+    device = flat.device
+    ms, W = plan[:, 2].tolist(), len(plan)
+    kept = torch.empty((W, max(wf)), dtype=torch.float32, device=device)
+    done = 0
+    for part in _length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
+        m, nv = [ms[i] for i in part], [wf[i] for i in part]
+        wave = tools.window_stage(flat, np.ascontiguousarray(plan[part]), max(m))
+        rag = _group_geometry(m, device, sr, FPS, nv=nv)
+        logits = detect(detector, transform.stft_batch(wave, clip_samples=rag.tab(rag.n_samples)), max(nv), rag=rag)
+        kept[done:done + len(part), :logits.shape[1]] = logits
+        plan[part, 7] = np.arange(done, done + len(part))
+        done += len(part)
+    logits, bits = _stitch_frames(kept, plan, wf, frames, sr, rates, core, context)
+    pairs = list(zip(ragged.split(logits, frames), ragged.split(bits, frames)))
+    if not return_all:
+        return pairs
+    first = _first_windows(plan, len(clips))
+    return pairs, [dict(plan=plan[first[r]:first[r + 1]], windows=[kept[plan[w, 7], :wf[w]] for w in range(first[r], first[r + 1])])
+                   for r in range(len(clips))]
+
+
 @torch.no_grad()
 def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0, context_seconds=2.0, max_batch=256,
-                 max_columns=65536, bits=None, return_all=False):
+                 max_columns=65536, bits=None, return_all=False, stitch_bits=False):
     """Recordings of ANY length, minutes and hours included: `clips` = list of 1-D f32 GPU waveforms, short and long mixed.
     denoise_ragged runs a recording as one clip, which ends at sos_conv2d_fwd's 4 GB image (about 16 minutes at 14 kHz), needs
     ~0.5 MB of activations per STFT column and steps both BiLSTMs serially through the whole file.  Here every recording is cut
@@ -359,31 +453,42 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
     (one buffer of windows x longest window, 4 bytes per output sample and overlap) and stitched ONCE after the last group, in
     one launch.  Nothing goes to the host between the groups.
     `bits` (one 1-D uint8 array or GPU tensor per recording, 1 = non-silent; `fps` a scalar or one value per recording;
-    `detector` may be None): the first model's decisions as in denoise_ragged.  The noise-interval signal of each recording is
-    made once at full length with the mask rule (tools.ragged_stage: padded rows, recordings x longest recording) and windowed
-    by the same stage kernel, so a sample's mask does not depend on the window it lands in.
+    `detector` may be None): the first model's decisions as in denoise_ragged.  Every group is staged by ONE
+    sos_window_stage_masked_f32 launch, which evaluates the mask rule in the RECORDING's coordinates (its frames, its ratio, its
+    last sample): a sample's mask does not depend on the window it lands in, the rows are bit for bit slices of
+    tools.ragged_stage's full-length ones, and nothing of a recording's full length is allocated.
+    stitch_bits=True: the decisions are the detector's, but ONE stream per recording -- detect_long first, then the `bits` path
+    on its device-resident bits, bit for bit denoise_long(None, denoiser, clips, bits=<detect_long's bits>, fps=fps) -- where
+    the default silences each window by that window's own detector pass, so that the two windows cross-faded around a core
+    boundary may have been denoised with different noise intervals there.  `fps` may then be one value per recording.
     Outputs come back in input order, each hop * (n // hop) samples long, views into one buffer.  return_all adds per recording
-    dict(plan=its window_plan rows (row = the order the windows ran in), windows=[dict(logits, bits) per window]), or with
-    `bits` dict(plan, bits, mask=the sample mask at full length).
-    ValueError before any launch: window_plan's (a recording below MIN_FRAMES frames is named), more than 65535 windows."""
+    dict(plan=its window_plan rows (row = the order the windows ran in), windows=[dict(logits, bits) per window], logits, bits=
+    the recording's stitched stream as detect_long makes it, one more small launch); with `bits` dict(plan, bits, mask=the
+    sample mask at full length, made only here); with stitch_bits dict(plan, logits, bits, mask).
+    ValueError before any launch: window_plan's (a recording below MIN_FRAMES frames is named), more than 65535 windows,
+    stitch_bits together with bits."""
     import numpy as np
     clips = list(clips)
-    for c in clips:
-        if c.dim() != 1:
-            raise ValueError("denoise_long expects 1-D waveforms")
-    if bits is None and not isinstance(fps, (int, float)):
-        raise ValueError("one fps per recording needs the recordings' frame decisions (bits=): the detector's groups share one rate")
+    if stitch_bits and bits is not None:
+        raise ValueError("stitch_bits=True takes the decisions from the detector: it cannot be combined with bits=")
+    if bits is None and not stitch_bits and not isinstance(fps, (int, float)):
+        raise ValueError("one fps per recording needs the recordings' frame decisions (bits=, or stitch_bits=True): the "
+                         "detector's groups share one rate")
     if bits is not None and len(bits) != len(clips):
         raise ValueError("bits must hold one array of frame decisions per recording")
     if not clips:
         return ([], []) if return_all else []
+    if stitch_bits:                                             # detect_long refuses what _long_plan refuses, before any launch
+        pairs = detect_long(detector, clips, sr, fps, window_seconds, context_seconds, max_batch, max_columns)
+        res = denoise_long(None, denoiser, clips, sr, fps, window_seconds, context_seconds, max_batch, max_columns,
+                           bits=[b for _, b in pairs], return_all=return_all)
+        if return_all:
+            for e, (lg, _) in zip(res[1], pairs):
+                e["logits"] = lg
+        return res
+    core, context, ns, plan = _long_plan("denoise_long", clips, sr, window_seconds, context_seconds)
     hop = transform.HOP_LENGTH
-    context = _hops(round(context_seconds * sr))
-    ns = [int(c.numel()) for c in clips]
-    plan = window_plan(ns, round(window_seconds * sr), context)
     W = len(plan)
-    if W > ragged.MAX_CLIPS:
-        raise ValueError(f"denoise_long: {W} windows in one call (at most {ragged.MAX_CLIPS}): longer windows, or fewer recordings")
     flat, _ = ragged.concat(clips)
     device = flat.device
     ms = plan[:, 2].tolist()
@@ -397,25 +502,29 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
             d_bits = torch.cat([b.to(device) for b in bits])
         else:                                                                            # host arrays: one upload
             d_bits = torch.from_numpy(np.concatenate([b.cpu().numpy() if torch.is_tensor(b) else b for b in bits])).to(device)
-        _, noise_rows, mask = tools.ragged_stage(flat, ragged.clip_table(ns, nb), max(ns), d_bits, [float(sr) / float(f) for f in rates])
-        noise_src = plan.copy()                                                          # the same windows of the padded rows
-        noise_src[:, 1] = plan[:, 0] * max(ns) + plan[:, 6]
+        rec_table, ratios = ragged.clip_table(ns, nb), [float(sr) / float(f) for f in rates]
         fps_w = rates[plan[:, 0]]
+    elif return_all:
+        frames = [n_video_frames(n, sr, fps) for n in ns]
+        wf = _window_frames(plan, sr, [fps] * len(clips), frames)
+        kept_logits = torch.empty((W, max(wf)), dtype=torch.float32, device=device)
     kept = torch.empty((W, hop * (max(ms) // hop)), dtype=torch.float32, device=device)
     seen, done = [None] * W, 0
     for part in _length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
         m = [ms[i] for i in part]
         sub = np.ascontiguousarray(plan[part])
-        wave = tools.window_stage(flat, sub, max(m))
         if bits is None:
+            wave = tools.window_stage(flat, sub, max(m))
             rag = _group_geometry(m, device, sr, fps)
             y, logits, wbits = _denoise_group_padded(detector, denoiser, wave, rag, sr, fps)
             if return_all:
+                kept_logits[done:done + len(part), :logits.shape[1]] = logits
                 for k, i in enumerate(part):
                     seen[i] = dict(logits=logits[k, :rag.n_vframes[k]], bits=wbits[k, :rag.n_vframes[k]])
         else:
             rag = _group_geometry(m, device, sr, FPS, nv=[max(1, n_video_frames(ms[i], sr, fps_w[i])) for i in part])
-            y = _denoise_group_staged(denoiser, wave, tools.window_stage(noise_rows.view(-1), np.ascontiguousarray(noise_src[part]), max(m)), rag)
+            wave, masked = tools.window_stage_masked(flat, d_bits, rec_table, ratios, sub, max(m))
+            y = _denoise_group_staged(denoiser, wave, masked, rag)
         kept[done:done + len(part), :y.shape[1]] = y
         plan[part, 7] = np.arange(done, done + len(part))
         done += len(part)
@@ -424,14 +533,15 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
     outs = ragged.split(tools.window_stitch(kept, rows, context), [hop * (n // hop) for n in ns])
     if not return_all:
         return outs
-    first = np.searchsorted(plan[:, 0], np.arange(len(clips) + 1))
+    first = _first_windows(plan, len(clips))
     extra = [dict(plan=plan[first[r]:first[r + 1]]) for r in range(len(clips))]
     if bits is None:
-        for r, e in enumerate(extra):
-            e["windows"] = seen[first[r]:first[r + 1]]
+        logits, sbits = _stitch_frames(kept_logits, plan, wf, frames, sr, [fps] * len(clips), core, context)
+        for r, (e, lg, b) in enumerate(zip(extra, ragged.split(logits, frames), ragged.split(sbits, frames))):
+            e["windows"], e["logits"], e["bits"] = seen[first[r]:first[r + 1]], lg, b
     else:
-        for e, b, m in zip(extra, ragged.split(d_bits, nb), ragged.split(mask, ns)):
-            e["bits"], e["mask"] = b, m
+        for e, b, n, ratio in zip(extra, ragged.split(d_bits, nb), ns, ratios):
+            e["bits"], e["mask"] = b, tools.bits_to_mask_batch(b[None], ratio, n)[0]     # the whole recording's, made only here
     return outs, extra
 
 

@@ -120,6 +120,58 @@ def window_stitch(rows, table, context):
     return out
 
 
+def window_frames_stitch(rows, table, win_frames, recs, ratios, core, context):
+    """The windows' frame logits stitched into ONE logit stream per recording in one launch (sos_window_frames_stitch_f32; the
+    rule and its float64 restatement: tests/frames_reference.py).  rows: contiguous f32 (R, stride) GPU tensor, a window's
+    logits from column 0; table: host rows of pipeline.window_plan, of which {core start, core end, window start, row} are
+    read; win_frames: the windows' numbers of logits; recs: host rows {frame offset in the output, frames, first window,
+    windows}, one per recording; ratios: samples per frame, one value or one per recording; core, context: samples.
+    -> one 1-D f32 GPU tensor, the recordings' logits back to back (sum of their frames)."""
+    L.require_cuda(rows)
+    tab, rec = _host_table(table, WINDOW_COLS), _host_table(recs, 4)
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
+    fr = np.ascontiguousarray(np.asarray(win_frames, dtype=np.int64).reshape(-1))
+    if len(fr) != tab.shape[0]:
+        raise ValueError("win_frames must hold one count per window of the table")
+    rat = ragged.per_clip(ratios, rec.shape[0], "ratios")
+    out = torch.empty(max(int(rec[:, 1].sum()), 0), dtype=torch.float32, device=rows.device)
+    d_tab, d_fr, d_rec, d_rat = (_upload(a, rows.device) for a in (tab, fr, rec, rat))
+    L.check(L.lib().sos_window_frames_stitch_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data,
+                                                 L.ptr(d_fr), fr.ctypes.data, tab.shape[0], L.ptr(d_rec), rec.ctypes.data,
+                                                 L.ptr(d_rat), rat.ctypes.data, rec.shape[0], int(core), int(context), L.ptr(out),
+                                                 L.stream_ptr()), "sos_window_frames_stitch_f32")
+    return out
+
+
+def window_stage_masked(flat, bits, clips, ratios, table, stride):
+    """Windows of recordings staged together with their noise intervals in one launch (sos_window_stage_masked_f32).  flat: the
+    recordings back to back, contiguous 1-D f32 GPU tensor; bits: their frame decisions back to back (uint8 GPU tensor, 1 =
+    non-silent); clips: host rows {sample offset, samples, bit offset, frames}, one per recording, and ratios: samples per
+    frame, one value or one per recording -- what ragged_stage takes; table: host rows of pipeline.window_plan, of which
+    {recording, source offset, samples, window start} are read.
+    -> (wave, masked), each (windows, stride): the window zero-filled to the stride, and window * mask likewise, the mask being
+    the WHOLE recording's (ragged_stage's `mask` at the window's samples): bit for bit slices of ragged_stage's full-length
+    rows, which are never made."""
+    L.require_cuda(flat, bits)
+    tab, clip = _host_table(table, WINDOW_COLS), _host_table(clips, 4)
+    if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("flat must be a contiguous 1-D float32 tensor")
+    if flat.numel() < int(clip[:, 1].sum()):
+        raise ValueError("the table names more samples than `flat` holds")
+    if bits.dim() != 1 or bits.dtype != torch.uint8 or not bits.is_contiguous() or bits.numel() < int(clip[:, 3].sum()):
+        raise ValueError("bits must be a contiguous 1-D uint8 tensor holding every frame of the table")
+    rat = ragged.per_clip(ratios, clip.shape[0], "ratios")
+    wave = torch.empty((tab.shape[0], int(stride)), dtype=torch.float32, device=flat.device)
+    masked = torch.empty_like(wave)
+    d_tab, d_clip, d_rat = (_upload(a, flat.device) for a in (tab, clip, rat))
+    L.check(L.lib().sos_window_stage_masked_f32(L.ptr(flat), L.ptr(bits), L.ptr(d_clip), clip.ctypes.data, L.ptr(d_rat),
+                                                rat.ctypes.data, clip.shape[0], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
+                                                int(stride), L.ptr(wave), L.ptr(masked), L.stream_ptr()),
+            "sos_window_stage_masked_f32")
+    return wave, masked
+
+
 def convert_bitstreammask_to_audiomask(ref_audio_signal, frames_to_audiosample_ratio, bitstream):
     """M2/tools.py:340-362 (string bits) / M1/tools.py:770-792 (int bits): same arguments, same
     RuntimeError on an invalid bit, same dtype as `ref_audio_signal`."""

@@ -4,7 +4,13 @@ several window lengths, in fp16, timed with HIP events around whole calls, peak 
 kernels alone (sos_window_stage_f32, sos_window_stitch_f32) on the recording's 30 s plan, as a rate over the bytes they move,
 next to a float4 copy (torch's copy kernel) of the same number of bytes.  --distance: how far the windowed result is from the
 whole-file result on a 60 s recording with the closed-form test networks in bf16x3 -- a characterisation of random-weight
-networks, nothing is asserted on it.  One line per configuration."""
+networks, nothing is asserted on it.  One line per configuration.
+--decisions: denoise_long(stitch_bits=True) -- one detector pass over all windows, one decision stream per recording, then the
+`bits=` path -- next to the default on the same recording; the `bits=` path on a mixed batch (the recording plus 63 recordings
+of 2 s) with time and peak memory; and the two kernels of that path alone (sos_window_stage_masked_f32,
+sos_window_frames_stitch_f32) as a rate next to a float4 copy of the same bytes.  --root CHECKOUT runs this script's lines on
+another checkout of the repository (its package and its built libraries), e.g. the parent commit for the `bits=` line:
+    python tools/long_bench.py --no-speed --decisions --root ../parent"""
 import argparse
 import os
 import sys
@@ -13,6 +19,8 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--root" in sys.argv[1:-1]:
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
 sys.path.insert(0, ROOT)
 import sos_amd  # noqa: E402
 from oracle import nets as onet  # noqa: E402
@@ -98,6 +106,73 @@ def speed(args, det, jm):
               f"({nbytes / (ms_copy / 1e3) / 1e12:.3f} TB/s)")
 
 
+def decisions(args, det, jm):
+    n = int(args.seconds * SR)
+    clip = _wave(800, n)
+    shorts = [_wave(801 + i, 2 * SR) for i in range(63)]
+    rng = np.random.default_rng(14)
+    mixed = [clip] + shorts
+    bits = [torch.from_numpy(rng.integers(0, 2, pipeline.n_video_frames(c.numel())).astype(np.uint8)).cuda() for c in mixed]
+    new = hasattr(pipeline, "detect_long")
+    kw = dict(window_seconds=30.0, context_seconds=args.context)
+    sos_amd.set_precision(args.precision)
+    try:
+        if new and not args.kernels_only:
+            for name, fn in (("default (each window silenced by its own detector pass)", lambda: pipeline.denoise_long(det, jm, [clip], **kw)),
+                             ("stitch_bits=True (one decision stream per recording)", lambda: pipeline.denoise_long(det, jm, [clip], stitch_bits=True, **kw)),
+                             ("detect_long alone", lambda: pipeline.detect_long(det, [clip], **kw))):
+                ms, peak = _timed(fn, args.iters)
+                print(f"{args.seconds:g} s at {SR} Hz, {args.precision}, 30 s windows: {name} {ms:9.1f} ms per call, peak {peak / 2**30:6.2f} GiB")
+        if not args.kernels_only:
+            for name, cl, bt in (("the recording alone", [clip], bits[:1]), ("the recording + 63 recordings of 2 s", mixed, bits)):
+                ms, peak = _timed(lambda: pipeline.denoise_long(None, jm, cl, bits=bt, fps=30.0, **kw), args.iters)
+                print(f"{args.seconds:g} s at {SR} Hz, {args.precision}, 30 s windows: bits= path, {name} {ms:9.1f} ms per call, "
+                      f"peak {peak / 2**30:6.2f} GiB (inputs resident: {sum(c.numel() for c in cl) * 4 / 2**30:.3f} GiB)")
+    finally:
+        sos_amd.set_precision("bf16")
+    if not new:
+        return
+    # the two kernels alone, on resident buffers: the mixed batch's plan
+    from sos_amd import ragged
+    ns = [int(c.numel()) for c in mixed]
+    core, context = pipeline._hops(round(30.0 * SR)), pipeline._hops(round(args.context * SR))
+    plan = np.ascontiguousarray(pipeline.window_plan(ns, core, context))
+    stride, W = int(plan[:, 2].max()), len(plan)
+    flat, d_bits = torch.cat(mixed), torch.cat(bits)
+    clips = ragged.clip_table(ns, [len(b) for b in bits])
+    rat = np.full(len(ns), SR / 30.0)
+    wave, masked = tools.window_stage_masked(flat, d_bits, clips, rat, plan, stride)
+    d_plan, d_clips, d_rat = torch.from_numpy(plan).cuda(), torch.from_numpy(clips).cuda(), torch.from_numpy(rat).cuda()
+    lib = L.lib()
+    ms_masked, _ = _timed(lambda: L.check(lib.sos_window_stage_masked_f32(L.ptr(flat), L.ptr(d_bits), L.ptr(d_clips), clips.ctypes.data,
+                                                                          L.ptr(d_rat), rat.ctypes.data, len(ns), L.ptr(d_plan),
+                                                                          plan.ctypes.data, W, stride, L.ptr(wave), L.ptr(masked),
+                                                                          L.stream_ptr())), 200)
+    ms_plain, _ = _timed(lambda: L.check(lib.sos_window_stage_f32(L.ptr(flat), flat.numel(), L.ptr(d_plan), plan.ctypes.data, W, stride,
+                                                                  L.ptr(wave), L.stream_ptr())), 200)
+    frames = [len(b) for b in bits]
+    rates = [30.0] * len(ns)
+    wf = np.asarray(pipeline._window_frames(plan, SR, rates, frames), dtype=np.int64)
+    first = pipeline._first_windows(plan, len(ns))
+    recs = np.ascontiguousarray(np.stack([ragged.offsets(frames), np.asarray(frames, dtype=np.int64), first[:-1], np.diff(first)], axis=1))
+    logit_rows = torch.randn((W, int(wf.max())), device="cuda")
+    out = tools.window_frames_stitch(logit_rows, plan, wf, recs, rat, core, context)
+    d_wf, d_recs = torch.from_numpy(wf).cuda(), torch.from_numpy(recs).cuda()
+    ms_frames, _ = _timed(lambda: L.check(lib.sos_window_frames_stitch_f32(L.ptr(logit_rows), W, logit_rows.shape[1], L.ptr(d_plan),
+                                                                           plan.ctypes.data, L.ptr(d_wf), wf.ctypes.data, W,
+                                                                           L.ptr(d_recs), recs.ctypes.data, L.ptr(d_rat), rat.ctypes.data,
+                                                                           len(ns), core, context, L.ptr(out), L.stream_ptr())), 200)
+    for name, ms, floats in (("sos_window_stage_masked_f32", ms_masked, int(plan[:, 2].sum()) + 2 * wave.numel()),
+                             ("sos_window_stage_f32 (the same windows, wave rows only)", ms_plain, int(plan[:, 2].sum()) + wave.numel()),
+                             ("sos_window_frames_stitch_f32", ms_frames, 2 * out.numel())):
+        src, dst = torch.empty(max(floats // 2, 1), device="cuda"), torch.empty(max(floats // 2, 1), device="cuda")
+        ms_copy, _ = _timed(lambda: dst.copy_(src), 200)
+        nbytes = 4.0 * floats
+        print(f"{name} ({W} windows of {len(ns)} recordings, resident buffers): {ms * 1e3:8.1f} us, {nbytes / 1e6:.2f} MB at "
+              f"{nbytes / (ms / 1e3) / 1e12:.3f} TB/s; a float4 copy of the same bytes {ms_copy * 1e3:8.1f} us "
+              f"({nbytes / (ms_copy / 1e3) / 1e12:.3f} TB/s)")
+
+
 def distance(args, det, jm):
     n = 60 * SR
     clip = _wave(810, n)
@@ -129,6 +204,9 @@ def main():
     ap.add_argument("--distance", action="store_true", help="also report the distance from the whole-file result (60 s, bf16x3)")
     ap.add_argument("--distance-windows", type=float, nargs="*", default=[10.0, 30.0])
     ap.add_argument("--no-speed", action="store_true")
+    ap.add_argument("--decisions", action="store_true", help="stitch_bits=True, the bits= path on a mixed batch, the two kernels alone")
+    ap.add_argument("--kernels-only", action="store_true", help="with --decisions: only the kernels' lines")
+    ap.add_argument("--root", default=None, help="measure another checkout of the repository (package and built libraries)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("long_bench needs an MI355X: nothing is measured without one")
@@ -136,6 +214,8 @@ def main():
     with torch.no_grad():
         if not args.no_speed:
             speed(args, det, jm)
+        if args.decisions:
+            decisions(args, det, jm)
         if args.distance:
             distance(args, det, jm)
 
