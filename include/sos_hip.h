@@ -220,7 +220,9 @@ typedef struct sos_conv_desc {
      * its batch-statistics scale / shift: every value read becomes max(x * in_scale[c] + in_shift[c], 0), rounded to the storage
      * type exactly as sos_bn_act_apply would have stored it, while the patch is staged; zero padding stays zero.  The separate
      * apply pass and the activated tensor are then not needed by this consumer.  One 16-bit channel segment, no temporal taps;
-     * built for the 96-channel context layers' tilings (EINVAL otherwise: the caller falls back to the materialised tensor). */
+     * built for the 96-channel context layers' tilings -- three n-tiles, 2 or 3 k-steps, patches of at most 64 staging instructions
+     * (768 / 576 pixels): other tilings are not offered to such a descriptor (EINVAL if none is left: the caller falls back to the
+     * materialised tensor). */
     const float* in_scale;
     const float* in_shift;
 } sos_conv_desc;

@@ -1861,6 +1861,8 @@ static const char* plan(const sos_conv_desc* d, const ConvCfg& c, ConvPlan* out)
     if (c.NC < 1 || TH < 1 || TW < 1 || c.NC * TH * TW > v.slots) return "the pixel tile does not fit the workgroup";
     if (v.row16 ? !v.nt : (v.ks < 1 || d->cin % (16 * v.ks))) return "no kernel takes this shape with these k-steps";
     const bool x3 = d->out_dtype == SOS_DT_BF16X3, staged = d->out_dtype != SOS_DT_F32 && d->out_sc == 1;
+    // (tests/conv_pin.py runs_as_pinned() mirrors the two refusals below -- a three-per-CU entry that is refused runs as its plain twin,
+    // which no caller can tell apart: keep the mirror in step)
     // the TIGHT epilogue (W3) and the 384-slot tiles store one 16-bit plane of whole 8-channel pieces; the 384-slot tiles'
     // statistics scratch lies over the staged tile, which the general store path (partial pieces) does not allow for
     const bool dense16 = d->out_dtype == SOS_DT_BF16 && d->out_sc == 1 && nseg_eff(d) == 1 && d->cout_store % 8 == 0;
@@ -1880,6 +1882,10 @@ static const char* plan(const sos_conv_desc* d, const ConvCfg& c, ConvPlan* out)
             inst = &i;
     if (!inst) return d->in_scale ? "fused input BatchNorm (in_scale) is built for three n-tiles, 2 or 3 k-steps, two slab buffers only"
                                   : "no kernel instance is built for this tiling";
+    // stage_issue_bn moves only the 64 staging instructions stage_prepare resolves per tile (64 / (2 ks + 1) pixels each); it has no
+    // tail pass like stage_issue's stage_patch_dma, so the end of a larger patch would reach the MFMAs unstaged
+    if (d->in_scale && (npix + 64 / (2 * v.ks + 1) - 1) / (64 / (2 * v.ks + 1)) > 64)
+        return "fused input BatchNorm (in_scale) stages patches of at most 64 instructions (768 / 576 pixels at 2 / 3 k-steps)";
     // LDS: the tap loop's, or the epilogue's staged output tile (+ pixel offsets + statistics scratch) if that is more
     size_t lds = loop_lds(npix, v);
     if (v.row16 || staged) {

@@ -1,4 +1,5 @@
-"""Correctness of EVERY candidate conv tiling (SOS_CONV_FORCE_CFG) vs torch, several shapes."""
+"""Correctness of EVERY candidate conv tiling (SOS_CONV_FORCE_CFG) vs torch, several shapes.
+Superseded: tests/test_gpu_conv_tilings.py pins every instance and tile geometry in-process and compares with float64 exactly."""
 import sys, os, subprocess
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if len(sys.argv) > 1 and sys.argv[1] == "child":
