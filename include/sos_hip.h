@@ -677,6 +677,27 @@ int sos_window_stage_f32(const float* x, int64_t total, const int64_t* table, co
 int sos_window_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
                           int nwin, int64_t context, float* out, sos_stream_t stream);
 
+/* ---- several signals of the same plan stitched in ONE launch, written where a download wants them (csrc/ragged_window.hip;
+ * the four signals of sos_amd.pipeline.denoise_long(signals=True) and of the windowed hand-off).
+ * sos_window_stitch_planes_f32: rows f32 [planes][n_rows][stride], planes 1 .. 8: plane q of window w is row q * n_rows + row.
+ *   table / table_host: the plan table above, unchanged; column 0 (the recording) is read here, to find the destination, and
+ *   column 3 is validated exactly as sos_window_stitch_f32 validates it, so one plan serves both calls.  recs / recs_host:
+ *   int64 [nrec][2] = {base, pitch}: sample p of plane q of recording r -- p counts within the recording's own output,
+ *   0 .. len_r, len_r = the sum of its cores -- goes to out[base_r + q * pitch_r + p]; out holds out_total floats.
+ *   base = the recording's output offset and pitch = out_total / planes is the plane-major layout [planes][sum len]; base = where
+ *   the recording's block starts and pitch >= len_r puts the planes of one recording next to each other (file-major).
+ *   pitch > len_r leaves a gap that is never written (it keeps a segment's start a multiple of four floats: 16-byte stores).
+ *   Each plane holds, bit for bit, what sos_window_stitch_f32 writes for that plane alone: the same one-writer-per-core rule,
+ *   weights and blend (one __device__ function serves both kernels); no atomics; a result does not depend on the batch, the
+ *   table order, the row order or the destination's alignment.
+ * SOS_EINVAL (sos_last_error() names the window or the recording), before any launch: everything sos_window_stitch_f32
+ * refuses, planes outside 1 .. 8, nrec outside 1 .. 65535, out_total < 0, a window whose recording is outside nrec or whose core
+ * ends past its recording's len_r, neighbours of different recordings, pitch < len_r, a (recording, plane) segment outside
+ * out_total, two segments that overlap.  The kernel follows the DEVICE tables and skips a window that fails the same tests. */
+int sos_window_stitch_planes_f32(const float* rows, int planes, int64_t n_rows, int64_t stride, const int64_t* table,
+                                 const int64_t* table_host, int nwin, int64_t context, const int64_t* recs,
+                                 const int64_t* recs_host, int nrec, int64_t out_total, float* out, sos_stream_t stream);
+
 /* ---- one decision stream per recording, and windows masked by it (csrc/ragged_window.hip; sos_amd.pipeline.detect_long and the
  * `bits=` path of denoise_long; float64 restatement of the frame stitch: tests/frames_reference.py).  One launch each.
  * sos_window_frames_stitch_f32: rows f32 [n_rows][stride] hold the windows' frame logits, window w (an entry of the plan table

@@ -12,6 +12,11 @@
 // Pure streaming, shaped like ragged_io.hip: a thread handles four consecutive samples, one 16-byte access where the address
 // allows it and scalar accesses otherwise; which of the two is taken changes no value, so a recording's output has the same bits
 // alone, in any batch, at any offset and with the table in any order.
+//   window_stitch_planes_kernel   window_stitch_kernel for up to eight signals of the SAME plan (rows [planes][n_rows][stride]) in
+//                          one launch: the four signals of denoise_long(signals=True) and of the windowed hand-off.  Each plane
+//                          holds the bits window_stitch_kernel gives for it alone (window_quad is the one statement of the
+//                          arithmetic); sample p of plane q of recording r goes to out[base_r + q pitch_r + p], {base, pitch} per
+//                          recording, so one launch writes plane-major or file-major, where the download wants the samples.
 // Two more for the detector half of the chain and the `bits=` path (pipeline.detect_long / denoise_long):
 //   window_frames_stitch_kernel   one row of frame logits per window -> ONE logit stream per recording.  The windows' frame grids
 //                          do not line up with the recording's (a frame is rho = sr / fps samples, windows start on samples), so
@@ -29,10 +34,13 @@
 // frames_win_ok / window_masked_ok below).
 #include "ragged.h"
 #include "mask_rule.h"
+#include <utility>
+#include <vector>
 
 #define RW_THREADS 256
 #define RW_MAX_GRID 1024                // workgroups along a row (they stride over what the grid does not cover)
 #define RW_STITCH_QUADS 4               // quads per thread the stitch grid is sized for
+#define RW_MAX_PLANES 8                 // signals one planes stitch takes
 #define RW_COLS 10                      // int64 per window, the row of pipeline.window_plan
 #define RW_MAX_CONTEXT ((int64_t)1 << 22)   // 2 context + 0.5 is exact in f32
 #define RW_REC_COLS 4                   // int64 per recording of the frame stitch: frame offset in the output, frames, first window, windows
@@ -114,6 +122,51 @@ __device__ __forceinline__ void window_load4(const float* base, int64_t i0, int6
     }
 }
 
+// The zones of a core of `len` samples: sample j < head blends with the window before, j >= tail with the window after;
+// before / after: the element of `rows` that holds sample cs of that neighbour's row.
+struct WindowZones { int64_t head, tail, before, after; };
+__device__ __forceinline__ WindowZones window_zones(const int64_t* table, const WindowRow& e, int64_t stride, int64_t context) {
+    const int64_t len = e.ce - e.cs;
+    WindowZones z = {context > 0 && e.prev >= 0 ? context : 0, context > 0 && e.next >= 0 ? len - context : len, 0, 0};
+    if (z.head) {
+        const WindowRow q = window_row(table, e.prev);
+        z.before = q.row * stride + (e.cs - q.start);
+    }
+    if (z.tail < len) {
+        const WindowRow q = window_row(table, e.next);
+        z.after = q.row * stride + (e.cs - q.start);            // negative for a while: only j >= tail is read
+    }
+    return z;
+}
+
+// The quad j0 .. j0 + 3 of a core (element own + j of `rows` holds its sample j): v = the window's own samples, blended with
+// the neighbour's inside the zones.  The ONE statement of the stitch's arithmetic: window_stitch_kernel and
+// window_stitch_planes_kernel (rows = the plane's) both call it.
+__device__ __forceinline__ void window_quad(const float* rows, int64_t own, const WindowZones& z, int64_t j0, int64_t len,
+                                            int64_t context, float span, float (&v)[4]) {
+    window_load4(rows, own + j0, j0, 0, len, v);
+    if (j0 < z.head) {
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        window_load4(rows, z.before + j0, j0, 0, z.head, a);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k < z.head) {
+                const float wt = ((float)(j0 + k + context) + 0.5f) / span;
+                v[k] = (1.f - wt) * a[k] + wt * v[k];
+            }
+    }
+    if (j0 + 4 > z.tail) {
+        float b[4] = {0.f, 0.f, 0.f, 0.f};
+        window_load4(rows, z.after + j0, j0, z.tail, len, b);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k >= z.tail && j0 + k < len) {
+                const float wt = ((float)(j0 + k - z.tail) + 0.5f) / span;
+                v[k] = (1.f - wt) * v[k] + wt * b[k];
+            }
+    }
+}
+
 __global__ __launch_bounds__(RW_THREADS) void window_stitch_kernel(const float* __restrict__ rows, int64_t n_rows, int64_t stride,
                                                                   const int64_t* __restrict__ table, int64_t nwin, int64_t context,
                                                                   int64_t total_out, float* __restrict__ out) {
@@ -124,43 +177,55 @@ __global__ __launch_bounds__(RW_THREADS) void window_stitch_kernel(const float* 
     const int64_t own = e.row * stride + (e.cs - e.start);      // ... and element own + j of `rows`
     float* dst = out + e.out + (e.cs - e.start);
     const bool dst_vec = ragged_aligned16(dst);
-    // the zones: j < head blends with the window before, j >= tail with the window after
-    const int64_t head = context > 0 && e.prev >= 0 ? context : 0, tail = context > 0 && e.next >= 0 ? len - context : len;
-    int64_t before = 0, after = 0;                              // element of `rows` that holds sample cs of the neighbour's row
-    if (head) {
-        const WindowRow q = window_row(table, e.prev);
-        before = q.row * stride + (e.cs - q.start);
-    }
-    if (tail < len) {
-        const WindowRow q = window_row(table, e.next);
-        after = q.row * stride + (e.cs - q.start);              // negative for a while: only j >= tail is read
-    }
+    const WindowZones z = window_zones(table, e, stride, context);
     const float span = (float)(2 * context);
     for (int64_t j0 = ((int64_t)blockIdx.x * RW_THREADS + threadIdx.x) * 4; j0 < len; j0 += (int64_t)gridDim.x * RW_THREADS * 4) {
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        window_load4(rows, own + j0, j0, 0, len, v);
-        if (j0 < head) {
-            float a[4] = {0.f, 0.f, 0.f, 0.f};
-            window_load4(rows, before + j0, j0, 0, head, a);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (j0 + k < head) {
-                    const float wt = ((float)(j0 + k + context) + 0.5f) / span;
-                    v[k] = (1.f - wt) * a[k] + wt * v[k];
-                }
-        }
-        if (j0 + 4 > tail) {
-            float b[4] = {0.f, 0.f, 0.f, 0.f};
-            window_load4(rows, after + j0, j0, tail, len, b);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (j0 + k >= tail && j0 + k < len) {
-                    const float wt = ((float)(j0 + k - tail) + 0.5f) / span;
-                    v[k] = (1.f - wt) * v[k] + wt * b[k];
-                }
-        }
+        window_quad(rows, own, z, j0, len, context, span, v);
         ragged_store4(dst, j0, len, j0 + 4 <= len && dst_vec, v);
     }
+}
+
+// Where a recording's planes go: sample p of plane q lies at out[base + q * pitch + p].
+struct PlaneRec { int64_t base, pitch; };
+__host__ __device__ static inline PlaneRec plane_rec(const int64_t* recs, int64_t r) { return {recs[2 * r], recs[2 * r + 1]}; }
+// `extent` samples of every plane (the host: the recording's output length; the kernel: up to the window's core end) lie inside
+// the out_total floats and inside their own plane.  planes <= 8 and every term <= INT64_MAX / 8: no sum overflows.
+__host__ __device__ static inline bool planes_inside(const PlaneRec& d, int planes, int64_t extent, int64_t out_total) {
+    if (!window_small(out_total) || d.base < 0 || d.base > out_total || extent < 0 || d.pitch < extent) return false;
+    if (planes > 1 && d.pitch > out_total / (planes - 1)) return false;
+    return ragged_clip_inside(d.base + (planes > 1 ? (planes - 1) * d.pitch : 0), extent, out_total);
+}
+
+#ifndef RW_PLANES_IN_GRID
+#define RW_PLANES_IN_GRID 0             // 1: one grid.z slice per plane instead of the inner loop: 134 us against 81 us (EXPERIMENTS.md 3.16)
+#endif
+
+// window_stitch_kernel for `planes` signals of the same plan: the table decode, the zone tests and the weights are the
+// window's, only the rows and the destination are the plane's.  A thread takes its quad through the planes gridDim.z apart.
+__global__ __launch_bounds__(RW_THREADS) void window_stitch_planes_kernel(
+    const float* __restrict__ rows, int planes, int64_t n_rows, int64_t stride, const int64_t* __restrict__ table, int64_t nwin,
+    int64_t context, int64_t total_core, const int64_t* __restrict__ recs, int64_t nrec, int64_t out_total,
+    float* __restrict__ out) {
+    const int64_t w = blockIdx.y;
+    if (window_stitch_why(table, w, nwin, n_rows, stride, context, total_core) != RW_OK) return;
+    const WindowRow e = window_row(table, w);
+    if (e.rec < 0 || e.rec >= nrec) return;
+    const PlaneRec d = plane_rec(recs, e.rec);
+    if (!planes_inside(d, planes, e.ce, out_total)) return;
+    const int64_t len = e.ce - e.cs;
+    const int64_t own = e.row * stride + (e.cs - e.start);
+    const WindowZones z = window_zones(table, e, stride, context);
+    if ((z.head && window_row(table, e.prev).rec != e.rec) || (z.tail < len && window_row(table, e.next).rec != e.rec)) return;
+    const float span = (float)(2 * context);
+    const int64_t plane = n_rows * stride;
+    for (int64_t j0 = ((int64_t)blockIdx.x * RW_THREADS + threadIdx.x) * 4; j0 < len; j0 += (int64_t)gridDim.x * RW_THREADS * 4)
+        for (int q = blockIdx.z; q < planes; q += gridDim.z) {
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            window_quad(rows + q * plane, own, z, j0, len, context, span, v);
+            float* dst = out + d.base + q * d.pitch + e.cs;
+            ragged_store4(dst, j0, len, j0 + 4 <= len && ragged_aligned16(dst), v);
+        }
 }
 
 static bool window_args_ok(const char* who, const void* a, const void* b, const int64_t* table, const int64_t* table_host, int nwin,
@@ -197,21 +262,22 @@ extern "C" int sos_window_stage_f32(const float* x, int64_t total, const int64_t
     return sos_check_launch("sos_window_stage_f32");
 }
 
-extern "C" int sos_window_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table,
-                                     const int64_t* table_host, int nwin, int64_t context, float* out, sos_stream_t stream) {
-    if (!window_args_ok("sos_window_stitch_f32", rows, out, table, table_host, nwin, stride)) return SOS_EINVAL;
+// What both stitches refuse of a plan, before any launch: false with the error set (it names the window), else the summed
+// output length the cores tile and the longest core.
+static bool window_stitch_plan_ok(const char* who, const int64_t* table_host, int nwin, int64_t n_rows, int64_t stride,
+                                  int64_t context, int64_t* total_out_p, int64_t* longest_p) {
     if (n_rows < 1 || n_rows > INT64_MAX / 8 / stride || context < 0 || context > RW_MAX_CONTEXT) {
-        sos_set_error("sos_window_stitch_f32: bad args (%lld rows of %lld; context %lld, 0 .. %lld)", (long long)n_rows,
-                      (long long)stride, (long long)context, (long long)RW_MAX_CONTEXT);
-        return SOS_EINVAL;
+        sos_set_error("%s: bad args (%lld rows of %lld; context %lld, 0 .. %lld)", who, (long long)n_rows, (long long)stride,
+                      (long long)context, (long long)RW_MAX_CONTEXT);
+        return false;
     }
     // the summed output length: the cores tile the recordings' outputs
     int64_t total_out = 0, longest = 0;
     for (int w = 0; w < nwin; ++w) {
         const WindowRow e = window_row(table_host, w);
         if (!window_small(e.cs) || !window_small(e.ce) || e.cs > e.ce || e.ce - e.cs > INT64_MAX / 8 - total_out) {
-            sos_set_error("sos_window_stitch_f32: window %d has the core %lld .. %lld", w, (long long)e.cs, (long long)e.ce);
-            return SOS_EINVAL;
+            sos_set_error("%s: window %d has the core %lld .. %lld", who, w, (long long)e.cs, (long long)e.ce);
+            return false;
         }
         total_out += e.ce - e.cs;
         longest = std::max(longest, e.ce - e.cs);
@@ -225,17 +291,104 @@ extern "C" int sos_window_stitch_f32(const float* rows, int64_t n_rows, int64_t 
                                              "has a core outside its own samples", "writes outside the summed output length",
                                              "names a neighbour that is no window of its recording or does not cover the overlap",
                                              "blends over a context that is not less than the window, or more than its core holds"};
-        sos_set_error("sos_window_stitch_f32: window %d %s (row %lld of %lld, samples %lld, stride %lld, start %lld, core %lld .. "
-                      "%lld, output %lld of %lld, neighbours %lld and %lld, context %lld)", w, reason[why], (long long)e.row,
+        sos_set_error("%s: window %d %s (row %lld of %lld, samples %lld, stride %lld, start %lld, core %lld .. "
+                      "%lld, output %lld of %lld, neighbours %lld and %lld, context %lld)", who, w, reason[why], (long long)e.row,
                       (long long)n_rows, (long long)e.n, (long long)stride, (long long)e.start, (long long)e.cs, (long long)e.ce,
                       (long long)e.out, (long long)total_out, (long long)e.prev, (long long)e.next, (long long)context);
-        return SOS_EINVAL;
+        return false;
     }
+    *total_out_p = total_out;
+    *longest_p = longest;
+    return true;
+}
+
+extern "C" int sos_window_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table,
+                                     const int64_t* table_host, int nwin, int64_t context, float* out, sos_stream_t stream) {
+    if (!window_args_ok("sos_window_stitch_f32", rows, out, table, table_host, nwin, stride)) return SOS_EINVAL;
+    int64_t total_out = 0, longest = 0;
+    if (!window_stitch_plan_ok("sos_window_stitch_f32", table_host, nwin, n_rows, stride, context, &total_out, &longest)) return SOS_EINVAL;
     // four quads per thread: a workgroup reads its row and both neighbours' before its first sample, which few samples do not repay
     const dim3 grid(ragged_grid((longest + 3) / 4, RW_THREADS * RW_STITCH_QUADS, RW_MAX_GRID), (unsigned)nwin);
     hipLaunchKernelGGL(window_stitch_kernel, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, rows, n_rows, stride, table,
                        (int64_t)nwin, context, total_out, out);
     return sos_check_launch("sos_window_stitch_f32");
+}
+
+extern "C" int sos_window_stitch_planes_f32(const float* rows, int planes, int64_t n_rows, int64_t stride, const int64_t* table,
+                                            const int64_t* table_host, int nwin, int64_t context, const int64_t* recs,
+                                            const int64_t* recs_host, int nrec, int64_t out_total, float* out,
+                                            sos_stream_t stream) {
+    const char* who = "sos_window_stitch_planes_f32";
+    if (!window_args_ok(who, rows, out, table, table_host, nwin, stride)) return SOS_EINVAL;
+    if (!recs || !recs_host) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
+    if (planes < 1 || planes > RW_MAX_PLANES || nrec < 1 || nrec > RAGGED_MAX_CLIPS || !window_small(out_total)) {
+        sos_set_error("%s: bad args (1 .. %d planes, got %d; 1 .. 65535 recordings, got %d; an output of %lld floats)", who,
+                      RW_MAX_PLANES, planes, nrec, (long long)out_total);
+        return SOS_EINVAL;
+    }
+    int64_t total_core = 0, longest = 0;
+    if (!window_stitch_plan_ok(who, table_host, nwin, n_rows, stride, context, &total_core, &longest)) return SOS_EINVAL;
+    if (n_rows > INT64_MAX / 8 / stride / planes) {
+        sos_set_error("%s: bad args (%d planes of %lld rows of %lld)", who, planes, (long long)n_rows, (long long)stride);
+        return SOS_EINVAL;
+    }
+    // a recording's output length: the sum of its cores
+    std::vector<int64_t> len(nrec, 0);
+    for (int w = 0; w < nwin; ++w) {
+        const WindowRow e = window_row(table_host, w);
+        if (e.rec < 0 || e.rec >= nrec) {
+            sos_set_error("%s: window %d names recording %lld of %d", who, w, (long long)e.rec, nrec);
+            return SOS_EINVAL;
+        }
+        len[e.rec] += e.ce - e.cs;
+    }
+    for (int w = 0; w < nwin; ++w) {
+        const WindowRow e = window_row(table_host, w);
+        if (e.ce > len[e.rec]) {
+            sos_set_error("%s: window %d has the core %lld .. %lld, outside the %lld output samples of recording %lld (the sum of "
+                          "its cores)", who, w, (long long)e.cs, (long long)e.ce, (long long)len[e.rec], (long long)e.rec);
+            return SOS_EINVAL;
+        }
+        for (int side = 0; side < 2 && context > 0; ++side) {
+            const int64_t o = side ? e.next : e.prev;
+            if (o >= 0 && window_row(table_host, o).rec != e.rec) {
+                sos_set_error("%s: window %d of recording %lld has the neighbour %lld, a window of recording %lld", who, w,
+                              (long long)e.rec, (long long)o, (long long)window_row(table_host, o).rec);
+                return SOS_EINVAL;
+            }
+        }
+    }
+    std::vector<std::pair<int64_t, int>> seg;                   // {start, recording * planes + plane} of the segments that hold samples
+    for (int r = 0; r < nrec; ++r) {
+        const PlaneRec d = plane_rec(recs_host, r);
+        if (d.pitch < len[r]) {
+            sos_set_error("%s: recording %d has the pitch %lld, less than its %lld output samples", who, r, (long long)d.pitch,
+                          (long long)len[r]);
+            return SOS_EINVAL;
+        }
+        if (!planes_inside(d, planes, len[r], out_total)) {
+            sos_set_error("%s: recording %d (base %lld, pitch %lld, %lld samples in each of %d planes) lies outside the %lld "
+                          "floats of the output", who, r, (long long)d.base, (long long)d.pitch, (long long)len[r], planes,
+                          (long long)out_total);
+            return SOS_EINVAL;
+        }
+        for (int q = 0; q < planes && len[r] > 0; ++q) seg.push_back({d.base + q * d.pitch, r * planes + q});
+    }
+    std::sort(seg.begin(), seg.end());
+    for (size_t i = 1; i < seg.size(); ++i) {
+        const int a = seg[i - 1].second, b = seg[i].second;
+        if (seg[i].first < seg[i - 1].first + len[a / planes]) {
+            sos_set_error("%s: plane %d of recording %d (%lld + %lld) and plane %d of recording %d (from %lld) overlap in the "
+                          "output", who, a % planes, a / planes, (long long)seg[i - 1].first, (long long)len[a / planes],
+                          b % planes, b / planes, (long long)seg[i].first);
+            return SOS_EINVAL;
+        }
+    }
+    const dim3 grid(ragged_grid((longest + 3) / 4, RW_THREADS * RW_STITCH_QUADS, RW_MAX_GRID), (unsigned)nwin,
+                    RW_PLANES_IN_GRID ? (unsigned)planes : 1u);
+    hipLaunchKernelGGL(window_stitch_planes_kernel, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, rows, planes, n_rows, stride,
+                       table, (int64_t)nwin, context, total_core, recs, (int64_t)nrec, out_total, out);
+    return sos_check_launch(who);
 }
 
 // ---- one logit stream per recording out of the windows' frame logits

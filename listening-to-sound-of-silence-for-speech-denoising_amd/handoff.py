@@ -613,9 +613,72 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
     return stat
 
 
+def _first_model_windows(net, mixed, noise, clean, all_bits, nb, ngt, ratios, framerates, sr, window_seconds, context_seconds,
+                         max_batch, max_columns, download):
+    """The windowed half of denoise_first_model: `mixed` (one 1-D GPU recording per file; `noise` / `clean`: the ground-truth
+    recordings or empty lists), all_bits = the files' `recovered_prediction` decisions (nb each) followed by the ground-truth
+    ones (ngt each) in one GPU buffer.  -> per file ([4 signals], [2 ground-truth signals] or None, host arrays of the
+    4 (6) signals as _write_individual_host takes them, or None without `download`).
+    The four signals: pipeline._long_signal_rows over the windows of all files, then ONE sos_window_stitch_planes_f32 launch into
+    a file-major buffer -- the four signals of a file next to each other, every segment on a multiple of four floats (16-byte
+    stores) -- and ONE device-to-host copy of it, with no launch in between.
+    The ground-truth signals (the STFT -> ISTFT round trips of `full_noise` and of the clean recording silenced on its
+    ground-truth silent intervals) are further recordings under a plan of their own, since their lengths may differ from the
+    mixed file's: sos_window_stage_f32 per group, sos_window_stage_masked_f32 and wave - masked for the clean windows
+    (M2/predict.py:321), one sos_window_stitch_f32, cropped to the output length as on the whole-file path."""
+    from . import engine as E
+    from . import pipeline
+    F, hop, device = len(mixed), transform.HOP_LENGTH, mixed[0].device
+    core, context, ns, plan = pipeline._long_plan("denoise_first_model", mixed, sr, window_seconds, context_seconds)
+    flat, _ = ragged.concat(mixed)
+    rates = np.asarray(framerates, dtype=np.float64)
+    kept = pipeline._long_signal_rows(net, flat, plan, all_bits, ragged.clip_table(ns, nb), ratios, rates[plan[:, 0]], sr,
+                                      max_batch, max_columns)
+    lens = [hop * (n // hop) for n in ns]
+    pitch = [-(-n // 4) * 4 for n in lens]
+    base = (4 * ragged.offsets(pitch)).tolist()
+    buf = pipeline._stitch_signals(kept, plan, context, recs=np.stack([base, pitch], axis=1), out_total=4 * sum(pitch))
+    host = buf.cpu().numpy() if download else None              # the four signals of every file: one copy
+    sigs = [[buf[base[i] + q * pitch[i]:base[i] + q * pitch[i] + lens[i]] for q in range(4)] for i in range(F)]
+    hosts = [[host[base[i] + q * pitch[i]:base[i] + q * pitch[i] + lens[i]] for q in range(4)] if download else None for i in range(F)]
+    if not noise:
+        return sigs, [None] * F, hosts
+    # recordings 0 .. F - 1: full_noise, F .. 2 F - 1: clean, with its ground-truth decisions
+    _, _, ng, gplan = pipeline._long_plan("denoise_first_model", noise + clean, sr, window_seconds, context_seconds)
+    gflat, _ = ragged.concat(noise + clean)
+    gtable = ragged.clip_table(ng, [0] * F + list(ngt))
+    gbits = all_bits[sum(nb):]
+    ms = gplan[:, 2].tolist()
+    gkept = torch.empty((len(gplan), hop * (max(ms) // hop)), dtype=torch.float32, device=device)
+    done = 0
+    for part in pipeline._length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
+        m = [ms[i] for i in part]
+        sub = np.ascontiguousarray(gplan[part])
+        wave = tools.window_stage(gflat, sub, max(m))
+        silenced = np.flatnonzero(sub[:, 0] >= F)
+        if len(silenced):
+            w, masked = tools.window_stage_masked(gflat, gbits, gtable, list(ratios) * 2, sub[silenced], max(m))
+            wave[torch.from_numpy(silenced).to(device)] = w - masked
+        grag = E.Ragged([1 + n // hop for n in m], device, n_samples=m)
+        y = transform.istft_batch(transform.stft_batch(wave, clip_samples=grag.tab(m)), clip_frames=grag.level(0))
+        gkept[done:done + len(part), :y.shape[1]] = y
+        gplan[part, 7] = np.arange(done, done + len(part))
+        done += len(part)
+    rows = gplan.copy()
+    rows[:, 2] = hop * (gplan[:, 2] // hop)
+    glens = [hop * (n // hop) for n in ng]
+    gt = ragged.split(tools.window_stitch(gkept, rows, context), glens)
+    gts = [[gt[i], gt[F + i]] for i in range(F)]
+    if download:                                                 # cropped like _write_individual: one more copy
+        gh = ragged.download([g[:lens[i]] for i in range(F) for g in gts[i]])
+        hosts = [hosts[i] + gh[2 * i:2 * i + 2] for i in range(F)]
+    return sigs, gts, hosts
+
+
 @torch.no_grad()
 def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR, snr=None, threshold="", unknown_clean_signal=True,
-                        save_individual_results=True, save_stat=True, pesq_fn=None, stoi_fn=None, max_batch=64, max_columns=65536):
+                        save_individual_results=True, save_stat=True, pesq_fn=None, stoi_fn=None, max_batch=64, max_columns=65536,
+                        window_seconds=None, context_seconds=2.0):
     """get_data_from_first_model + denoise_files(batch_metrics=True) over the files of pred_data.json in ragged groups instead
     of one file at a time: the same WAVE files, stat.json, eval_results<suffixes>.json and returned `stat` list (in the JSON's
     file order), with the number of launches, copies and host waits following the number of GROUPS, not of files.
@@ -629,7 +692,14 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
         `full_noise` and the silenced clean signal are further rows of the group;
       - the four (six) signals of every file of a group come down in one copy (sos_ragged_unpack_f32);
       - the measures of all files go through _batch_measures (stoi_fn=True: STOI in the same launch sequence).
-    A file with fewer than pipeline.MIN_FRAMES STFT frames raises ValueError naming it before any group is staged or run."""
+    window_seconds (None: every file runs whole, as above): files of ANY length, the counterpart of detect_files(window_seconds=).
+    Every file is cut into overlapping windows (pipeline.window_plan), the windows of ALL files are grouped by max_batch /
+    max_columns and staged by one sos_window_stage_masked_f32 launch per group at the file's own sr / framerate, and ONE
+    sos_window_stitch_planes_f32 launch cross-fades the four signals of every file into a file-major buffer, which comes down
+    in one copy (_first_model_windows).  A file shorter than two windows is one window: the whole-file computation.  Same
+    files, keys, order, types and measures as the whole-file path; activation memory follows max_columns, not the file.
+    A file with fewer than pipeline.MIN_FRAMES STFT frames raises ValueError naming it before any group is staged or run, and
+    so do pipeline.window_plan's argument rules."""
     from . import engine as E
     from . import pipeline
     with open(first_model_json_path, 'r') as fp:
@@ -649,6 +719,19 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
     gt_bits = [np.asarray([0 if b == '0' else 1 for b in d[GT_BIT_STREAM_LABEL]], dtype=np.uint8) for d in files] if known else []
     ratios = [float(sr) / d['framerate'] for d in files]
     stat, work = [], []
+
+    def file_info(i):
+        d = files[i]
+        data = dict(id=os.path.splitext(os.path.basename(d['path']))[0], sr=sr)
+        info = OrderedDict([('id', str(data['id'])), ('path', str(d['path']))])
+        if known:
+            info['clean_audio_path'] = clean_paths[i]
+        info['mixed_audio_path'] = mixed_paths[i]
+        if known:
+            info['full_noise_path'] = noise_paths[i]
+        info.update([('bitstream', d[BIT_STREAM_LABEL]), ('sr', sr), ('snr', obj['snr'])])
+        return data, info
+
     if F:
         ys, _ = audio_io.load_batch_device(mixed_paths + clean_paths + noise_paths, sr=sr)
         mixed, clean, noise = ys[:F], ys[F:2 * F], ys[2 * F:]
@@ -661,7 +744,16 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
         all_bits = torch.from_numpy(np.concatenate(rec_bits + gt_bits)).to(device)       # every bit string: one copy
         d_bits = ragged.split(all_bits, [len(b) for b in rec_bits + gt_bits])
         work = [None] * F
-    for part in (pipeline._ragged_groups(mixed, max_batch, max_columns) if F else []):
+    if F and window_seconds is not None:
+        for i, y in enumerate(clean + noise):                # the ground-truth recordings are windowed under a plan of their own
+            if 1 + y.numel() // hop < pipeline.MIN_FRAMES:
+                raise ValueError("%s: %d samples at %d Hz are fewer than the %d STFT frames (%d samples) a window needs"
+                                 % ((clean_paths + noise_paths)[i], y.numel(), sr, pipeline.MIN_FRAMES, pipeline.MIN_FRAMES * hop))
+        sigs, gts, hosts = _first_model_windows(net, mixed, noise, clean, all_bits, [len(b) for b in rec_bits],
+                                                [len(b) for b in gt_bits], ratios, [d['framerate'] for d in files], sr,
+                                                window_seconds, context_seconds, max_batch, max_columns, save_individual_results)
+        work = [file_info(i) + (sigs[i], gts[i] if known else None, hosts[i]) for i in range(F)]
+    for part in (pipeline._ragged_groups(mixed, max_batch, max_columns) if F and window_seconds is None else []):
         B = len(part)
         rows = [mixed[i] for i in part]
         bits_g = [d_bits[i] for i in part]
@@ -705,15 +797,7 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
             host = ragged.split(tools.ragged_unpack(both, tab).cpu().numpy(), tab[:, 1])
         per = 6 if known else 4
         for k, i in enumerate(part):
-            d = files[i]
-            data = dict(id=os.path.splitext(os.path.basename(d['path']))[0], sr=sr)
-            info = OrderedDict([('id', str(data['id'])), ('path', str(d['path']))])
-            if known:
-                info['clean_audio_path'] = clean_paths[i]
-            info['mixed_audio_path'] = mixed_paths[i]
-            if known:
-                info['full_noise_path'] = noise_paths[i]
-            info.update([('bitstream', d[BIT_STREAM_LABEL]), ('sr', sr), ('snr', obj['snr'])])
+            data, info = file_info(i)
             sig_i = [sigs[q * B + k, :n_out[k]] for q in range(4)]
             gt_i = [gt[q * B + k, :n_gt[q * B + k]] for q in range(2)] if known else None
             host_i = host[per * k:per * (k + 1)] if host is not None else None

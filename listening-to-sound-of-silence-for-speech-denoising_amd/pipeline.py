@@ -433,9 +433,39 @@ def detect_long(detector, clips, sr=SR, fps=FPS, window_seconds=30.0, context_se
                    for r in range(len(clips))]
 
 
+def _long_signal_rows(denoiser, flat, plan, d_bits, rec_table, ratios, fps_w, sr, max_batch, max_columns):
+    """The groups of denoise_long(bits=, signals=True) and of the windowed hand-off: the windows of `plan` out of the recordings
+    back to back in `flat`, staged with the recordings' masks (one sos_window_stage_masked_f32 launch per group) and run
+    through _denoise_group_staged(signals=True).  -> kept (4, windows, longest row): the four signals' rows, plane by plane;
+    plan[:, 7] is set to the row each window ran in.  Nothing goes to the host."""
+    import numpy as np
+    hop = transform.HOP_LENGTH
+    ms, W = plan[:, 2].tolist(), len(plan)
+    kept = torch.empty((4, W, hop * (max(ms) // hop)), dtype=torch.float32, device=flat.device)
+    done = 0
+    for part in _length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
+        m, B = [ms[i] for i in part], len(part)
+        rag = _group_geometry(m, flat.device, sr, FPS, nv=[max(1, n_video_frames(ms[i], sr, fps_w[i])) for i in part])
+        wave, masked = tools.window_stage_masked(flat, d_bits, rec_table, ratios, np.ascontiguousarray(plan[part]), max(m))
+        y = _denoise_group_staged(denoiser, wave, masked, rag, signals=True)
+        kept[:, done:done + B, :y.shape[1]] = y.reshape(4, B, y.shape[1])
+        plan[part, 7] = np.arange(done, done + B)
+        done += B
+    return kept
+
+
+def _stitch_signals(kept, plan, context, recs=None, out_total=None):
+    """The rows of _long_signal_rows cross-faded in ONE sos_window_stitch_planes_f32 launch.  Without `recs`: (4, total), the
+    recordings' outputs back to back in each plane; with recs = host rows {base, pitch} per recording: the flat buffer of
+    out_total floats with plane q of recording r from base_r + q * pitch_r on (the hand-off's file-major download)."""
+    rows = plan.copy()
+    rows[:, 2] = transform.HOP_LENGTH * (plan[:, 2] // transform.HOP_LENGTH)            # what a window's row holds
+    return tools.window_stitch_planes(kept, rows, context, recs=recs, out_total=out_total)
+
+
 @torch.no_grad()
 def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0, context_seconds=2.0, max_batch=256,
-                 max_columns=65536, bits=None, return_all=False, stitch_bits=False):
+                 max_columns=65536, bits=None, return_all=False, stitch_bits=False, signals=False):
     """Recordings of ANY length, minutes and hours included: `clips` = list of 1-D f32 GPU waveforms, short and long mixed.
     denoise_ragged runs a recording as one clip, which ends at sos_conv2d_fwd's 4 GB image (about 16 minutes at 14 kHz), needs
     ~0.5 MB of activations per STFT column and steps both BiLSTMs serially through the whole file.  Here every recording is cut
@@ -465,10 +495,17 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
     dict(plan=its window_plan rows (row = the order the windows ran in), windows=[dict(logits, bits) per window], logits, bits=
     the recording's stitched stream as detect_long makes it, one more small launch); with `bits` dict(plan, bits, mask=the
     sample mask at full length, made only here); with stitch_bits dict(plan, logits, bits, mask).
+    signals=True (with `bits` or stitch_bits): the four signals the hand-off writes, not the output alone.  Every group runs
+    _denoise_group_staged(signals=True), its (4 B, len) rows are kept in one (4, windows, longest) buffer, and after the last
+    group ONE sos_window_stitch_planes_f32 launch cross-fades all four.  -> (outs, extra): outs as without `signals`, bit for
+    bit; extra[r] holds `noisy_input`, `noise_intervals`, `predicted_full_noise` (the ISTFTs of the mixed, the noise-interval
+    and the predicted-noise spectrograms, stitched), each as long as the output, plus return_all's keys if that is set.
     ValueError before any launch: window_plan's (a recording below MIN_FRAMES frames is named), more than 65535 windows,
-    stitch_bits together with bits."""
+    stitch_bits together with bits, signals without decisions for the whole recording (neither bits nor stitch_bits)."""
     import numpy as np
     clips = list(clips)
+    if signals and bits is None and not stitch_bits:
+        raise ValueError("signals=True needs one decision stream per recording: pass bits=, or stitch_bits=True")
     if stitch_bits and bits is not None:
         raise ValueError("stitch_bits=True takes the decisions from the detector: it cannot be combined with bits=")
     if bits is None and not stitch_bits and not isinstance(fps, (int, float)):
@@ -477,11 +514,11 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
     if bits is not None and len(bits) != len(clips):
         raise ValueError("bits must hold one array of frame decisions per recording")
     if not clips:
-        return ([], []) if return_all else []
+        return ([], []) if return_all or signals else []
     if stitch_bits:                                             # detect_long refuses what _long_plan refuses, before any launch
         pairs = detect_long(detector, clips, sr, fps, window_seconds, context_seconds, max_batch, max_columns)
         res = denoise_long(None, denoiser, clips, sr, fps, window_seconds, context_seconds, max_batch, max_columns,
-                           bits=[b for _, b in pairs], return_all=return_all)
+                           bits=[b for _, b in pairs], return_all=return_all, signals=signals)
         if return_all:
             for e, (lg, _) in zip(res[1], pairs):
                 e["logits"] = lg
@@ -508,33 +545,45 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
         frames = [n_video_frames(n, sr, fps) for n in ns]
         wf = _window_frames(plan, sr, [fps] * len(clips), frames)
         kept_logits = torch.empty((W, max(wf)), dtype=torch.float32, device=device)
-    kept = torch.empty((W, hop * (max(ms) // hop)), dtype=torch.float32, device=device)
-    seen, done = [None] * W, 0
-    for part in _length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
-        m = [ms[i] for i in part]
-        sub = np.ascontiguousarray(plan[part])
-        if bits is None:
-            wave = tools.window_stage(flat, sub, max(m))
-            rag = _group_geometry(m, device, sr, fps)
-            y, logits, wbits = _denoise_group_padded(detector, denoiser, wave, rag, sr, fps)
-            if return_all:
-                kept_logits[done:done + len(part), :logits.shape[1]] = logits
-                for k, i in enumerate(part):
-                    seen[i] = dict(logits=logits[k, :rag.n_vframes[k]], bits=wbits[k, :rag.n_vframes[k]])
-        else:
-            rag = _group_geometry(m, device, sr, FPS, nv=[max(1, n_video_frames(ms[i], sr, fps_w[i])) for i in part])
-            wave, masked = tools.window_stage_masked(flat, d_bits, rec_table, ratios, sub, max(m))
-            y = _denoise_group_staged(denoiser, wave, masked, rag)
-        kept[done:done + len(part), :y.shape[1]] = y
-        plan[part, 7] = np.arange(done, done + len(part))
-        done += len(part)
-    rows = plan.copy()
-    rows[:, 2] = hop * (plan[:, 2] // hop)                                               # what a window's row holds
-    outs = ragged.split(tools.window_stitch(kept, rows, context), [hop * (n // hop) for n in ns])
+    lens = [hop * (n // hop) for n in ns]
+    if signals:
+        kept = _long_signal_rows(denoiser, flat, plan, d_bits, rec_table, ratios, fps_w, sr, max_batch, max_columns)
+        four = _stitch_signals(kept, plan, context)             # (4, total): mixed, noise intervals, predicted noise, output
+        outs = ragged.split(four[3], lens)
+        extra = [dict(noisy_input=a, noise_intervals=b, predicted_full_noise=c)
+                 for a, b, c in zip(*(ragged.split(four[q], lens) for q in range(3)))]
+        if not return_all:
+            return outs, extra
+    else:
+        kept = torch.empty((W, hop * (max(ms) // hop)), dtype=torch.float32, device=device)
+        seen, done = [None] * W, 0
+        for part in _length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
+            m = [ms[i] for i in part]
+            sub = np.ascontiguousarray(plan[part])
+            if bits is None:
+                wave = tools.window_stage(flat, sub, max(m))
+                rag = _group_geometry(m, device, sr, fps)
+                y, logits, wbits = _denoise_group_padded(detector, denoiser, wave, rag, sr, fps)
+                if return_all:
+                    kept_logits[done:done + len(part), :logits.shape[1]] = logits
+                    for k, i in enumerate(part):
+                        seen[i] = dict(logits=logits[k, :rag.n_vframes[k]], bits=wbits[k, :rag.n_vframes[k]])
+            else:
+                rag = _group_geometry(m, device, sr, FPS, nv=[max(1, n_video_frames(ms[i], sr, fps_w[i])) for i in part])
+                wave, masked = tools.window_stage_masked(flat, d_bits, rec_table, ratios, sub, max(m))
+                y = _denoise_group_staged(denoiser, wave, masked, rag)
+            kept[done:done + len(part), :y.shape[1]] = y
+            plan[part, 7] = np.arange(done, done + len(part))
+            done += len(part)
+        rows = plan.copy()
+        rows[:, 2] = hop * (plan[:, 2] // hop)                                           # what a window's row holds
+        outs = ragged.split(tools.window_stitch(kept, rows, context), lens)
+        extra = [dict() for _ in clips]
     if not return_all:
         return outs
     first = _first_windows(plan, len(clips))
-    extra = [dict(plan=plan[first[r]:first[r + 1]]) for r in range(len(clips))]
+    for r, e in enumerate(extra):
+        e["plan"] = plan[first[r]:first[r + 1]]
     if bits is None:
         logits, sbits = _stitch_frames(kept_logits, plan, wf, frames, sr, [fps] * len(clips), core, context)
         for r, (e, lg, b) in enumerate(zip(extra, ragged.split(logits, frames), ragged.split(sbits, frames))):

@@ -120,6 +120,44 @@ def window_stitch(rows, table, context):
     return out
 
 
+MAX_PLANES = 8                      # signals one planes stitch takes (csrc/ragged_window.hip: RW_MAX_PLANES)
+
+
+def window_stitch_planes(rows, table, context, recs=None, out_total=None):
+    """window_stitch for several signals of the same plan in ONE launch (sos_window_stitch_planes_f32).  rows: contiguous f32
+    (planes, R, stride) GPU tensor, 1 .. 8 planes; table, context: as window_stitch, and column 0 names each window's recording.
+    Without `recs` the layout is plane-major: -> (planes, total), row q bit for bit window_stitch(rows[q], table, context).
+    recs: host rows {base, pitch}, one per recording: sample p of plane q of recording r goes to element base_r + q * pitch_r + p
+    of the flat buffer of `out_total` floats that is returned (file-major: the planes of a recording next to each other;
+    pitch > the recording's length leaves a gap).  What no segment covers stays zero."""
+    L.require_cuda(rows)
+    tab = _host_table(table, WINDOW_COLS)
+    if rows.dim() != 3 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous float32 (planes, R, stride) tensor")
+    planes = rows.shape[0]
+    if recs is None:
+        if out_total is not None:
+            raise ValueError("out_total goes with recs")
+        nrec = int(tab[:, 0].max()) + 1
+        if int(tab[:, 0].min()) < 0 or nrec > ragged.MAX_CLIPS:
+            raise ValueError(f"the table names recordings outside 0 .. {ragged.MAX_CLIPS - 1}")
+        lens = np.zeros(nrec, dtype=np.int64)
+        np.add.at(lens, tab[:, 0], tab[:, 5] - tab[:, 4])
+        total = max(int(lens.sum()), 0)
+        rec = np.ascontiguousarray(np.stack([ragged.offsets(lens.tolist()), np.full(nrec, total, dtype=np.int64)], axis=1))
+        out = torch.empty((planes, total), dtype=torch.float32, device=rows.device)          # the segments tile it
+    else:
+        if out_total is None:
+            raise ValueError("recs needs out_total, the length of the flat buffer")
+        rec = _host_table(recs, 2)
+        out = torch.zeros(max(int(out_total), 0), dtype=torch.float32, device=rows.device)
+    d_tab, d_rec = _upload(tab, rows.device), _upload(rec, rows.device)
+    L.check(L.lib().sos_window_stitch_planes_f32(L.ptr(rows), planes, rows.shape[1], rows.shape[2], L.ptr(d_tab), tab.ctypes.data,
+                                                 tab.shape[0], int(context), L.ptr(d_rec), rec.ctypes.data, rec.shape[0],
+                                                 out.numel(), L.ptr(out), L.stream_ptr()), "sos_window_stitch_planes_f32")
+    return out
+
+
 def window_frames_stitch(rows, table, win_frames, recs, ratios, core, context):
     """The windows' frame logits stitched into ONE logit stream per recording in one launch (sos_window_frames_stitch_f32; the
     rule and its float64 restatement: tests/frames_reference.py).  rows: contiguous f32 (R, stride) GPU tensor, a window's

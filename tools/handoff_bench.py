@@ -6,7 +6,11 @@ ragged-group form, in 'mixed' precision:
 (real-recording branch: unknown clean signal, WAVE files and JSONs written).  Both forms are warmed once, then alternate,
 --repeats times each; per stage and form the median wall time from an idle device to an idle device (file reads and writes
 included), the spread of the repeats, files/s and the number of host waits -- device-to-host downloads (Tensor.cpu calls),
-each of which blocks the host until the stream has drained -- are printed."""
+each of which blocks the host until the stream has drained -- are printed.
+--window-seconds W: stage 2 only, the same file set through denoise_first_model whole (window_seconds=None) and in windows of W
+seconds (+ --context-seconds), alternating, with the time and the peak device memory of each; then one synthetic file of
+--long-minutes minutes (default 17: above the 16 minutes at which the whole-file path ends), which the whole-file call refuses
+and the windowed call denoises.  A demonstration and a measurement: nothing is asserted."""
 import argparse
 import json
 import os
@@ -68,6 +72,65 @@ def make_dataset(root, n_files, seed):
     return os.path.join(root, "dataset.json"), sum(f["duration"] for f in files)
 
 
+def once_peak(fn):
+    """once() plus the allocator's peak during the call, in bytes."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    t, waits = once(fn)
+    return t, waits, torch.cuda.max_memory_allocated()
+
+
+def make_pred_data(root, name, n, fr=30):
+    """pred_data.json of one synthetic recording of n samples at 14 kHz (unknown clean signal)."""
+    rng = np.random.default_rng(n)
+    t = np.arange(n) / 14000
+    sig = 0.3 * (np.sin(2 * np.pi * 0.7 * t) > -0.2) * np.sin(2 * np.pi * 220 * t) + 0.05 * rng.standard_normal(n)
+    os.makedirs(os.path.join(root, "recovered"))
+    audio_io.write_wav(os.path.join(root, "recovered", name + "_mixed.wav"), sig.astype(np.float32), 14000)
+    nfr = int(round(n / 14000 * fr))
+    bits = "".join("1" if (i // 10) % 3 else "0" for i in range(nfr))
+    files = [dict(path="/bench/%s.wav" % name, framerate=fr, bit_stream=bits, recovered_prediction=bits,
+                  mixed_audio="recovered/%s_mixed.wav" % name)]
+    path = os.path.join(root, "pred_data.json")
+    with open(path, "w") as fp:
+        json.dump(dict(dataset_path="/bench", num_videos=1, data_total_frames=60, data_center_frames=1, sigmoid_threshold=0.5,
+                       snr=None, files=files), fp)
+    return path
+
+
+def windows(args, jm, pred, tmp, secs):
+    """Stage 2 whole against windowed on the file set of `pred`, then the file above 16 minutes."""
+    out = lambda name: os.path.join(tmp, name)                                            # noqa: E731
+    kw = dict(window_seconds=args.window_seconds, context_seconds=args.context_seconds)
+    whole = lambda: handoff.denoise_first_model(jm, pred, out("m2_whole"), sr=14000, max_batch=args.max_batch)             # noqa: E731
+    win = lambda: handoff.denoise_first_model(jm, pred, out("m2_windows"), sr=14000, max_batch=args.max_batch, **kw)       # noqa: E731
+    whole(), win()
+    runs = dict(whole=[], windows=[])
+    for _ in range(args.repeats):
+        runs["whole"].append(once_peak(whole))
+        runs["windows"].append(once_peak(win))
+    print(f"{args.files} files, {secs:.0f} s of audio, 'mixed' precision, stage 2 whole against windows of {args.window_seconds:g} s + "
+          f"{args.context_seconds:g} s, {args.repeats} alternating repeats (median, min, max)")
+    for k, v in runs.items():
+        report("stage 2 (denoise)", k, args.files, [r[:2] for r in v])
+        print(f"      peak device memory {max(r[2] for r in v) / 2**30:.2f} GiB")
+    n = int(args.long_minutes * 60 * 14000)
+    long_pred = make_pred_data(os.path.join(tmp, "long"), "long", n)
+    try:
+        handoff.denoise_first_model(jm, long_pred, out("long_whole"), sr=14000)
+        print(f"one file of {args.long_minutes:g} minutes: the whole-file call went through")
+    except (RuntimeError, ValueError) as e:
+        print(f"one file of {args.long_minutes:g} minutes ({n} samples): the whole-file call refuses: {str(e).splitlines()[0][:200]}")
+    long_win = lambda: handoff.denoise_first_model(jm, long_pred, out("long_windows"), sr=14000, **kw)                     # noqa: E731
+    long_win()
+    t, waits, peak = once_peak(long_win)
+    stat = long_win()
+    arr, _, rate = audio_io.read_wave(stat[0]["denoised_output"])
+    print(f"one file of {args.long_minutes:g} minutes in windows of {args.window_seconds:g} s: {t * 1e3:.1f} ms ({n / 14000 / t:.0f} x real "
+          f"time), peak device memory {peak / 2**30:.2f} GiB, host waits {waits}; denoised_output.wav holds {arr.shape[0]} samples at "
+          f"{rate} Hz, finite: {bool(np.isfinite(arr).all())}")
+
+
 def report(stage, name, n_files, runs):
     ts, waits = [r[0] for r in runs], [r[1] for r in runs]
     med = float(np.median(ts))
@@ -82,6 +145,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-batch", type=int, default=64)
+    ap.add_argument("--window-seconds", type=float, default=None, help="stage 2 whole against windowed, and one file above 16 minutes")
+    ap.add_argument("--context-seconds", type=float, default=2.0)
+    ap.add_argument("--long-minutes", type=float, default=17.0)
     args = ap.parse_args()
     print(torch.cuda.get_device_name(0))
     det = dnet.get_network()
@@ -104,6 +170,10 @@ def main():
         s2_file = lambda: handoff.denoise_files(jm, handoff.get_data_from_first_model(pred, sr=14000), out("m2_file"),   # noqa: E731
                                                 batch_metrics=True)
         s2_batch = lambda: handoff.denoise_first_model(jm, pred, out("m2_batch"), sr=14000, max_batch=args.max_batch)    # noqa: E731
+        if args.window_seconds is not None:
+            windows(args, jm, pred, tmp, secs)
+            sos_amd.set_precision("bf16")
+            return
         s2_file(), s2_batch()
         runs = {k: [] for k in ("s1_file", "s1_batch", "s2_file", "s2_batch")}
         for _ in range(args.repeats):                                                     # the forms alternate

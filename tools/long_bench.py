@@ -10,7 +10,11 @@ networks, nothing is asserted on it.  One line per configuration.
 of 2 s) with time and peak memory; and the two kernels of that path alone (sos_window_stage_masked_f32,
 sos_window_frames_stitch_f32) as a rate next to a float4 copy of the same bytes.  --root CHECKOUT runs this script's lines on
 another checkout of the repository (its package and its built libraries), e.g. the parent commit for the `bits=` line:
-    python tools/long_bench.py --no-speed --decisions --root ../parent"""
+    python tools/long_bench.py --no-speed --decisions --root ../parent
+--signals: the four signals of the hand-off on the same mixed batch: sos_window_stitch_planes_f32 (4 planes, file-major, one
+launch) against the sequence it replaces -- four sos_window_stitch_f32 launches and one sos_ragged_unpack_f32 launch over every
+output sample -- alternating, --signal-runs times each, next to a float4 copy of the one launch's bytes; the file-major launch
+with pitches that leave segments off 16-byte boundaries; and denoise_long(bits=, signals=True) next to the plain `bits=` call."""
 import argparse
 import os
 import sys
@@ -173,6 +177,76 @@ def decisions(args, det, jm):
               f"({nbytes / (ms_copy / 1e3) / 1e12:.3f} TB/s)")
 
 
+def signals(args, det, jm):
+    from sos_amd import ragged
+    n = int(args.seconds * SR)
+    mixed = [_wave(800, n)] + [_wave(801 + i, 2 * SR) for i in range(63)]
+    rng = np.random.default_rng(14)
+    bits = [torch.from_numpy(rng.integers(0, 2, pipeline.n_video_frames(c.numel())).astype(np.uint8)).cuda() for c in mixed]
+    kw = dict(window_seconds=30.0, context_seconds=args.context)
+    if not args.kernels_only:
+        sos_amd.set_precision(args.precision)
+        try:
+            for name, fn in (("bits= path, the output alone", lambda: pipeline.denoise_long(None, jm, mixed, bits=bits, fps=30.0, **kw)),
+                             ("bits= path, signals=True (four signals)", lambda: pipeline.denoise_long(None, jm, mixed, bits=bits, fps=30.0, signals=True, **kw))):
+                ms, peak = _timed(fn, args.iters)
+                print(f"{args.seconds:g} s + 63 x 2 s at {SR} Hz, {args.precision}, 30 s windows: {name} {ms:9.1f} ms per call, peak {peak / 2**30:6.2f} GiB")
+        finally:
+            sos_amd.set_precision("bf16")
+    # the kernels alone, on resident buffers: the mixed batch's plan, four planes of random rows
+    hop, planes = transform.HOP_LENGTH, 4
+    ns = [int(c.numel()) for c in mixed]
+    core, context = pipeline._hops(round(30.0 * SR)), pipeline._hops(round(args.context * SR))
+    held = np.ascontiguousarray(pipeline.window_plan(ns, core, context))
+    held[:, 2] = hop * (held[:, 2] // hop)                      # what a window's row holds
+    W, stride = len(held), int(held[:, 2].max())
+    lens = [hop * (m // hop) for m in ns]
+    total = sum(lens)
+    rows = torch.randn((planes, W, stride), device="cuda")
+    d_held = torch.from_numpy(held).cuda()
+    lib = L.lib()
+
+    def layout(pitch):
+        recs = np.ascontiguousarray(np.stack([planes * ragged.offsets(pitch), np.asarray(pitch, dtype=np.int64)], axis=1))
+        return recs, torch.from_numpy(recs).cuda(), torch.empty(planes * sum(pitch), device="cuda")
+
+    def one_launch(recs, d_recs, out):
+        return lambda: L.check(lib.sos_window_stitch_planes_f32(L.ptr(rows), planes, W, stride, L.ptr(d_held), held.ctypes.data, W,
+                                                                context, L.ptr(d_recs), recs.ctypes.data, len(ns), out.numel(),
+                                                                L.ptr(out), L.stream_ptr()))
+
+    aligned, odd = one_launch(*layout([-(-m // 4) * 4 for m in lens])), one_launch(*layout(lens))
+    # the sequence: one stitch per plane into a plane-major buffer, then one unpack launch over every output sample (its table
+    # takes whole rows, so the four planes are its four rows: the bytes of the reordering, not the reordering itself)
+    major, flat = torch.empty((planes, total), device="cuda"), torch.empty(planes * total, device="cuda")
+    utab = np.ascontiguousarray(np.asarray([(q, total, q * total) for q in range(planes)], dtype=np.int64))
+    d_utab = torch.from_numpy(utab).cuda()
+
+    def sequence():
+        for q in range(planes):
+            L.check(lib.sos_window_stitch_f32(L.ptr(rows[q]), W, stride, L.ptr(d_held), held.ctypes.data, W, context, L.ptr(major[q]),
+                                              L.stream_ptr()))
+        L.check(lib.sos_ragged_unpack_f32(L.ptr(major), planes, total, L.ptr(d_utab), utab.ctypes.data, planes, L.ptr(flat), L.stream_ptr()))
+
+    floats = planes * (2 * total + 2 * context * (W - len(ns)))
+    src, dst = torch.empty(floats // 2, device="cuda"), torch.empty(floats // 2, device="cuda")
+    runs = []
+    for _ in range(args.signal_runs):                           # the two alternate
+        runs.append((_timed(aligned, 200)[0], _timed(sequence, 200)[0], _timed(lambda: dst.copy_(src), 200)[0], _timed(odd, 200)[0]))
+    nbytes = 4.0 * floats
+    for i, (a, b, c, d) in enumerate(runs):
+        print(f"run {i}: sos_window_stitch_planes_f32 ({planes} planes, {W} windows of {len(ns)} recordings, file-major) {a * 1e3:8.1f} us "
+              f"({nbytes / 1e6:.1f} MB at {nbytes / (a / 1e3) / 1e12:.3f} TB/s); {planes} x sos_window_stitch_f32 + sos_ragged_unpack_f32 "
+              f"{b * 1e3:8.1f} us; ratio {b / a:.2f}; a float4 copy of the one launch's bytes {c * 1e3:8.1f} us; file-major with "
+              f"pitch = length (segments off 16-byte boundaries) {d * 1e3:8.1f} us")
+    one, seq = [r[0] for r in runs], [r[1] for r in runs]
+    spread = max(max(one) - min(one), max(seq) - min(seq))
+    print(f"{len(runs)} alternating runs: one launch {np.median(one) * 1e3:.1f} us (min {min(one) * 1e3:.1f}, max {max(one) * 1e3:.1f}), the "
+          f"sequence {np.median(seq) * 1e3:.1f} us (min {min(seq) * 1e3:.1f}, max {max(seq) * 1e3:.1f}), ratio of the medians "
+          f"{np.median(seq) / np.median(one):.2f}; slowest one launch {'below' if max(one) + spread < min(seq) else 'NOT below'} the "
+          f"fastest sequence by more than the spread between runs ({spread * 1e3:.1f} us)")
+
+
 def distance(args, det, jm):
     n = 60 * SR
     clip = _wave(810, n)
@@ -206,6 +280,8 @@ def main():
     ap.add_argument("--no-speed", action="store_true")
     ap.add_argument("--decisions", action="store_true", help="stitch_bits=True, the bits= path on a mixed batch, the two kernels alone")
     ap.add_argument("--kernels-only", action="store_true", help="with --decisions: only the kernels' lines")
+    ap.add_argument("--signals", action="store_true", help="the planes stitch against four stitches and an unpack; signals=True")
+    ap.add_argument("--signal-runs", type=int, default=3, help="with --signals: alternating runs of the one launch and the sequence")
     ap.add_argument("--root", default=None, help="measure another checkout of the repository (package and built libraries)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -216,6 +292,8 @@ def main():
             speed(args, det, jm)
         if args.decisions:
             decisions(args, det, jm)
+        if args.signals:
+            signals(args, det, jm)
         if args.distance:
             distance(args, det, jm)
 
