@@ -734,6 +734,41 @@ int sos_window_stage_masked_f32(const float* x, const uint8_t* bits, const int64
                                 const int64_t* table_host, int nwin, int64_t stride, float* wave, float* masked,
                                 sos_stream_t stream);
 
+/* ---- live audio denoised in windows, the state between two calls on the device (csrc/stream_window.hip;
+ * sos_amd.pipeline.StreamDenoiser; the rule: pipeline.StreamPlan, float64 restatement tests/stream_reference.py).  One launch
+ * each whatever the number of slots; no allocation, no host synchronisation, no atomics.  A slot is one stream.
+ *   ring f32 [slots][cap]: sample p of the stream of slot s lies at ring[s][p % cap].
+ *   tail f32 [slots][2][2 context]: the overlap [b - context, b + context) of the last window's row around its core end b.
+ * Every table comes twice, on the device and on the HOST (int64 rows).
+ * sos_stream_push_f32: flat holds `total` floats, the chunks back to back; rows {slot, source offset, samples, stream position}:
+ *   ring[slot][(position + j) % cap] = flat[source offset + j], j < samples.  samples <= cap (0: nothing is written); a slot
+ *   appears at most once per table.
+ * sos_stream_stage_f32: rows {slot, stream position, samples}; rows f32 [nwin][stride]: rows[w][j] = ring[slot][(position + j)
+ *   % cap] for j < samples, zero from there to the stride (sos_window_stage_f32 with a modular source index).  samples <= cap
+ *   and <= stride.
+ * sos_stream_stitch_f32: rows f32 [n_rows][stride]; table rows {slot, row, window start, samples of the row, core start, core
+ *   end, flags, parity}: sample i of row `row` is sample window start + i of the stream; flags: 1 = a window ran before this
+ *   one, 2 = one will run after it.  out f32 [nwin][out_stride]: out[w][0 ..] = the samples [lo, hi) of the stream that are
+ *   final after this window, lo = core start - context with a previous window (else core start), hi = core end - context with
+ *   a next one (else core end).  With a previous window the first 2 context of them are blended with tail[slot][parity]:
+ *   w = (i + 0.5) / (2 context), out = (1 - w) tail + w row, in f32 -- the statement and the bits of sos_window_stitch_f32;
+ *   every other sample is copied bit for bit.  With a next window the row's samples [core end - context, core end + context)
+ *   go to tail[slot][parity ^ 1]: the caller flips the slot's parity after such a call.  context = 0 is a plain cut.  The
+ *   grid follows nwin, the strides and the context alone; a slot's bits do not depend on the other rows, its slot index or the
+ *   table's order.
+ * SOS_EINVAL before any launch (sos_last_error() names the row): null pointers, rows or slots outside 1 .. 65535, cap or a
+ * stride < 1, a slot outside the slots, a slot twice in one table (push, stitch), samples above cap or the stride, a negative
+ * position, a chunk outside `total`, a row outside n_rows, a core outside its row, an overlap outside its row, more context
+ * than the core holds, flags outside 0 .. 3, a parity outside 0 .. 1, more emitted samples than out_stride, context < 0 or
+ * above 2^22.  The kernels follow the DEVICE table and skip a row that fails the same bounds. */
+int sos_stream_push_f32(const float* flat, int64_t total, const int64_t* table, const int64_t* table_host, int nrows, float* ring,
+                        int64_t slots, int64_t cap, sos_stream_t stream);
+int sos_stream_stage_f32(const float* ring, int64_t slots, int64_t cap, const int64_t* table, const int64_t* table_host, int nwin,
+                         int64_t stride, float* rows, sos_stream_t stream);
+int sos_stream_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
+                          int nwin, int64_t slots, int64_t context, float* tail, float* out, int64_t out_stride,
+                          sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,9 @@ SIGNATURES = {
     "sos_window_stitch_planes_f32": [_P, _I, _L, _L, _P, _P, _I, _L, _P, _P, _I, _L, _P, _P],
     "sos_window_frames_stitch_f32": [_P, _L, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _L, _L, _P, _P],
     "sos_window_stage_masked_f32": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _L, _P, _P, _P],
+    "sos_stream_push_f32": [_P, _L, _P, _P, _I, _P, _L, _L, _P],
+    "sos_stream_stage_f32": [_P, _L, _L, _P, _P, _I, _L, _P, _P],
+    "sos_stream_stitch_f32": [_P, _L, _L, _P, _P, _I, _L, _L, _P, _P, _L, _P],
     "sos_time_unstack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
     "sos_spatial_mean_bwd": [_P, _L, _L, _I, _L, _I, _I, _I, _P, _I, _P],
 }

@@ -743,3 +743,215 @@ class GraphedDenoiser:
                 for k, i in enumerate(part):
                     outs[i] = y[k]
         return outs
+
+
+class StreamPlan:
+    """window_plan for ONE stream whose length is not known yet (host only; float64 restatement: tests/stream_reference.py).
+    core, context: samples, rounded and refused as window_plan rounds and refuses them.  A stream that has received n_in samples
+    has handed out the windows 0 .. k - 1:
+      window k is ready, as an inner window, as soon as n_in >= (k + 2) core -- only then is it certain that window_plan of the
+      final length does not make k the last window, which extends to the end; it reads [max(k core - context, 0),
+      (k + 1) core + context);
+      at close() the length n is known and exactly one window is left, K - 1 with K = max(1, hop * (n // hop) // core), which
+      reads up to n.
+    feed(n) -> the rows of the windows that became ready, close() -> the last one, as int64 (windows, 10) in window_plan's
+    columns with the recording 0 and every offset counted in the stream: feed + close yield window_plan([n])'s rows in order.
+    After window k the samples emitted(row) are final: [k core - context, (k + 1) core - context), from 0 for k = 0 and up to
+    hop * (n // hop) for the last window; these ranges tile the output.  Between two windows at most 2 core + context samples
+    are pending (`pending`: received and not below `base`, the first sample a later window still reads)."""
+
+    def __init__(self, core, context):
+        window_plan([], core, context)                          # the refusals are its own
+        self.core, self.context = _hops(core), _hops(context)
+        self.n_in = self.k = 0
+
+    @property
+    def base(self):
+        return max(self.k * self.core - self.context, 0)
+
+    @property
+    def pending(self):
+        return self.n_in - self.base
+
+    def feed(self, n):
+        import numpy as np
+        if n < 0:
+            raise ValueError(f"StreamPlan.feed: {n} samples")
+        self.n_in += int(n)
+        rows = []
+        while self.n_in >= (self.k + 2) * self.core:
+            k, cs, ce = self.k, self.k * self.core, (self.k + 1) * self.core
+            start = max(cs - self.context, 0)
+            rows.append((0, start, ce + self.context - start, start, cs, ce, start, k, k - 1 if k else -1, k + 1))
+            self.k += 1
+        return np.asarray(rows, dtype=np.int64).reshape(-1, tools.WINDOW_COLS)
+
+    def close(self):
+        """The last window's row (1, 10); ValueError for a stream below MIN_FRAMES frames, as window_plan refuses it.  Either
+        way the plan is that of a new stream afterwards."""
+        n, k = self.n_in, self.k
+        self.n_in = self.k = 0
+        row = window_plan([n], self.core, self.context)[-1:]
+        assert int(row[0, 7]) == k, (n, k, row)
+        return row
+
+    def emitted(self, row):
+        """[lo, hi) of the stream: the samples that are final after the window `row`."""
+        return (int(row[4]) - self.context if row[8] >= 0 else int(row[4])), (int(row[5]) - self.context if row[9] >= 0 else int(row[5]))
+
+
+class StreamDenoiser:
+    """denoise_long for audio that is still arriving: a session of `slots` concurrent streams (a monitor feed, call channels, a
+    capture still being written).  push() takes chunks of ANY size for any of the slots and returns, per slot, the denoised
+    samples that have become final; close() ends streams and returns what was left; drop() forgets streams.  The concatenated
+    output of a stream is denoise_long's result for the same audio with the same window_seconds / context_seconds: the plan
+    (StreamPlan: window_plan without knowing the length), the windows' rows and the cross-fade are bit for bit the same, and with
+    max_batch = 1 so is every sample, since every window then runs alone through the same launch sequence on the same shape
+    (tests/test_gpu_stream_denoiser.py); with several windows in a group it differs as denoise_long's own batches differ.
+    State lives on the device and is never downloaded: a ring of 2 core + context samples per slot (what has arrived and
+    belongs to no finished window yet) and the overlap of each slot's last window, which the next one is blended with.  The host
+    knows every count from the chunk sizes, so after the first calls (plans, tables, workspaces) no call waits for the device.
+    push(): ONE sos_stream_push_f32 launch copies all chunks into their rings (a chunk larger than the free ring goes in pieces,
+    one launch per piece of all slots); then, while a window is ready, one step with at most one window per slot: the ready
+    windows grouped by max_batch / max_columns like denoise_long's, and per group one sos_stream_stage_f32 launch, the launch
+    sequence of denoise_long's default path (_denoise_group_padded: the window's own detector pass with its own frame count)
+    and one sos_stream_stitch_f32 launch.  close() runs the last windows of all named slots as one ragged call (their lengths
+    differ) the same way.
+    Latency: window k runs once (k + 2) core samples are in, so a sample is returned at most 2 core + context samples after it
+    arrived (plus the compute time of its window); the first sample of a stream waits for 2 core.
+    graph=True: per (windows, samples) of a group the launch sequence is captured once, exactly as
+    GraphedDenoiser._capture_mixed captures it (two eager runs on a side stream first, the tables uploaded before the
+    capture), the stage writes straight into the graph's input and the stitch reads its output; stage, stitch and their table
+    uploads stay outside the graph.  close() runs eagerly: the last windows' lengths do not repeat.  `captures` counts them.
+    Not here: one decision stream per recording (denoise_long's stitch_bits needs frames of the future), given decisions
+    (`bits=`), and the four hand-off signals (`signals=`).
+    ValueError before any launch: window_plan's argument rules, slots outside 1 .. 65535, a slot outside the slots (push) or
+    without an open stream (close, drop), a chunk that is not 1-D float32, a closed stream below MIN_FRAMES frames (the slot is
+    named and free again; the other named slots stay open)."""
+
+    def __init__(self, detector, denoiser, slots, sr=SR, fps=FPS, window_seconds=2.0, context_seconds=0.5, max_batch=256,
+                 max_columns=65536, graph=False, device=None):
+        self.core, self.context = _hops(round(window_seconds * sr)), _hops(round(context_seconds * sr))
+        StreamPlan(self.core, self.context)
+        if not 1 <= int(slots) <= ragged.MAX_CLIPS:
+            raise ValueError(f"StreamDenoiser: 1 .. {ragged.MAX_CLIPS} slots, got {slots}")
+        self.detector, self.denoiser, self.sr, self.fps = detector, denoiser, sr, fps
+        self.max_batch, self.max_columns, self.graph = min(int(max_batch), ragged.MAX_CLIPS), int(max_columns), bool(graph)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.capacity = 2 * self.core + self.context
+        self.ring = torch.zeros((int(slots), self.capacity), dtype=torch.float32, device=self.device)
+        self.tail = torch.zeros((int(slots), 2, max(2 * self.context, 1)), dtype=torch.float32, device=self.device)
+        self.plans, self.parity = [None] * int(slots), [0] * int(slots)
+        self._graphs, self.captures = {}, 0
+
+    def _open(self, slots, who):
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        for s in slots:
+            if not isinstance(s, int) or not 0 <= s < len(self.plans) or self.plans[s] is None:
+                raise ValueError(f"StreamDenoiser.{who}: slot {s!r} has no open stream")
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"StreamDenoiser.{who}: a slot is named twice")
+        return slots
+
+    def _flat(self, chunks):
+        """The chunks back to back in one device buffer (host arrays go up in one copy) and where each starts."""
+        import numpy as np
+        from .engine import upload
+        host = [c for c in chunks if not torch.is_tensor(c) and c.shape[0]]
+        up = iter(ragged.split(upload(np.concatenate(host), torch.float32, self.device), [c.shape[0] for c in host]) if host else [])
+        parts = [(c.to(self.device).contiguous() if torch.is_tensor(c) else next(up)) for c in chunks if c.shape[0]]
+        flat = (torch.cat(parts) if len(parts) > 1 else parts[0]) if parts else None
+        return flat, ragged.offsets([c.shape[0] for c in chunks]).tolist()
+
+    @torch.no_grad()
+    def push(self, chunks):
+        """chunks: {slot: 1-D float32 GPU tensor or numpy array, of any length, empty included}; a slot without an open stream
+        begins one.  -> {slot: 1-D f32 GPU tensor of the samples that became final, possibly empty}."""
+        import numpy as np
+        for s, c in chunks.items():
+            if not isinstance(s, int) or not 0 <= s < len(self.plans):
+                raise ValueError(f"StreamDenoiser.push: unknown slot {s!r} (0 .. {len(self.plans) - 1})")
+            if not (torch.is_tensor(c) or isinstance(c, np.ndarray)) or c.ndim != 1 or c.dtype != (torch.float32 if torch.is_tensor(c) else np.float32):
+                raise ValueError(f"StreamDenoiser.push: slot {s}: a chunk is a 1-D float32 GPU tensor or numpy array")
+            if torch.is_tensor(c):
+                tools.L.require_cuda(c)
+        slots = list(chunks)
+        for s in slots:
+            if self.plans[s] is None:
+                self.plans[s], self.parity[s] = StreamPlan(self.core, self.context), 0
+        flat, offs = self._flat([chunks[s] for s in slots])
+        left = [int(chunks[s].shape[0]) for s in slots]
+        outs = {s: [] for s in slots}
+        while any(left):
+            rows, ready = [], []
+            for i, s in enumerate(slots):
+                plan = self.plans[s]
+                take = min(left[i], self.capacity - plan.pending)
+                if take:
+                    rows.append((s, offs[i], take, plan.n_in))
+                    offs[i], left[i] = offs[i] + take, left[i] - take
+                    ready.append([(s, row) for row in plan.feed(take)])
+            tools.stream_push(flat, rows, self.ring)              # a window is pending or the ring has room: rows is not empty
+            while any(ready):                                   # a step: at most one window per slot
+                self._run([q.pop(0) for q in ready if q], outs, self.graph)
+        empty = torch.empty(0, dtype=torch.float32, device=self.device)
+        return {s: (torch.cat(o) if len(o) > 1 else o[0]) if o else empty for s, o in outs.items()}
+
+    @torch.no_grad()
+    def close(self, slots):
+        """Ends the streams of `slots` (an iterable of slots, or one): -> {slot: the remaining final samples}; the slots are free."""
+        slots = self._open(slots, "close")
+        hop = transform.HOP_LENGTH
+        short = [s for s in slots if 1 + self.plans[s].n_in // hop < MIN_FRAMES]
+        if short:                                               # the other named streams stay open
+            told = "; ".join(f"slot {s} got {self.plans[s].n_in} samples" for s in short)
+            for s in short:
+                self.plans[s] = None
+            raise ValueError(f"StreamDenoiser.close: streams need at least {MIN_FRAMES} STFT frames ({MIN_FRAMES * hop} samples): {told}")
+        items = [(s, self.plans[s].close()[0]) for s in slots]
+        outs = {s: [] for s in slots}
+        self._run(items, outs, False)
+        for s in slots:
+            self.plans[s] = None
+        return {s: o[0] for s, o in outs.items()}
+
+    def drop(self, slots):
+        """Forgets the streams of `slots` without output; the slots are free."""
+        for s in self._open(slots, "drop"):
+            self.plans[s] = None
+
+    def _run(self, items, outs, graph):
+        """One window (slot, row of StreamPlan) per slot: staged, denoised and stitched in groups; appends to outs[slot]."""
+        hop = transform.HOP_LENGTH
+        ms = [int(row[2]) for _, row in items]
+        for part in _length_groups(ms, self.max_batch, self.max_columns):
+            group, m = [items[i] for i in part], [ms[i] for i in part]
+            stage = [(s, int(row[6]), int(row[2])) for s, row in group]
+            if graph:
+                y = self._replay(m, stage)
+            else:
+                wave = tools.stream_stage(self.ring, stage, max(m))
+                y = _denoise_group_padded(self.detector, self.denoiser, wave, _group_geometry(m, self.device, self.sr, self.fps),
+                                          self.sr, self.fps)[0]
+            table = [(s, i, int(row[6]), hop * (int(row[2]) // hop), int(row[4]), int(row[5]),
+                      (tools.STREAM_HAS_PREV if row[8] >= 0 else 0) | (tools.STREAM_HAS_NEXT if row[9] >= 0 else 0), self.parity[s])
+                     for i, (s, row) in enumerate(group)]
+            out, lens = tools.stream_stitch(y, table, self.context, self.tail)
+            for i, (s, row) in enumerate(group):
+                outs[s].append(out[i, :lens[i]])
+                if row[9] >= 0:
+                    self.parity[s] ^= 1
+
+    def _replay(self, m, stage):
+        """The group's launch sequence from its graph, captured at the first group of these (windows, samples)."""
+        wv = tuple(t._version for net in (self.detector, self.denoiser) for t in list(net.parameters()) + list(net.buffers()))
+        key = (tuple(m), self.device.index, get_mode(), hash(wv))
+        entry = self._graphs.get(key)
+        if entry is None:                                       # _capture_mixed clones the staged rows into the graph's input
+            entry = self._graphs[key] = GraphedDenoiser(self.detector, self.denoiser, self.sr, self.fps)._capture_mixed(
+                tools.stream_stage(self.ring, stage, max(m)), _group_geometry(m, self.device, self.sr, self.fps))
+            self.captures += 1
+        else:
+            tools.stream_stage(self.ring, stage, max(m), out=entry[1])
+        entry[0].replay()
+        return entry[2]

@@ -210,6 +210,74 @@ def window_stage_masked(flat, bits, clips, ratios, table, stride):
     return wave, masked
 
 
+STREAM_PUSH_COLS, STREAM_STAGE_COLS, STREAM_STITCH_COLS = 4, 3, 8      # int64 per row (csrc/stream_window.hip: SW_*_COLS)
+STREAM_HAS_PREV, STREAM_HAS_NEXT = 1, 2                                # flags of a stream_stitch row
+
+
+def _stream_ring(ring):
+    if ring.dim() != 2 or ring.dtype != torch.float32 or not ring.is_contiguous():
+        raise ValueError("ring must be a contiguous float32 (slots, capacity) tensor")
+
+
+def stream_push(flat, table, ring):
+    """Chunks of live audio into their streams' rings in one launch (sos_stream_push_f32).  flat: the chunks back to back,
+    contiguous 1-D f32 GPU tensor; table: host rows {slot, source offset, samples, stream position}, a slot at most once; ring:
+    (slots, capacity) f32 GPU tensor, written in place: ring[slot, (position + j) % capacity] = flat[source offset + j]."""
+    L.require_cuda(flat, ring)
+    tab = _host_table(table, STREAM_PUSH_COLS)
+    _stream_ring(ring)
+    if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("flat must be a contiguous 1-D float32 tensor")
+    d_tab = _upload(tab, flat.device)
+    L.check(L.lib().sos_stream_push_f32(L.ptr(flat), flat.numel(), L.ptr(d_tab), tab.ctypes.data, tab.shape[0], L.ptr(ring),
+                                        ring.shape[0], ring.shape[1], L.stream_ptr()), "sos_stream_push_f32")
+
+
+def stream_stage(ring, table, stride, out=None):
+    """Windows of streams as zero-filled rows in one launch (sos_stream_stage_f32): window_stage out of the rings.  table: host
+    rows {slot, stream position, samples}.  -> rows (windows, stride): rows[w, j] = ring[slot, (position + j) % capacity] for
+    j < samples, zero beyond; `out`: a contiguous f32 (windows, stride) tensor to write instead (a captured graph's input)."""
+    L.require_cuda(ring, out)
+    tab = _host_table(table, STREAM_STAGE_COLS)
+    _stream_ring(ring)
+    if out is None:
+        out = torch.empty((tab.shape[0], int(stride)), dtype=torch.float32, device=ring.device)
+    elif out.shape != (tab.shape[0], int(stride)) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 (windows, stride) tensor")
+    d_tab = _upload(tab, ring.device)
+    L.check(L.lib().sos_stream_stage_f32(L.ptr(ring), ring.shape[0], ring.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
+                                         int(stride), L.ptr(out), L.stream_ptr()), "sos_stream_stage_f32")
+    return out
+
+
+def stream_stitch(rows, table, context, tail, out_stride=None):
+    """What is final of each stream after one more window, in one launch (sos_stream_stitch_f32).  rows: contiguous f32
+    (R, stride) GPU tensor; table: host rows {slot, row, window start, samples of the row, core start, core end, flags, parity};
+    tail: (slots, 2, 2 context) f32 GPU tensor, the saved overlaps: half `parity` is read, half `parity ^ 1` written for a
+    window with a next one (the caller then flips the slot's parity).
+    -> (out (windows, out_stride), lengths): out[w, :lengths[w]] = the stream's samples [core start - context (core start
+    without a previous window), core end - context (core end without a next one)), the first 2 context of them blended with
+    the saved overlap exactly as window_stitch blends them.  out_stride: default the longest of `lengths`."""
+    L.require_cuda(rows, tail)
+    tab = _host_table(table, STREAM_STITCH_COLS)
+    context = int(context)
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
+    if tail.dim() != 3 or tuple(tail.shape[1:]) != (2, max(2 * context, 1)) or tail.dtype != torch.float32 or not tail.is_contiguous():
+        raise ValueError("tail must be a contiguous float32 (slots, 2, 2 context) tensor (one column at context 0)")
+    lo = tab[:, 4] - np.where(tab[:, 6] & STREAM_HAS_PREV, context, 0)
+    hi = tab[:, 5] - np.where(tab[:, 6] & STREAM_HAS_NEXT, context, 0)
+    lengths = np.maximum(hi - lo, 0)
+    if out_stride is None:
+        out_stride = max(int(lengths.max()), 1)
+    out = torch.empty((tab.shape[0], int(out_stride)), dtype=torch.float32, device=rows.device)
+    d_tab = _upload(tab, rows.device)
+    L.check(L.lib().sos_stream_stitch_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
+                                          tail.shape[0], context, L.ptr(tail), L.ptr(out), int(out_stride), L.stream_ptr()),
+            "sos_stream_stitch_f32")
+    return out, lengths.tolist()
+
+
 def convert_bitstreammask_to_audiomask(ref_audio_signal, frames_to_audiosample_ratio, bitstream):
     """M2/tools.py:340-362 (string bits) / M1/tools.py:770-792 (int bits): same arguments, same
     RuntimeError on an invalid bit, same dtype as `ref_audio_signal`."""
