@@ -341,6 +341,21 @@ int sos_conv2d_wgrad_reduce(const sos_wgrad_desc* desc, sos_stream_t stream);
 int sos_wgrad_tune(const sos_wgrad_desc* desc, int iters, float* best_ms, sos_stream_t stream);
 int sos_wgrad_tune_save(const char* path);
 int sos_wgrad_tune_load(const char* path);
+/* Host-only query of the launch sos_conv2d_wgrad would make for `desc` right now (run-time knobs, measured table and cached plans
+ * as they stand): launches nothing, needs no GPU and dereferences no pointer of the descriptor (they only have to be non-null).
+ * Returns the code the launch would return (SOS_EINVAL / SOS_ENOSPC for a refused descriptor, message in sos_last_error) and, on
+ * SOS_OK, fills the first min(n_out, SOS_WGRAD_DESCRIBE_N) ints of `out`:
+ *    0 route: 0 split-K GEMM, 1 thin 1x1 streaming kernel, 2 thin kh x 1 (taps) streaming kernel, 3 tiled kernels
+ *    1 kernel kind: 0 wgrad_kernel<MT, NTB, BAL>, 1 wgrad16_kernel<M16, N16, FT>, 2 wgrad_thin_kernel<M16, N16>,
+ *                   3 wgrad_thin_taps_kernel<M16, KH>, 4 wgrad_gemm_kernel
+ *    2..4 the template arguments a, b, v of the kernel instance that resolved (0 where the kind has fewer)
+ *    5 ksplit (partial planes the reduce folds), 6 grid size (workgroups), 7 dynamic LDS bytes
+ *    tiled route only (0 elsewhere):
+ *    8 MT, 9 NTB, 10 NC (residue classes), 11 log2 TH, 12 log2 TW, 13 pixel order, 14 workgroups per CU of the plan,
+ *    15 dbuf (two operand buffers), 16 xcdmap (XCD-aware workgroup ids), 17 ntg (tap-row groups), 18 pixel tiles in all (ksplit never
+ *    exceeds it). */
+#define SOS_WGRAD_DESCRIBE_N 19
+int sos_wgrad_describe(const sos_wgrad_desc* desc, int32_t* out, int n_out);
 
 /* ---- backward of the BatchNorm(+activation) / bias(+activation) tail of a conv block (autograd of
  * nn.BatchNorm2d + ReLU/PReLU in train mode).  dy: grad of the block output; x: raw conv output;

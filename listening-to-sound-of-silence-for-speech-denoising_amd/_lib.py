@@ -64,6 +64,7 @@ ADAM_CHUNK = 16384          # SOS_ADAM_CHUNK of include/sos_hip.h
 GUARD_FLOATS = 5            # SOS_GUARD_FLOATS
 RESAMPLE_CHUNK = 4096       # SOS_RESAMPLE_CHUNK
 MIX_CHUNK = 4096            # SOS_MIX_CHUNK
+WGRAD_DESCRIBE_N = 19       # SOS_WGRAD_DESCRIBE_N
 EXPECTED_ABI = 10           # sos_abi_version() of the library these argument lists were written for
 
 # name -> argtypes, exactly the prototypes of include/sos_hip.h
@@ -123,6 +124,7 @@ SIGNATURES = {
     "sos_wgrad_tune": [C.POINTER(WgradDesc), _I, C.POINTER(C.c_float), _P],
     "sos_wgrad_tune_save": [C.c_char_p],
     "sos_wgrad_tune_load": [C.c_char_p],
+    "sos_wgrad_describe": [C.POINTER(WgradDesc), C.POINTER(C.c_int32), _I],
     "sos_pcm_to_mono_f32": [_P, _I, _I, _L, _P, _P],
     "sos_resample_f32": [_P, _L, _D, _P, _I, _I, _P, _L, _P],
     "sos_resample_batch_f32": [_P, _P, _P, _I, _D, _P, _I, _I, _P, _P],

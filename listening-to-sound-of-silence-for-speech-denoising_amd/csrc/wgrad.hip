@@ -138,7 +138,7 @@ struct WgStage {
         tab = (unsigned)(uintptr_t)smem + (unsigned)p.bufbytes * (p.dbuf ? 2 : 1);
         glim = min(p.M - m0, p.g_cs - p.g_off - m0 - 7);
         // temporal taps: column n = dt * tcin + c is channel c of the frame dt - tpad away (an n-group never straddles two
-        // frames: tcin is a multiple of the widest n-group)
+        // frames: wg_make_plan() offers only n-groups that divide tcin)
         const int nc = p.tT ? n0 % p.tcin : n0;
         dtoff = p.tT ? n0 / p.tcin - p.tpad : 0;
         xlim = p.tT ? min(p.tcin - nc, p.x_cs - p.x_off - nc - 7) : min(p.N - n0, p.x_cs - p.x_off - n0 - 7);
@@ -747,6 +747,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 struct WgGemmParams {
     const bf16_t* g; const bf16_t* x; float* partial;
     int K, g_cs, x_cs, Mp, Np, tiles_n, ntiles, ksplit, kper;
+    int g_off, x_off;          // g / x point at the first owned channel: the tensors end this many channels before pixel K's start
 };
 #define WGG_KT 64
 #define WGG_BUF 32768          // one stage: 16 KB of G + 16 KB of X
@@ -767,8 +768,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_gemm_kernel(WgGemmParams p) {
     const int split = bid / p.ntiles, tile = bid - split * p.ntiles;
     const int m0 = (tile / p.tiles_n) * 128, n0 = (tile % p.tiles_n) * 128;
     const int kbeg = split * p.kper, kend = min(p.K, kbeg + p.kper);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, (unsigned)((long long)kend * p.g_cs * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (unsigned)((long long)kend * p.x_cs * 2), 0x00020000);
+    // (the range ends where pixel kend's channel run would start in the TENSOR, g_off / x_off channels before it does from the shifted
+    // base: a piece of the last pixel that reaches past the channel run -- it can only feed rows / columns that are never stored --
+    // is then out of range (zeros) instead of a read behind the allocation)
+    const long long gend = ((long long)kend * p.g_cs - p.g_off) * 2, xend = ((long long)kend * p.x_cs - p.x_off) * 2;
+    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, (unsigned)(gend > 0 ? gend : 0), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (unsigned)(xend > 0 ? xend : 0), 0x00020000);
     // DMA: instruction i of a stage fills 1 KB = 16 pixels x 64 B of sub-image (i & 15) >> 2 of G (i < 16) or X
     const unsigned lane_g = (unsigned)(((lane >> 2) * p.g_cs + (lane & 3) * 8) * 2);
     const unsigned lane_x = (unsigned)(((lane >> 2) * p.x_cs + (lane & 3) * 8) * 2);
@@ -1202,6 +1207,9 @@ static bool wg_thin_shape(const sos_wgrad_desc* d, const WgCtx& c) {
 static bool wg_thin_taps_shape(const sos_wgrad_desc* d, const WgCtx& c) {
     if (c.temporal || c.kn.no_thin || d->kw != 1 || d->kh != 5 || d->stride != 1 || d->N > 16 || c.m16 != 4) return false;
     if (d->Hg != d->Hx || d->Wg != d->Wx || d->pad_left != 0 || d->Wg < 32) return false;
+    // the kernel fetches 64 channels from g_off and 16 from x_off whatever M and N are: they must lie inside a pixel's channel
+    // run (as in wg_thin_shape), or the last pixel's pieces would be read from behind the tensor.  Anything else: tiled kernel.
+    if (d->g_off + 16 * c.m16 > d->g_cs || d->x_off + 16 > d->x_cs) return false;
     return !(d->pad_mode == SOS_PAD_REFLECT && d->pad_top >= d->Hg) && wg_batch_fits32(d);
 }
 // workgroups (= partial planes) of the streaming kernels over `npix` pixels: one per CU, at least 16 stages per wave
@@ -1287,6 +1295,10 @@ static bool wg_make_plan(const sos_wgrad_desc* d, const WgCtx& c, int mt, int nt
     if (mt < 1 || mt > WG_MT_MAX || mt > c.ntiles_m || ntb < 1 || ntb > WG_NTB_MAX || ntb > c.ntiles_n || ntb * c.taps > WG_WAVES * WG_PAIRS ||
         lnc < 0 || lnc > 6 || lth < 0 || kord < 0 || kord > 1 || occ < 1 || occ > WG_OCC_MAX || !wg_tiled_kernel(c, mt, ntb))
         return false;
+    // temporal taps: column n = dt * t_cin + c, and a workgroup reads its NTB n-tiles from ONE frame (WgStage: dtoff, xlim) -- an
+    // n-group must not straddle two frames, so the channels per frame (N / taps; a multiple of 128) must be a multiple of the
+    // n-group.  NTB = 3 is not: its second n-group would take columns 96..127 from their frame and zeros for 128..191.
+    if (c.temporal && (d->t_taps < 1 || (d->N / d->t_taps) % (ntb * 32))) return false;
     const size_t lds_max = 160 * 1024;
     const int NC = 1 << lnc, ltw = 8 - lnc - lth;
     if (ltw < 2) return false;
@@ -1451,6 +1463,7 @@ struct WgLaunch {
     size_t lds;
     union { WgParams tiled; WgGemmParams gemm; WgThinParams thin; WgThinTapParams taps; };    // the kernel's one argument
     int ksplit;                // partial planes: [ksplit][taps_all][Mp][Np]
+    int mt, ntb, occ;          // the plan's channel tile and workgroups per CU (tiled route; sos_wgrad_describe reports them)
 };
 
 static void wg_resolve_tiled(const WgRoute& r, const WgPlan& pl, WgLaunch* L) {
@@ -1498,6 +1511,7 @@ static void wg_resolve_tiled(const WgRoute& r, const WgPlan& pl, WgLaunch* L) {
     L->threads = WG_THREADS;
     L->lds = (size_t)p.bufbytes * (p.dbuf ? 2 : 1) + (size_t)(256 + p.npixp) * 8;
     L->ksplit = ksplit;
+    L->mt = pl.mt; L->ntb = pl.ntb; L->occ = pl.occ;
 }
 
 // route (+ plan on the tiled route; null: the one wg_choose_plan() gives) -> launch.  Launches nothing; a launch without a kernel
@@ -1520,6 +1534,7 @@ static int wg_resolve(const WgRoute& r, const WgPlan* plan, WgLaunch* L) {
     } else if (r.kind == WG_GEMM) {
         WgGemmParams& q = L->gemm;
         operands(q, K);
+        q.g_off = d->g_off; q.x_off = d->x_off;
         q.tiles_n = (q.Np + 127) / 128;
         q.ntiles = ((q.Mp + 127) / 128) * q.tiles_n;
         const int cap = wg_split_cap(d);
@@ -1577,6 +1592,33 @@ static int wgrad_impl(const sos_wgrad_desc* d, sos_stream_t stream, const int wh
 extern "C" int sos_conv2d_wgrad(const sos_wgrad_desc* d, sos_stream_t stream) { return wgrad_impl(d, stream, 3); }
 extern "C" int sos_conv2d_wgrad_partial(const sos_wgrad_desc* d, sos_stream_t stream) { return wgrad_impl(d, stream, 1); }
 extern "C" int sos_conv2d_wgrad_reduce(const sos_wgrad_desc* d, sos_stream_t stream) { return wgrad_impl(d, stream, 2); }
+
+// Host-only query (no launch, no device, no pointer dereferenced): the route and the launch sos_conv2d_wgrad would resolve for the
+// descriptor right now (knobs, measured table and model cache as they stand).  Returns the code the launch would return; on SOS_OK
+// fills the first min(n_out, SOS_WGRAD_DESCRIBE_N) ints of `out` in the order documented in include/sos_hip.h.
+extern "C" int sos_wgrad_describe(const sos_wgrad_desc* desc, int32_t* out, int n_out) {
+    WgRoute r;
+    WgLaunch L;
+    memset(&L, 0, sizeof(L));
+    int rc = wg_route(desc, "sos_wgrad_describe", &r);
+    if (!rc) rc = wg_resolve(r, nullptr, &L);
+    if (rc) return rc;
+    const WgInstance* inst = nullptr;
+    for (const WgInstance& i : wg_instances)
+        if (i.k == L.kernel) inst = &i;
+    if (!inst) { sos_set_error("sos_wgrad_describe: the resolved kernel is not an entry of the instance list"); return SOS_EINVAL; }
+    int32_t v[SOS_WGRAD_DESCRIBE_N];
+    memset(v, 0, sizeof(v));
+    v[0] = (int32_t)r.kind; v[1] = (int32_t)inst->kind; v[2] = inst->a; v[3] = inst->b; v[4] = inst->v;
+    v[5] = L.ksplit; v[6] = (int32_t)L.grid.x; v[7] = (int32_t)L.lds;
+    if (r.kind == WG_TILED) {
+        const WgParams& p = L.tiled;
+        v[8] = L.mt; v[9] = L.ntb; v[10] = p.NC; v[11] = p.logTH; v[12] = p.logTW; v[13] = p.kord; v[14] = L.occ;
+        v[15] = p.dbuf; v[16] = p.xcdmap; v[17] = p.ntg; v[18] = p.nsteps;
+    }
+    for (int i = 0; out && i < n_out && i < SOS_WGRAD_DESCRIBE_N; ++i) out[i] = v[i];
+    return SOS_OK;
+}
 
 // ---- measured plans (round 4).  sos_wgrad_tune times, for the SHAPE of `d`, every channel tile (MT x NTB, one or two workgroups
 // per CU) with the cost model's six cheapest pixel tiles each, in two stages like sos_conv2d_tune (all candidates over `iters`

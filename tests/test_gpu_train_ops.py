@@ -144,11 +144,17 @@ def test_conv_weight_grad(case, mode_x3):
 def test_conv_weight_grad_forced_tiles(tile, ch, monkeypatch):
     """Every (residue classes, tile height, tile width, pixel order) of the weight-gradient kernels gives the same gradient:
     the tile and the order of its pixels along the contraction (row- or column-major, which decides the border k-steps that
-    are skipped) are performance choices only.  SOS_WGRAD_TILE = "classes,log2 TH,log2 TW,order" forces one."""
-    from sos_amd import engine as E
+    are skipped) are performance choices only.  SOS_WGRAD_TILE = "classes,log2 TH,log2 TW,order" forces one -- and the forced tile
+    is the one that runs (sos_wgrad_describe), on the 32x32 kernel for 96 channels and on the 16x16x32 kernel for 48."""
+    import wgrad_pin
+    from sos_amd import engine as E, _lib as L
     monkeypatch.setenv("SOS_WGRAD_TILE", tile)
     B, H, W, k, dil = 2, 37, 45, (5, 5), (4, 4)
     pad = (8, 8)
+    rc, ran = wgrad_pin.describe(L.lib(), wgrad_pin.geometry_desc(wgrad_pin.Shape("forced tile", ch, ch, k, dil, Hg=H, Wg=W, B=B),
+                                                                 (E.pad_to(ch, 16), 0, E.pad_to(ch, 16), 0)))
+    assert rc == 0 and (ran.nc, ran.lth, ran.ltw, ran.order) == tuple(int(v) for v in tile.split(",")), (rc, ran)
+    assert ran.kind == ("wgrad" if ch == 96 else "wgrad16")
     x = torch.from_numpy(hashed(51, (B, ch, H, W)).astype(np.float32))
     xa, xheld = _act_from_nchw(x, False)
     w = torch.zeros(ch, ch, 5, 5, requires_grad=True)
