@@ -784,6 +784,37 @@ int sos_stream_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, con
                           int nwin, int64_t slots, int64_t context, float* tail, float* out, int64_t out_stride,
                           sos_stream_t stream);
 
+/* ---- live audio resampled in chunks, the state between two calls on the device (csrc/stream_resample.hip;
+ * sos_amd.audio_io.StreamResampler; float64 restatement of the rule: tests/stream_resample_reference.py).  Notation of
+ * sos_resample_f32: scale = min(1, ratio), index_step = (int)(scale * num_table), time(t) = resampy's running f64 sum,
+ * n(t) = floor(time(t)); R = nwin / index_step bounds what either wing of an output reads.
+ * sos_stream_resample_ready (host only, no HIP call): after n_recv samples of a stream, *t_ready = the number of outputs that are
+ *   final -- every t with n(t) + 1 + R <= n_recv: computed with n_in = n_recv it has the value it has for any longer signal --
+ *   and *base = max(n(t_ready) - (R - 1), 0), the first sample a later output still reads.  n_recv - *base <= 2 R - 1.  Both
+ *   come from the running sum the kernel evaluates.  SOS_EINVAL: ratio <= 0, nwin < 1, num_table < 1, index_step < 1,
+ *   n_recv < 0 or above 2^52, null pointers; SOS_ENOSPC: the time register needs more segments than the kernel argument holds.
+ * sos_stream_resample_f32: ONE launch whatever nrows is.  ring f32 [slots][cap] as sos_stream_push_f32 writes it (sample p of
+ *   the stream of slot s at ring[s][p % cap]); win, nwin, num_table: as sos_resample_f32.  table: int64 [nrows][6] on the device,
+ *   table_host: the same values on the HOST; a row is
+ *     {slot, t_lo, t_hi, n_in, n_valid, output offset}
+ *   and writes the outputs t_lo <= t < t_hi of the slot's stream to out[output offset ..] (out holds `total` floats): output t
+ *   as sos_resample_f32 computes it for a signal of n_in samples, zero for t >= n_valid.  While a stream runs, n_in = the
+ *   samples received, t_hi <= *t_ready and n_valid = t_hi; at its end n_in = its length, n_valid = (int64)(n_in * ratio) and
+ *   t_hi = the output length.  The concatenated outputs of a stream are bit for bit what sos_resample_f32 writes for the whole
+ *   signal, whatever the chunking, the slot, the other rows and the table's order.  The time register starts at 0 for every
+ *   stream and is built up to the largest t_hi of the call; if it needed more segments than the kernel argument holds (120)
+ *   that would be SOS_ENOSPC before the launch.  It does not within the positions accepted: it takes about two segments per
+ *   binade of the register, 102 for the 2^52 input samples of a 48 -> 14 kHz stream (counted on the host with
+ *   sos_resample_time_segments), so the bound on a stream is n_in <= 2^52: 2 970 years at 48 kHz.
+ * SOS_EINVAL before any launch (sos_last_error() names the row): null pointers, rows or slots outside 1 .. 65535, cap < 1, a
+ * slot outside the slots, a slot twice in one table, t_lo < 0 or t_lo > t_hi, n_in < 0, n_valid outside 0 .. (int64)(n_in * ratio),
+ * output offset + (t_hi - t_lo) > total, a row that reads a sample at or past n_in or more than `cap` samples before n_in (its
+ * ring does not hold them any more), the filter refusals above, (nwin + 1) * 4 bytes > 160 KB.  The kernel follows the DEVICE
+ * table and skips a row that fails the same bounds. */
+int sos_stream_resample_ready(double ratio, int nwin, int num_table, int64_t n_recv, int64_t* t_ready, int64_t* base);
+int sos_stream_resample_f32(const float* ring, int64_t slots, int64_t cap, const int64_t* table, const int64_t* table_host, int nrows,
+                            double ratio, const float* win, int nwin, int num_table, float* out, int64_t total, sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

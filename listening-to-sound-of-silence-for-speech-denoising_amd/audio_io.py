@@ -21,6 +21,7 @@ import torch
 
 from . import _lib as L
 from . import ragged
+from . import tools
 
 # resampy 0.2.2 `kaiser_best`: 64 zero crossings, 2**9 table points per crossing, Kaiser beta, roll-off
 KAISER_BEST = dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596)
@@ -112,6 +113,145 @@ def resample_batch_device(clips, orig_sr, target_sr, res_type="kaiser_best", fix
         L.check(h.sos_resample_batch_f32(L.ptr(x[i0:]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, ratio, L.ptr(win),
                                          win.numel(), num_table, L.ptr(out[o0:]), L.stream_ptr()), "sos_resample_batch_f32")
     return ragged.split(out, n_out)
+
+
+class StreamResampler:
+    """resample_device for audio that is still arriving: a session of `slots` concurrent streams at one pair of rates (a capture
+    device, a call leg, a monitor feed at 48 / 44.1 / 16 / 8 kHz in front of the 14 kHz networks, and back).
+      push({slot: chunk}) -> {slot: 1-D f32 GPU tensor}: chunks are 1-D float32 GPU tensors or numpy arrays of ANY length, 0
+          included; a slot without an open stream begins one at output 0.  Returned are the outputs that have become final,
+          possibly none, as views of one output buffer.
+      close(slots) -> {slot: the rest}; the slots are free afterwards.      drop(slots): forgets streams without output.
+    The concatenated output of a stream is BIT FOR BIT resample_device(the whole signal, orig_sr, target_sr, res_type, fix),
+    whatever the chunking, the slot and the other streams: no truncated filter wings at the chunk edges, one running time
+    register per stream (the rule: csrc/stream_resample.hip; float64 restatement tests/stream_resample_reference.py).  Output t
+    is final once the R samples of its right wing are in (R = nwin // index_step: 64 when upsampling, 202 from 44.1 kHz and 219
+    from 48 kHz down to 14 kHz), so the added latency is R + 1 input samples, 4.6 ms at 48 -> 14 kHz and at 14 -> 48 kHz.
+    State lives on the device and is never downloaded: one ring of max_chunk + 2 R - 1 samples per slot (2 R - 1: the most that
+    later outputs still read once the final ones are out).  The host knows every count from the chunk sizes and
+    sos_stream_resample_ready, so after the first call (filter table, code object) no call waits for the device.  A push costs
+    two launches whatever the number of slots (sos_stream_push_f32, sos_stream_resample_f32); a chunk larger than the free ring
+    goes in pieces of two launches each.  orig_sr == target_sr passes chunks through.
+    ValueError before any launch: slots outside 1 .. 65535, an unknown slot (push), a slot without an open stream or named twice
+    (close, drop), a chunk that is not 1-D float32, an unsupported res_type, a ratio too small for the filter table
+    (index_step < 1), max_chunk < 1, close of a stream too short to resample (the slot is named and free again; the other
+    named slots stay open)."""
+
+    def __init__(self, slots, orig_sr, target_sr, res_type="kaiser_best", fix=True, max_chunk=16384, device=None):
+        if not 1 <= int(slots) <= ragged.MAX_CLIPS:
+            raise ValueError(f"StreamResampler: 1 .. {ragged.MAX_CLIPS} slots, got {slots}")
+        if res_type != "kaiser_best":
+            raise ValueError("StreamResampler: res_type %r is not supported (the reference uses librosa's default 'kaiser_best')" % (res_type,))
+        if int(max_chunk) < 1:
+            raise ValueError(f"StreamResampler: max_chunk is at least 1 sample, got {max_chunk}")
+        self.orig_sr, self.target_sr, self.fix = orig_sr, target_sr, bool(fix)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.ratio = float(target_sr) / orig_sr
+        self.n_recv, self.t_done, self.base = [None] * int(slots), [0] * int(slots), [0] * int(slots)   # n_recv None: no stream
+        self.ring = None
+        if orig_sr == target_sr:
+            return
+        nwin = KAISER_BEST["num_zeros"] * 2 ** KAISER_BEST["precision"] + 1
+        index_step = int(min(1.0, self.ratio) * 2 ** KAISER_BEST["precision"])
+        if index_step < 1:
+            raise ValueError("StreamResampler: ratio %g (%s->%s) is too small for the filter's %d-point table"
+                             % (self.ratio, orig_sr, target_sr, 2 ** KAISER_BEST["precision"]))
+        self.R = nwin // index_step
+        self.capacity = int(max_chunk) + 2 * self.R - 1
+        self.win, self.num_table = _filter_on(self.device, self.ratio, res_type)
+        self.ring = torch.zeros((int(slots), self.capacity), dtype=torch.float32, device=self.device)
+
+    def _open(self, slots, who):
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        for s in slots:
+            if not isinstance(s, int) or not 0 <= s < len(self.n_recv) or self.n_recv[s] is None:
+                raise ValueError(f"StreamResampler.{who}: slot {s!r} has no open stream")
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"StreamResampler.{who}: a slot is named twice")
+        return slots
+
+    def _ready(self, n_recv):
+        t, b = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().sos_stream_resample_ready(self.ratio, self.win.numel(), self.num_table, n_recv, C.byref(t), C.byref(b)),
+                "sos_stream_resample_ready")
+        return t.value, b.value
+
+    def out_length(self, slot):
+        """The number of samples the stream of `slot` gives in all if it is closed now (0: too short to resample)."""
+        n = self.n_recv[slot]
+        if self.ring is None:
+            return n
+        n_res = int(n * self.ratio)
+        return (int(np.ceil(n * self.ratio)) if self.fix else n_res) if n_res >= 1 else 0
+
+    def push(self, chunks):
+        for s, c in chunks.items():
+            if not isinstance(s, int) or not 0 <= s < len(self.n_recv):
+                raise ValueError(f"StreamResampler.push: unknown slot {s!r} (0 .. {len(self.n_recv) - 1})")
+            if not (torch.is_tensor(c) or isinstance(c, np.ndarray)) or c.ndim != 1 or c.dtype != (torch.float32 if torch.is_tensor(c) else np.float32):
+                raise ValueError(f"StreamResampler.push: slot {s}: a chunk is a 1-D float32 GPU tensor or numpy array")
+            if torch.is_tensor(c):
+                L.require_cuda(c)
+        slots = list(chunks)
+        for s in slots:
+            if self.n_recv[s] is None:
+                self.n_recv[s], self.t_done[s], self.base[s] = 0, 0, 0
+        flat, offs = tools.stream_flat([chunks[s] for s in slots], self.device)
+        left = [int(chunks[s].shape[0]) for s in slots]
+        if self.ring is None:                                   # the same rate: the chunks themselves, on the device
+            for i, s in enumerate(slots):
+                self.n_recv[s] += left[i]
+            return dict(zip(slots, ragged.split(flat, left) if flat is not None else [self._empty()] * len(slots)))
+        # every count is the host's: what each slot emits in this call, hence where its outputs lie in the one buffer
+        first = [self.t_done[s] for s in slots]
+        counts = [self._ready(self.n_recv[s] + left[i])[0] - first[i] for i, s in enumerate(slots)]
+        where = ragged.offsets(counts).tolist()
+        out = torch.empty(sum(counts), dtype=torch.float32, device=self.device)
+        while any(left):
+            fill, rows = [], []
+            for i, s in enumerate(slots):
+                take = min(left[i], self.capacity - (self.n_recv[s] - self.base[s]))      # at least min(left, max_chunk)
+                if take:
+                    fill.append((s, offs[i], take, self.n_recv[s]))
+                    offs[i], left[i], self.n_recv[s] = offs[i] + take, left[i] - take, self.n_recv[s] + take
+                    t_new, base = self._ready(self.n_recv[s])
+                    if t_new > self.t_done[s]:
+                        rows.append((s, self.t_done[s], t_new, self.n_recv[s], t_new, where[i] + self.t_done[s] - first[i]))
+                    self.t_done[s], self.base[s] = t_new, base
+            tools.stream_push(flat, fill, self.ring)
+            if rows:
+                tools.stream_resample(self.ring, rows, self.ratio, self.win, self.num_table, out=out)
+        return dict(zip(slots, ragged.split(out, counts)))
+
+    def close(self, slots):
+        slots = self._open(slots, "close")
+        short = [s for s in slots if self.out_length(s) < 1 and self.ring is not None]
+        if short:                                               # the other named streams stay open
+            told = "; ".join("slot %d: Input signal length=%d is too small to resample from %s->%s"
+                             % (s, self.n_recv[s], self.orig_sr, self.target_sr) for s in short)
+            for s in short:
+                self.n_recv[s] = None
+            raise ValueError(f"StreamResampler.close: {told}")
+        if self.ring is None:
+            out, counts = None, [0] * len(slots)
+        else:
+            counts = [self.out_length(s) - self.t_done[s] for s in slots]
+            where = ragged.offsets(counts).tolist()
+            out = torch.empty(sum(counts), dtype=torch.float32, device=self.device)
+            rows = [(s, self.t_done[s], self.out_length(s), self.n_recv[s], int(self.n_recv[s] * self.ratio), where[i])
+                    for i, s in enumerate(slots) if counts[i]]
+            if rows:
+                tools.stream_resample(self.ring, rows, self.ratio, self.win, self.num_table, out=out)
+        for s in slots:
+            self.n_recv[s] = None
+        return dict(zip(slots, ragged.split(out, counts) if out is not None else [self._empty()] * len(slots)))
+
+    def drop(self, slots):
+        for s in self._open(slots, "drop"):
+            self.n_recv[s] = None
+
+    def _empty(self):
+        return torch.empty(0, dtype=torch.float32, device=self.device)
 
 
 def pcm_to_mono_device(pcm, fmt):

@@ -11,7 +11,7 @@
 // resample_kernel: one output sample per thread; the filter half-window (32 769 + 1 floats = 128 KB) lives
 // in LDS, so the ~2 x 202 taps of an output at 44.1 -> 14 kHz cost one ds_read2_b32 (w[o], w[o+1]) and one
 // L1-resident input read each.  A workgroup walks RS_PER_WG consecutive outputs to amortise the table load.
-#include "ragged.h"
+#include "resample_core.h"
 #include <stdlib.h>
 
 #define RS_THREADS 256
@@ -53,48 +53,7 @@ extern "C" int sos_pcm_to_mono_f32(const void* pcm, int format, int channels, in
     return sos_check_launch("sos_pcm_to_mono_f32");
 }
 
-// resampy keeps the source time of output t in a RUNNING f64 sum (time_register += 1/ratio), and because it
-// walks the filter table with the truncated step int(scale * num_table), its result is not continuous where
-// that time crosses an integer -- which the exact time t * 441/140 does at every 140th output of 44.1 -> 14 kHz.
-// Matching it therefore needs the running sum bit for bit.  A sequential f64 sum is piecewise linear: while the
-// register and register + inc share a binade [2^e, 2^(e+1)) every addition rounds on the same grid and adds the
-// same d = rn_grid(inc).  The host builds that piecewise description (a few entries per binade: one explicit
-// step across each binade boundary, one where a round-to-even tie settles, then a run) and the kernel evaluates
-// time(t) = fma(t - k0, d, s0) exactly.
-#define RS_MAXSEG 120
-struct RsSegs {
-    int n;
-    long long k0[RS_MAXSEG];
-    double s0[RS_MAXSEG], d[RS_MAXSEG];
-};
-
-static int rs_build_segments(double inc, long long n_out, RsSegs* g) {
-    long long k = 0;
-    double s = 0.0;
-    g->n = 0;
-    while (k < n_out) {
-        if (g->n == RS_MAXSEG) return -1;
-        const int i = g->n++;
-        volatile double s1v = s + inc;                   // one literal step of the running sum
-        const double s1 = s1v;
-        g->k0[i] = k; g->s0[i] = s; g->d[i] = s1 - s;
-        int e;
-        const double limit = s > 0.0 ? ldexp(1.0, (frexp(s, &e), e)) : 0.0;      // top of s's binade
-        volatile double s2v = s1 + inc;
-        const double s2 = s2v;
-        if (!(s > 0.0) || !(s2 < limit) || (s2 - s1) != (s1 - s)) { k += 1; s = s1; continue; }   // explicit single step
-        const double d = s1 - s;
-        // largest M with s + M*d + inc < limit: steps k .. k+M+1 all add d
-        long long M = (long long)((limit - inc - s) / d);
-        if (M < 1) M = 1;
-        for (;;) { volatile double v = fma((double)M, d, s) + inc; if (v < limit || M == 1) break; --M; }
-        for (;;) { volatile double v = fma((double)(M + 1), d, s) + inc; if (!(v < limit)) break; ++M; }
-        k += M + 1;
-        s = fma((double)(M + 1), d, s);
-    }
-    return 0;
-}
-
+// The time register (RsSegs, rs_build_segments) and the arithmetic of one output (rs_output): resample_core.h.
 extern "C" int sos_resample_time_segments(double ratio, int64_t n_out, int64_t* k0, double* s0, double* d, int capacity) {
     RsSegs g;
     if (!(ratio > 0.0) || n_out < 1 || !k0 || !s0 || !d) { sos_set_error("sos_resample_time_segments: bad args"); return SOS_EINVAL; }
@@ -106,50 +65,6 @@ extern "C" int sos_resample_time_segments(double ratio, int64_t n_out, int64_t* 
     return g.n;
 }
 
-// win: half window already scaled by min(1, ratio), nwin entries.  Output t:
-//   time = resampy's running sum (RsSegs); n = floor(time); frac = scale * (time - n)
-//   left wing : sum_i (w[o + i*step] + eta * (w[o + i*step + 1] - w[o + i*step])) * x[n - i],    o = int(frac * num_table)
-//   right wing: the same with frac' = scale - frac over x[n + 1 + k]
-// where the difference table has a zero last entry (resampy: interp_delta[-1] = 0): LDS holds w[nwin] = w[nwin-1].
-// One output sample of one clip: x = the clip's first sample, w = the window in LDS.  Both kernels below call this, so a
-// clip gets the same bits from either.
-__device__ __forceinline__ float rs_output(const float* __restrict__ x, int64_t n_in, const RsSegs& seg, double scale,
-                                           const float* w, int nwin, int num_table, int index_step, int64_t t) {
-    int sg = seg.n - 1;
-    while (sg > 0 && seg.k0[sg] > t) --sg;
-    const double time = fma((double)(t - seg.k0[sg]), seg.d[sg], seg.s0[sg]);
-    const int64_t n = (int64_t)time;
-    double frac = scale * (time - (double)n);
-    double index_frac = frac * (double)num_table;
-    int o = (int)index_frac;
-    float eta = (float)(index_frac - (double)o);
-    float acc = 0.f;
-    {
-        const int64_t lim = (int64_t)((nwin - o) / index_step);
-        const int i_max = (int)(n + 1 < lim ? n + 1 : lim);
-        const float* xp = x + n;
-        for (int i = 0; i < i_max; ++i, o += index_step) {
-            const float a = w[o], b = w[o + 1];
-            acc = fmaf(fmaf(eta, b - a, a), xp[-i], acc);
-        }
-    }
-    frac = scale - frac;
-    index_frac = frac * (double)num_table;
-    o = (int)index_frac;
-    eta = (float)(index_frac - (double)o);
-    {
-        const int64_t lim = (int64_t)((nwin - o) / index_step);
-        const int64_t rem = n_in - n - 1;
-        const int k_max = (int)(rem < lim ? rem : lim);
-        const float* xp = x + n + 1;
-        for (int k = 0; k < k_max; ++k, o += index_step) {
-            const float a = w[o], b = w[o + 1];
-            acc = fmaf(fmaf(eta, b - a, a), xp[k], acc);
-        }
-    }
-    return acc;
-}
-
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __restrict__ x, int64_t n_in, RsSegs seg,
                                                               double scale, const float* __restrict__ win, int nwin,
                                                               int num_table, int index_step, float* __restrict__ out,
@@ -159,7 +74,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
     __syncthreads();
     const int64_t t0 = (int64_t)blockIdx.x * RS_PER_WG;
     for (int64_t t = t0 + threadIdx.x; t < t0 + RS_PER_WG && t < n_out; t += RS_THREADS)      // t >= n_valid: librosa
-        out[t] = t < n_valid ? rs_output(x, n_in, seg, scale, w, nwin, num_table, index_step, t) : 0.f;   // fix_length's zeros
+        out[t] = t < n_valid ? rs_output(RsLinear{x}, n_in, seg, scale, w, nwin, num_table, index_step, t) : 0.f;   // fix_length's zeros
 }
 
 // The same for a ragged batch: clip c is x[tab[0][c] .. + tab[1][c]) -> out[tab[2][c] .. + tab[3][c]), of which the first
@@ -194,7 +109,7 @@ __global__ __launch_bounds__(THREADS) void resample_batch_kernel(const float* __
         const float* xc = x + in_off;
         float* oc = out + out_off;
         for (int64_t t = t0 + threadIdx.x; t < t0 + RS_PER_WG && t < n_out; t += THREADS)
-            oc[t] = t < n_valid ? rs_output(xc, n_in, seg, scale, w, nwin, num_table, index_step, t) : 0.f;
+            oc[t] = t < n_valid ? rs_output(RsLinear{xc}, n_in, seg, scale, w, nwin, num_table, index_step, t) : 0.f;
     }
 }
 

@@ -823,18 +823,28 @@ class StreamDenoiser:
     GraphedDenoiser._capture_mixed captures it (two eager runs on a side stream first, the tables uploaded before the
     capture), the stage writes straight into the graph's input and the stitch reads its output; stage, stitch and their table
     uploads stay outside the graph.  close() runs eagerly: the last windows' lengths do not repeat.  `captures` counts them.
+    in_sr / out_sr (default None: the streams are at `sr` on both sides and nothing below applies): audio at the rate of its
+    device.  With in_sr, pushed chunks are at in_sr and pass through an audio_io.StreamResampler(slots, in_sr, sr) first; with
+    out_sr, what push and close return has passed through a second one, sr -> out_sr.  Both are exact: the networks see, bit for
+    bit, resample_device(the whole input, in_sr, sr), and the caller gets resample_device(the whole denoised stream, sr, out_sr)
+    -- a live stream and a file of the same audio give the same samples (tests/test_gpu_stream_resample.py).  close() drains in
+    order: the input resampler, the last window, the output resampler; drop() forgets all three.  Each side adds R + 1 samples
+    of latency at its input rate (R = 219 at 48 -> 14 kHz, 64 at 14 -> 48 kHz: 4.6 ms each) and two launches per call.
     Not here: one decision stream per recording (denoise_long's stitch_bits needs frames of the future), given decisions
-    (`bits=`), and the four hand-off signals (`signals=`).
+    (`bits=`), the four hand-off signals (`signals=`), and a res_type other than kaiser_best.
     ValueError before any launch: window_plan's argument rules, slots outside 1 .. 65535, a slot outside the slots (push) or
-    without an open stream (close, drop), a chunk that is not 1-D float32, a closed stream below MIN_FRAMES frames (the slot is
-    named and free again; the other named slots stay open)."""
+    without an open stream (close, drop), a chunk that is not 1-D float32, a closed stream below MIN_FRAMES frames at `sr` (the
+    slot is named and free again; the other named slots stay open), StreamResampler's refusals of in_sr / out_sr."""
 
     def __init__(self, detector, denoiser, slots, sr=SR, fps=FPS, window_seconds=2.0, context_seconds=0.5, max_batch=256,
-                 max_columns=65536, graph=False, device=None):
+                 max_columns=65536, graph=False, device=None, in_sr=None, out_sr=None):
         self.core, self.context = _hops(round(window_seconds * sr)), _hops(round(context_seconds * sr))
         StreamPlan(self.core, self.context)
         if not 1 <= int(slots) <= ragged.MAX_CLIPS:
             raise ValueError(f"StreamDenoiser: 1 .. {ragged.MAX_CLIPS} slots, got {slots}")
+        from .audio_io import StreamResampler
+        self.rs_in = None if in_sr is None else StreamResampler(slots, in_sr, sr, device=device)
+        self.rs_out = None if out_sr is None else StreamResampler(slots, sr, out_sr, max_chunk=self.core, device=device)   # a step's output
         self.detector, self.denoiser, self.sr, self.fps = detector, denoiser, sr, fps
         self.max_batch, self.max_columns, self.graph = min(int(max_batch), ragged.MAX_CLIPS), int(max_columns), bool(graph)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -855,13 +865,7 @@ class StreamDenoiser:
 
     def _flat(self, chunks):
         """The chunks back to back in one device buffer (host arrays go up in one copy) and where each starts."""
-        import numpy as np
-        from .engine import upload
-        host = [c for c in chunks if not torch.is_tensor(c) and c.shape[0]]
-        up = iter(ragged.split(upload(np.concatenate(host), torch.float32, self.device), [c.shape[0] for c in host]) if host else [])
-        parts = [(c.to(self.device).contiguous() if torch.is_tensor(c) else next(up)) for c in chunks if c.shape[0]]
-        flat = (torch.cat(parts) if len(parts) > 1 else parts[0]) if parts else None
-        return flat, ragged.offsets([c.shape[0] for c in chunks]).tolist()
+        return tools.stream_flat(chunks, self.device)
 
     @torch.no_grad()
     def push(self, chunks):
@@ -875,6 +879,13 @@ class StreamDenoiser:
                 raise ValueError(f"StreamDenoiser.push: slot {s}: a chunk is a 1-D float32 GPU tensor or numpy array")
             if torch.is_tensor(c):
                 tools.L.require_cuda(c)
+        if self.rs_in is not None:                              # chunks at in_sr -> what of them is final at the model rate
+            chunks = self.rs_in.push(chunks)
+        outs = self._push(chunks)
+        return outs if self.rs_out is None else self.rs_out.push(outs)
+
+    def _push(self, chunks):
+        """push() for checked chunks at the model rate."""
         slots = list(chunks)
         for s in slots:
             if self.plans[s] is None:
@@ -902,6 +913,8 @@ class StreamDenoiser:
         """Ends the streams of `slots` (an iterable of slots, or one): -> {slot: the remaining final samples}; the slots are free."""
         slots = self._open(slots, "close")
         hop = transform.HOP_LENGTH
+        if self.rs_in is not None or self.rs_out is not None:
+            return self._close_resampled(slots)
         short = [s for s in slots if 1 + self.plans[s].n_in // hop < MIN_FRAMES]
         if short:                                               # the other named streams stay open
             told = "; ".join(f"slot {s} got {self.plans[s].n_in} samples" for s in short)
@@ -915,10 +928,40 @@ class StreamDenoiser:
             self.plans[s] = None
         return {s: o[0] for s, o in outs.items()}
 
+    def _close_resampled(self, slots):
+        """close() with in_sr / out_sr: the input resampler is drained first, then the last window, then the output resampler."""
+        hop = transform.HOP_LENGTH
+        # the stream's length at the model rate once its input resampler is closed
+        total = {s: self.rs_in.out_length(s) if self.rs_in is not None else self.plans[s].n_in for s in slots}
+        short = [s for s in slots if 1 + total[s] // hop < MIN_FRAMES]
+        if short:                                               # the other named streams stay open
+            told = "; ".join(f"slot {s} got {total[s]} samples" for s in short)
+            self._forget(short)
+            raise ValueError(f"StreamDenoiser.close: streams need at least {MIN_FRAMES} STFT frames ({MIN_FRAMES * hop} samples at "
+                             f"{self.sr} Hz): {told}")
+        parts = {s: [] for s in slots}
+        if self.rs_in is not None:
+            for s, y in self._push(self.rs_in.close(slots)).items():
+                parts[s].append(y)
+        self._run([(s, self.plans[s].close()[0]) for s in slots], parts, False)
+        for s in slots:
+            self.plans[s] = None
+        outs = {s: torch.cat(o) if len(o) > 1 else o[0] for s, o in parts.items()}
+        if self.rs_out is None:
+            return outs
+        head, rest = self.rs_out.push(outs), self.rs_out.close(slots)
+        return {s: torch.cat([head[s], rest[s]]) for s in slots}
+
+    def _forget(self, slots):
+        for s in slots:
+            self.plans[s] = None
+            for rs in (self.rs_in, self.rs_out):
+                if rs is not None and rs.n_recv[s] is not None:
+                    rs.drop([s])
+
     def drop(self, slots):
         """Forgets the streams of `slots` without output; the slots are free."""
-        for s in self._open(slots, "drop"):
-            self.plans[s] = None
+        self._forget(self._open(slots, "drop"))
 
     def _run(self, items, outs, graph):
         """One window (slot, row of StreamPlan) per slot: staged, denoised and stitched in groups; appends to outs[slot]."""

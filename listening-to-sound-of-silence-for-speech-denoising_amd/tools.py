@@ -278,6 +278,43 @@ def stream_stitch(rows, table, context, tail, out_stride=None):
     return out, lengths.tolist()
 
 
+STREAM_RESAMPLE_COLS = 6                                               # int64 per row (csrc/stream_resample.hip: SRS_COLS)
+
+
+def stream_resample(ring, table, ratio, win, num_table, out=None):
+    """Outputs of streams resampled out of their rings in one launch (sos_stream_resample_f32).  ring: (slots, capacity) f32 GPU
+    tensor as stream_push fills it; table: host rows {slot, t_lo, t_hi, n_in, n_valid, output offset}, a slot at most once: the
+    outputs t_lo <= t < t_hi of the slot's stream, each as audio_io.resample_device computes it for a signal of n_in samples
+    (zero from n_valid on), go to out[output offset ..]; ratio = target / orig; win, num_table: the filter's half window on the
+    GPU, scaled by min(1, ratio), and its points per zero crossing (audio_io._filter_on).
+    -> out, a contiguous 1-D f32 GPU tensor: the one given, or a new one that ends with the last row's outputs."""
+    L.require_cuda(ring, win, out)
+    tab = _host_table(table, STREAM_RESAMPLE_COLS)
+    _stream_ring(ring)
+    if win.dim() != 1 or win.dtype != torch.float32 or not win.is_contiguous():
+        raise ValueError("win must be a contiguous 1-D float32 tensor")
+    if out is None:
+        out = torch.empty(max(int((tab[:, 5] + np.maximum(tab[:, 2] - tab[:, 1], 0)).max()), 0), dtype=torch.float32, device=ring.device)
+    elif out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous 1-D float32 tensor")
+    d_tab = _upload(tab, ring.device)
+    L.check(L.lib().sos_stream_resample_f32(L.ptr(ring), ring.shape[0], ring.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
+                                            float(ratio), L.ptr(win), win.numel(), int(num_table), L.ptr(out), out.numel(),
+                                            L.stream_ptr()), "sos_stream_resample_f32")
+    return out
+
+
+def stream_flat(chunks, device):
+    """Chunks (1-D f32 GPU tensors or numpy arrays) back to back in one device buffer (host arrays go up in one copy) and where
+    each starts: -> (flat or None if all are empty, offsets)."""
+    from .engine import upload
+    host = [c for c in chunks if not torch.is_tensor(c) and c.shape[0]]
+    up = iter(ragged.split(upload(np.concatenate(host), torch.float32, device), [c.shape[0] for c in host]) if host else [])
+    parts = [(c.to(device).contiguous() if torch.is_tensor(c) else next(up)) for c in chunks if c.shape[0]]
+    flat = (torch.cat(parts) if len(parts) > 1 else parts[0]) if parts else None
+    return flat, ragged.offsets([c.shape[0] for c in chunks]).tolist()
+
+
 def convert_bitstreammask_to_audiomask(ref_audio_signal, frames_to_audiosample_ratio, bitstream):
     """M2/tools.py:340-362 (string bits) / M1/tools.py:770-792 (int bits): same arguments, same
     RuntimeError on an invalid bit, same dtype as `ref_audio_signal`."""
