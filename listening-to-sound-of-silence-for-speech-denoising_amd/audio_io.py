@@ -21,6 +21,7 @@ import torch
 
 from . import _lib as L
 from . import ragged
+from . import session
 from . import tools
 
 # resampy 0.2.2 `kaiser_best`: 64 zero crossings, 2**9 table points per crossing, Kaiser beta, roll-off
@@ -161,15 +162,6 @@ class StreamResampler:
         self.win, self.num_table = _filter_on(self.device, self.ratio, res_type)
         self.ring = torch.zeros((int(slots), self.capacity), dtype=torch.float32, device=self.device)
 
-    def _open(self, slots, who):
-        slots = [slots] if isinstance(slots, int) else list(slots)
-        for s in slots:
-            if not isinstance(s, int) or not 0 <= s < len(self.n_recv) or self.n_recv[s] is None:
-                raise ValueError(f"StreamResampler.{who}: slot {s!r} has no open stream")
-        if len(set(slots)) != len(slots):
-            raise ValueError(f"StreamResampler.{who}: a slot is named twice")
-        return slots
-
     def _ready(self, n_recv):
         t, b = C.c_int64(0), C.c_int64(0)
         L.check(L.lib().sos_stream_resample_ready(self.ratio, self.win.numel(), self.num_table, n_recv, C.byref(t), C.byref(b)),
@@ -185,13 +177,7 @@ class StreamResampler:
         return (int(np.ceil(n * self.ratio)) if self.fix else n_res) if n_res >= 1 else 0
 
     def push(self, chunks):
-        for s, c in chunks.items():
-            if not isinstance(s, int) or not 0 <= s < len(self.n_recv):
-                raise ValueError(f"StreamResampler.push: unknown slot {s!r} (0 .. {len(self.n_recv) - 1})")
-            if not (torch.is_tensor(c) or isinstance(c, np.ndarray)) or c.ndim != 1 or c.dtype != (torch.float32 if torch.is_tensor(c) else np.float32):
-                raise ValueError(f"StreamResampler.push: slot {s}: a chunk is a 1-D float32 GPU tensor or numpy array")
-            if torch.is_tensor(c):
-                L.require_cuda(c)
+        session.check_chunks("StreamResampler.push", chunks, len(self.n_recv))
         slots = list(chunks)
         for s in slots:
             if self.n_recv[s] is None:
@@ -201,30 +187,27 @@ class StreamResampler:
         if self.ring is None:                                   # the same rate: the chunks themselves, on the device
             for i, s in enumerate(slots):
                 self.n_recv[s] += left[i]
-            return dict(zip(slots, ragged.split(flat, left) if flat is not None else [self._empty()] * len(slots)))
+            return dict(zip(slots, ragged.split(flat, left) if flat is not None else [session.empty(self.device)] * len(slots)))
         # every count is the host's: what each slot emits in this call, hence where its outputs lie in the one buffer
-        first = [self.t_done[s] for s in slots]
-        counts = [self._ready(self.n_recv[s] + left[i])[0] - first[i] for i, s in enumerate(slots)]
-        where = ragged.offsets(counts).tolist()
+        counts = [self._ready(self.n_recv[s] + left[i])[0] - self.t_done[s] for i, s in enumerate(slots)]
+        where = {s: w - self.t_done[s] for s, w in zip(slots, ragged.offsets(counts).tolist())}      # of the stream's output 0
         out = torch.empty(sum(counts), dtype=torch.float32, device=self.device)
-        while any(left):
-            fill, rows = [], []
-            for i, s in enumerate(slots):
-                take = min(left[i], self.capacity - (self.n_recv[s] - self.base[s]))      # at least min(left, max_chunk)
-                if take:
-                    fill.append((s, offs[i], take, self.n_recv[s]))
-                    offs[i], left[i], self.n_recv[s] = offs[i] + take, left[i] - take, self.n_recv[s] + take
-                    t_new, base = self._ready(self.n_recv[s])
-                    if t_new > self.t_done[s]:
-                        rows.append((s, self.t_done[s], t_new, self.n_recv[s], t_new, where[i] + self.t_done[s] - first[i]))
-                    self.t_done[s], self.base[s] = t_new, base
+        # a slot's ring has room for at least min(left, max_chunk)
+        for fill in session.fill_rounds(slots, offs, left, lambda s: (self.capacity - (self.n_recv[s] - self.base[s]), self.n_recv[s])):
+            rows = []
+            for s, _, take, _ in fill:
+                self.n_recv[s] += take
+                t_new, base = self._ready(self.n_recv[s])
+                if t_new > self.t_done[s]:
+                    rows.append((s, self.t_done[s], t_new, self.n_recv[s], t_new, where[s] + self.t_done[s]))
+                self.t_done[s], self.base[s] = t_new, base
             tools.stream_push(flat, fill, self.ring)
             if rows:
                 tools.stream_resample(self.ring, rows, self.ratio, self.win, self.num_table, out=out)
         return dict(zip(slots, ragged.split(out, counts)))
 
     def close(self, slots):
-        slots = self._open(slots, "close")
+        slots = session.open_slots("StreamResampler.close", slots, self.n_recv)
         short = [s for s in slots if self.out_length(s) < 1 and self.ring is not None]
         if short:                                               # the other named streams stay open
             told = "; ".join("slot %d: Input signal length=%d is too small to resample from %s->%s"
@@ -244,14 +227,11 @@ class StreamResampler:
                 tools.stream_resample(self.ring, rows, self.ratio, self.win, self.num_table, out=out)
         for s in slots:
             self.n_recv[s] = None
-        return dict(zip(slots, ragged.split(out, counts) if out is not None else [self._empty()] * len(slots)))
+        return dict(zip(slots, ragged.split(out, counts) if out is not None else [session.empty(self.device)] * len(slots)))
 
     def drop(self, slots):
-        for s in self._open(slots, "drop"):
+        for s in session.open_slots("StreamResampler.drop", slots, self.n_recv):
             self.n_recv[s] = None
-
-    def _empty(self):
-        return torch.empty(0, dtype=torch.float32, device=self.device)
 
 
 def pcm_to_mono_device(pcm, fmt):

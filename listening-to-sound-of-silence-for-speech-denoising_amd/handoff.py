@@ -613,61 +613,58 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
     return stat
 
 
+def _round_trip(wave, ns):
+    """STFT -> ISTFT of the rows of a padded buffer, every row at its own `ns` samples (hop * (n // hop) come back)."""
+    from . import engine as E
+    rag = E.Ragged([1 + n // transform.HOP_LENGTH for n in ns], wave.device, n_samples=ns)
+    return transform.istft_batch(transform.stft_batch(wave, clip_samples=rag.tab(ns)), clip_frames=rag.level(0))
+
+
 def _first_model_windows(net, mixed, noise, clean, all_bits, nb, ngt, ratios, framerates, sr, window_seconds, context_seconds,
                          max_batch, max_columns, download):
     """The windowed half of denoise_first_model: `mixed` (one 1-D GPU recording per file; `noise` / `clean`: the ground-truth
     recordings or empty lists), all_bits = the files' `recovered_prediction` decisions (nb each) followed by the ground-truth
     ones (ngt each) in one GPU buffer.  -> per file ([4 signals], [2 ground-truth signals] or None, host arrays of the
     4 (6) signals as _write_individual_host takes them, or None without `download`).
-    The four signals: pipeline._long_signal_rows over the windows of all files, then ONE sos_window_stitch_planes_f32 launch into
+    The four signals: windows._masked_group(signals=True) over the windows of all files, then ONE sos_window_stitch_planes_f32 launch into
     a file-major buffer -- the four signals of a file next to each other, every segment on a multiple of four floats (16-byte
     stores) -- and ONE device-to-host copy of it, with no launch in between.
     The ground-truth signals (the STFT -> ISTFT round trips of `full_noise` and of the clean recording silenced on its
     ground-truth silent intervals) are further recordings under a plan of their own, since their lengths may differ from the
     mixed file's: sos_window_stage_f32 per group, sos_window_stage_masked_f32 and wave - masked for the clean windows
     (M2/predict.py:321), one sos_window_stitch_f32, cropped to the output length as on the whole-file path."""
-    from . import engine as E
-    from . import pipeline
-    F, hop, device = len(mixed), transform.HOP_LENGTH, mixed[0].device
-    core, context, ns, plan = pipeline._long_plan("denoise_first_model", mixed, sr, window_seconds, context_seconds)
+    from . import windows
+    F, device = len(mixed), mixed[0].device
+    core, context, ns, plan = windows._long_plan("denoise_first_model", mixed, sr, window_seconds, context_seconds)
     flat, _ = ragged.concat(mixed)
     rates = np.asarray(framerates, dtype=np.float64)
-    kept = pipeline._long_signal_rows(net, flat, plan, all_bits, ragged.clip_table(ns, nb), ratios, rates[plan[:, 0]], sr,
-                                      max_batch, max_columns)
-    lens = [hop * (n // hop) for n in ns]
+    kept = windows._run_windows(plan, flat.device, max_batch, max_columns, windows._masked_group(
+        net, flat, all_bits, ragged.clip_table(ns, nb), ratios, rates[plan[:, 0]], sr, signals=True), planes=4)
+    lens = windows._out_lengths(ns)
     pitch = [-(-n // 4) * 4 for n in lens]
     base = (4 * ragged.offsets(pitch)).tolist()
-    buf = pipeline._stitch_signals(kept, plan, context, recs=np.stack([base, pitch], axis=1), out_total=4 * sum(pitch))
+    buf = windows._stitch_signals(kept, plan, context, recs=np.stack([base, pitch], axis=1), out_total=4 * sum(pitch))
     host = buf.cpu().numpy() if download else None              # the four signals of every file: one copy
     sigs = [[buf[base[i] + q * pitch[i]:base[i] + q * pitch[i] + lens[i]] for q in range(4)] for i in range(F)]
     hosts = [[host[base[i] + q * pitch[i]:base[i] + q * pitch[i] + lens[i]] for q in range(4)] if download else None for i in range(F)]
     if not noise:
         return sigs, [None] * F, hosts
     # recordings 0 .. F - 1: full_noise, F .. 2 F - 1: clean, with its ground-truth decisions
-    _, _, ng, gplan = pipeline._long_plan("denoise_first_model", noise + clean, sr, window_seconds, context_seconds)
+    _, _, ng, gplan = windows._long_plan("denoise_first_model", noise + clean, sr, window_seconds, context_seconds)
     gflat, _ = ragged.concat(noise + clean)
     gtable = ragged.clip_table(ng, [0] * F + list(ngt))
     gbits = all_bits[sum(nb):]
-    ms = gplan[:, 2].tolist()
-    gkept = torch.empty((len(gplan), hop * (max(ms) // hop)), dtype=torch.float32, device=device)
-    done = 0
-    for part in pipeline._length_groups(ms, min(max_batch, ragged.MAX_CLIPS), max_columns):
-        m = [ms[i] for i in part]
-        sub = np.ascontiguousarray(gplan[part])
+
+    def run_group(part, sub, m, rows):
         wave = tools.window_stage(gflat, sub, max(m))
         silenced = np.flatnonzero(sub[:, 0] >= F)
         if len(silenced):
             w, masked = tools.window_stage_masked(gflat, gbits, gtable, list(ratios) * 2, sub[silenced], max(m))
             wave[torch.from_numpy(silenced).to(device)] = w - masked
-        grag = E.Ragged([1 + n // hop for n in m], device, n_samples=m)
-        y = transform.istft_batch(transform.stft_batch(wave, clip_samples=grag.tab(m)), clip_frames=grag.level(0))
-        gkept[done:done + len(part), :y.shape[1]] = y
-        gplan[part, 7] = np.arange(done, done + len(part))
-        done += len(part)
-    rows = gplan.copy()
-    rows[:, 2] = hop * (gplan[:, 2] // hop)
-    glens = [hop * (n // hop) for n in ng]
-    gt = ragged.split(tools.window_stitch(gkept, rows, context), glens)
+        return _round_trip(wave, m)
+
+    gkept = windows._run_windows(gplan, device, max_batch, max_columns, run_group)
+    gt = ragged.split(tools.window_stitch(gkept, windows._row_plan(gplan), context), windows._out_lengths(ng))
     gts = [[gt[i], gt[F + i]] for i in range(F)]
     if download:                                                 # cropped like _write_individual: one more copy
         gh = ragged.download([g[:lens[i]] for i in range(F) for g in gts[i]])
@@ -773,10 +770,8 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
         gt = None
         if known:
             wave[2 * B:].sub_(masked[2 * B:])        # silent intervals of the clean signal truly silent (M2/predict.py:321)
-            Tg = [1 + n // hop for n in ns[B:]]
-            grag = E.Ragged(Tg, device, n_samples=ns[B:])
-            gt = transform.istft_batch(transform.stft_batch(wave[B:], clip_samples=grag.tab(ns[B:])), clip_frames=grag.level(0))
-            n_gt = [hop * (t - 1) for t in Tg]
+            gt = _round_trip(wave[B:], ns[B:])
+            n_gt = [hop * (n // hop) for n in ns[B:]]
         host = None
         if save_individual_results:                  # the signals of the whole group: one unpack launch, one download
             if known:                                # ground-truth rows follow the group's 4 B rows, cropped like _write_individual

@@ -30,6 +30,10 @@ import sos_amd  # noqa: E402
 from oracle import nets as onet  # noqa: E402
 from sos_amd import _lib as L  # noqa: E402
 from sos_amd import pipeline, tools, transform  # noqa: E402
+try:
+    from sos_amd import windows  # noqa: E402
+except ImportError:                 # --root: a checkout from before the windowed layer had a module of its own
+    windows = pipeline
 
 SR = 14000
 
@@ -86,7 +90,7 @@ def speed(args, det, jm):
         sos_amd.set_precision("bf16")
     # the two kernels alone, on resident buffers
     hop = transform.HOP_LENGTH
-    context = pipeline._hops(round(args.context * SR))
+    context = windows._hops(round(args.context * SR))
     plan = np.ascontiguousarray(pipeline.window_plan([n], round(30.0 * SR), context))
     stride = int(plan[:, 2].max())
     rows = tools.window_stage(clip, plan, stride)
@@ -139,7 +143,7 @@ def decisions(args, det, jm):
     # the two kernels alone, on resident buffers: the mixed batch's plan
     from sos_amd import ragged
     ns = [int(c.numel()) for c in mixed]
-    core, context = pipeline._hops(round(30.0 * SR)), pipeline._hops(round(args.context * SR))
+    core, context = windows._hops(round(30.0 * SR)), windows._hops(round(args.context * SR))
     plan = np.ascontiguousarray(pipeline.window_plan(ns, core, context))
     stride, W = int(plan[:, 2].max()), len(plan)
     flat, d_bits = torch.cat(mixed), torch.cat(bits)
@@ -156,8 +160,8 @@ def decisions(args, det, jm):
                                                                   L.ptr(wave), L.stream_ptr())), 200)
     frames = [len(b) for b in bits]
     rates = [30.0] * len(ns)
-    wf = np.asarray(pipeline._window_frames(plan, SR, rates, frames), dtype=np.int64)
-    first = pipeline._first_windows(plan, len(ns))
+    wf = np.asarray(windows._window_frames(plan, SR, rates, frames), dtype=np.int64)
+    first = windows._first_windows(plan, len(ns))
     recs = np.ascontiguousarray(np.stack([ragged.offsets(frames), np.asarray(frames, dtype=np.int64), first[:-1], np.diff(first)], axis=1))
     logit_rows = torch.randn((W, int(wf.max())), device="cuda")
     out = tools.window_frames_stitch(logit_rows, plan, wf, recs, rat, core, context)
@@ -196,7 +200,7 @@ def signals(args, det, jm):
     # the kernels alone, on resident buffers: the mixed batch's plan, four planes of random rows
     hop, planes = transform.HOP_LENGTH, 4
     ns = [int(c.numel()) for c in mixed]
-    core, context = pipeline._hops(round(30.0 * SR)), pipeline._hops(round(args.context * SR))
+    core, context = windows._hops(round(30.0 * SR)), windows._hops(round(args.context * SR))
     held = np.ascontiguousarray(pipeline.window_plan(ns, core, context))
     held[:, 2] = hop * (held[:, 2] // hop)                      # what a window's row holds
     W, stride = len(held), int(held[:, 2].max())

@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 import sos_amd  # noqa: E402
 from oracle import nets as onet  # noqa: E402
 from sos_amd import _lib as L  # noqa: E402
-from sos_amd import pipeline, tools  # noqa: E402
+from sos_amd import pipeline, tools, windows  # noqa: E402
 
 SR = 14000
 
@@ -106,7 +106,7 @@ def sessions(args, det, jm):
 
 def kernels(args):
     slots = max(args.slots)
-    core, context = pipeline._hops(round(args.window * SR)), pipeline._hops(round(args.context * SR))
+    core, context = windows._hops(round(args.window * SR)), windows._hops(round(args.context * SR))
     cap, m = 2 * core + context, core + 2 * context
     ring, tail = torch.randn((slots, cap), device="cuda"), torch.randn((slots, 2, 2 * context), device="cuda")
     stage = np.ascontiguousarray(np.asarray([(s, 5 * core - context, m) for s in range(slots)], dtype=np.int64))
