@@ -456,6 +456,30 @@ enum { SOS_PCM_S16 = 0, SOS_PCM_S32 = 1, SOS_PCM_F32 = 2, SOS_PCM_U8 = 3 };
 /* pcm: interleaved [n_frames][channels] device samples -> out f32 [n_frames] = mean over channels of
  * sample / 2^(bits-1) (u8: (v-128)/128; f32: as is). */
 int sos_pcm_to_mono_f32(const void* pcm, int format, int channels, int64_t n_frames, float* out, sos_stream_t stream);
+/* The same decode WITHOUT the mix-down, and its inverse, for a group of files in one launch each (csrc/pcm_io.hip;
+ * sos_amd.audio_io.decode_planes_batch_device / encode_batch_device; float64 restatement: tests/pcm_reference.py).  Both follow
+ * the ragged conventions below (sos_ragged_stage_f32): an int64 table in two copies, table on the device and table_host on the
+ * HOST; the host validates its own copy before any launch, the kernels follow the device copy and skip a row that does not lie
+ * inside the totals the host summed.  1 .. 65535 files per call.
+ * sos_pcm_planes_batch_f32: pcm = the interleaved [frames][channels] samples of files that share one SOS_PCM_* format, back to
+ *   back.  Row per file, int64 [nfiles][4] = {element offset into pcm, frames, channels (1 .. 64), first output sample}; files
+ *   lie in table order without overlap on both sides.  out: f32 channel planes, channel c of file f at out[row.out + c * frames
+ *   .. + frames), every value bit for bit sample / 2^(bits-1) as sos_pcm_to_mono_f32 converts it (one channel: the same bits).
+ * sos_pcm_encode_batch: planes = f32 channel planes.  Row per file, int64 [nfiles][5] = {first plane sample, plane length
+ *   available, channels (1 .. 64), frames to write, output ELEMENT offset}: channel c is planes[row.first + c * available ..
+ *   + available).  out: interleaved [frames][channels] per file in `format`, files back to back in table order; an element is
+ *   2 / 3 / 4 / 1 / 4 bytes for SOS_ENC_S16 / S24 (packed, little-endian) / S32 / U8 / F32.  Per sample: x = the plane's value
+ *   below `available`, 0 from there to `frames` (crop and zero-fill happen here); F32 copies the bits; otherwise q =
+ *   rint((double)x * S) half to even with S = 2^15 / 2^23 / 2^31 / 2^7, NaN -> 0, saturated to [-S, S - 1]; U8 stores q + 128.
+ *   clipped: int64 [nfiles], set by the call to the number of the file's samples that were NaN or changed by saturation
+ *   (+-inf included; 0 for F32).  No dither.  No byte outside a file's frames * channels * width bytes is written.
+ * SOS_EINVAL (sos_last_error() names the file): null pointers, nfiles outside 1 .. 65535, an unknown format, channels outside
+ * 1 .. 64, negative frames / available, or a row that overlaps its predecessor or lies outside the totals. */
+enum { SOS_ENC_S16 = 0, SOS_ENC_S32 = 1, SOS_ENC_F32 = 2, SOS_ENC_U8 = 3, SOS_ENC_S24 = 4 };
+int sos_pcm_planes_batch_f32(const void* pcm, int format, const int64_t* table, const int64_t* table_host, int nfiles, float* out,
+                             sos_stream_t stream);
+int sos_pcm_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int format, void* out,
+                         int64_t* clipped, sos_stream_t stream);
 /* Band-limited resampling by `ratio` = sr_new / sr_orig (resampy 0.2.2 `resample_f`): win = the filter's half
  * window (nwin floats, num_table samples per zero crossing), already multiplied by min(1, ratio).  Writes
  * out[0 .. n_out): the first floor(n_in * ratio) entries are resampled, the rest zero (librosa pads to

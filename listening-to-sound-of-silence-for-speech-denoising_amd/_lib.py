@@ -126,6 +126,8 @@ SIGNATURES = {
     "sos_wgrad_tune_load": [C.c_char_p],
     "sos_wgrad_describe": [C.POINTER(WgradDesc), C.POINTER(C.c_int32), _I],
     "sos_pcm_to_mono_f32": [_P, _I, _I, _L, _P, _P],
+    "sos_pcm_planes_batch_f32": [_P, _I, _P, _P, _I, _P, _P],
+    "sos_pcm_encode_batch": [_P, _P, _P, _I, _I, _P, _P, _P],
     "sos_resample_f32": [_P, _L, _D, _P, _I, _I, _P, _L, _P],
     "sos_resample_batch_f32": [_P, _P, _P, _I, _D, _P, _I, _I, _P, _P],
     "sos_resample_time_segments": [_D, _L, _P, _P, _P, _I],

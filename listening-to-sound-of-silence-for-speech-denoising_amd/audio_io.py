@@ -8,6 +8,9 @@
       of launches and copies that does not grow with the list (`load_batch_device` / `resample_batch_device` stay in HBM)
   to_mono(y)
   write_wav(path, y, sr, norm=False)
+and, beyond librosa's names, the channel-preserving pair under recordings.py (csrc/pcm_io.hip):
+  load_channels_batch_device(paths, sr=None) / decode_planes_batch_device(arrs, kinds): every channel as an f32 plane
+  encode_batch_device(planes, fmt, frames=None) + wave_container(...): planes -> s16 / s24 / s32 / u8 / f32 WAVE data
 
 The RIFF container is parsed here on the host (bytes -> header fields + one frombuffer view, no per-sample
 Python); sample conversion, channel mix-down and the band-limited resampler are HIP kernels
@@ -248,6 +251,13 @@ def pcm_to_mono_device(pcm, fmt):
 def read_wave(path):
     """Parse a RIFF/WAVE file -> (samples ndarray (n_frames, channels) in a kernel format, fmt, sample rate).
     PCM 8/16/24/32-bit, IEEE float 32/64, WAVE_FORMAT_EXTENSIBLE wrappers of those."""
+    return read_wave_info(path)[:3]
+
+
+def read_wave_info(path):
+    """read_wave plus what the file itself stores: (samples, fmt, sample rate, info) with info = dict(tag, bits, channels, rate,
+    frames) -- `bits` as stored, so 24 stays 24 although the samples are carried as s32, and 64 stays 64 although they are
+    carried as f32."""
     with open(path, "rb") as fp:
         buf = bytearray(os.fstat(fp.fileno()).st_size)       # writable backing store: the sample view goes to torch
         fp.readinto(buf)
@@ -293,7 +303,43 @@ def read_wave(path):
         arr, kind = np.frombuffer(data, dtype="<f8").astype(np.float32), "f32"
     else:
         raise WaveFormatError("%s: unsupported WAVE format tag %d with %d bits" % (path, tag, bits))
-    return arr.reshape(n, ch), kind, rate
+    return arr.reshape(n, ch), kind, rate, dict(tag=tag, bits=bits, channels=ch, rate=rate, frames=n)
+
+
+def wave_info(path):
+    """read_wave_info's `info` from the chunk headers alone (the samples are not read), with the same refusals."""
+    with open(path, "rb") as fp:
+        size_all = os.fstat(fp.fileno()).st_size
+        head = fp.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise WaveFormatError("%s: not a RIFF/WAVE file" % path)
+        fmt, nbytes = None, None
+        while True:
+            ck = fp.read(8)
+            if len(ck) < 8:
+                break
+            cid, size = ck[:4], struct.unpack("<I", ck[4:])[0]
+            if cid == b"fmt ":
+                body = fp.read(size + (size & 1))
+                if size < 16 or len(body) < 16:
+                    raise WaveFormatError("%s: short fmt chunk" % path)
+                tag, ch, rate, _, _, bits = struct.unpack_from("<HHIIHH", body, 0)
+                if tag == 0xFFFE and size >= 26 and len(body) >= 26:
+                    tag = struct.unpack_from("<H", body, 24)[0]
+                fmt = (tag, ch, rate, bits)
+            elif cid == b"data":
+                nbytes = max(0, min(size, size_all - fp.tell()))
+                break
+            else:
+                fp.seek(size + (size & 1), os.SEEK_CUR)
+    if fmt is None or nbytes is None:
+        raise WaveFormatError("%s: missing fmt or data chunk" % path)
+    tag, ch, rate, bits = fmt
+    if ch < 1:
+        raise WaveFormatError("%s: no channels" % path)
+    if (tag, bits) not in ((1, 8), (1, 16), (1, 24), (1, 32), (3, 32), (3, 64)):
+        raise WaveFormatError("%s: unsupported WAVE format tag %d with %d bits" % (path, tag, bits))
+    return dict(tag=tag, bits=bits, channels=ch, rate=rate, frames=nbytes // ((bits // 8) * ch))
 
 
 def load_device(path, sr=22050, mono=True, offset=0.0, duration=None, res_type="kaiser_best", device="cuda"):
@@ -357,6 +403,137 @@ def load_batch_device(paths, sr=22050, mono=True, offset=0.0, duration=None, res
         for i, y in zip(idx, resample_batch_device([ys[i] for i in idx], r, sr, res_type)):
             ys[i] = y
     return ys, [sr] * len(paths)
+
+
+# ------------------------------------------------------------------------------------ channel planes (csrc/pcm_io.hip)
+# encode formats: name -> (SOS_ENC_* of include/sos_hip.h, bytes per element, WAVE format tag, stored bits)
+ENCODINGS = {"s16": (0, 2, 1, 16), "s32": (1, 4, 1, 32), "f32": (2, 4, 3, 32), "u8": (3, 1, 1, 8), "s24": (4, 3, 1, 24)}
+
+
+def _back_to_back(tensors):
+    """One 1-D tensor holding the elements of `tensors` in order: a view when they already lie back to back in one buffer (what
+    ragged.split, resample_batch_device and denoise_long return), their concatenation otherwise."""
+    first = tensors[0]
+    at, base = first.storage_offset(), first.untyped_storage().data_ptr()
+    for t in tensors:
+        if not t.is_contiguous() or t.untyped_storage().data_ptr() != base or t.storage_offset() != at or t.dtype != first.dtype:
+            return torch.cat([t.reshape(-1) for t in tensors])
+        at += t.numel()
+    return first.as_strided((at - first.storage_offset(),), (1,), first.storage_offset())
+
+
+def planes_of(channels):
+    """The equally long 1-D f32 GPU tensors of one file's channels as one (channels, n) tensor (a view if they lie back to back)."""
+    return _back_to_back(list(channels)).view(len(channels), -1)
+
+
+def decode_planes_batch_device(arrs, kinds, device="cuda"):
+    """arrs: one (frames, channels) host array per file as read_wave returns it, kinds: its sample format ('s16', 's32', 'f32',
+    'u8'); channel counts (1 .. 64) may differ from file to file.  -> one (channels, frames) f32 GPU tensor per file, views into
+    ONE buffer, every value bit for bit what pcm_to_mono_device gives a one-channel file (sample / 2^(bits-1)).  Files that share
+    a sample format go up in one copy of their concatenated frames and through one sos_pcm_planes_batch_f32 launch (per 65535
+    files).  ValueError before any launch: an unknown format, a file that is not 2-D or has 0 or more than 64 channels."""
+    arrs, kinds = list(arrs), list(kinds)
+    if len(arrs) != len(kinds):
+        raise ValueError("decode_planes_batch_device: one kind per array (%d arrays, %d kinds)" % (len(arrs), len(kinds)))
+    by_kind = {}
+    for i, (a, k) in enumerate(zip(arrs, kinds)):
+        if k not in _FMT:
+            raise ValueError("decode_planes_batch_device: file %d has the unsupported sample format %r" % (i, k))
+        if a.ndim != 2 or not 1 <= a.shape[1] <= 64:
+            raise ValueError("decode_planes_batch_device: file %d must be (frames, 1 .. 64 channels), got shape %s" % (i, a.shape))
+        if a.shape[0]:
+            by_kind.setdefault(k, []).append(i)
+    if not torch.cuda.is_available():
+        raise RuntimeError("sos_amd.audio_io needs an MI355X: there is no CPU fallback")
+    sizes = np.asarray([a.size for a in arrs], dtype=np.int64)
+    order = [i for idx in by_kind.values() for i in idx]
+    out = torch.empty(int(sizes.sum()), dtype=torch.float32, device=device)
+    where = dict(zip(order, ragged.offsets(sizes[order]).tolist()))
+    h = L.lib()
+    for k, idx in by_kind.items():
+        pcm = torch.from_numpy(np.concatenate([arrs[i].reshape(-1) for i in idx])).to(device)
+        off = ragged.offsets(sizes[idx])
+        for c0 in range(0, len(idx), ragged.MAX_CLIPS):
+            sel = idx[c0:c0 + ragged.MAX_CLIPS]
+            o0 = where[sel[0]]
+            tab = np.asarray([[off[c0 + j] - off[c0], arrs[i].shape[0], arrs[i].shape[1], where[i] - o0] for j, i in enumerate(sel)],
+                             dtype=np.int64)
+            tab_dev = torch.from_numpy(tab).to(device)
+            L.check(h.sos_pcm_planes_batch_f32(L.ptr(pcm[int(off[c0]):]), _FMT[k], L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p),
+                                               len(sel), L.ptr(out[o0:]), L.stream_ptr()), "sos_pcm_planes_batch_f32")
+    return [out[where[i]:where[i] + a.size].view(a.shape[1], a.shape[0]) if a.shape[0]
+            else torch.zeros((a.shape[1], 0), dtype=torch.float32, device=device) for i, a in enumerate(arrs)]
+
+
+def load_channels_batch_device(paths, sr=None, res_type="kaiser_best", device="cuda"):
+    """Every channel of every file of a list, nothing mixed down: (ys, srs, infos) with ys[i] a (channels, n) f32 GPU tensor (a
+    view into one buffer), srs[i] its rate and infos[i] = read_wave_info's dict(tag, bits, channels, rate, frames) of the SOURCE
+    (bits as stored).  Every file is parsed on the host; files that share a sample format go up in one copy and through one
+    decode launch (decode_planes_batch_device); with `sr`, all channels of all files that share a native rate other than `sr` go
+    through ONE resample_batch_device call, channel c of file i bit for bit resample_device(ys[i][c]).  sr=None keeps the native
+    rates.  (load_device / load_batch_device with mono=False keep raising: they are librosa's signatures.)"""
+    paths = list(paths)
+    parsed = [read_wave_info(p) for p in paths]
+    ys = decode_planes_batch_device([p[0] for p in parsed], [p[1] for p in parsed], device)
+    rates, infos = [p[2] for p in parsed], [p[3] for p in parsed]
+    if sr is None:
+        return ys, rates, infos
+    by_rate = {}
+    for i, r in enumerate(rates):
+        if r != sr and ys[i].shape[1]:
+            by_rate.setdefault(r, []).append(i)
+    for r, idx in by_rate.items():
+        outs = resample_batch_device([ys[i][c] for i in idx for c in range(ys[i].shape[0])], r, sr, res_type)
+        k = 0
+        for i in idx:
+            ch = ys[i].shape[0]
+            ys[i] = planes_of(outs[k:k + ch])
+            k += ch
+    return ys, [sr] * len(paths), infos
+
+
+def encode_batch_device(planes, fmt, frames=None):
+    """planes: one (channels, n) f32 GPU tensor per file; fmt: 's16', 's24' (packed, 3 bytes little-endian), 's32', 'u8' or
+    'f32'; frames: samples per channel to write per file (default: n).  -> (data, offsets, clipped): one uint8 GPU tensor with
+    the files' interleaved [frames][channels] data back to back, the host int64 byte offsets (files + 1 entries) and an int64
+    GPU tensor of per-file counts, from ONE sos_pcm_encode_batch launch (per 65535 files).  Per sample: the plane's value below
+    n and 0 from there to `frames` (crop / zero-fill happen in the kernel); f32 copies the bits; otherwise q = rint(x * S) half
+    to even in double with S = 2^(bits-1), NaN -> 0, saturated to [-S, S - 1]; u8 stores q + 128.  clipped[f] counts the samples
+    that were NaN or changed by saturation (+-inf included).  NO dither is applied (out of scope): quantisation error is
+    correlated with the signal, as with soundfile's and scipy's integer writers.  Float64 restatement: tests/pcm_reference.py."""
+    planes = list(planes)
+    if fmt not in ENCODINGS:
+        raise ValueError("encode_batch_device: unsupported sample format %r (one of %s)" % (fmt, ", ".join(sorted(ENCODINGS))))
+    code, width = ENCODINGS[fmt][:2]
+    for i, p in enumerate(planes):
+        if not torch.is_tensor(p) or p.dim() != 2 or p.dtype != torch.float32 or not 1 <= p.shape[0] <= 64:
+            raise ValueError("encode_batch_device: file %d must be a (1 .. 64 channels, n) float32 tensor" % i)
+    L.require_cuda(*planes)
+    frames = [int(p.shape[1]) for p in planes] if frames is None else [int(f) for f in frames]
+    if len(frames) != len(planes) or min(frames, default=0) < 0:
+        raise ValueError("encode_batch_device: frames holds one non-negative count per file")
+    chans = np.asarray([p.shape[0] for p in planes], dtype=np.int64)
+    avail = np.asarray([p.shape[1] for p in planes], dtype=np.int64)
+    elems = chans * np.asarray(frames, dtype=np.int64)
+    offsets = np.concatenate([ragged.offsets(elems), [elems.sum()]]).astype(np.int64) * width
+    if not planes:
+        return torch.zeros(0, dtype=torch.uint8, device="cuda"), offsets, torch.zeros(0, dtype=torch.int64, device="cuda")
+    device = planes[0].device
+    flat = _back_to_back(planes) if int((chans * avail).sum()) else torch.zeros(1, dtype=torch.float32, device=device)
+    src = ragged.offsets(chans * avail)
+    data = torch.empty(max(int(offsets[-1]), 1), dtype=torch.uint8, device=device)
+    clipped = torch.empty(len(planes), dtype=torch.int64, device=device)
+    h = L.lib()
+    for c0 in range(0, len(planes), ragged.MAX_CLIPS):
+        c1 = min(c0 + ragged.MAX_CLIPS, len(planes))
+        e0 = int(offsets[c0]) // width
+        tab = np.ascontiguousarray(np.stack([src[c0:c1] - src[c0], avail[c0:c1], chans[c0:c1], np.asarray(frames[c0:c1], dtype=np.int64),
+                                             offsets[c0:c1] // width - e0], axis=1), dtype=np.int64)
+        tab_dev = torch.from_numpy(tab).to(device)
+        L.check(h.sos_pcm_encode_batch(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, code,
+                                       L.ptr(data[e0 * width:]), L.ptr(clipped[c0:]), L.stream_ptr()), "sos_pcm_encode_batch")
+    return data[:int(offsets[-1])], offsets, clipped
 
 
 def load_batch(paths, sr=22050, mono=True, offset=0.0, duration=None, dtype=np.float32, res_type="kaiser_best"):
@@ -431,18 +608,36 @@ def wave_bytes(y, sr):
         raise ValueError("Unsupported data type '%s'" % y.dtype)
     tag = 3 if kind == "f" else 1
     bits = y.dtype.itemsize * 8
+    data = np.ascontiguousarray(y).astype(y.dtype.newbyteorder("<"), copy=False).tobytes()
+    return _riff(data, tag, ch, sr, bits, y.shape[0])
+
+
+def _riff(data, tag, ch, sr, bits, frames):
+    """The chunks around `data`: a 16-byte fmt chunk for PCM; an 18-byte one and a `fact` chunk with the frame count otherwise."""
     align = ch * (bits // 8)
     fmt = struct.pack("<HHIIHH", tag, ch, int(sr), int(sr) * align, align, bits)
     if tag != 1:
         fmt += b"\x00\x00"
     head = b"fmt " + struct.pack("<I", len(fmt)) + fmt
     if tag != 1:
-        head += b"fact" + struct.pack("<II", 4, y.shape[0])
-    data = np.ascontiguousarray(y).astype(y.dtype.newbyteorder("<"), copy=False).tobytes()
+        head += b"fact" + struct.pack("<II", 4, frames)
     if len(head) + len(data) + 12 > 0xFFFFFFFF:
         raise ValueError("Data exceeds wave file size limit")
     body = b"WAVE" + head + b"data" + struct.pack("<I", len(data)) + data
     return b"RIFF" + struct.pack("<I", len(body)) + body
+
+
+def wave_container(data_bytes, tag, channels, rate, bits):
+    """The RIFF/WAVE file around already-encoded interleaved data (encode_batch_device's bytes): tag 1 (PCM) with a 16-byte
+    fmt chunk, tag 3 (IEEE float) with an 18-byte fmt chunk and a `fact` chunk, the chunks of wave_bytes -- for mono or
+    interleaved f32 data, wave_container(y.tobytes(), 3, channels, sr, 32) == wave_bytes(y, sr)."""
+    data = bytes(data_bytes)
+    if tag not in (1, 3) or bits % 8 or bits < 8 or channels < 1:
+        raise ValueError("wave_container: tag 1 (PCM) or 3 (float), whole bytes per sample, at least one channel")
+    align = channels * (bits // 8)
+    if len(data) % align:
+        raise ValueError("wave_container: %d bytes are no whole number of %d-byte frames" % (len(data), align))
+    return _riff(data, tag, channels, rate, bits, len(data) // align)
 
 
 def write_wav(path, y, sr, norm=False):

@@ -1,0 +1,295 @@
+// pcm_io.hip -- the two copies between "WAVE data as the file holds it" and "one f32 plane per channel", each for a group of
+// files in ONE launch (audio_io.decode_planes_batch_device / encode_batch_device; float64 restatement: tests/pcm_reference.py):
+//   pcm_planes_kernel   interleaved [frames][channels] samples of one format, files back to back -> f32 channel planes
+//   pcm_encode_kernel   f32 channel planes -> interleaved s16 / packed s24 / s32 / u8 / f32, files back to back, plus the
+//                       number of samples per file that saturated or were NaN
+// Pure streaming, no reuse: every input sample is read once, every output byte written once.  A thread takes four consecutive
+// INTERLEAVED elements, so adjacent lanes cover adjacent elements of the interleaved side: one 4 * width byte access where the
+// file's first element lies on such a boundary, element by element otherwise.  The plane side is one 16-byte access for a
+// one-channel file whose plane is aligned, scalar otherwise (four interleaved elements of a c-channel file lie c planes apart).
+// Which access is taken changes no value.  Packed s24 is written as absolute dwords: a thread owns three aligned dwords = twelve
+// bytes of the file's byte range wherever the file starts, and only the threads at the two ends of a file store single bytes.
+// Bounds: the rule of ragged.h -- the host refuses a row of table_host outside the elements it summed (SOS_EINVAL), the kernels
+// skip a row of the DEVICE table that fails the same rule.
+#include "ragged.h"
+#include "pcm_core.h"
+
+#define PIO_THREADS 256
+#define PIO_MAX_GRID 1024               // workgroups along a file (they stride over what the grid does not cover)
+#define PIO_MAX_CHANNELS 64
+#define PIO_PLANES_COLS 4               // int64 per file: pcm element offset, frames, channels, first output sample
+#define PIO_ENCODE_COLS 5               // int64 per file: first plane sample, plane length, channels, frames, output element offset
+
+// `n` rows of `ch` channels starting at `off` lie inside `total` elements (no overflowing multiply)
+__host__ __device__ static inline bool pio_inside(int64_t off, int64_t n, int64_t ch, int64_t total) {
+    return ch >= 1 && ch <= PIO_MAX_CHANNELS && n >= 0 && n <= total / ch && ragged_clip_inside(off, n * ch, total);
+}
+
+template <typename T> struct alignas(4 * sizeof(T)) PioVec4 { T v[4]; };
+
+template <typename T>
+__global__ __launch_bounds__(PIO_THREADS) void pcm_planes_kernel(const T* __restrict__ pcm, const int64_t* __restrict__ table,
+                                                                 int64_t total, float* __restrict__ out) {
+    const int64_t* te = table + (int64_t)blockIdx.y * PIO_PLANES_COLS;
+    const int64_t off = te[0], frames = te[1], ch = te[2], ooff = te[3];
+    if (!pio_inside(off, frames, ch, total) || !pio_inside(ooff, frames, ch, total)) return;
+    const int64_t n = frames * ch;
+    const T* src = pcm + off;
+    float* dst = out + ooff;
+    const bool src_vec = ((uintptr_t)src & (4 * sizeof(T) - 1)) == 0;
+    const bool dst_vec = ch == 1 && ragged_aligned16(dst);
+    for (int64_t e0 = ((int64_t)blockIdx.x * PIO_THREADS + threadIdx.x) * 4; e0 < n; e0 += (int64_t)gridDim.x * PIO_THREADS * 4) {
+        const bool full = e0 + 4 <= n;
+        T s[4] = {};
+        if (full && src_vec) {
+            const PioVec4<T> q = *(const PioVec4<T>*)(src + e0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s[k] = q.v[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (e0 + k < n) s[k] = src[e0 + k];
+        }
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = Pcm<T>::cvt(s[k]);
+        if (ch == 1) {
+            ragged_store4(dst, e0, n, full && dst_vec, v);
+        } else {
+            int64_t i = e0 / ch, c = e0 - i * ch;             // frame and channel of the first element
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (e0 + k < n) dst[c * frames + i] = v[k];
+                if (++c == ch) { c = 0; ++i; }
+            }
+        }
+    }
+}
+
+// ---- encode.  The rule (include/sos_hip.h): q = rint(x * S) half to even in double (a float times a power of two is exact
+// there), NaN -> 0 and counted, saturated to [-S, S - 1] and counted when that changed it.
+template <int BITS>
+__device__ __forceinline__ int32_t pio_quantise(float x, int& clipped) {
+    const double S = (double)((int64_t)1 << (BITS - 1));
+    const double d = (double)x * S;
+    const double r = rint(d);
+    const bool nan = d != d, hi = r > S - 1.0, lo = r < -S;  // selects, no branches (rint(NaN) compares false twice)
+    clipped += (int)(nan | hi | lo);
+    const double q = nan ? 0.0 : hi ? S - 1.0 : lo ? -S : r;
+    return (int32_t)q;                                       // |q| <= 2^31: one v_cvt_i32_f64
+}
+
+template <int FMT> struct PioEnc;
+template <> struct PioEnc<SOS_ENC_S16> { typedef int16_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)pio_quantise<16>(x, n); } };
+template <> struct PioEnc<SOS_ENC_S32> { typedef int32_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)pio_quantise<32>(x, n); } };
+template <> struct PioEnc<SOS_ENC_U8> { typedef uint8_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)(pio_quantise<8>(x, n) + 128); } };
+template <> struct PioEnc<SOS_ENC_F32> { typedef float T; static __device__ __forceinline__ T put(float x, int&) { return x; } };
+
+// element e of a file's interleaved output: plane[c][i], 0 from the plane's end on
+struct PioPlanes {
+    const float* p;
+    int64_t avail, ch;
+    __device__ __forceinline__ float at(int64_t i, int64_t c) const { return i < avail ? p[c * avail + i] : 0.f; }
+};
+
+// the file's count: the workgroup's waves add up in LDS, then one integer atomic per workgroup that counted anything (integer
+// adds commute: the same sum on every run).  Every thread of the workgroup calls it.
+__device__ __forceinline__ void pio_add_clipped(int clipped, int64_t* dst) {
+    __shared__ int block_count;
+    if (threadIdx.x == 0) block_count = 0;
+    __syncthreads();
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) clipped += __shfl_down(clipped, s, 64);
+    if ((threadIdx.x & 63) == 0 && clipped) atomicAdd(&block_count, clipped);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_count) atomicAdd((unsigned long long*)dst, (unsigned long long)block_count);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(PIO_THREADS) void pcm_encode_kernel(const float* __restrict__ planes, const int64_t* __restrict__ table,
+                                                                 int64_t total_in, int64_t total_out,
+                                                                 typename PioEnc<FMT>::T* __restrict__ out,
+                                                                 int64_t* __restrict__ clipped) {
+    typedef typename PioEnc<FMT>::T T;
+    const int64_t* te = table + (int64_t)blockIdx.y * PIO_ENCODE_COLS;
+    const int64_t first = te[0], avail = te[1], ch = te[2], frames = te[3], ooff = te[4];
+    if (!pio_inside(first, avail, ch, total_in) || !pio_inside(ooff, frames, ch, total_out)) return;
+    const int64_t n = frames * ch;
+    const PioPlanes pl{planes + first, avail, ch};
+    T* dst = out + ooff;
+    const bool dst_vec = ((uintptr_t)dst & (4 * sizeof(T) - 1)) == 0;
+    const bool src_vec = ch == 1 && ragged_aligned16(pl.p);
+    int count = 0;
+    for (int64_t e0 = ((int64_t)blockIdx.x * PIO_THREADS + threadIdx.x) * 4; e0 < n; e0 += (int64_t)gridDim.x * PIO_THREADS * 4) {
+        const bool full = e0 + 4 <= n;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (ch == 1) {
+            const int64_t end = n < avail ? n : avail;           // zeros from the plane's end on
+            ragged_load4(pl.p, e0, end, src_vec && e0 + 4 <= end, v);
+        } else {
+            int64_t i = e0 / ch, c = e0 - i * ch;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (e0 + k < n) v[k] = pl.at(i, c);
+                if (++c == ch) { c = 0; ++i; }
+            }
+        }
+        PioVec4<T> q;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int hit = 0;
+            q.v[k] = PioEnc<FMT>::put(v[k], hit);
+            if (e0 + k < n) count += hit;
+        }
+        if (full && dst_vec) {
+            *(PioVec4<T>*)(dst + e0) = q;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (e0 + k < n) dst[e0 + k] = q.v[k];
+        }
+    }
+    if (FMT != SOS_ENC_F32) pio_add_clipped(count, clipped + blockIdx.y);
+}
+
+// packed s24: thread u of a file owns the twelve bytes [12 u - lead, 12 u - lead + 12) of the file's 3 n bytes, lead = the
+// file's first byte address mod 4, i.e. three ALIGNED dwords.  They hold (parts of) at most five samples; a sample is counted
+// by the thread that owns its first byte.  Whole dwords where all twelve bytes are the file's, single bytes at its two ends.
+__global__ __launch_bounds__(PIO_THREADS) void pcm_encode_s24_kernel(const float* __restrict__ planes, const int64_t* __restrict__ table,
+                                                                     int64_t total_in, int64_t total_out, uint8_t* __restrict__ out,
+                                                                     int64_t* __restrict__ clipped) {
+    const int64_t* te = table + (int64_t)blockIdx.y * PIO_ENCODE_COLS;
+    const int64_t first = te[0], avail = te[1], ch = te[2], frames = te[3], ooff = te[4];
+    if (!pio_inside(first, avail, ch, total_in) || !pio_inside(ooff, frames, ch, total_out)) return;
+    const int64_t n = frames * ch, nbytes = 3 * n;
+    const PioPlanes pl{planes + first, avail, ch};
+    uint8_t* dst = out + 3 * ooff;
+    const int64_t lead = (int64_t)((uintptr_t)dst & 3);
+    const int64_t units = (nbytes + lead + 11) / 12;
+    int count = 0;
+    for (int64_t u = (int64_t)blockIdx.x * PIO_THREADS + threadIdx.x; u < units; u += (int64_t)gridDim.x * PIO_THREADS) {
+        const int64_t p = 12 * u - lead;                         // first byte of the unit, relative to the file (< 0 only for u = 0)
+        const int64_t e_lo = p > 0 ? p / 3 : 0;
+        int64_t i = e_lo / ch, c = e_lo - i * ch;
+        unsigned __int128 bits = 0;                              // the five samples' bytes, little-endian, back to back
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int64_t e = e_lo + k;
+            if (e < n && 3 * e < p + 12) {
+                int hit = 0;
+                const int32_t q = pio_quantise<24>(pl.at(i, c), hit);
+                if (3 * e >= p) count += hit;                    // its first byte is this unit's
+                bits |= (unsigned __int128)((uint32_t)q & 0xffffffu) << (24 * k);
+            }
+            if (++c == ch) { c = 0; ++i; }
+        }
+        const int64_t shift = p - 3 * e_lo;                      // 0 .. 2, or -lead for the unit that begins before the file
+        bits = shift >= 0 ? bits >> (8 * shift) : bits << (-8 * shift);
+        const uint32_t w[3] = {(uint32_t)bits, (uint32_t)(bits >> 32), (uint32_t)(bits >> 64)};
+        if (p >= 0 && p + 12 <= nbytes) {
+            uint32_t* d = (uint32_t*)(dst + p);
+            d[0] = w[0]; d[1] = w[1]; d[2] = w[2];
+        } else {
+#pragma unroll
+            for (int b = 0; b < 12; ++b)
+                if (p + b >= 0 && p + b < nbytes) dst[p + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+        }
+    }
+    pio_add_clipped(count, clipped + blockIdx.y);
+}
+
+// Host: the rows [off_col, + table[len_col] * table[ch_col]) of both sides.  Sums each side, then holds every row to the sums;
+// returns nfiles, or the first row it cannot accept (what is wrong goes to `why`).
+struct PioSide { int off_col, len_col; int64_t total = 0, longest = 0; };
+static int pio_check_rows(const int64_t* table, int nfiles, int cols, int ch_col, PioSide* a, PioSide* b, const char** why) {
+    for (int f = 0; f < nfiles; ++f) {
+        const int64_t* te = table + (int64_t)f * cols;
+        const int64_t ch = te[ch_col];
+        if (ch < 1 || ch > PIO_MAX_CHANNELS) { *why = "channels outside 1 .. 64"; return f; }
+        for (PioSide* s : {a, b}) {
+            const int64_t len = te[s->len_col];
+            if (len < 0 || len > (INT64_MAX / 8 - s->total) / ch) { *why = "a length that is negative or too large"; return f; }
+            s->total += len * ch;
+            s->longest = std::max(s->longest, len * ch);
+        }
+    }
+    for (int f = 0; f < nfiles; ++f) {
+        const int64_t* te = table + (int64_t)f * cols;
+        for (PioSide* s : {a, b})
+            if (!pio_inside(te[s->off_col], te[s->len_col], te[ch_col], s->total)) { *why = "a span outside the totals of the table"; return f; }
+    }
+    return nfiles;
+}
+
+extern "C" int sos_pcm_planes_batch_f32(const void* pcm, int format, const int64_t* table, const int64_t* table_host, int nfiles,
+                                        float* out, sos_stream_t stream) {
+    if (!pcm || !table || !table_host || !out) { sos_set_error("sos_pcm_planes_batch_f32: null pointer"); return SOS_EINVAL; }
+    if (!ragged_clips_ok(table_host, nfiles)) {
+        sos_set_error("sos_pcm_planes_batch_f32: bad args (1 .. 65535 files, got %d)", nfiles);
+        return SOS_EINVAL;
+    }
+    if (format != SOS_PCM_S16 && format != SOS_PCM_S32 && format != SOS_PCM_F32 && format != SOS_PCM_U8) {
+        sos_set_error("sos_pcm_planes_batch_f32: unknown sample format %d", format);
+        return SOS_EINVAL;
+    }
+    PioSide in{0, 1}, pl{3, 1};
+    const char* why = "";
+    const int bad = pio_check_rows(table_host, nfiles, PIO_PLANES_COLS, 2, &in, &pl, &why);
+    if (bad < nfiles) {
+        const int64_t* te = table_host + (int64_t)bad * PIO_PLANES_COLS;
+        sos_set_error("sos_pcm_planes_batch_f32: file %d (pcm element %lld, %lld frames, %lld channels, output %lld) has %s (%lld "
+                      "elements)", bad, (long long)te[0], (long long)te[1], (long long)te[2], (long long)te[3], why, (long long)in.total);
+        return SOS_EINVAL;
+    }
+    const dim3 grid(ragged_grid((in.longest + 3) / 4, PIO_THREADS, PIO_MAX_GRID), (unsigned)nfiles);
+    hipStream_t st = (hipStream_t)stream;
+    switch (format) {
+    case SOS_PCM_S16: hipLaunchKernelGGL(pcm_planes_kernel<int16_t>, grid, dim3(PIO_THREADS), 0, st, (const int16_t*)pcm, table, in.total, out); break;
+    case SOS_PCM_S32: hipLaunchKernelGGL(pcm_planes_kernel<int32_t>, grid, dim3(PIO_THREADS), 0, st, (const int32_t*)pcm, table, in.total, out); break;
+    case SOS_PCM_U8: hipLaunchKernelGGL(pcm_planes_kernel<uint8_t>, grid, dim3(PIO_THREADS), 0, st, (const uint8_t*)pcm, table, in.total, out); break;
+    default: hipLaunchKernelGGL(pcm_planes_kernel<float>, grid, dim3(PIO_THREADS), 0, st, (const float*)pcm, table, in.total, out); break;
+    }
+    return sos_check_launch("sos_pcm_planes_batch_f32");
+}
+
+extern "C" int sos_pcm_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int format,
+                                    void* out, int64_t* clipped, sos_stream_t stream) {
+    if (!planes || !table || !table_host || !out || !clipped) { sos_set_error("sos_pcm_encode_batch: null pointer"); return SOS_EINVAL; }
+    if (!ragged_clips_ok(table_host, nfiles)) {
+        sos_set_error("sos_pcm_encode_batch: bad args (1 .. 65535 files, got %d)", nfiles);
+        return SOS_EINVAL;
+    }
+    if (format != SOS_ENC_S16 && format != SOS_ENC_S24 && format != SOS_ENC_S32 && format != SOS_ENC_U8 && format != SOS_ENC_F32) {
+        sos_set_error("sos_pcm_encode_batch: unknown sample format %d", format);
+        return SOS_EINVAL;
+    }
+    PioSide in{0, 1}, enc{4, 3};
+    const char* why = "";
+    const int bad = pio_check_rows(table_host, nfiles, PIO_ENCODE_COLS, 2, &in, &enc, &why);
+    if (bad < nfiles) {
+        const int64_t* te = table_host + (int64_t)bad * PIO_ENCODE_COLS;
+        sos_set_error("sos_pcm_encode_batch: file %d (plane sample %lld, %lld available, %lld channels, %lld frames, output element "
+                      "%lld) has %s (%lld plane samples, %lld output elements)", bad, (long long)te[0], (long long)te[1],
+                      (long long)te[2], (long long)te[3], (long long)te[4], why, (long long)in.total, (long long)enc.total);
+        return SOS_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(clipped, 0, (size_t)nfiles * sizeof(int64_t), st) != hipSuccess) {
+        sos_set_error("sos_pcm_encode_batch: cannot clear the counts");
+        return SOS_ELAUNCH;
+    }
+    // s24: a thread per twelve bytes = four elements, plus the unit a file that starts off a dword adds
+    const dim3 grid(ragged_grid((enc.longest + 3) / 4 + 1, PIO_THREADS, PIO_MAX_GRID), (unsigned)nfiles);
+#define PIO_GO(F) hipLaunchKernelGGL(pcm_encode_kernel<F>, grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, enc.total, \
+                                     (PioEnc<F>::T*)out, clipped)
+    switch (format) {
+    case SOS_ENC_S16: PIO_GO(SOS_ENC_S16); break;
+    case SOS_ENC_S32: PIO_GO(SOS_ENC_S32); break;
+    case SOS_ENC_U8: PIO_GO(SOS_ENC_U8); break;
+    case SOS_ENC_F32: PIO_GO(SOS_ENC_F32); break;
+    default: hipLaunchKernelGGL(pcm_encode_s24_kernel, grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, enc.total,
+                                (uint8_t*)out, clipped); break;
+    }
+#undef PIO_GO
+    return sos_check_launch("sos_pcm_encode_batch");
+}

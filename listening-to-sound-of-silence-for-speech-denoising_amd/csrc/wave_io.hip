@@ -12,18 +12,14 @@
 // in LDS, so the ~2 x 202 taps of an output at 44.1 -> 14 kHz cost one ds_read2_b32 (w[o], w[o+1]) and one
 // L1-resident input read each.  A workgroup walks RS_PER_WG consecutive outputs to amortise the table load.
 #include "resample_core.h"
+#include "pcm_core.h"
 #include <stdlib.h>
 
 #define RS_THREADS 256
 #define RS_PER_WG 4096          // = SOS_RESAMPLE_CHUNK of include/sos_hip.h
 #define RS_BATCH_THREADS 1024   // the batch kernel's workgroup (EXPERIMENTS.md 3.4)
 
-template <typename T> struct Pcm;
-template <> struct Pcm<int16_t> { static __device__ __forceinline__ float cvt(int16_t v) { return (float)v * (1.0f / 32768.0f); } };
-template <> struct Pcm<int32_t> { static __device__ __forceinline__ float cvt(int32_t v) { return (float)((double)v * (1.0 / 2147483648.0)); } };
-template <> struct Pcm<uint8_t> { static __device__ __forceinline__ float cvt(uint8_t v) { return ((float)v - 128.0f) * (1.0f / 128.0f); } };
-template <> struct Pcm<float> { static __device__ __forceinline__ float cvt(float v) { return v; } };
-
+// Pcm<T>::cvt, the sample-to-float rule: pcm_core.h (shared with pcm_io.hip)
 // interleaved [n_frames][channels] -> mono f32 (np.mean over channels of the f32 samples)
 template <typename T>
 __global__ void pcm_to_mono_kernel(const T* __restrict__ pcm, int channels, int64_t n_frames, float* __restrict__ out) {

@@ -1,0 +1,128 @@
+"""Recordings in, denoised recordings out: WAVE files of any channel count, rate and sample format through the chain of
+windows.denoise_long and back into files with the SAME number of frames, channels, rate and sample format.  Every channel is
+denoised on its own (no decision stream is shared between the channels of a file); the decode, the two resamplings, the windows
+and the encode each run in launches shared by all files and channels of a group (csrc/pcm_io.hip, csrc/wave_io.hip,
+csrc/ragged_window.hip)."""
+import os
+
+import numpy as np
+import torch
+
+from . import audio_io
+from . import labels
+from . import ragged
+from . import transform
+from . import windows
+from .pipeline import FPS, MIN_FRAMES, SR
+
+# the format a source is written back in: (WAVE format tag, stored bits) -> audio_io.ENCODINGS name.  A float64 source is
+# written as f32 (the networks compute in f32 at best).
+_SOURCE_FORMAT = {(1, 8): "u8", (1, 16): "s16", (1, 24): "s24", (1, 32): "s32", (3, 32): "f32", (3, 64): "f32"}
+
+
+def _model_samples(frames, rate):
+    """Samples of a channel of `frames` frames at `rate` once it is at the networks' rate (resample_batch_device's length)."""
+    return int(frames) if rate == SR else int(np.ceil(int(frames) * (float(SR) / rate)))
+
+
+def _check_files(paths, out_dir, sample_format, suffix):
+    """Everything that can be refused from the chunk headers alone: -> (infos, formats, out_paths)."""
+    if sample_format is not None and sample_format not in audio_io.ENCODINGS:
+        raise ValueError("denoise_recordings: unsupported sample_format %r (one of %s)"
+                         % (sample_format, ", ".join(sorted(audio_io.ENCODINGS))))
+    infos, formats, out_paths = [], [], []
+    hop = transform.HOP_LENGTH
+    for path in paths:
+        info = audio_io.wave_info(path)                 # WaveFormatError (a ValueError) names the file: format, channels
+        n = _model_samples(info["frames"], info["rate"]) if info["rate"] > 0 else 0
+        if 1 + n // hop < MIN_FRAMES:
+            raise ValueError("%s: recordings need at least %d STFT frames (%d samples at %d Hz); got %d frames at %d Hz = %d samples"
+                             % (path, MIN_FRAMES, MIN_FRAMES * hop, SR, info["frames"], info["rate"], n))
+        if info["channels"] > 64:
+            raise ValueError("%s: %d channels (at most 64)" % (path, info["channels"]))
+        infos.append(info)
+        formats.append(sample_format or _SOURCE_FORMAT[(info["tag"], info["bits"])])
+        out_paths.append(os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0] + suffix + ".wav"))
+    if len(set(out_paths)) != len(out_paths):
+        raise ValueError("denoise_recordings: two inputs share a file name and would be written to the same output")
+    return infos, formats, out_paths
+
+
+def _resample_back(clips, rates):
+    """Every clip whose file's rate differs from SR back to that rate: one resample_batch_device launch per rate."""
+    by_rate = {}
+    for k, r in enumerate(rates):
+        if r != SR:
+            by_rate.setdefault(r, []).append(k)
+    clips = list(clips)
+    for r, idx in by_rate.items():
+        for k, y in zip(idx, audio_io.resample_batch_device([clips[k] for k in idx], SR, r)):
+            clips[k] = y
+    return clips
+
+
+@torch.no_grad()
+def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, context_seconds=2.0, max_batch=256,
+                       max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix=""):
+    """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
+    channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32; a float64 source is written as float32);
+    sample_format= ('s16', 's24', 's32', 'u8', 'f32') forces one format for all files.
+    Per group of files of at most `max_bytes` of decoded f32 samples (ragged.byte_groups): the files are parsed on the host;
+    one upload and one sos_pcm_planes_batch_f32 launch per sample format decode every channel into its own plane; one
+    resample_batch_device launch per native rate other than 14 kHz brings all channels to the networks' rate; ONE
+    windows.denoise_long call runs all channels of all files of the group as recordings (file order, channel order within a
+    file; window_seconds, context_seconds, max_batch, max_columns as there); one resample launch per native rate goes back; one
+    sos_pcm_encode_batch launch per output format crops or zero-fills every channel to the source's frame count (the networks
+    return hop * (n // hop) samples and the resampler ceil(n * ratio)) and quantises it -- round half to even, saturating, NO
+    dither; one download brings the group's bytes and counts to the host, and only then are its files written
+    (audio_io.wave_container).  No call in the loop waits for the device except that download.
+    -> one dict per file: path, out_path, channels, rate, frames, format, clipped (samples that saturated or were NaN, all
+    channels), windows (denoise_long windows, all channels).
+    ValueError before any launch of the call, naming the file: fewer than MIN_FRAMES STFT frames at 14 kHz, an unsupported
+    format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format;
+    window_plan's argument rules; a group with more than 65535 windows."""
+    paths = [os.fspath(p) for p in paths]
+    infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix)
+    core, context = windows._hops(round(window_seconds * SR)), windows._hops(round(context_seconds * SR))
+    groups = ragged.byte_groups([4 * i["frames"] * i["channels"] for i in infos], max_bytes)
+    plans = []                                          # host only: refuses bad window arguments and a group of too many windows
+    for group in groups:
+        plans.append(windows.window_plan([_model_samples(infos[f]["frames"], infos[f]["rate"]) for f in group
+                                          for _ in range(infos[f]["channels"])], core, context))
+        if len(plans[-1]) > ragged.MAX_CLIPS:
+            raise ValueError("denoise_recordings: the group of %s .. %s has %d windows over all channels (at most %d): lower max_bytes "
+                             "or use longer windows" % (paths[group[0]], paths[group[-1]], len(plans[-1]), ragged.MAX_CLIPS))
+    os.makedirs(out_dir, exist_ok=True)
+    results = []
+    for group, plan in zip(groups, plans):
+        ys, _, _ = audio_io.load_channels_batch_device([paths[f] for f in group], sr=SR)
+        owner = [f for f, y in zip(group, ys) for _ in range(y.shape[0])]                           # the file of each channel
+        clips = [y[c] for y in ys for c in range(y.shape[0])]
+        outs = windows.denoise_long(detector, denoiser, clips, SR, FPS, window_seconds, context_seconds, max_batch, max_columns)
+        outs = _resample_back(outs, [infos[f]["rate"] for f in owner])
+        per_file, k = {}, 0
+        for f, y in zip(group, ys):
+            per_file[f] = audio_io.planes_of(outs[k:k + y.shape[0]])
+            k += y.shape[0]
+        by_format = {}
+        for f in group:
+            by_format.setdefault(formats[f], []).append(f)
+        parts, spans = [], {}
+        for fmt, files in by_format.items():
+            data, offsets, clipped = audio_io.encode_batch_device([per_file[f] for f in files], fmt,
+                                                                  frames=[infos[f]["frames"] for f in files])
+            for j, f in enumerate(files):
+                spans[f] = (len(parts), int(offsets[j]), int(offsets[j + 1]), j)
+            parts += [data, clipped.view(torch.uint8)]
+        host = ragged.split(torch.cat(parts).cpu().numpy(), [p.numel() for p in parts])            # the group's one download
+        n_windows = np.bincount(plan[:, 0], minlength=len(clips))
+        for f in group:
+            part, b0, b1, j = spans[f]
+            tag, bits = audio_io.ENCODINGS[formats[f]][2:]
+            blob = audio_io.wave_container(host[part][b0:b1].tobytes(), tag, infos[f]["channels"], infos[f]["rate"], bits)
+            with open(out_paths[f], "wb") as fp:
+                fp.write(blob)
+            results.append(dict(path=paths[f], out_path=out_paths[f], channels=infos[f]["channels"], rate=infos[f]["rate"],
+                                frames=infos[f]["frames"], format=formats[f], clipped=int(host[part + 1].view(np.int64)[j]),
+                                windows=int(sum(n_windows[k] for k, o in enumerate(owner) if o == f))))
+    return results

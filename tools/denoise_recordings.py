@@ -1,0 +1,50 @@
+"""Denoise WAVE recordings from the command line (recordings.denoise_recordings): every written file keeps its source's frame
+count, channels, rate and sample format.
+
+  python tools/denoise_recordings.py DETECTOR.pth DENOISER.pth OUT_DIR in1.wav in2.wav ... [--sample-format s16] [--suffix _dn]
+
+The checkpoints are the reference's (`{clock, model_state_dict, ...}` as the agents save them) or bare state dicts."""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import sos_amd  # noqa: E402
+from sos_amd import audio_io, recordings  # noqa: E402
+from sos_amd.common import MyConfig  # noqa: E402
+from sos_amd.denoiser import networks as jnet  # noqa: E402
+from sos_amd.detector import networks as dnet  # noqa: E402
+
+
+def _load(net, path):
+    ck = torch.load(path, map_location="cpu")
+    net.load_state_dict(ck["model_state_dict"] if "model_state_dict" in ck else ck)
+    return net.cuda().eval()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("detector", help="checkpoint of the silent-interval detector")
+    ap.add_argument("denoiser", help="checkpoint of the denoiser")
+    ap.add_argument("out_dir")
+    ap.add_argument("files", nargs="+")
+    ap.add_argument("--window-seconds", type=float, default=30.0)
+    ap.add_argument("--context-seconds", type=float, default=2.0)
+    ap.add_argument("--max-batch", type=int, default=256)
+    ap.add_argument("--max-columns", type=int, default=65536)
+    ap.add_argument("--sample-format", choices=sorted(audio_io.ENCODINGS), default=None, help="one format for all files (default: each source's)")
+    ap.add_argument("--suffix", default="")
+    ap.add_argument("--precision", default="mixed", choices=["bf16", "bf16x3", "fp16", "mixed"])
+    args = ap.parse_args()
+    det, jm = _load(dnet.get_network(), args.detector), _load(jnet.get_network(MyConfig()), args.denoiser)
+    sos_amd.set_precision(args.precision)
+    for r in recordings.denoise_recordings(det, jm, args.files, args.out_dir, args.window_seconds, args.context_seconds, args.max_batch,
+                                           args.max_columns, sample_format=args.sample_format, suffix=args.suffix):
+        print("%s -> %s: %d x %d frames at %d Hz, %s, %d windows, %d samples clipped"
+              % (r["path"], r["out_path"], r["channels"], r["frames"], r["rate"], r["format"], r["windows"], r["clipped"]))
+
+
+if __name__ == "__main__":
+    main()

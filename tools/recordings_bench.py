@@ -1,0 +1,189 @@
+"""Recordings benchmark (run on the GPU box): N synthetic recordings of 1 .. 10 s (seeded lengths, stereo 16-bit PCM at 44.1 kHz)
+in a temporary directory, in 'mixed' precision:
+  1. recordings.denoise_recordings (one group) against the loop it replaces -- per file and per channel: read_wave, decode,
+     resample_device, denoise_long, resample_device back, download, numpy quantisation; then one write per file.  Both forms are
+     warmed once, then alternate, --repeats times each; the median wall time from an idle device to an idle device (file reads
+     and writes included), the spread, files/s and the number of host waits (Tensor.cpu calls) are printed.
+  2. the share of a denoise_recordings call that is not denoise_long: the same channels, already decoded and at 14 kHz, through
+     denoise_long alone, timed the same way.
+  3. the two kernels of csrc/pcm_io.hip on --kernel-mib MiB of planes (stereo files of 2^20 frames): bytes read plus bytes
+     written per second, from device events over --kernel-reps launches, against Tensor.copy_ of a float32 buffer moving the same
+     number of bytes in the same run; the encode once on planes that never saturate and once on planes of which 9 % do (every
+     workgroup then adds to its file's count).
+A measurement: nothing is asserted."""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import sos_amd  # noqa: E402
+from oracle import nets as onet  # noqa: E402
+from sos_amd import audio_io, pipeline, recordings, windows  # noqa: E402
+from sos_amd.common import MyConfig  # noqa: E402
+from sos_amd.denoiser import networks as jnet  # noqa: E402
+from sos_amd.detector import networks as dnet  # noqa: E402
+
+WAITS = [0]
+RATE = 44100
+
+
+def _count_downloads():
+    orig = torch.Tensor.cpu
+
+    def cpu(self, *a, **k):
+        if self.is_cuda:
+            WAITS[0] += 1
+        return orig(self, *a, **k)
+    torch.Tensor.cpu = cpu
+
+
+def once(fn):
+    """(wall seconds, host waits) of one call, from an idle device to an idle device."""
+    torch.cuda.synchronize()
+    WAITS[0] = 0
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, WAITS[0]
+
+
+def make_files(root, n_files, seed):
+    rng = np.random.default_rng(seed)
+    paths, secs = [], 0.0
+    for i in range(n_files):
+        n = int(rng.integers(RATE, 10 * RATE + 1))
+        t = np.arange(n) / RATE
+        sig = np.stack([0.3 * (np.sin(2 * np.pi * 0.7 * t + i + c) > -0.2) * np.sin(2 * np.pi * (220 + 40 * c) * t)
+                        + 0.05 * rng.standard_normal(n) for c in range(2)], axis=1)
+        paths.append(os.path.join(root, "rec_%03d.wav" % i))
+        with open(paths[-1], "wb") as fp:
+            fp.write(audio_io.wave_bytes(np.rint(sig * 32767).clip(-32768, 32767).astype(np.int16), RATE))
+        secs += n / RATE
+    return paths, secs
+
+
+def per_file_loop(det, jm, paths, out_dir):
+    """What a caller had before denoise_recordings: every channel on its own through the mono pieces, quantised on the host."""
+    os.makedirs(out_dir, exist_ok=True)
+    for path in paths:
+        arr, kind, rate = audio_io.read_wave(path)
+        chans = []
+        for c in range(arr.shape[1]):
+            y = audio_io.pcm_to_mono_device(torch.from_numpy(np.ascontiguousarray(arr[:, c:c + 1])).cuda(), kind)
+            y = audio_io.resample_device(y, rate, pipeline.SR)
+            y = windows.denoise_long(det, jm, [y])[0]
+            y = audio_io.resample_device(y, pipeline.SR, rate).cpu().numpy()
+            x = np.zeros(arr.shape[0], dtype=np.float32)
+            x[:min(len(y), len(x))] = y[:len(x)]
+            chans.append(np.clip(np.rint(x.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16))
+        with open(os.path.join(out_dir, os.path.basename(path)), "wb") as fp:
+            fp.write(audio_io.wave_bytes(np.stack(chans, axis=1), rate))
+
+
+def report(name, n_files, runs):
+    ts, waits = [r[0] for r in runs], [r[1] for r in runs]
+    med = float(np.median(ts))
+    print(f"  {name:26s}: {med * 1e3:9.1f} ms (min {min(ts) * 1e3:.1f}, max {max(ts) * 1e3:.1f})   {n_files / med:8.1f} files/s   "
+          f"host waits {int(np.median(waits))}")
+    return med
+
+
+def device_ms(fn, reps):
+    """Milliseconds per call from device events around `reps` calls, after one warm-up call."""
+    fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def kernels(args, amplitude):
+    frames, ch = 1 << 20, 2
+    n_files = max(1, (args.kernel_mib << 20) // (4 * frames * ch))
+    samples = n_files * ch * frames
+    flat = torch.empty(samples, dtype=torch.float32, device="cuda").uniform_(-amplitude, amplitude)
+    planes = [v.view(ch, frames) for v in flat.split(ch * frames)]
+    print(f"kernels: {n_files} files of {ch} x {frames} frames = {samples * 4 / 2**20:.0f} MiB of planes uniform in +-{amplitude:g} "
+          f"({100 * float((flat.abs() >= 1).float().mean()):.1f} % of the samples saturate), {args.kernel_reps} launches each (bytes read + "
+          "bytes written per second; the entry points themselves, tables already on the device)")
+    L = audio_io.L
+    rows = []
+    assert torch.equal(audio_io.encode_batch_device(planes[:1], "f32")[0].view(torch.float32), planes[0].T.reshape(-1))
+    for fmt in ("s16", "s24", "s32", "u8", "f32"):
+        code, width = audio_io.ENCODINGS[fmt][:2]
+        tab = np.asarray([[i * ch * frames, frames, ch, frames, i * ch * frames] for i in range(n_files)], dtype=np.int64)
+        tab_dev, out = torch.from_numpy(tab).cuda(), torch.empty(samples * width, dtype=torch.uint8, device="cuda")
+        counts = torch.empty(n_files, dtype=torch.int64, device="cuda")
+        go = lambda: L.check(L.lib().sos_pcm_encode_batch(L.ptr(flat), L.ptr(tab_dev), tab.ctypes.data_as(L.C.c_void_p), n_files,   # noqa: E731
+                                                          code, L.ptr(out), L.ptr(counts), L.stream_ptr()))
+        rows.append(("encode " + fmt, samples * (4 + width), device_ms(go, args.kernel_reps)))
+    for kind, dtype in (("s16", np.int16), ("s32", np.int32), ("u8", np.uint8), ("f32", np.float32)) if amplitude < 1 else ():
+        pcm = torch.zeros(samples, dtype=getattr(torch, np.dtype(dtype).name), device="cuda")
+        tab = np.asarray([[i * ch * frames, frames, ch, i * ch * frames] for i in range(n_files)], dtype=np.int64)
+        tab_dev, out = torch.from_numpy(tab).cuda(), torch.empty(samples, dtype=torch.float32, device="cuda")
+        go = lambda: L.check(L.lib().sos_pcm_planes_batch_f32(L.ptr(pcm), audio_io._FMT[kind], L.ptr(tab_dev),      # noqa: E731
+                                                              tab.ctypes.data_as(L.C.c_void_p), n_files, L.ptr(out), L.stream_ptr()))
+        rows.append(("decode " + kind, samples * (4 + dtype().itemsize), device_ms(go, args.kernel_reps)))
+    for name, nbytes, ms in rows:
+        src = torch.empty(nbytes // 8, dtype=torch.float32, device="cuda").normal_()
+        dst = torch.empty_like(src)
+        copy_ms = device_ms(lambda: dst.copy_(src), args.kernel_reps)
+        print(f"  {name:11s}: {ms:7.3f} ms  {nbytes / ms / 1e6:7.1f} GB/s    Tensor.copy_ of the same bytes: {copy_ms:7.3f} ms  "
+              f"{nbytes / copy_ms / 1e6:7.1f} GB/s    ratio {copy_ms / ms:.2f}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--max-batch", type=int, default=64)
+    ap.add_argument("--kernel-mib", type=int, default=512)
+    ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--amplitudes", type=float, nargs="+", default=[0.9, 1.1], help="encode inputs: nothing saturates below 1")
+    ap.add_argument("--skip-loop", action="store_true", help="only the kernels")
+    args = ap.parse_args()
+    print(torch.cuda.get_device_name(0))
+    _count_downloads()
+    if not args.skip_loop:
+        det = dnet.get_network()
+        det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+        jm = jnet.get_network(MyConfig())
+        jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+        det, jm = det.cuda().eval(), jm.cuda().eval()
+        sos_amd.set_precision("mixed")
+        with tempfile.TemporaryDirectory() as tmp:
+            paths, secs = make_files(tmp, args.files, args.seed)
+            group = lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "group"), max_batch=args.max_batch)   # noqa: E731
+            loop = lambda: per_file_loop(det, jm, paths, os.path.join(tmp, "loop"))                                            # noqa: E731
+            ys, _, _ = audio_io.load_channels_batch_device(paths, sr=pipeline.SR)
+            clips = [y[c] for y in ys for c in range(y.shape[0])]
+            long_only = lambda: windows.denoise_long(det, jm, clips, max_batch=args.max_batch)                                 # noqa: E731
+            group(), loop(), long_only()                                                  # warm-up of all forms
+            runs = dict(group=[], loop=[], long_only=[])
+            for _ in range(args.repeats):                                                 # the forms alternate
+                runs["group"].append(once(group))
+                runs["loop"].append(once(loop))
+                runs["long_only"].append(once(long_only))
+            print(f"{args.files} stereo s16 files at {RATE} Hz, {secs:.0f} s of audio x 2 channels, 'mixed' precision, {args.repeats} "
+                  "alternating repeats (median, min, max)")
+            g = report("denoise_recordings", args.files, runs["group"])
+            lp = report("per file and channel", args.files, runs["loop"])
+            d = report("denoise_long alone", args.files, runs["long_only"])
+            print(f"  per file and channel / group = {lp / g:.2f}; share of the group call that is not denoise_long: {100 * (1 - d / g):.1f} %")
+        sos_amd.set_precision("bf16")
+    for amplitude in args.amplitudes:                            # decode is timed once, with the first amplitude below 1
+        kernels(args, amplitude)
+
+
+if __name__ == "__main__":
+    main()
