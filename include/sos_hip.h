@@ -773,6 +773,34 @@ int sos_window_stage_masked_f32(const float* x, const uint8_t* bits, const int64
                                 const int64_t* table_host, int nwin, int64_t stride, float* wave, float* masked,
                                 sos_stream_t stream);
 
+/* ---- one decision stream shared by the recordings of a group -- the channels of a file (csrc/ragged_window.hip;
+ * sos_amd.windows.detect_long(link=); numpy restatement of the reduction and the decision: tests/link_reference.py).
+ * sos_window_frames_link_f32 is sos_window_frames_stitch_f32 with a link table, in ONE launch: rows, table, frames, recs,
+ *   ratios, core and context are that call's, and every member recording's frame i is stitched by that call's rule (one
+ *   __device__ function serves both kernels: the same bits).  Column 0 of `recs`, a recording's own frame offset, is NOT used
+ *   for output here and is not validated.  links / links_host: int64 [ngroups][4] = {frame offset of the group's stream in the
+ *   outputs, frames F, first index into `members`, member count}; members / members_host: int64 recording indices (rows of
+ *   `recs`), sum(member count) of them.  Frame i of group g is reduced over its members IN MEMBER ORDER --
+ *     mode 0 (any):  x = fmaxf(... fmaxf(v_0, v_1) ..., v_last)          (bit 1 = non-silent: speech if any member has speech)
+ *     mode 1 (mean): x = (((v_0 + v_1) + ...) + v_last) / (float)count   (f32 sum, one f32 divide)
+ *   -- a group of one keeps its member's logits bit for bit in both modes -- and decided as sos_threshold_bits decides:
+ *   out_logits[offset + i] = x, out_bits[offset + i] = 1 / (1 + expf(-x)) >= threshold (mask_rule.h, one statement for
+ *   both).  out_logits f32 and out_bits uint8 hold sum(F) elements each, the groups' streams back to back.  One thread and
+ *   one writer per output frame, no atomics, no LDS.  A recording that is in no group is not read.
+ * SOS_EINVAL before any launch, without touching the device (sos_last_error() names the group, the member or the window): null
+ * pointers, the argument rules of sos_window_frames_stitch_f32, ngroups outside 1 .. 65535, a mode other than 0 or 1, a
+ * threshold that is not finite, a group without members or with more than nrec, member ranges outside the sum of the member
+ * counts, a group stream outside sum(F) or overlapping another, a member index outside nrec, a recording that appears twice (in
+ * two groups or in one), a member whose frames differ from its group's or whose ratio differs from the group's first member's,
+ * and for every member what sos_window_frames_stitch_f32 refuses of a recording and its windows.  The kernel follows the
+ * DEVICE tables and gives a group or a frame that fails the same tests no work. */
+int sos_window_frames_link_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table, const int64_t* table_host,
+                               const int64_t* frames, const int64_t* frames_host, int nwin, const int64_t* recs,
+                               const int64_t* recs_host, const double* ratios, const double* ratios_host, int nrec, int64_t core,
+                               int64_t context, const int64_t* links, const int64_t* links_host, const int64_t* members,
+                               const int64_t* members_host, int ngroups, int mode, float threshold, float* out_logits,
+                               uint8_t* out_bits, sos_stream_t stream);
+
 /* ---- live audio denoised in windows, the state between two calls on the device (csrc/stream_window.hip;
  * sos_amd.pipeline.StreamDenoiser; the rule: pipeline.StreamPlan, float64 restatement tests/stream_reference.py).  One launch
  * each whatever the number of slots; no allocation, no host synchronisation, no atomics.  A slot is one stream.

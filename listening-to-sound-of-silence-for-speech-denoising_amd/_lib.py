@@ -156,6 +156,7 @@ SIGNATURES = {
     "sos_window_stitch_f32": [_P, _L, _L, _P, _P, _I, _L, _P, _P],
     "sos_window_stitch_planes_f32": [_P, _I, _L, _L, _P, _P, _I, _L, _P, _P, _I, _L, _P, _P],
     "sos_window_frames_stitch_f32": [_P, _L, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _L, _L, _P, _P],
+    "sos_window_frames_link_f32": [_P, _L, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P],
     "sos_window_stage_masked_f32": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _L, _P, _P, _P],
     "sos_stream_push_f32": [_P, _L, _P, _P, _I, _P, _L, _L, _P],
     "sos_stream_stage_f32": [_P, _L, _L, _P, _P, _I, _L, _P, _P],

@@ -221,7 +221,7 @@ __global__ void threshold_kernel(const float* __restrict__ logits, int64_t n, fl
                                  float* __restrict__ conf) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float s = 1.0f / (1.0f + expf(-logits[i]));
+    const float s = frame_sigmoid(logits[i]);                  // mask_rule.h
     bits[i] = s >= thr ? 1 : 0;
     if (conf) conf[i] = s;
 }

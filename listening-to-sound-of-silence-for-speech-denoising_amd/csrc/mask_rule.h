@@ -15,6 +15,12 @@ __host__ __device__ __forceinline__ int64_t frame_edge(int64_t i, double ratio) 
 #endif
 }
 
+// The frame decision (M1/predict.py:117-119): sigmoid of a logit in f32.  bit = frame_sigmoid(x) >= threshold, 1 = non-silent.
+// The ONE statement of it: threshold_kernel (frontend.hip) and window_frames_link_kernel (ragged_window.hip) give the same
+// bits for the same logit.
+__device__ __forceinline__ float frame_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ uint8_t frame_decision(float x, float thr) { return frame_sigmoid(x) >= thr ? 1 : 0; }
+
 // Pre-flip mask value of sample j: 1 if j lies in [int(i*r), int((i+1)*r - 1)) of a silent
 // frame i (bit 0), else 0.  All index arithmetic in IEEE double with explicit (un-fused)
 // multiply/add so it reproduces Python's float64 evaluation bit for bit.

@@ -29,11 +29,17 @@
 //                          wave rows and their masked rows x * mask, mask = mask_sample(bits of the recording, its frames, its
 //                          ratio, its samples, window start + j): slices of what sos_ragged_stage_f32 makes at full length, bit
 //                          for bit, with nothing of full length written.
+//   window_frames_link_kernel     window_frames_stitch_kernel with a link table: the stitched logits of the recordings of a GROUP
+//                          (the channels of a file) reduced in member order -- any: fmaxf, mean: a sequential f32 sum and one
+//                          divide -- and thresholded (mask_rule.h: frame_decision), ONE logit and ONE decision stream per group
+//                          in one launch.  stitched_frame is the one statement of the stitch both kernels call; numpy
+//                          restatement of the reduction and the decision: tests/link_reference.py.
 // Bounds: the rule of ragged.h -- the host refuses a table entry that leaves what it sized from table_host (SOS_EINVAL), the
 // kernels skip an entry of the DEVICE table that fails the same test (window_stage_ok / window_stitch_why / frames_rec_ok /
 // frames_win_ok / window_masked_ok below).
 #include "ragged.h"
 #include "mask_rule.h"
+#include <cmath>
 #include <utility>
 #include <vector>
 
@@ -400,9 +406,12 @@ __host__ __device__ static inline FrameRec frame_rec(const int64_t* recs, int64_
 }
 // a recording can be followed: its frames lie inside the summed output, its windows inside the table, its ratio places every
 // frame centre inside int64 (a NaN fails rho > 0)
+__host__ __device__ static inline bool frames_rec_windows_ok(const FrameRec& r, double rho, int64_t nwin) {
+    return r.F >= 0 && r.F <= RW_MAX_FRAMES && r.first >= 0 && r.K >= 1 && r.K <= nwin && r.first <= nwin - r.K && rho > 0.0 &&
+           rho <= RW_MAX_RATIO;
+}
 __host__ __device__ static inline bool frames_rec_ok(const FrameRec& r, double rho, int64_t nwin, int64_t total_frames) {
-    return ragged_clip_inside(r.foff, r.F, total_frames) && r.F <= RW_MAX_FRAMES && r.first >= 0 && r.K >= 1 && r.K <= nwin &&
-           r.first <= nwin - r.K && rho > 0.0 && rho <= RW_MAX_RATIO;
+    return ragged_clip_inside(r.foff, r.F, total_frames) && frames_rec_windows_ok(r, rho, nwin);
 }
 // a window can be read: its row exists and holds its `frames` logits
 __host__ __device__ static inline bool frames_win_ok(const WindowRow& e, int64_t frames, int64_t n_rows, int64_t stride) {
@@ -417,6 +426,38 @@ __device__ __forceinline__ int64_t frame_in_window(double c, int64_t start, doub
     return j < 0.0 ? 0 : j > (double)(frames - 1) ? frames - 1 : (int64_t)j;
 }
 
+// The stitched logit of frame i of ONE recording (`rec`, rho samples per frame; span = 2 context): the ONE statement of the
+// frame stitch's arithmetic, window_frames_stitch_kernel and window_frames_link_kernel both call it.  false: a window it needs
+// fails frames_win_ok, and the frame is left alone.
+__device__ __forceinline__ bool stitched_frame(const float* __restrict__ rows, int64_t n_rows, int64_t stride,
+                                               const int64_t* __restrict__ table, const int64_t* __restrict__ frames,
+                                               const FrameRec& rec, double rho, int64_t core, int64_t context, double span,
+                                               int64_t i, float* out) {
+    const double c = (double)i + 0.5;                           // exact
+    const double p = __dmul_rn(c, rho);                         // the frame's centre, in samples of the recording
+    const int64_t own = (int64_t)p / core, k = own < rec.K - 1 ? own : rec.K - 1;      // frames past the last core belong to the last window
+    const int64_t w = rec.first + k;
+    const WindowRow e = window_row(table, w);
+    const int64_t fe = frames[w];
+    if (!frames_win_ok(e, fe, n_rows, stride)) return false;
+    float v = rows[e.row * stride + frame_in_window(c, e.start, rho, fe)];
+    if (context > 0) {
+        // core >= 2 context: at most one of the two zones holds p
+        const int side = k > 0 && p < (double)(e.cs + context) ? -1 : k < rec.K - 1 && p >= (double)(e.ce - context) ? 1 : 0;
+        if (side) {
+            const WindowRow q = window_row(table, w + side);
+            const int64_t fq = frames[w + side];
+            if (!frames_win_ok(q, fq, n_rows, stride)) return false;
+            const float u = rows[q.row * stride + frame_in_window(c, q.start, rho, fq)];
+            const double b = (double)((side < 0 ? e.cs : e.ce) - context);
+            const float wt = (float)__ddiv_rn(__dadd_rn(p, -b), span);   // float64, rounded once
+            v = side < 0 ? (1.f - wt) * u + wt * v : (1.f - wt) * v + wt * u;
+        }
+    }
+    *out = v;
+    return true;
+}
+
 __global__ __launch_bounds__(RW_THREADS) void window_frames_stitch_kernel(
     const float* __restrict__ rows, int64_t n_rows, int64_t stride, const int64_t* __restrict__ table,
     const int64_t* __restrict__ frames, int64_t nwin, const int64_t* __restrict__ recs, const double* __restrict__ ratios,
@@ -428,29 +469,89 @@ __global__ __launch_bounds__(RW_THREADS) void window_frames_stitch_kernel(
     float* dst = out + rec.foff;
     const double span = (double)(2 * context);
     for (int64_t i = (int64_t)blockIdx.x * RW_THREADS + threadIdx.x; i < rec.F; i += (int64_t)gridDim.x * RW_THREADS) {
-        const double c = (double)i + 0.5;                       // exact
-        const double p = __dmul_rn(c, rho);                     // the frame's centre, in samples of the recording
-        const int64_t own = (int64_t)p / core, k = own < rec.K - 1 ? own : rec.K - 1;      // frames past the last core belong to the last window
-        const int64_t w = rec.first + k;
-        const WindowRow e = window_row(table, w);
-        const int64_t fe = frames[w];
-        if (!frames_win_ok(e, fe, n_rows, stride)) continue;
-        float v = rows[e.row * stride + frame_in_window(c, e.start, rho, fe)];
-        if (context > 0) {
-            // core >= 2 context: at most one of the two zones holds p
-            const int side = k > 0 && p < (double)(e.cs + context) ? -1 : k < rec.K - 1 && p >= (double)(e.ce - context) ? 1 : 0;
-            if (side) {
-                const WindowRow q = window_row(table, w + side);
-                const int64_t fq = frames[w + side];
-                if (!frames_win_ok(q, fq, n_rows, stride)) continue;
-                const float u = rows[q.row * stride + frame_in_window(c, q.start, rho, fq)];
-                const double b = (double)((side < 0 ? e.cs : e.ce) - context);
-                const float wt = (float)__ddiv_rn(__dadd_rn(p, -b), span);   // float64, rounded once
-                v = side < 0 ? (1.f - wt) * u + wt * v : (1.f - wt) * v + wt * u;
-            }
-        }
-        dst[i] = v;
+        float v;
+        if (stitched_frame(rows, n_rows, stride, table, frames, rec, rho, core, context, span, i, &v)) dst[i] = v;
     }
+}
+
+// ---- one logit and one decision stream per GROUP of linked recordings (the channels of a file)
+
+#define RW_LINK_COLS 4                  // int64 per group: frame offset in the outputs, frames, first index into `members`, members
+struct LinkRow { int64_t foff, F, first, count; };
+__host__ __device__ static inline LinkRow link_row(const int64_t* links, int64_t g) {
+    const int64_t* te = links + g * RW_LINK_COLS;
+    return {te[0], te[1], te[2], te[3]};
+}
+// a group can be followed: its stream lies inside the summed output, its members inside `members`
+__host__ __device__ static inline bool link_ok(const LinkRow& lk, int64_t nmem, int64_t total_frames) {
+    return ragged_clip_inside(lk.foff, lk.F, total_frames) && lk.count >= 1 && ragged_clip_inside(lk.first, lk.count, nmem);
+}
+
+// window_frames_stitch_kernel with a link table: the stitched logits of a group's members reduced in member order (mode 0:
+// fmaxf, mode 1: a sequential f32 sum and one f32 divide by the member count) and thresholded (mask_rule.h), one thread and
+// one writer per frame of the group.  The members' own frame offsets (column 0 of `recs`) are not read.
+__global__ __launch_bounds__(RW_THREADS) void window_frames_link_kernel(
+    const float* __restrict__ rows, int64_t n_rows, int64_t stride, const int64_t* __restrict__ table,
+    const int64_t* __restrict__ frames, int64_t nwin, const int64_t* __restrict__ recs, const double* __restrict__ ratios,
+    int64_t nrec, const int64_t* __restrict__ links, const int64_t* __restrict__ members, int64_t nmem, int64_t core,
+    int64_t context, int mode, float thr, int64_t total_frames, float* __restrict__ out_logits, uint8_t* __restrict__ out_bits) {
+    const LinkRow lk = link_row(links, blockIdx.y);
+    if (core < 1 || !link_ok(lk, nmem, total_frames)) return;
+    const int64_t* mem = members + lk.first;
+    for (int64_t m = 0; m < lk.count; ++m) {                    // every member can be followed, or the group gets no work
+        const int64_t r = mem[m];
+        if (r < 0 || r >= nrec) return;
+        const FrameRec rec = frame_rec(recs, r);
+        if (rec.F != lk.F || !frames_rec_windows_ok(rec, ratios[r], nwin)) return;
+    }
+    const double span = (double)(2 * context);
+    for (int64_t i = (int64_t)blockIdx.x * RW_THREADS + threadIdx.x; i < lk.F; i += (int64_t)gridDim.x * RW_THREADS) {
+        float acc = 0.f;
+        bool ok = true;
+        for (int64_t m = 0; m < lk.count && ok; ++m) {
+            const int64_t r = mem[m];
+            float v = 0.f;
+            ok = stitched_frame(rows, n_rows, stride, table, frames, frame_rec(recs, r), ratios[r], core, context, span, i, &v);
+            acc = m == 0 ? v : mode == 0 ? fmaxf(acc, v) : acc + v;
+        }
+        if (!ok) continue;
+        if (mode == 1) acc = acc / (float)lk.count;
+        out_logits[lk.foff + i] = acc;
+        out_bits[lk.foff + i] = frame_decision(acc, thr);
+    }
+}
+
+// What both frame entries refuse of their arguments, before any table is read: false with the error set.
+static bool frames_args_ok(const char* who, const float* rows, const void* out, const int64_t* table, const int64_t* table_host,
+                           const int64_t* frames, const int64_t* frames_host, int nwin, const int64_t* recs,
+                           const int64_t* recs_host, const double* ratios, const double* ratios_host, int nrec, int64_t n_rows,
+                           int64_t stride, int64_t core, int64_t context) {
+    if (!window_args_ok(who, rows, out, table, table_host, nwin, stride)) return false;
+    if (!frames || !frames_host || !recs || !recs_host || !ratios || !ratios_host) { sos_set_error("%s: null pointer", who); return false; }
+    if (nrec < 1 || nrec > RAGGED_MAX_CLIPS || n_rows < 1 || n_rows > INT64_MAX / 8 / stride || core < 1 || context < 0 ||
+        context > RW_MAX_CONTEXT || core < 2 * context) {
+        sos_set_error("%s: bad args (1 .. 65535 recordings, got %d; %lld rows of %lld; core %lld >= 1 and >= twice the context "
+                      "%lld, 0 .. %lld)", who, nrec, (long long)n_rows, (long long)stride, (long long)core, (long long)context,
+                      (long long)RW_MAX_CONTEXT);
+        return false;
+    }
+    return true;
+}
+
+// Every window of recording r can be read: false with the error set, which names the window.
+static bool frames_windows_ok(const char* who, int r, const FrameRec& rec, const int64_t* table_host, const int64_t* frames_host,
+                              int64_t n_rows, int64_t stride) {
+    for (int64_t w = rec.first; w < rec.first + rec.K; ++w) {
+        const WindowRow e = window_row(table_host, w);
+        if (!frames_win_ok(e, frames_host[w], n_rows, stride)) {
+            sos_set_error("%s: window %lld of recording %d names a row outside the rows, or frames outside the stride (row "
+                          "%lld of %lld, frames %lld, stride %lld, start %lld, core %lld .. %lld)", who, (long long)w, r,
+                          (long long)e.row, (long long)n_rows, (long long)frames_host[w], (long long)stride,
+                          (long long)e.start, (long long)e.cs, (long long)e.ce);
+            return false;
+        }
+    }
+    return true;
 }
 
 extern "C" int sos_window_frames_stitch_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table,
@@ -459,15 +560,9 @@ extern "C" int sos_window_frames_stitch_f32(const float* rows, int64_t n_rows, i
                                             const double* ratios_host, int nrec, int64_t core, int64_t context, float* out,
                                             sos_stream_t stream) {
     const char* who = "sos_window_frames_stitch_f32";
-    if (!window_args_ok(who, rows, out, table, table_host, nwin, stride)) return SOS_EINVAL;
-    if (!frames || !frames_host || !recs || !recs_host || !ratios || !ratios_host) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
-    if (nrec < 1 || nrec > RAGGED_MAX_CLIPS || n_rows < 1 || n_rows > INT64_MAX / 8 / stride || core < 1 || context < 0 ||
-        context > RW_MAX_CONTEXT || core < 2 * context) {
-        sos_set_error("%s: bad args (1 .. 65535 recordings, got %d; %lld rows of %lld; core %lld >= 1 and >= twice the context "
-                      "%lld, 0 .. %lld)", who, nrec, (long long)n_rows, (long long)stride, (long long)core, (long long)context,
-                      (long long)RW_MAX_CONTEXT);
+    if (!frames_args_ok(who, rows, out, table, table_host, frames, frames_host, nwin, recs, recs_host, ratios, ratios_host, nrec,
+                        n_rows, stride, core, context))
         return SOS_EINVAL;
-    }
     RaggedSum nf;
     int bad = ragged_sum_column(recs_host, nrec, RW_REC_COLS, 1, 0, RW_MAX_FRAMES, &nf);
     if (bad < nrec) {
@@ -483,20 +578,104 @@ extern "C" int sos_window_frames_stitch_f32(const float* rows, int64_t n_rows, i
                           (long long)rec.F, (long long)nf.total, (long long)rec.first, (long long)rec.K, nwin, ratios_host[r]);
             return SOS_EINVAL;
         }
-        for (int64_t w = rec.first; w < rec.first + rec.K; ++w) {
-            const WindowRow e = window_row(table_host, w);
-            if (!frames_win_ok(e, frames_host[w], n_rows, stride)) {
-                sos_set_error("%s: window %lld of recording %d names a row outside the rows, or frames outside the stride (row "
-                              "%lld of %lld, frames %lld, stride %lld, start %lld, core %lld .. %lld)", who, (long long)w, r,
-                              (long long)e.row, (long long)n_rows, (long long)frames_host[w], (long long)stride,
-                              (long long)e.start, (long long)e.cs, (long long)e.ce);
-                return SOS_EINVAL;
-            }
-        }
+        if (!frames_windows_ok(who, r, rec, table_host, frames_host, n_rows, stride)) return SOS_EINVAL;
     }
     const dim3 grid(ragged_grid(nf.longest, RW_THREADS, RW_MAX_GRID), (unsigned)nrec);
     hipLaunchKernelGGL(window_frames_stitch_kernel, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, rows, n_rows, stride, table,
                        frames, (int64_t)nwin, recs, ratios, core, context, nf.total, out);
+    return sos_check_launch(who);
+}
+
+extern "C" int sos_window_frames_link_f32(const float* rows, int64_t n_rows, int64_t stride, const int64_t* table,
+                                          const int64_t* table_host, const int64_t* frames, const int64_t* frames_host, int nwin,
+                                          const int64_t* recs, const int64_t* recs_host, const double* ratios,
+                                          const double* ratios_host, int nrec, int64_t core, int64_t context, const int64_t* links,
+                                          const int64_t* links_host, const int64_t* members, const int64_t* members_host,
+                                          int ngroups, int mode, float threshold, float* out_logits, uint8_t* out_bits,
+                                          sos_stream_t stream) {
+    const char* who = "sos_window_frames_link_f32";
+    if (!frames_args_ok(who, rows, out_logits, table, table_host, frames, frames_host, nwin, recs, recs_host, ratios, ratios_host,
+                        nrec, n_rows, stride, core, context))
+        return SOS_EINVAL;
+    if (!links || !links_host || !members || !members_host || !out_bits) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
+    if (ngroups < 1 || ngroups > RAGGED_MAX_CLIPS || (mode != 0 && mode != 1) || !std::isfinite(threshold)) {
+        sos_set_error("%s: bad args (1 .. 65535 groups, got %d; mode %d, 0 = any or 1 = mean; threshold %g must be finite)", who,
+                      ngroups, mode, (double)threshold);
+        return SOS_EINVAL;
+    }
+    RaggedSum nf;
+    int bad = ragged_sum_column(links_host, ngroups, RW_LINK_COLS, 1, 0, RW_MAX_FRAMES, &nf);
+    if (bad < ngroups) {
+        sos_set_error("%s: group %d has %lld frames (0 .. %lld)", who, bad, (long long)link_row(links_host, bad).F,
+                      (long long)RW_MAX_FRAMES);
+        return SOS_EINVAL;
+    }
+    // `members` holds what the groups count: every group's range must lie inside that
+    int64_t nmem = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        const LinkRow lk = link_row(links_host, g);
+        if (lk.count < 1 || lk.count > nrec) {
+            sos_set_error(lk.count == 0 ? "%s: group %d has no members (%lld; 1 .. %d, the recordings)"
+                                        : "%s: group %d has a member count of %lld (1 .. %d, the recordings)", who, g,
+                          (long long)lk.count, nrec);
+            return SOS_EINVAL;
+        }
+        nmem += lk.count;
+    }
+    std::vector<std::pair<int64_t, int>> streams;              // {frame offset, group} of the groups that hold frames
+    for (int g = 0; g < ngroups; ++g) {
+        const LinkRow lk = link_row(links_host, g);
+        if (!link_ok(lk, nmem, nf.total)) {
+            sos_set_error("%s: group %d (frames %lld + %lld of %lld, members %lld + %lld of %lld) lies outside the summed output or "
+                          "the members", who, g, (long long)lk.foff, (long long)lk.F, (long long)nf.total, (long long)lk.first,
+                          (long long)lk.count, (long long)nmem);
+            return SOS_EINVAL;
+        }
+        if (lk.F > 0) streams.push_back({lk.foff, g});
+    }
+    std::sort(streams.begin(), streams.end());
+    for (size_t k = 1; k < streams.size(); ++k)
+        if (streams[k].first < streams[k - 1].first + link_row(links_host, streams[k - 1].second).F) {
+            sos_set_error("%s: group %d and group %d overlap in the output (frames from %lld and from %lld)", who,
+                          streams[k - 1].second, streams[k].second, (long long)streams[k - 1].first, (long long)streams[k].first);
+            return SOS_EINVAL;
+        }
+    std::vector<int> group_of(nrec, -1);
+    for (int g = 0; g < ngroups; ++g) {
+        const LinkRow lk = link_row(links_host, g);
+        const double rho = ratios_host[std::min<int64_t>(std::max<int64_t>(members_host[lk.first], 0), nrec - 1)];
+        for (int64_t m = 0; m < lk.count; ++m) {
+            const int64_t r = members_host[lk.first + m];
+            if (r < 0 || r >= nrec) {
+                sos_set_error("%s: member %lld of group %d names recording %lld of %d", who, (long long)m, g, (long long)r, nrec);
+                return SOS_EINVAL;
+            }
+            if (group_of[r] >= 0) {
+                sos_set_error("%s: recording %lld appears twice, as member %lld of group %d and in group %d", who, (long long)r,
+                              (long long)m, g, group_of[r]);
+                return SOS_EINVAL;
+            }
+            group_of[r] = g;
+            const FrameRec rec = frame_rec(recs_host, r);
+            if (!frames_rec_windows_ok(rec, ratios_host[r], nwin)) {
+                sos_set_error("%s: recording %lld, member %lld of group %d (frames %lld, windows %lld + %lld of %d, %g samples per "
+                              "frame) lies outside the table, or has a ratio outside (0, 2^30]", who, (long long)r, (long long)m, g,
+                              (long long)rec.F, (long long)rec.first, (long long)rec.K, nwin, ratios_host[r]);
+                return SOS_EINVAL;
+            }
+            if (rec.F != lk.F || ratios_host[r] != rho) {
+                sos_set_error("%s: recording %lld, member %lld of group %d, has %lld frames of %g samples; its group has %lld frames "
+                              "and its first member %g samples per frame: the members of a group share one frame grid", who,
+                              (long long)r, (long long)m, g, (long long)rec.F, ratios_host[r], (long long)lk.F, rho);
+                return SOS_EINVAL;
+            }
+            if (!frames_windows_ok(who, (int)r, rec, table_host, frames_host, n_rows, stride)) return SOS_EINVAL;
+        }
+    }
+    const dim3 grid(ragged_grid(nf.longest, RW_THREADS, RW_MAX_GRID), (unsigned)ngroups);
+    hipLaunchKernelGGL(window_frames_link_kernel, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, rows, n_rows, stride, table,
+                       frames, (int64_t)nwin, recs, ratios, (int64_t)nrec, links, members, nmem, core, context, mode, threshold,
+                       nf.total, out_logits, out_bits);
     return sos_check_launch(who);
 }
 

@@ -1,6 +1,8 @@
 """Recordings in, denoised recordings out: WAVE files of any channel count, rate and sample format through the chain of
-windows.denoise_long and back into files with the SAME number of frames, channels, rate and sample format.  Every channel is
-denoised on its own (no decision stream is shared between the channels of a file); the decode, the two resamplings, the windows
+windows.denoise_long and back into files with the SAME number of frames, channels, rate and sample format.  By default every
+channel is denoised on its own; link_channels='any' / 'mean' silences the channels of a file by ONE stream of decisions shared
+between them (windows.denoise_long(stitch_bits=True, link=): one sos_window_frames_link_f32 launch for all files of a group), so
+that the noise floors of a stereo pair drop in and out together.  The decode, the two resamplings, the windows
 and the encode each run in launches shared by all files and channels of a group (csrc/pcm_io.hip, csrc/wave_io.hip,
 csrc/ragged_window.hip)."""
 import os
@@ -11,6 +13,7 @@ import torch
 from . import audio_io
 from . import labels
 from . import ragged
+from . import tools
 from . import transform
 from . import windows
 from .pipeline import FPS, MIN_FRAMES, SR
@@ -25,8 +28,11 @@ def _model_samples(frames, rate):
     return int(frames) if rate == SR else int(np.ceil(int(frames) * (float(SR) / rate)))
 
 
-def _check_files(paths, out_dir, sample_format, suffix):
-    """Everything that can be refused from the chunk headers alone: -> (infos, formats, out_paths)."""
+def _check_files(paths, out_dir, sample_format, suffix, link_channels=None):
+    """Everything that can be refused from the arguments and the chunk headers alone: -> (infos, formats, out_paths)."""
+    if link_channels is not None and link_channels not in tools.LINK_MODES:
+        raise ValueError("denoise_recordings: unknown link_channels %r (None, or one of %s)"
+                         % (link_channels, ", ".join(sorted(tools.LINK_MODES))))
     if sample_format is not None and sample_format not in audio_io.ENCODINGS:
         raise ValueError("denoise_recordings: unsupported sample_format %r (one of %s)"
                          % (sample_format, ", ".join(sorted(audio_io.ENCODINGS))))
@@ -63,7 +69,7 @@ def _resample_back(clips, rates):
 
 @torch.no_grad()
 def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, context_seconds=2.0, max_batch=256,
-                       max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix=""):
+                       max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None):
     """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
     channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32; a float64 source is written as float32);
     sample_format= ('s16', 's24', 's32', 'u8', 'f32') forces one format for all files.
@@ -76,13 +82,17 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     return hop * (n // hop) samples and the resampler ceil(n * ratio)) and quantises it -- round half to even, saturating, NO
     dither; one download brings the group's bytes and counts to the host, and only then are its files written
     (audio_io.wave_container).  No call in the loop waits for the device except that download.
+    link_channels: None -- every channel gets its own silent-interval decisions, per window (denoise_long's default mode) -- or
+    'any' / 'mean': the channels of a file share ONE decision stream, the group's denoise_long call runs with stitch_bits=True,
+    link=<the file of each channel>, link_mode=link_channels ('any': a frame is speech if any channel has speech, so noise is
+    only estimated where every channel is silent; 'mean': the mean logit decides).  A mono file is a group of one.
     -> one dict per file: path, out_path, channels, rate, frames, format, clipped (samples that saturated or were NaN, all
     channels), windows (denoise_long windows, all channels).
     ValueError before any launch of the call, naming the file: fewer than MIN_FRAMES STFT frames at 14 kHz, an unsupported
-    format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format;
+    format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format or link_channels;
     window_plan's argument rules; a group with more than 65535 windows."""
     paths = [os.fspath(p) for p in paths]
-    infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix)
+    infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix, link_channels)
     core, context = windows._hops(round(window_seconds * SR)), windows._hops(round(context_seconds * SR))
     groups = ragged.byte_groups([4 * i["frames"] * i["channels"] for i in infos], max_bytes)
     plans = []                                          # host only: refuses bad window arguments and a group of too many windows
@@ -98,7 +108,9 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
         ys, _, _ = audio_io.load_channels_batch_device([paths[f] for f in group], sr=SR)
         owner = [f for f, y in zip(group, ys) for _ in range(y.shape[0])]                           # the file of each channel
         clips = [y[c] for y in ys for c in range(y.shape[0])]
-        outs = windows.denoise_long(detector, denoiser, clips, SR, FPS, window_seconds, context_seconds, max_batch, max_columns)
+        linked = dict(stitch_bits=True, link=owner, link_mode=link_channels) if link_channels is not None else {}
+        outs = windows.denoise_long(detector, denoiser, clips, SR, FPS, window_seconds, context_seconds, max_batch, max_columns,
+                                    **linked)
         outs = _resample_back(outs, [infos[f]["rate"] for f in owner])
         per_file, k = {}, 0
         for f, y in zip(group, ys):

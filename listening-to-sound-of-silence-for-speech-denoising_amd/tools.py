@@ -182,6 +182,64 @@ def window_frames_stitch(rows, table, win_frames, recs, ratios, core, context):
     return out
 
 
+LINK_MODES = {"any": 0, "mean": 1}          # the `mode` of sos_window_frames_link_f32
+
+
+def link_tables(link, frames):
+    """The link tables of sos_window_frames_link_f32 (host only).  link: one group id per recording, None = a group of its
+    own; recordings with equal ids are linked.  frames: the recordings' frame counts (members of a group must agree: the
+    caller's check).  Groups stand in the order of their first member, members in recording order.
+    -> (links int64 (groups, 4) = {frame offset of the group's stream, frames, first index into members, member count},
+    members int64 (recordings,), group int64 (recordings,) = the group of each recording)."""
+    index, rows, group = {}, [], []
+    for r, g in enumerate(link):
+        key = ("alone", r) if g is None else ("id", g)
+        if key not in index:
+            index[key] = len(rows)
+            rows.append([])
+        rows[index[key]].append(r)
+        group.append(index[key])
+    counts = [len(m) for m in rows]
+    fr = [int(frames[m[0]]) for m in rows]
+    links = np.stack([ragged.offsets(fr), np.asarray(fr, dtype=np.int64), ragged.offsets(counts),
+                      np.asarray(counts, dtype=np.int64)], axis=1) if rows else np.zeros((0, 4), dtype=np.int64)
+    return (np.ascontiguousarray(links, dtype=np.int64), np.asarray([r for m in rows for r in m], dtype=np.int64),
+            np.asarray(group, dtype=np.int64))
+
+
+def window_frames_link(rows, table, win_frames, recs, ratios, core, context, links, members, mode, threshold=0.5):
+    """window_frames_stitch, the reduction over the recordings of a group and the decision in ONE launch
+    (sos_window_frames_link_f32): one logit and one decision stream per GROUP.  rows .. context: as window_frames_stitch
+    (the recs rows' frame offsets are not used); links: host rows {frame offset of the group's stream, frames, first index into
+    members, member count}; members: recording indices; mode: 'any' (fmaxf in member order: a frame is speech if any member
+    has speech) or 'mean' (sequential f32 sum in member order, one f32 divide); threshold: of the sigmoid, as threshold_bits.
+    -> (logits f32, bits uint8), 1-D GPU tensors of sum(frames of the groups) elements, the groups' streams back to back."""
+    L.require_cuda(rows)
+    tab, rec, lk = _host_table(table, WINDOW_COLS), _host_table(recs, 4), _host_table(links, 4)
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
+    fr = np.ascontiguousarray(np.asarray(win_frames, dtype=np.int64).reshape(-1))
+    if len(fr) != tab.shape[0]:
+        raise ValueError("win_frames must hold one count per window of the table")
+    if mode not in LINK_MODES:
+        raise ValueError(f"mode must be one of {sorted(LINK_MODES)}, got {mode!r}")
+    mem = np.ascontiguousarray(np.asarray(members, dtype=np.int64).reshape(-1))
+    if len(mem) < 1 or len(mem) != int(lk[:, 3].sum()):
+        raise ValueError("members must hold one recording index per member the links count")
+    rat = ragged.per_clip(ratios, rec.shape[0], "ratios")
+    total = max(int(lk[:, 1].sum()), 0)
+    logits = torch.empty(total, dtype=torch.float32, device=rows.device)
+    bits = torch.empty(total, dtype=torch.uint8, device=rows.device)
+    d_tab, d_fr, d_rec, d_rat, d_lk, d_mem = (_upload(a, rows.device) for a in (tab, fr, rec, rat, lk, mem))
+    L.check(L.lib().sos_window_frames_link_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data,
+                                               L.ptr(d_fr), fr.ctypes.data, tab.shape[0], L.ptr(d_rec), rec.ctypes.data,
+                                               L.ptr(d_rat), rat.ctypes.data, rec.shape[0], int(core), int(context), L.ptr(d_lk),
+                                               lk.ctypes.data, L.ptr(d_mem), mem.ctypes.data, lk.shape[0], LINK_MODES[mode],
+                                               float(threshold), L.ptr(logits), L.ptr(bits), L.stream_ptr()),
+            "sos_window_frames_link_f32")
+    return logits, bits
+
+
 def window_stage_masked(flat, bits, clips, ratios, table, stride):
     """Windows of recordings staged together with their noise intervals in one launch (sos_window_stage_masked_f32).  flat: the
     recordings back to back, contiguous 1-D f32 GPU tensor; bits: their frame decisions back to back (uint8 GPU tensor, 1 =

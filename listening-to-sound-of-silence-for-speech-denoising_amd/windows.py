@@ -96,6 +96,37 @@ def _stitch_frames(kept, plan, wf, frames, sr, rates, core, context):
     return logits, tools.threshold_bits(logits, SIGMOID_THRESHOLD)[0]
 
 
+def _check_link(who, link, link_mode, n_recordings):
+    """What can be refused of `link` / `link_mode` from the arguments alone."""
+    if link_mode not in tools.LINK_MODES:
+        raise ValueError(f"{who}: link_mode must be one of {sorted(tools.LINK_MODES)}, got {link_mode!r}")
+    if link is not None and len(link) != n_recordings:
+        raise ValueError(f"{who}: link must hold one group id (or None) per recording: {n_recordings}, got {len(link)}")
+
+
+def _link_tables(link, ns, rates, frames):
+    """tools.link_tables of `link`, host only.  ValueError: members of a group that differ in samples, fps or frames."""
+    links, members, group = tools.link_tables(link, frames)
+    for r, g in enumerate(group):
+        m = int(members[links[g, 2]])                           # the group's first member
+        if (ns[r], float(rates[r]), frames[r]) != (ns[m], float(rates[m]), frames[m]):
+            raise ValueError(f"linked recordings share one frame grid: recording {r} has {ns[r]} samples, {float(rates[r])} fps and "
+                             f"{frames[r]} frames, recording {m} of its group {link[r]!r} has {ns[m]}, {float(rates[m])} and {frames[m]}")
+    return links, members, group
+
+
+def _link_frames(kept, plan, wf, frames, sr, rates, core, context, tables, link_mode):
+    """_stitch_frames for linked recordings (tables: _link_tables'): -> [(logits, bits) per recording], every member of a group
+    the SAME two tensors, views of the groups' streams that ONE sos_window_frames_link_f32 launch makes for all groups."""
+    links, members, group = tables
+    first = _first_windows(plan, len(frames))
+    recs = np.stack([ragged.offsets(frames), np.asarray(frames, dtype=np.int64), first[:-1], np.diff(first)], axis=1)
+    logits, bits = tools.window_frames_link(kept, plan, wf, recs, [float(sr) / float(f) for f in rates], core, context, links,
+                                            members, link_mode, SIGMOID_THRESHOLD)
+    lg, b = ragged.split(logits, links[:, 1]), ragged.split(bits, links[:, 1])
+    return [(lg[g], b[g]) for g in group]
+
+
 def _recording_frames(n_frames, ns, sr, rates):
     if n_frames is None:
         return [n_video_frames(n, sr, f) for n, f in zip(ns, rates)]
@@ -133,7 +164,7 @@ def _run_windows(plan, device, max_batch, max_columns, run_group, planes=None, w
 
 @torch.no_grad()
 def detect_long(detector, clips, sr=SR, fps=FPS, window_seconds=30.0, context_seconds=2.0, max_batch=256, max_columns=65536,
-                n_frames=None, return_all=False):
+                n_frames=None, return_all=False, link=None, link_mode="any"):
     """The detector half of denoise_long: ONE stream of frame decisions per recording of any length.  `clips` are cut, staged
     and grouped exactly as denoise_long does it (window_plan, one sos_window_stage_f32 launch, one STFT and one detect() call
     with per-window frame counts per group); every group's logits are kept in one (windows, most frames of a window) buffer,
@@ -144,16 +175,25 @@ def detect_long(detector, clips, sr=SR, fps=FPS, window_seconds=30.0, context_se
     fps: a scalar or one value per recording.  n_frames: the recordings' numbers of decisions (a file's label is not always
     n_video_frames(samples, sr, fps) long); default n_video_frames.  A recording shorter than two cores is one window with
     exactly these frames: denoise_ragged's clip, logits and bits bit for bit.
+    link: one group id per recording (None: a group of its own); recordings with equal ids -- the channels of a file -- share
+    ONE decision stream.  The stitch and the threshold launch are then replaced by ONE sos_window_frames_link_f32 launch, which
+    stitches every member, reduces the members' logits in recording order (link_mode 'any': the maximum, a frame is speech if
+    any member has speech; 'mean': the f32 mean; numpy restatement tests/link_reference.py) and decides; every member of a
+    group gets the SAME (logits, bits) tensors.  The members of a group must agree in samples, fps and frames.  link=None:
+    nothing changes.
     -> [(logits f32 (F,), bits uint8 (F,)) per recording], views of one buffer each, in input order; return_all adds per
     recording dict(plan=its window_plan rows (row = the order the windows ran in), windows=[logits per window]).
-    ValueError before any launch as denoise_long."""
+    ValueError before any launch as denoise_long; also a `link` of the wrong length, an unknown link_mode, linked recordings
+    that differ in samples, fps or frames."""
     clips = list(clips)
+    _check_link("detect_long", link, link_mode, len(clips))
     if not clips:
         return ([], []) if return_all else []
     core, context, ns, plan = _long_plan("detect_long", clips, sr, window_seconds, context_seconds)
     rates = ragged.per_clip(fps, len(clips), "fps")
     frames = _recording_frames(n_frames, ns, sr, rates)
     wf = _window_frames(plan, sr, rates, frames)
+    tables = None if link is None else _link_tables(link, ns, rates, frames)
     flat, _ = ragged.concat(clips)
 
     def run_group(part, sub, m, rows):
@@ -163,8 +203,11 @@ def detect_long(detector, clips, sr=SR, fps=FPS, window_seconds=30.0, context_se
         return detect(detector, transform.stft_batch(wave, clip_samples=rag.tab(rag.n_samples)), max(nv), rag=rag)
 
     kept = _run_windows(plan, flat.device, max_batch, max_columns, run_group, width=max(wf))
-    logits, bits = _stitch_frames(kept, plan, wf, frames, sr, rates, core, context)
-    pairs = list(zip(ragged.split(logits, frames), ragged.split(bits, frames)))
+    if link is None:
+        logits, bits = _stitch_frames(kept, plan, wf, frames, sr, rates, core, context)
+        pairs = list(zip(ragged.split(logits, frames), ragged.split(bits, frames)))
+    else:
+        pairs = _link_frames(kept, plan, wf, frames, sr, rates, core, context, tables, link_mode)
     if not return_all:
         return pairs
     first = _first_windows(plan, len(clips))
@@ -192,7 +235,7 @@ def _stitch_signals(kept, plan, context, recs=None, out_total=None):
 
 @torch.no_grad()
 def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0, context_seconds=2.0, max_batch=256,
-                 max_columns=65536, bits=None, return_all=False, stitch_bits=False, signals=False):
+                 max_columns=65536, bits=None, return_all=False, stitch_bits=False, signals=False, link=None, link_mode="any"):
     """Recordings of ANY length, minutes and hours included: `clips` = list of 1-D f32 GPU waveforms, short and long mixed.
     denoise_ragged runs a recording as one clip, which ends at sos_conv2d_fwd's 4 GB image (about 16 minutes at 14 kHz), needs
     ~0.5 MB of activations per STFT column and steps both BiLSTMs serially through the whole file.  Here every recording is cut
@@ -218,6 +261,9 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
     on its device-resident bits, bit for bit denoise_long(None, denoiser, clips, bits=<detect_long's bits>, fps=fps) -- where
     the default silences each window by that window's own detector pass, so that the two windows cross-faded around a core
     boundary may have been denoised with different noise intervals there.  `fps` may then be one value per recording.
+    link / link_mode (with stitch_bits=True only): detect_long's -- recordings with equal group ids, the channels of a file, are
+    silenced by ONE shared stream, so their noise floors drop in and out together: bit for bit denoise_long(None, denoiser,
+    clips, bits=<the group's stream for each recording>, fps=fps).
     Outputs come back in input order, each hop * (n // hop) samples long, views into one buffer.  return_all adds per recording
     dict(plan=its window_plan rows (row = the order the windows ran in), windows=[dict(logits, bits) per window], logits, bits=
     the recording's stitched stream as detect_long makes it, one more small launch); with `bits` dict(plan, bits, mask=the
@@ -228,8 +274,13 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
     bit; extra[r] holds `noisy_input`, `noise_intervals`, `predicted_full_noise` (the ISTFTs of the mixed, the noise-interval
     and the predicted-noise spectrograms, stitched), each as long as the output, plus return_all's keys if that is set.
     ValueError before any launch: window_plan's (a recording below MIN_FRAMES frames is named), more than 65535 windows,
-    stitch_bits together with bits, signals without decisions for the whole recording (neither bits nor stitch_bits)."""
+    stitch_bits together with bits, signals without decisions for the whole recording (neither bits nor stitch_bits), link
+    without stitch_bits, and what detect_long refuses of link and link_mode."""
     clips = list(clips)
+    if link is not None and not stitch_bits:
+        raise ValueError("link= shares the detector's one stream per recording between recordings: it needs stitch_bits=True (the "
+                         "default mode decides per window, and bits= already is a decision)")
+    _check_link("denoise_long", link, link_mode, len(clips))
     if signals and bits is None and not stitch_bits:
         raise ValueError("signals=True needs one decision stream per recording: pass bits=, or stitch_bits=True")
     if stitch_bits and bits is not None:
@@ -242,7 +293,8 @@ def denoise_long(detector, denoiser, clips, sr=SR, fps=FPS, window_seconds=30.0,
     if not clips:
         return ([], []) if return_all or signals else []
     if stitch_bits:                                             # detect_long refuses what _long_plan refuses, before any launch
-        pairs = detect_long(detector, clips, sr, fps, window_seconds, context_seconds, max_batch, max_columns)
+        pairs = detect_long(detector, clips, sr, fps, window_seconds, context_seconds, max_batch, max_columns, link=link,
+                            link_mode=link_mode)
         res = denoise_long(None, denoiser, clips, sr, fps, window_seconds, context_seconds, max_batch, max_columns,
                            bits=[b for _, b in pairs], return_all=return_all, signals=signals)
         if return_all:

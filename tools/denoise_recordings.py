@@ -2,6 +2,7 @@
 count, channels, rate and sample format.
 
   python tools/denoise_recordings.py DETECTOR.pth DENOISER.pth OUT_DIR in1.wav in2.wav ... [--sample-format s16] [--suffix _dn]
+                                     [--link-channels any]
 
 The checkpoints are the reference's (`{clock, model_state_dict, ...}` as the agents save them) or bare state dicts."""
 import argparse
@@ -36,12 +37,16 @@ def main():
     ap.add_argument("--max-columns", type=int, default=65536)
     ap.add_argument("--sample-format", choices=sorted(audio_io.ENCODINGS), default=None, help="one format for all files (default: each source's)")
     ap.add_argument("--suffix", default="")
+    ap.add_argument("--link-channels", choices=["any", "mean"], default=None,
+                    help="the channels of a file share one stream of silent-interval decisions: a frame is speech if ANY channel has "
+                         "speech, or if the MEAN logit says so (default: every channel decides on its own)")
     ap.add_argument("--precision", default="mixed", choices=["bf16", "bf16x3", "fp16", "mixed"])
     args = ap.parse_args()
     det, jm = _load(dnet.get_network(), args.detector), _load(jnet.get_network(MyConfig()), args.denoiser)
     sos_amd.set_precision(args.precision)
     for r in recordings.denoise_recordings(det, jm, args.files, args.out_dir, args.window_seconds, args.context_seconds, args.max_batch,
-                                           args.max_columns, sample_format=args.sample_format, suffix=args.suffix):
+                                           args.max_columns, sample_format=args.sample_format, suffix=args.suffix,
+                                           link_channels=args.link_channels):
         print("%s -> %s: %d x %d frames at %d Hz, %s, %d windows, %d samples clipped"
               % (r["path"], r["out_path"], r["channels"], r["frames"], r["rate"], r["format"], r["windows"], r["clipped"]))
 

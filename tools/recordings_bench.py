@@ -10,6 +10,13 @@ in a temporary directory, in 'mixed' precision:
      written per second, from device events over --kernel-reps launches, against Tensor.copy_ of a float32 buffer moving the same
      number of bytes in the same run; the encode once on planes that never saturate and once on planes of which 9 % do (every
      workgroup then adds to its file's count).
+  4. with --link-channels any|mean: (a) denoise_recordings(link_channels=) against link_channels=None on the same files, both
+     warmed, alternating, in the same run of the program -- the linked mode runs denoise_long(stitch_bits=True), a separate
+     detector pass, so it is expected to cost more, and the figure is what the shared stream costs; (b) the ONE
+     sos_window_frames_link_f32 launch against what it replaces -- one stitch launch, one torch reduction per file in a Python
+     loop, one concatenation and one threshold launch -- on the same random logit rows of the same files' plan
+     (--link-window-seconds long windows), wall time per call from an idle device to an idle device, --link-reps calls each,
+     alternating.  Both forms are checked to give the same bits before they are timed.
 A measurement: nothing is asserted."""
 import argparse
 import os
@@ -23,7 +30,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sos_amd  # noqa: E402
 from oracle import nets as onet  # noqa: E402
-from sos_amd import audio_io, pipeline, recordings, windows  # noqa: E402
+from sos_amd import audio_io, pipeline, ragged, recordings, tools, windows  # noqa: E402
 from sos_amd.common import MyConfig  # noqa: E402
 from sos_amd.denoiser import networks as jnet  # noqa: E402
 from sos_amd.detector import networks as dnet  # noqa: E402
@@ -141,6 +148,53 @@ def kernels(args, amplitude):
               f"{nbytes / copy_ms / 1e6:7.1f} GB/s    ratio {copy_ms / ms:.2f}")
 
 
+def link_launch(args, paths):
+    """4 (b): the link launch against stitch + per-file reduction + threshold on the same rows."""
+    infos = [audio_io.wave_info(p) for p in paths]
+    ns = [recordings._model_samples(i["frames"], i["rate"]) for i in infos for _ in range(i["channels"])]
+    owner = [f for f, i in enumerate(infos) for _ in range(i["channels"])]
+    core, context = windows._hops(round(args.link_window_seconds * pipeline.SR)), windows._hops(round(args.link_window_seconds / 8 * pipeline.SR))
+    plan = windows.window_plan(ns, core, context)
+    frames = [pipeline.n_video_frames(n) for n in ns]
+    rates = [pipeline.FPS] * len(ns)
+    wf = windows._window_frames(plan, pipeline.SR, rates, frames)
+    first = windows._first_windows(plan, len(ns))
+    recs = np.stack([ragged.offsets(frames), np.asarray(frames, dtype=np.int64), first[:-1], np.diff(first)], axis=1)
+    links, members, _ = tools.link_tables(owner, frames)
+    ratio = pipeline.SR / pipeline.FPS
+    rows = torch.empty((len(plan), max(wf)), dtype=torch.float32, device="cuda").normal_()
+    chans = [[int(m) for m in members[f:f + n]] for _, _, f, n in links]
+    mode = args.link_channels
+
+    def one():
+        return tools.window_frames_link(rows, plan, wf, recs, ratio, core, context, links, members, mode, pipeline.SIGMOID_THRESHOLD)
+
+    def pieces():
+        per = ragged.split(tools.window_frames_stitch(rows, plan, wf, recs, ratio, core, context), frames)
+        out = []
+        for ch in chans:                                        # one reduction per file
+            x = per[ch[0]]
+            for m in ch[1:]:
+                x = torch.maximum(x, per[m]) if mode == "any" else x + per[m]
+            out.append(x / float(len(ch)) if mode == "mean" else x)
+        logits = torch.cat(out)
+        return logits, tools.threshold_bits(logits, pipeline.SIGMOID_THRESHOLD)[0]
+
+    a, b = one(), pieces()
+    same = torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    runs = dict(one=[], pieces=[])
+    for _ in range(args.link_reps):
+        runs["one"].append(once(one)[0])
+        runs["pieces"].append(once(pieces)[0])
+    t1, t2 = float(np.median(runs["one"])), float(np.median(runs["pieces"]))
+    print(f"link launch: {len(links)} files, {len(ns)} channels, {len(plan)} windows of {args.link_window_seconds:g} s, {int(links[:, 1].sum())} "
+          f"group frames, mode {mode}, {args.link_reps} alternating calls each (median wall time, idle device to idle device); "
+          f"same logits and bits: {same}")
+    print(f"  one sos_window_frames_link_f32 launch         : {t1 * 1e6:8.1f} us (min {min(runs['one']) * 1e6:.1f}, max {max(runs['one']) * 1e6:.1f})")
+    print(f"  stitch + reduction per file + cat + threshold : {t2 * 1e6:8.1f} us (min {min(runs['pieces']) * 1e6:.1f}, max {max(runs['pieces']) * 1e6:.1f})"
+          f"   ratio {t2 / t1:.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=64)
@@ -151,9 +205,38 @@ def main():
     ap.add_argument("--kernel-reps", type=int, default=20)
     ap.add_argument("--amplitudes", type=float, nargs="+", default=[0.9, 1.1], help="encode inputs: nothing saturates below 1")
     ap.add_argument("--skip-loop", action="store_true", help="only the kernels")
+    ap.add_argument("--link-channels", choices=["any", "mean"], default=None, help="measure the shared decision stream (4.) and nothing else")
+    ap.add_argument("--link-window-seconds", type=float, default=2.0, help="4 (b): the windows of the link-launch comparison")
+    ap.add_argument("--link-reps", type=int, default=50)
     args = ap.parse_args()
     print(torch.cuda.get_device_name(0))
     _count_downloads()
+    if args.link_channels:
+        det = dnet.get_network()
+        det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+        jm = jnet.get_network(MyConfig())
+        jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+        det, jm = det.cuda().eval(), jm.cuda().eval()
+        sos_amd.set_precision("mixed")
+        with tempfile.TemporaryDirectory() as tmp:
+            paths, secs = make_files(tmp, args.files, args.seed)
+            forms = dict(unlinked=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "unlinked"), max_batch=args.max_batch),
+                         linked=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "linked"), max_batch=args.max_batch,
+                                                                      link_channels=args.link_channels))
+            for fn in forms.values():                                                     # warm-up of both forms
+                fn()
+            runs = {k: [] for k in forms}
+            for _ in range(args.repeats):                                                 # the forms alternate
+                for k, fn in forms.items():
+                    runs[k].append(once(fn))
+            print(f"{args.files} stereo s16 files at {RATE} Hz, {secs:.0f} s of audio x 2 channels, 'mixed' precision, {args.repeats} "
+                  "alternating repeats (median, min, max)")
+            u = report("link_channels=None", args.files, runs["unlinked"])
+            k = report("link_channels=%r" % args.link_channels, args.files, runs["linked"])
+            print(f"  linked / unlinked = {k / u:.3f}")
+            link_launch(args, paths)
+        sos_amd.set_precision("bf16")
+        return
     if not args.skip_loop:
         det = dnet.get_network()
         det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
