@@ -112,7 +112,6 @@ def _run_up(lp, src, dst, c_off, rag=None, lsrc=0, ldst=0):
     """Four output-parity phases of the transposed conv, each a small stride-1 conv written to the
     interleaved positions of `dst` (cropped to dst's size == the reference's nearest-resize fix-up
     F.interpolate(out, skip.size()) which drops the surplus last row/column, M2/networks.py:199-203)."""
-    row = dst.nseg * dst.cs
     for (ph, pw), w in lp["phases"].items():
         Ho = min(src.H, (dst.H - ph + 1) // 2)
         Wo = min(src.W, (dst.W - pw + 1) // 2)
@@ -123,10 +122,8 @@ def _run_up(lp, src, dst, c_off, rag=None, lsrc=0, ldst=0):
             ws, wd = rag.widths(lsrc), rag.widths(ldst)
             wo = [min(a, (b - pw + 1) // 2) for a, b in zip(ws, wd)]
             rk = dict(wl_tab=rag.tab(ws), wo_tab=rag.tab(wo), valid_cols=sum(wo))
-        E.conv(src, 0, lp["cin_store"], w, 1 + ph, 1 + pw, lp["cout"], lp["scale"], lp["shift"], L.ACT_PRELU,
-               out=dst.t, out_dtype=dst.dtype_code, sb=dst.H * dst.W * row, sh=2 * dst.W * row, sw=2 * row, sc=1,
-               c_off=c_off, cout_store=lp["cout"], third=dst.cs, slope=lp["slope"], Ho=Ho, Wo=Wo,
-               out_elem_offset=(ph * dst.W + pw) * row, **rk)
+        E.conv_to_phase(src, 0, lp["cin_store"], w, 1 + ph, 1 + pw, lp["cout"], lp["scale"], lp["shift"], L.ACT_PRELU, dst,
+                        2, ph, pw, c_off=c_off, slope=lp["slope"], Ho=Ho, Wo=Wo, **rk)
 
 
 class InpaintNet(nn.Module):
@@ -324,6 +321,13 @@ class ContextAggNet(nn.Module):
         if started is not None:
             torch.cuda.current_stream(dev).wait_stream(started["side"])      # join: the feature matrix is complete
         h = CN.run_lstm(plan["lstm"], (feat, B, 1, T, nfeat, nseg), B, T, x3, dev, lengths=lengths)
+        return self._fc_head(plan, h, F, x3)[2]
+
+    @staticmethod
+    def _fc_head(plan, h, F, x3):
+        """fc over the BiLSTM output h (Act [B,1,T,*]) -> (hidden Acts a0, a1, sigmoid mask f32 (B,2,F,T)); the inference
+        and the training plan carry the same keys."""
+        B, T, dev = h.B, h.W, h.t.device
         f0, f2, f4 = plan["fc0"], plan["fc2"], plan["fc4"]
         a0 = E.Act(B, 1, T, E.pad_to(600, 16), x3, dev)
         a1 = E.Act(B, 1, T, E.pad_to(600, 16), x3, dev)
@@ -335,7 +339,7 @@ class ContextAggNet(nn.Module):
         # fc output index c*F+f of pixel (b,t) lands at out[b, c, f, t]  (permute(0,2,1).view, :92)
         E.conv(a1, 0, f4["cin_store"], f4["w"], 1, 1, 2 * F, f4["scale"], f4["shift"], L.ACT_SIGMOID, out=out,
                out_dtype=L.DT_F32, sb=2 * F * T, sh=0, sw=1, sc=T, Ho=1, Wo=T)
-        return out
+        return a0, a1, out
 
     # ------------------------------------------------------------------ training path
     def build_train_plan(self, x3):
@@ -373,16 +377,7 @@ class ContextAggNet(nn.Module):
         if before_lstm is not None:    # agent.train_concurrent: the recurrence, the FC head and their backward leave the chip
             before_lstm()              # mostly idle (8 workgroups stepping through T frames): another model's forward may start
         h, tl = TO.lstm_forward_train(plan["lstm"], (feat, B, 1, T, nfeat, nseg), B, T, x3, dev)
-        f0, f2, f4 = plan["fc0"], plan["fc2"], plan["fc4"]
-        a0 = E.Act(B, 1, T, E.pad_to(600, 16), x3, dev)
-        a1 = E.Act(B, 1, T, E.pad_to(600, 16), x3, dev)
-        E.conv_to_act(h, 0, f0["cin_store"], f0["w"], 1, 1, 600, f0["scale"], f0["shift"], L.ACT_RELU, a0,
-                      cout_store=a0.cs, Ho=1, Wo=T)
-        E.conv_to_act(a0, 0, f2["cin_store"], f2["w"], 1, 1, 600, f2["scale"], f2["shift"], L.ACT_RELU, a1,
-                      cout_store=a1.cs, Ho=1, Wo=T)
-        out = torch.empty((B, 2, F, T), dtype=torch.float32, device=dev)
-        E.conv(a1, 0, f4["cin_store"], f4["w"], 1, 1, 2 * F, f4["scale"], f4["shift"], L.ACT_SIGMOID, out=out,
-               out_dtype=L.DT_F32, sb=2 * F * T, sh=0, sw=1, sc=T, Ho=1, Wo=T)
+        a0, a1, out = self._fc_head(plan, h, F, x3)
         return out, dict(tx=tx, tn=tn, tl=tl, h=h, a0=a0, a1=a1, out=out, dims=(B, F, T), n=n, n_extra=n_extra)
 
     def backward(self, plan, tape, g_out, grads, x3, prefix="stage2", side=None, tail=None, before_join=None):

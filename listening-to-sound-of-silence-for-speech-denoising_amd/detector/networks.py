@@ -81,6 +81,20 @@ class AudioVisualNet(nn.Module):
                     fc2=CN.linear_plan(self.fc1[2], E.pad_to(100, 16), x3),
                     fc2abs=CN.linear_plan(self.fc1[2], E.pad_to(100, 16), x3, absolute=True))
 
+    @staticmethod
+    def _fc_head(plan, h, x3, zero):
+        """fc1 over the BiLSTM output h (Act [B,1,n,*]) -> (hidden Act m, logits f32 (B, n)); the inference and the training
+        plan carry the same keys.  zero: the training path zeroes m's padding channels."""
+        B, n, dev = h.B, h.W, h.t.device
+        f0, f2 = plan["fc0"], plan["fc2"]
+        m = E.Act(B, 1, n, E.pad_to(f0["cout"], 16), x3, dev, zero=zero)
+        E.conv_to_act(h, 0, f0["cin_store"], f0["w"], 1, 1, f0["cout"], f0["scale"], f0["shift"], L.ACT_RELU, m,
+                      cout_store=m.cs, Ho=1, Wo=n)
+        out = torch.empty((B, n), dtype=torch.float32, device=dev)
+        E.conv(m, 0, f2["cin_store"], f2["w"], 1, 1, 1, f2["scale"], f2["shift"], L.ACT_NONE, out=out,
+               out_dtype=L.DT_F32, sb=n, sh=0, sw=1, sc=1, Ho=1, Wo=n)
+        return m, out
+
     # ------------------------------------------------------------------ training path
     def _build_train_plan(self):
         x3 = E.is_x3()
@@ -107,13 +121,7 @@ class AudioVisualNet(nn.Module):
             frames = E.pack_input(v.float().permute(0, 2, 1, 3, 4).reshape(B * n, 3, v.shape[3], v.shape[4]), x3)
             tape_vid = TO.video_forward_train(plan["vid"], frames, B, n, feat, nseg * nfeat, nfeat, 8 * F, x3)
         h, tape_lstm = TO.lstm_forward_train(plan["lstm"], (feat, B, 1, n, nfeat, nseg), B, n, x3, dev)
-        f0, f2 = plan["fc0"], plan["fc2"]
-        m = E.Act(B, 1, n, E.pad_to(f0["cout"], 16), x3, dev, zero=True)
-        E.conv_to_act(h, 0, f0["cin_store"], f0["w"], 1, 1, f0["cout"], f0["scale"], f0["shift"], L.ACT_RELU, m,
-                      cout_store=m.cs, Ho=1, Wo=n)
-        out = torch.empty((B, n), dtype=torch.float32, device=dev)
-        E.conv(m, 0, f2["cin_store"], f2["w"], 1, 1, 1, f2["scale"], f2["shift"], L.ACT_NONE, out=out,
-               out_dtype=L.DT_F32, sb=n, sh=0, sw=1, sc=1, Ho=1, Wo=n)
+        m, out = self._fc_head(plan, h, x3, zero=True)
         tape = dict(plan=plan, enc=tape_enc, vid=tape_vid, lstm=tape_lstm, h=h, m=m, gather=gather, dims=(B, F, T, n), x3=x3)
         return out, tape
 
@@ -201,13 +209,7 @@ class AudioVisualNet(nn.Module):
         if before_lstm is not None:
             before_lstm()
         h = CN.run_lstm(plan["lstm"], (feat, B, 1, n, nfeat, nseg), B, n, x3, dev, lengths=lengths)
-        f0, f2 = plan["fc0"], plan["fc2"]
-        m = E.Act(B, 1, n, E.pad_to(f0["cout"], 16), x3, dev)
-        E.conv_to_act(h, 0, f0["cin_store"], f0["w"], 1, 1, f0["cout"], f0["scale"], f0["shift"], L.ACT_RELU, m,
-                      cout_store=m.cs, Ho=1, Wo=n)
-        out = torch.empty((B, n), dtype=torch.float32, device=dev)
-        E.conv(m, 0, f2["cin_store"], f2["w"], 1, 1, 1, f2["scale"], f2["shift"], L.ACT_NONE, out=out,
-               out_dtype=L.DT_F32, sb=n, sh=0, sw=1, sc=1, Ho=1, Wo=n)
+        m, out = self._fc_head(plan, h, x3, zero=False)
         if not return_scale:
             return out
         fa = plan["fc2abs"]

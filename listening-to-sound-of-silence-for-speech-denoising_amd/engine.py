@@ -492,12 +492,19 @@ def conv(src, cin_off, cin, wgt, kh, kw, cout, scale, shift, act, *, out, out_dt
     return stats
 
 
-def conv_to_act(src, cin_off, cin, wgt, kh, kw, cout, scale, shift, act, dst, c_off=0, cout_store=None, **kw_):
-    """Conv whose output is (a channel slice of) a dense NHWC Act."""
+def conv_to_phase(src, cin_off, cin, wgt, kh, kw, cout, scale, shift, act, dst, s, rh, rw, c_off=0, cout_store=None, **kw_):
+    """Conv whose output pixel (i, j) is pixel (s * i + rh, s * j + rw) of (a channel slice of) a dense NHWC Act: phase
+    (rh, rw) of its stride-s grid.  The one place that writes this geometry; Ho / Wo (the phase's own size) are the caller's."""
     row = dst.nseg * dst.cs
     return conv(src, cin_off, cin, wgt, kh, kw, cout, scale, shift, act, out=dst.t, out_dtype=dst.dtype_code,
-                sb=dst.H * dst.W * row, sh=dst.W * row, sw=row, sc=1, c_off=c_off,
-                cout_store=cout if cout_store is None else cout_store, third=dst.cs, **kw_)
+                sb=dst.H * dst.W * row, sh=s * dst.W * row, sw=s * row, sc=1, c_off=c_off,
+                cout_store=cout if cout_store is None else cout_store, third=dst.cs,
+                out_elem_offset=(rh * dst.W + rw) * row, **kw_)
+
+
+def conv_to_act(src, cin_off, cin, wgt, kh, kw, cout, scale, shift, act, dst, c_off=0, cout_store=None, **kw_):
+    """Conv whose output is (a channel slice of) a dense NHWC Act."""
+    return conv_to_phase(src, cin_off, cin, wgt, kh, kw, cout, scale, shift, act, dst, 1, 0, 0, c_off, cout_store, **kw_)
 
 
 def lstm_gate_perm(H, device):
@@ -804,14 +811,14 @@ def wgrad_join():
 
 
 def wgrad(g, g_off, M, x, x_off, N, kh, kw, dw, *, stride=1, dil=(1, 1), pad=(0, 0), pad_mode=L.PAD_ZERO,
-          accumulate=False, scale=1.0, gs=None, temporal=None, defer=False):
+          accumulate=False, scale=1.0, temporal=None, defer=False):
     """dw[m][n][a][b] (+)= scale * sum_p G[p][m] X[p*stride + (a,b)*dil - pad][n] (sos_conv2d_wgrad).
     g, x: Act.  In bf16x3 mode the product (g_hi+g_lo)(x_hi+x_lo) is taken as hi*hi + hi*lo + lo*hi
     with three accumulating passes over the thirds.  temporal = (frames per clip, kt, channels per frame): column
     n = dt * channels + c pairs image b of G with channel c of frame b + dt - (kt - 1) // 2 of X (sos_wgrad_desc)."""
     import ctypes
     dev = g.t.device
-    gs = cur_gs() if gs is None else gs
+    gs = cur_gs()
     passes = [(0, 0)] if not g.x3 else [(0, 0), (0, 2), (2, 0)]
     first = True
     for gt, xt in passes:

@@ -13,18 +13,16 @@ import torch
 from . import _lib as L
 from . import engine as E
 
-
-
-
 # SOS_FUSED_STATS=0: separate sos_bn_stats pass instead of the statistics fused into the conv epilogue (A/B timing)
-FUSED_STATS = __import__("os").environ.get("SOS_FUSED_STATS", "1") != "0"
+FUSED_STATS = os.environ.get("SOS_FUSED_STATS", "1") != "0"
 # SOS_FUSED_STATS_UNET=1: the U-Net's DownConvBlocks take their statistics from the conv epilogue too (14 statistics passes per step
 # less).  Measured +0.1 % on the step (531.9 -> 532.6, inside the noise): opt-in only
-FUSED_STATS_UNET = __import__("os").environ.get("SOS_FUSED_STATS_UNET", "0") == "1"
+FUSED_STATS_UNET = os.environ.get("SOS_FUSED_STATS_UNET", "0") == "1"
 
 
 def ones_zeros(n, device):
-    """(scale, shift) of a conv with no affine epilogue: NULL for both (sos_conv_desc: y = act(acc))."""
+    """(scale, shift) of a conv with no affine epilogue: NULL for both (sos_conv_desc: y = act(acc)).  The package passes
+    None, None itself; the name stays for the tests and probes that call it."""
     return None, None
 
 
@@ -70,6 +68,16 @@ def bn_bwd(dy, dy_off, raw, raw_off, C, saved, gamma, act, slope, dx, dx_off=0):
     return dgamma, dbeta, dslope
 
 
+def block_bwd(dy, dy_off, raw, lp, saved, act, x3):
+    """Gradient head of a conv + BatchNorm + activation block: the gradient buffer of the conv's raw output and bn_bwd into
+    it.  Returns (d_raw, dgamma, dbeta, dslope)."""
+    # the BN kernels write whole 8-channel runs: zero the buffer when its padding goes beyond that (the consumers contract
+    # the padding channels against zero weights, and garbage * 0 is still NaN for NaN garbage)
+    d_raw = E.Act(raw.B, raw.H, raw.W, raw.cs, x3, raw.t.device, zero=raw.cs > E.pad_to(lp["cout"], 8))
+    slope = lp["prelu"].weight if act == L.ACT_PRELU else None
+    return (d_raw,) + bn_bwd(dy, dy_off, raw, 0, lp["cout"], saved, lp["bn"].weight, act, slope, d_raw)
+
+
 def act_bwd_from_y(dy, y, act, dz, C):
     a, b, c = E.view(dy, 0, C), E.view(y, 0, C), E.view(dz, 0, C)
     L.check(L.lib().sos_act_bwd_from_y(ctypes.byref(a), ctypes.byref(b), act, ctypes.byref(c), L.stream_ptr()),
@@ -84,18 +92,6 @@ def dgrad_weight(w, x3):
 
 
 # ------------------------------------------------------------------ zero-padded Conv2d+BN+ReLU stack
-WGRAD_SIDE = os.environ.get("SOS_WGRAD_SIDE", "0") == "1"      # A/B switch of the side stream below (measured: 479-483 vs 483-488 utt/s without: off)
-_SIDE = {}
-
-
-def _side_stream(dev, cur):
-    key = (dev.index, cur.cuda_stream)
-    s = _SIDE.get(key)
-    if s is None:
-        s = _SIDE[key] = torch.cuda.Stream(device=dev)
-    return s
-
-
 def encoder_train_plan(enc, x3):
     plan = []
     for i, blk in enumerate(enc):
@@ -129,10 +125,9 @@ def encoder_forward_train(plan, a, feat, x3):
     cur = a
     for i, lp in enumerate(plan):
         cs = E.pad_to(lp["cout"], 16)
-        one, zero = ones_zeros(lp["w"].shape[1], dev)
         raw = E.Act(B, H, W, cs, x3, dev)
         # the conv's epilogue also produces the BatchNorm partial sums of its (bf16) output tile
-        st = E.conv_to_act(cur, 0, lp["cin_store"], lp["w"], lp["kh"], lp["kw"], lp["cout"], one, zero, L.ACT_NONE, raw,
+        st = E.conv_to_act(cur, 0, lp["cin_store"], lp["w"], lp["kh"], lp["kw"], lp["cout"], None, None, L.ACT_NONE, raw,
                            cout_store=cs, dil=lp["dil"], pad=lp["pad"], Ho=H, Wo=W, stats_c=lp["cout"] if FUSED_STATS else 0)
         last = i == len(plan) - 1
         y = None if last else E.Act(B, H, W, cs, x3, dev, zero=cs > E.pad_to(lp["cout"], 8))
@@ -146,53 +141,24 @@ def encoder_backward(plan, tape, dy, grads, prefix, x3, need_input_grad=False):
     """dy: Act grad of the last block's NHWC output (already converted from the feature layout).
     Fills grads[name] for conv weights and BN affine params."""
     dev = dy.t.device
-    cur = torch.cuda.current_stream(dev)
-    # side stream for the weight gradients: single-process training only (with a gradient sink the buckets' copies and
-    # collectives are ordered on the main stream), never inside a stream capture
-    side = _side_stream(dev, cur) if (WGRAD_SIDE and type(grads) is dict and not torch.cuda.is_current_stream_capturing()) else None
-    gs = E.cur_gs()
-    try:
-        return _encoder_backward(plan, tape, dy, grads, prefix, x3, need_input_grad, dev, cur, side, gs)
-    finally:
-        if side is not None:
-            cur.wait_stream(side)
-
-
-def _encoder_backward(plan, tape, dy, grads, prefix, x3, need_input_grad, dev, cur, side, gs):
     for i in range(len(plan) - 1, -1, -1):
         lp, tp = plan[i], tape[i]
-        raw = tp["raw"]
-        # the BN kernels write whole 8-channel runs: zero the buffer when its padding goes beyond
-        # that (garbage * zero weight would still be NaN for NaN garbage)
-        d_raw = E.Act(raw.B, raw.H, raw.W, raw.cs, x3, dev, zero=raw.cs > E.pad_to(lp["cout"], 8))
-        dgamma, dbeta, _ = bn_bwd(dy, 0, raw, 0, lp["cout"], tp["saved"], lp["bn"].weight, L.ACT_RELU, None, d_raw)
+        d_raw, dgamma, dbeta, _ = block_bwd(dy, 0, tp["raw"], lp, tp["saved"], L.ACT_RELU, x3)
         grads[f"{prefix}.{i}.block.1.weight"] = dgamma
         grads[f"{prefix}.{i}.block.1.bias"] = dbeta
-        dw_shape = (lp["cout"], lp["cin"], lp["kh"], lp["kw"])       # (the folded first block: (O, kw * I, kh, 1), un-folded below)
-        if side is not None and "unfold" not in lp:
-            # the weight gradient (MFMA bound, one workgroup per CU) depends only on d_raw and the block's input: it runs on
-            # a side stream under the data gradient + the BatchNorm backward passes of the block below (HBM bound).  A folded
-            # first block stays on the main stream: its un-fold copy below reads dw right away (ADVICE r4: stream race)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                dw = torch.empty(dw_shape, dtype=torch.float32, device=dev)
-                E.wgrad(d_raw, 0, lp["cout"], tp["inp"], 0, lp["cin"], lp["kh"], lp["kw"], dw, dil=lp["dil"], pad=lp["pad"], gs=gs)
-            d_raw.t.record_stream(side)
-            dw.record_stream(cur)
-        else:
-            dw = torch.empty(dw_shape, dtype=torch.float32, device=dev)
-            # (the reduce of the partial sums may trail on a side stream when nothing touches dw before the optimizer: engine.wgrad)
-            E.wgrad(d_raw, 0, lp["cout"], tp["inp"], 0, lp["cin"], lp["kh"], lp["kw"], dw, dil=lp["dil"], pad=lp["pad"],
-                    defer="unfold" not in lp and type(grads) is dict)
+        # (the folded first block: (O, kw * I, kh, 1), un-folded below)
+        dw = torch.empty((lp["cout"], lp["cin"], lp["kh"], lp["kw"]), dtype=torch.float32, device=dev)
+        # (the reduce of the partial sums may trail on a side stream when nothing touches dw before the optimizer: engine.wgrad)
+        E.wgrad(d_raw, 0, lp["cout"], tp["inp"], 0, lp["cin"], lp["kh"], lp["kw"], dw, dil=lp["dil"], pad=lp["pad"],
+                defer="unfold" not in lp and type(grads) is dict)
         grads[f"{prefix}.{i}.block.0.weight"] = lp["unfold"](dw) if "unfold" in lp else dw
         if i == 0 and not need_input_grad:
             break
         inp = tp["inp"]
         d_in = E.Act(inp.B, inp.H, inp.W, inp.cs, x3, dev)
-        one, zero = ones_zeros(lp["wd"].shape[1], dev)
         dg = lp.get("dg", lp)           # geometry of the data gradient: the layer's own (a folded first block keeps it in `dg`)
         # "same" convs: pad' = dil*(k-1) - pad == pad
-        E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], dg["kh"], dg["kw"], dg["cin"], one, zero, L.ACT_NONE, d_in,
+        E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], dg["kh"], dg["kw"], dg["cin"], None, None, L.ACT_NONE, d_in,
                       cout_store=inp.cs, dil=dg["dil"],
                       pad=(dg["dil"][0] * (dg["kh"] - 1) - dg["pad"][0], dg["dil"][1] * (dg["kw"] - 1) - dg["pad"][1]),
                       Ho=inp.H, Wo=inp.W)
@@ -200,34 +166,37 @@ def _encoder_backward(plan, tape, dy, grads, prefix, x3, need_input_grad, dev, c
     return dy
 
 
-# ------------------------------------------------------------------ video branch (Conv3dBlock stack) of the audio-visual variant
-def _phase_dgrad_weights(w2, s, pad, cout_cs, x3):
-    """Data gradient of a zero-padded stride-s conv as s*s stride-1 convs over dy, one per input phase (rh, rw):
-    dx[s*j + r] = sum_m w[k0 + s*m] dy[j + c - m], k0 = (r + pad) % s, c = (r + pad - k0) / s  (per axis), i.e. a
-    correlation with the flipped sub-kernel g[m'] = w[k0 + s*(M-1-m')] and left padding (M-1) - c.
-    Returns {(rh, rw): (packed (I, O, Mh, Mw) weight, Mh, Mw, pad_h, pad_w)} (phases without taps are skipped:
-    their gradient is zero)."""
-    O, I, kh, kw = w2.shape
-    wt = w2.detach().float().transpose(0, 1)                       # (I, O, kh, kw)
+# ------------------------------------------------------------------ strided convs: one data-gradient conv per input phase
+def phase_taps(k, s, pad, r):
+    """One axis of the rule "the data gradient of a zero-padded stride-s conv is s stride-1 convs over dy, one per input
+    phase r": dx[s*j + r] = sum_m w[k0 + s*m] dy[j + c - m], k0 = (r + pad) % s, c = (r + pad - k0) / s, i.e. a correlation
+    with the flipped sub-kernel g[m'] = w[k0 + s*(M-1-m')] and left padding (M-1) - c.
+    Returns (the taps k0 + s*m in the order they are packed (flipped), the left padding).  Host only.  The left padding can be
+    NEGATIVE (k 3, s 3, pad 1, r = 2: one tap, left padding -1 -- the video branch's stride-3 blocks): the correlation then
+    starts inside dy, and engine.conv takes such a pad as it is.  A phase no tap reaches has an empty list: its gradient is zero."""
+    k0 = (r + pad) % s
+    taps = list(range(k0, k, s))
+    return taps[::-1], len(taps) - 1 - (r + pad - k0) // s
 
-    def axis(r, k, p):
-        k0 = (r + p) % s
-        taps = list(range(k0, k, s))
-        c = (r + p - k0) // s
-        return taps, c
 
+def _phase_dgrad_weights(w, kh, kw, s, pad, cout_cs, x3):
+    """The s*s data-gradient convs (phase_taps on both axes) of the conv weight `w` -- a zero-argument callable returning
+    (O, I, kh, kw) in the stored input-channel order, not evaluated when the packed tensors are refreshed by the gather
+    kernel (engine.PackRecorder).  Returns {(rh, rw): (packed (I, O, Mh, Mw) weight, Mh, Mw, pad_h, pad_w)}, rh outer,
+    without the phases that have no taps."""
     phases = {}
     for rh in range(s):
-        th, ch = axis(rh, kh, pad[0])
+        th, ph = phase_taps(kh, s, pad[0], rh)
         for rw in range(s):
-            tw, cw = axis(rw, kw, pad[1])
+            tw, pw = phase_taps(kw, s, pad[1], rw)
             if not th or not tw:
                 continue
-            sub = wt[:, :, th[::-1]][:, :, :, tw[::-1]].contiguous()
-            phases[(rh, rw)] = (E.pack_weight(sub, cout_cs, x3), len(th), len(tw), len(th) - 1 - ch, len(tw) - 1 - cw)
+            sub = lambda th=th, tw=tw: w()[:, :, th][:, :, :, tw].transpose(0, 1).contiguous()     # noqa: E731  (I, O, Mh, Mw)
+            phases[(rh, rw)] = (E.pack_weight(sub, cout_cs, x3), len(th), len(tw), ph, pw)
     return phases
 
 
+# ------------------------------------------------------------------ video branch (Conv3dBlock stack) of the audio-visual variant
 def video_train_plan(enc, x3):
     from .common_nets import NO_TEMPORAL_TAPS
     plan = []
@@ -235,7 +204,8 @@ def video_train_plan(enc, x3):
         conv, bn = blk.block[0], blk.block[1]
         kt, kh, kw = conv.kernel_size
         O, I, s = conv.out_channels, conv.in_channels, conv.stride[1]
-        w2 = conv.weight.detach().permute(0, 2, 1, 3, 4).reshape(O, kt * I, kh, kw)
+        # (the weight views are callables, each evaluated within this iteration only: engine.pack_weight)
+        w2 = lambda: conv.weight.detach().permute(0, 2, 1, 3, 4).reshape(O, kt * I, kh, kw)              # noqa: E731
         cin_store = E.pad_to(kt * I, 16)
         pad = (conv.padding[1], conv.padding[2])
         lp = dict(w=E.pack_weight(w2, cin_store, x3), conv=conv, bn=bn, kt=kt, kh=kh, kw=kw, stride=s, pad=pad, cin=I,
@@ -247,15 +217,13 @@ def video_train_plan(enc, x3):
         if lp["native"]:
             # data gradient: dx[t] = sum_dt corr(dy[t + tpad - dt], w[:, :, dt]) -- a conv over dy with temporal taps
             # s' = kt - 1 - dt, written as the "forward" weight (kt*O, I, kh, kw) whose data-gradient transform is taken
-            w2n = conv.weight.detach().flip(2).permute(2, 0, 1, 3, 4).reshape(kt * O, I, kh, kw)
-            if s == 1:
-                lp["wd"] = dgrad_weight(w2n, x3)
-            else:
-                lp["wd_phases"] = _phase_dgrad_weights(w2n, s, pad, kt * cout_cs, x3)
-        elif s == 1:
-            lp["wd"] = dgrad_weight(w2, x3)
+            wdg = lambda: conv.weight.detach().flip(2).permute(2, 0, 1, 3, 4).reshape(kt * O, I, kh, kw)    # noqa: E731
         else:
-            lp["wd_phases"] = _phase_dgrad_weights(w2, s, pad, cout_cs, x3)
+            wdg = w2
+        if s == 1:
+            lp["wd"] = dgrad_weight(wdg(), x3)
+        else:
+            lp["wd_phases"] = _phase_dgrad_weights(wdg, kh, kw, s, pad, kt * cout_cs if lp["native"] else cout_cs, x3)
         plan.append(lp)
     return plan
 
@@ -279,13 +247,12 @@ def video_forward_train(plan, frames, B, T, feat, feat_row, feat_third, feat_c_o
         Ho = (H + 2 * lp["pad"][0] - lp["kh"]) // s + 1
         Wo = (W + 2 * lp["pad"][1] - lp["kw"]) // s + 1
         cs = E.pad_to(lp["cout"], 16)
-        one, zero = ones_zeros(lp["w"].shape[1], dev)
         raw = E.Act(B * T, Ho, Wo, cs, x3, dev)
         if lp["native"]:
-            E.conv_to_act(cur, 0, C, lp["w"], lp["kh"], lp["kw"], lp["cout"], one, zero, L.ACT_NONE, raw,
+            E.conv_to_act(cur, 0, C, lp["w"], lp["kh"], lp["kw"], lp["cout"], None, None, L.ACT_NONE, raw,
                           cout_store=cs, stride=s, pad=lp["pad"], Ho=Ho, Wo=Wo, temporal=(T, lp["kt"]))
         else:
-            E.conv_to_act(st, 0, lp["cin_store"], lp["w"], lp["kh"], lp["kw"], lp["cout"], one, zero, L.ACT_NONE, raw,
+            E.conv_to_act(st, 0, lp["cin_store"], lp["w"], lp["kh"], lp["kw"], lp["cout"], None, None, L.ACT_NONE, raw,
                           cout_store=cs, stride=s, pad=lp["pad"], Ho=Ho, Wo=Wo)
         y = E.Act(B * T, Ho, Wo, cs, x3, dev, zero=cs > E.pad_to(lp["cout"], 8))
         saved = E.bn_train(raw, 0, lp["cout"], lp["bn"], L.ACT_RELU, None, y, 0)
@@ -294,6 +261,24 @@ def video_forward_train(plan, frames, B, T, feat, feat_row, feat_third, feat_c_o
     L.check(L.lib().sos_spatial_mean(L.ptr(cur.t), B * T, cur.H * cur.W, C, cur.cs, cur.nseg, L.ptr(feat), feat_row,
                                      feat_third, feat_c_off, L.stream_ptr()), "sos_spatial_mean")
     return dict(blocks=tape, out=cur)
+
+
+def _video_dgrad(lp, d_raw, like, C, x3, temporal):
+    """Data gradient of a video block, C channels into a new buffer shaped like `like` (the frames with temporal = (T, kt)
+    taps inside the kernel, else the time-stacked input): the flipped conv, or one conv per input phase for a strided block."""
+    s, (kh, kw) = lp["stride"], (lp["kh"], lp["kw"])
+    # (the phases of a strided block skip what no tap reaches; the padding channels: see block_bwd)
+    dx = E.Act(like.B, like.H, like.W, like.cs, x3, d_raw.t.device, zero=s > 1 or like.cs > E.pad_to(C, 8))
+    if s == 1:
+        E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], kh, kw, C, None, None, L.ACT_NONE, dx, cout_store=dx.cs,
+                      pad=(kh - 1 - lp["pad"][0], kw - 1 - lp["pad"][1]), Ho=dx.H, Wo=dx.W, temporal=temporal)
+        return dx
+    for (rh, rw), (w, Mh, Mw, ph, pw) in lp["wd_phases"].items():
+        Hp, Wp = (dx.H - rh + s - 1) // s, (dx.W - rw + s - 1) // s
+        if Hp >= 1 and Wp >= 1:
+            E.conv_to_phase(d_raw, 0, d_raw.cs, w, Mh, Mw, C, None, None, L.ACT_NONE, dx, s, rh, rw, cout_store=dx.cs,
+                            pad=(ph, pw), Ho=Hp, Wo=Wp, temporal=temporal)
+    return dx
 
 
 def video_backward(plan, tape, dfeat, f_row, f_third, f_c_off, grads, prefix, B, T, x3):
@@ -308,14 +293,12 @@ def video_backward(plan, tape, dfeat, f_row, f_third, f_c_off, grads, prefix, B,
                                          L.ptr(dy.t), dy.cs, L.stream_ptr()), "sos_spatial_mean_bwd")
     for i in range(len(plan) - 1, -1, -1):
         lp, tp = plan[i], tape["blocks"][i]
-        raw, st = tp["raw"], tp["stacked"]
-        d_raw = E.Act(raw.B, raw.H, raw.W, raw.cs, x3, dev, zero=raw.cs > E.pad_to(lp["cout"], 8))
-        dgamma, dbeta, _ = bn_bwd(dy, 0, raw, 0, lp["cout"], tp["saved"], lp["bn"].weight, L.ACT_RELU, None, d_raw)
+        raw, st, src = tp["raw"], tp["stacked"], tp["src"]
+        d_raw, dgamma, dbeta, _ = block_bwd(dy, 0, raw, lp, tp["saved"], L.ACT_RELU, x3)
         grads[f"{prefix}.{i}.block.1.weight"], grads[f"{prefix}.{i}.block.1.bias"] = dgamma, dbeta
         kt, I, O = lp["kt"], lp["cin"], lp["cout"]
         dw2 = torch.empty((O, kt * I, lp["kh"], lp["kw"]), dtype=torch.float32, device=dev)
         if lp["native"]:
-            src = tp["src"]
             E.wgrad(d_raw, 0, O, src, 0, kt * I, lp["kh"], lp["kw"], dw2, stride=lp["stride"], pad=lp["pad"],
                     temporal=(T, kt, I))
         elif lp["stride"] >= 3:
@@ -337,43 +320,9 @@ def video_backward(plan, tape, dfeat, f_row, f_third, f_c_off, grads, prefix, B,
             break
         if lp["native"]:
             # data gradient straight onto the frames: conv over d_raw with (flipped) temporal taps
-            src = tp["src"]
-            dx = E.Act(src.B, src.H, src.W, src.cs, x3, dev, zero=lp["stride"] > 1)
-            if lp["stride"] == 1:
-                one, zero = ones_zeros(lp["wd"].shape[1], dev)
-                E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], lp["kh"], lp["kw"], I, one, zero, L.ACT_NONE, dx,
-                              cout_store=dx.cs, pad=(lp["kh"] - 1 - lp["pad"][0], lp["kw"] - 1 - lp["pad"][1]), Ho=src.H, Wo=src.W,
-                              temporal=(T, kt))
-            else:
-                s = lp["stride"]
-                row = dx.nseg * dx.cs
-                for (rh, rw), (w, Mh, Mw, ph, pw) in lp["wd_phases"].items():
-                    Hp, Wp = (src.H - rh + s - 1) // s, (src.W - rw + s - 1) // s
-                    if Hp < 1 or Wp < 1:
-                        continue
-                    one, zero = ones_zeros(w.shape[1], dev)
-                    E.conv(d_raw, 0, d_raw.cs, w, Mh, Mw, I, one, zero, L.ACT_NONE, out=dx.t, out_dtype=dx.dtype_code,
-                           sb=dx.H * dx.W * row, sh=s * dx.W * row, sw=s * row, sc=1, cout_store=dx.cs, third=dx.cs,
-                           pad=(ph, pw), Ho=Hp, Wo=Wp, out_elem_offset=(rh * dx.W + rw) * row, temporal=(T, kt))
-            dy = dx
+            dy = _video_dgrad(lp, d_raw, src, I, x3, (T, kt))
             continue
-        d_st = E.Act(st.B, st.H, st.W, st.cs, x3, dev, zero=lp["stride"] > 1 or st.cs > E.pad_to(kt * I, 8))
-        if lp["stride"] == 1:
-            one, zero = ones_zeros(lp["wd"].shape[1], dev)
-            E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], lp["kh"], lp["kw"], kt * I, one, zero, L.ACT_NONE, d_st,
-                          cout_store=st.cs, pad=(lp["kh"] - 1 - lp["pad"][0], lp["kw"] - 1 - lp["pad"][1]), Ho=st.H, Wo=st.W)
-        else:
-            s = lp["stride"]
-            row = d_st.nseg * d_st.cs
-            for (rh, rw), (w, Mh, Mw, ph, pw) in lp["wd_phases"].items():
-                Hp, Wp = (st.H - rh + s - 1) // s, (st.W - rw + s - 1) // s
-                if Hp < 1 or Wp < 1:
-                    continue
-                one, zero = ones_zeros(w.shape[1], dev)
-                E.conv(d_raw, 0, d_raw.cs, w, Mh, Mw, kt * I, one, zero, L.ACT_NONE, out=d_st.t, out_dtype=d_st.dtype_code,
-                       sb=d_st.H * d_st.W * row, sh=s * d_st.W * row, sw=s * row, sc=1, cout_store=st.cs, third=d_st.cs,
-                       pad=(ph, pw), Ho=Hp, Wo=Wp, out_elem_offset=(rh * d_st.W + rw) * row)
-        src = tp["src"]
+        d_st = _video_dgrad(lp, d_raw, st, kt * I, x3, None)
         if st is src:                                    # 1x1x1 block on an unstacked input
             dy = d_st
         else:
@@ -463,8 +412,7 @@ def lstm_backward(lp, tape, dh, grads, prefix, B, T, x3, dev):
     # input gradient
     nseg = 3 if x3 else 1
     dfeat = torch.empty((B, T, nseg * I), dtype=E.act_dtype(), device=dev)
-    one, zero = ones_zeros(lp["wd"].shape[1], dev)
-    E.conv(dga, 0, dga.cs, lp["wd"], 1, 1, I, one, zero, L.ACT_NONE, out=dfeat,
+    E.conv(dga, 0, dga.cs, lp["wd"], 1, 1, I, None, None, L.ACT_NONE, out=dfeat,
            out_dtype=L.DT_BF16X3 if x3 else L.DT_BF16, sb=T * nseg * I, sh=0, sw=nseg * I, sc=1, third=I, Ho=1, Wo=T)
     return dfeat
 
@@ -485,9 +433,7 @@ def linear_backward(lp, a_in, dz, grads, prefix, x3, dev):
     grads[f"{prefix}.weight"] = dw
     grads[f"{prefix}.bias"] = colsum(dz, 0, lp["cout"])
     d_in = E.Act(a_in.B, 1, a_in.W, a_in.cs, x3, dev)
-    one, zero = ones_zeros(lp["wd"].shape[1], dev)
-    E.conv_to_act(dz, 0, dz.cs, lp["wd"], 1, 1, lp["cin"], one, zero, L.ACT_NONE, d_in, cout_store=a_in.cs, Ho=1,
-                  Wo=a_in.W)
+    E.conv_to_act(dz, 0, dz.cs, lp["wd"], 1, 1, lp["cin"], None, None, L.ACT_NONE, d_in, cout_store=a_in.cs, Ho=1, Wo=a_in.W)
     return d_in
 
 
@@ -530,15 +476,8 @@ def down_train_plan(blk, x3, in_perm=None, first=False):
         plan["wd"] = E.pack_weight(lambda: wperm().flip(2, 3).transpose(0, 1).contiguous(), cout_cs, x3)
     else:
         assert s == 2 and d == 1
-        phases = {}
-        for ph in (0, 1):
-            for pw in (0, 1):
-                Mh, Mw = (k + 1 - ph) // 2, (k + 1 - pw) // 2
-                a = [ph + 2 * (Mh - 1 - t) for t in range(Mh)]
-                b = [pw + 2 * (Mw - 1 - t) for t in range(Mw)]
-                sub = lambda a=a, b=b: wperm()[:, :, a][:, :, :, b].transpose(0, 1).contiguous()     # noqa: E731  (I, O, Mh, Mw)
-                phases[(ph, pw)] = (E.pack_weight(sub, cout_cs, x3), Mh, Mw)
-        plan["wd_phases"] = phases
+        # the valid conv on the reflect-padded domain: pad 0 (the phases' left pads are the full M - 1)
+        plan["wd_phases"] = _phase_dgrad_weights(wperm, k, k, 2, (0, 0), cout_cs, x3)
     return plan
 
 
@@ -547,12 +486,9 @@ def up_train_plan(blk, x3):
     ct, bn, prelu = blk.block[0], blk.block[1], blk.block[2]
     cin_store = E.pad_to(ct.in_channels, 16)
     w = lambda: ct.weight.detach().float()                                            # noqa: E731  (Cin, Cout, 3, 3)
-    taps = {0: [1], 1: [2, 0]}
-    phases = {}
-    for ph in (0, 1):
-        for pw in (0, 1):
-            sub = lambda ph=ph, pw=pw: w()[:, :, taps[ph]][:, :, :, taps[pw]].permute(1, 0, 2, 3).contiguous()   # noqa: E731
-            phases[(ph, pw)] = E.pack_weight(sub, cin_store, x3)
+    # the forward pass IS the data gradient of the k3 s2 p1 conv whose weight (O=Cin, I=Cout) this is: one conv per output
+    # phase (phase_taps: the taps [1] / [2, 0], left pad 0)
+    phases = _phase_dgrad_weights(w, 3, 3, 2, (1, 1), cin_store, x3)
     # data gradient: d_in[hi] = sum_a d_raw[2hi - 1 + a] W[ci][co][a] -> stride-2 conv, weight (O=Cin, I=Cout)
     wd = E.pack_weight(w, E.pad_to(ct.out_channels, 16), x3)
     return dict(phases=phases, wd=wd, ct=ct, bn=bn, prelu=prelu, cout=ct.out_channels, cin=ct.in_channels,
@@ -562,9 +498,8 @@ def up_train_plan(blk, x3):
 def down_forward_train(lp, src, cin_off, dst, c_off, Ho, Wo, x3):
     dev = src.t.device
     cs = E.pad_to(lp["cout"], 16)
-    one, zero = ones_zeros(lp["w"].shape[1], dev)
     raw = E.Act(src.B, Ho, Wo, cs, x3, dev)
-    st = E.conv_to_act(src, cin_off, lp["cin_store"], lp["w"], lp["k"], lp["kw"], lp["cout"], one, zero, L.ACT_NONE, raw,
+    st = E.conv_to_act(src, cin_off, lp["cin_store"], lp["w"], lp["k"], lp["kw"], lp["cout"], None, None, L.ACT_NONE, raw,
                        cout_store=cs, stride=lp["stride"], dil=(lp["dil"], lp["dil"]), pad=(lp["pad"], lp["pad_w"]),
                        pad_mode=L.PAD_REFLECT, Ho=Ho, Wo=Wo, stats_c=lp["cout"] if (FUSED_STATS and FUSED_STATS_UNET) else 0)
     saved = E.bn_train(raw, 0, lp["cout"], lp["bn"], L.ACT_PRELU, lp["prelu"].weight, dst, c_off, stats=st)
@@ -575,12 +510,9 @@ def up_forward_train(lp, src, dst, c_off, x3):
     dev = src.t.device
     cs = E.pad_to(lp["cout"], 16)
     raw = E.Act(src.B, 2 * src.H, 2 * src.W, cs, x3, dev, zero=cs > lp["cout"])
-    row = raw.nseg * raw.cs
-    for (ph, pw), w in lp["phases"].items():
-        one, zero = ones_zeros(w.shape[1], dev)
-        E.conv(src, 0, lp["cin_store"], w, 1 + ph, 1 + pw, lp["cout"], one, zero, L.ACT_NONE, out=raw.t,
-               out_dtype=raw.dtype_code, sb=raw.H * raw.W * row, sh=2 * raw.W * row, sw=2 * row, sc=1,
-               cout_store=lp["cout"], third=raw.cs, Ho=src.H, Wo=src.W, out_elem_offset=(ph * raw.W + pw) * row)
+    for (rh, rw), (w, Mh, Mw, ph, pw) in lp["phases"].items():
+        E.conv_to_phase(src, 0, lp["cin_store"], w, Mh, Mw, lp["cout"], None, None, L.ACT_NONE, raw, 2, rh, rw,
+                        pad=(ph, pw), Ho=src.H, Wo=src.W)
     # batch statistics over the UNCROPPED output (the reference resizes after the block), then crop
     if (dst.H, dst.W) == (raw.H, raw.W):            # nothing to crop (up1.1: 2 x 128 x 89 = 256 x 178): straight into the concat buffer
         saved = E.bn_train(raw, 0, lp["cout"], lp["bn"], L.ACT_PRELU, lp["prelu"].weight, dst, c_off)
@@ -672,27 +604,23 @@ def _reflect_dgrad(lp, d_raw, src, cin_off, gb, x3):
     dpad = E.Act(src.B, H + 2 * p, W + 2 * p, cin_cs, x3, dev, zero=(lp["stride"] != 1 and not fused))
     drow = dst.nseg * dst.cs
     if lp["stride"] == 1:
-        one, zero = ones_zeros(lp["wd"].shape[1], dev)
         if fused:
-            E.conv(d_raw, 0, d_raw.cs, lp["wd"], k, k, lp["cin"], one, zero, L.ACT_NONE, out=dst.t, out_dtype=dst.dtype_code,
+            E.conv(d_raw, 0, d_raw.cs, lp["wd"], k, k, lp["cin"], None, None, L.ACT_NONE, out=dst.t, out_dtype=dst.dtype_code,
                    sb=H * W * drow, sh=0, sw=drow, sc=1, c_off=cin_off, cout_store=lp["cin"], third=dst.cs, dil=(d, d),
                    pad=((k - 1) * d, (k - 1) * d), Ho=dpad.H, Wo=dpad.W, accumulate=accumulate, fold=(dpad, p, H, W, 1, 0, 1, 0))
         else:
-            E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], k, k, lp["cin"], one, zero, L.ACT_NONE, dpad, cout_store=cin_cs,
+            E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], k, k, lp["cin"], None, None, L.ACT_NONE, dpad, cout_store=cin_cs,
                           dil=(d, d), pad=((k - 1) * d, (k - 1) * d), Ho=dpad.H, Wo=dpad.W)
     else:
-        row = dpad.nseg * dpad.cs
-        for (ph, pw), (w, Mh, Mw) in lp["wd_phases"].items():
-            Ho, Wo = (dpad.H - ph + 1) // 2, (dpad.W - pw + 1) // 2
-            one, zero = ones_zeros(w.shape[1], dev)
-            if fused:
-                E.conv(d_raw, 0, d_raw.cs, w, Mh, Mw, lp["cin"], one, zero, L.ACT_NONE, out=dst.t, out_dtype=dst.dtype_code,
+        for (rh, rw), (w, Mh, Mw, ph, pw) in lp["wd_phases"].items():
+            Ho, Wo = (dpad.H - rh + 1) // 2, (dpad.W - rw + 1) // 2
+            if fused:       # (the fold addresses the dense gradient itself: not a phase-strided store)
+                E.conv(d_raw, 0, d_raw.cs, w, Mh, Mw, lp["cin"], None, None, L.ACT_NONE, out=dst.t, out_dtype=dst.dtype_code,
                        sb=H * W * drow, sh=0, sw=drow, sc=1, c_off=cin_off, cout_store=lp["cin"], third=dst.cs,
-                       pad=(Mh - 1, Mw - 1), Ho=Ho, Wo=Wo, accumulate=accumulate, fold=(dpad, p, H, W, 2, ph, 2, pw))
+                       pad=(ph, pw), Ho=Ho, Wo=Wo, accumulate=accumulate, fold=(dpad, p, H, W, 2, rh, 2, rw))
             else:
-                E.conv(d_raw, 0, d_raw.cs, w, Mh, Mw, lp["cin"], one, zero, L.ACT_NONE, out=dpad.t, out_dtype=dpad.dtype_code,
-                       sb=dpad.H * dpad.W * row, sh=2 * dpad.W * row, sw=2 * row, sc=1, cout_store=cin_cs, third=dpad.cs,
-                       pad=(Mh - 1, Mw - 1), Ho=Ho, Wo=Wo, out_elem_offset=(ph * dpad.W + pw) * row)
+                E.conv_to_phase(d_raw, 0, d_raw.cs, w, Mh, Mw, lp["cin"], None, None, L.ACT_NONE, dpad, 2, rh, rw,
+                                cout_store=cin_cs, pad=(ph, pw), Ho=Ho, Wo=Wo)
     if fused:
         reflect_fold_border(dpad, H, W, p, dst, cin_off, lp["cin"])
     else:
@@ -705,9 +633,8 @@ _INV_PERM = {}           # (concat permutation, device) -> its inverse as a devi
 def down_backward(t, gb, grads, name, x3, need_src_grad=True):
     lp, raw = t["lp"], t["raw"]
     dev = raw.t.device
-    d_raw = E.Act(raw.B, raw.H, raw.W, raw.cs, x3, dev, zero=raw.cs > E.pad_to(lp["cout"], 8))
-    dgamma, dbeta, dslope = bn_bwd(gb.read(t["dst"], t["c_off"], lp["cout"]), t["c_off"], raw, 0, lp["cout"], t["saved"],
-                                   lp["bn"].weight, L.ACT_PRELU, lp["prelu"].weight, d_raw)
+    d_raw, dgamma, dbeta, dslope = block_bwd(gb.read(t["dst"], t["c_off"], lp["cout"]), t["c_off"], raw, lp, t["saved"],
+                                             L.ACT_PRELU, x3)
     grads[f"{name}.block.2.weight"], grads[f"{name}.block.2.bias"], grads[f"{name}.block.3.weight"] = dgamma, dbeta, dslope
     dw = torch.empty((lp["cout"], lp["cin"], lp["k"], lp["kw"]), dtype=torch.float32, device=dev)
     E.wgrad(d_raw, 0, lp["cout"], t["src"], t["cin_off"], lp["cin"], lp["k"], lp["kw"], dw, stride=lp["stride"],
@@ -742,14 +669,11 @@ def up_backward(t, gb, grads, name, x3):
     else:                                           # zero-pad the cropped rows / columns back (mid.8: 128 x 90 -> 128 x 89)
         dy_full, dy_off = E.Act(raw.B, raw.H, raw.W, raw.cs, x3, dev, zero=raw.cs > E.pad_to(lp["cout"], 8)), 0
         copy_crop(gdst, t["c_off"], dy_full, 0, lp["cout"])
-    d_raw = E.Act(raw.B, raw.H, raw.W, raw.cs, x3, dev, zero=raw.cs > E.pad_to(lp["cout"], 8))
-    dgamma, dbeta, dslope = bn_bwd(dy_full, dy_off, raw, 0, lp["cout"], t["saved"], lp["bn"].weight, L.ACT_PRELU,
-                                   lp["prelu"].weight, d_raw)
+    d_raw, dgamma, dbeta, dslope = block_bwd(dy_full, dy_off, raw, lp, t["saved"], L.ACT_PRELU, x3)
     grads[f"{name}.block.1.weight"], grads[f"{name}.block.1.bias"], grads[f"{name}.block.2.weight"] = dgamma, dbeta, dslope
     dw = torch.empty_like(lp["ct"].weight, dtype=torch.float32)                      # (Cin, Cout, 3, 3)
     E.wgrad(src, 0, lp["cin"], d_raw, 0, lp["cout"], 3, 3, dw, stride=2, pad=(1, 1), defer=type(grads) is dict)
     grads[f"{name}.block.0.weight"] = dw
     gsrc = gb.of(src)
-    one, zero = ones_zeros(lp["wd"].shape[1], dev)
-    E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], 3, 3, lp["cin"], one, zero, L.ACT_NONE, gsrc, cout_store=lp["cin"],
+    E.conv_to_act(d_raw, 0, d_raw.cs, lp["wd"], 3, 3, lp["cin"], None, None, L.ACT_NONE, gsrc, cout_store=lp["cin"],
                   stride=2, pad=(1, 1), Ho=src.H, Wo=src.W, accumulate=not gb.first_write(src, 0, lp["cin"]))

@@ -160,6 +160,30 @@ def test_denoiser_train_step_matches_reference_autograd(golden, precision):
         sos_amd.set_precision("bf16")
 
 
+@pytest.mark.parametrize("model", ["detector", "audiovisual", "joint"])
+def test_training_plan_is_recorded_and_verified(golden, model):
+    """After one training forward the plan's packed weights are under a PackRecorder that verified (every packed tensor a pure
+    relocation of parameter elements): a plan builder that slipped out of the recorder -- a pack_weight bypassed, a weight
+    derived by arithmetic -- would pass every numeric test and only cost host time on each optimizer step."""
+    from sos_amd.common import MyConfig
+    from sos_amd.denoiser import networks as jnet
+    from sos_amd.detector import networks as dnet
+    B, T, nfr = 2, 89, 30
+    x = spec_input(100 + B, B, T).cuda()
+    if model == "joint":
+        net = jnet.get_network(MyConfig()).cuda().train()
+        net(x, silent_gate(x.cpu()).cuda())
+    elif model == "detector":
+        net = dnet.get_network().cuda().train()
+        net(x, nfr)
+    else:
+        from test_audiovisual import video_input
+        i_s, i_v, _, B, T, Tv, HW = [int(v) for v in golden("audiovisual")["train_idx"]]
+        net = dnet.get_network(video=True).cuda().train()
+        net(spec_input(i_s, B, T).cuda(), v=video_input(i_v, B, Tv, HW, HW).cuda())
+    assert net._tcache.rec is not None and net._tcache.rec.ok
+
+
 @pytest.mark.parametrize("first", [(5, 5), (1, 7)], ids=["first5x5", "first1x7"])
 def test_encoder_block_backward_exact(first, monkeypatch):
     """Three Conv2d+BN(train)+ReLU blocks (dilated 5x5 or 1x7, 5x5, 1x1) forward + backward through the HIP
