@@ -342,6 +342,19 @@ def wave_info(path):
     return dict(tag=tag, bits=bits, channels=ch, rate=rate, frames=nbytes // ((bits // 8) * ch))
 
 
+def file_groups(paths, max_bytes):
+    """Consecutive files in groups of at most max_bytes of mono f32 samples at their native rates (a file larger than that is
+    a group of its own), from the chunk headers alone: 4 bytes per frame wave_info counts, the frames the loader decodes.  A
+    file that wave_info refuses counts 0 bytes: the loader reports what is wrong with it."""
+    sizes = []
+    for path in paths:
+        try:
+            sizes.append(4 * wave_info(path)["frames"])
+        except (OSError, WaveFormatError):
+            sizes.append(0)
+    return ragged.byte_groups(sizes, max_bytes)
+
+
 def load_device(path, sr=22050, mono=True, offset=0.0, duration=None, res_type="kaiser_best", device="cuda"):
     """`librosa.load` with the result left in HBM: (y f32 GPU tensor, sr).  mono=False is not on the
     reference's path (every call site takes the default) and raises."""

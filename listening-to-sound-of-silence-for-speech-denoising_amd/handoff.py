@@ -14,10 +14,15 @@ own checked-in outputs in tests/golden/handoff/).  Both branches of the scripts 
 `_mixed / _clean / _full_noise` WAVE files, objective measures in stat.json).  The PNG plots (cv2 / matplotlib) are
 not built; the `waveform` / `spectrum` keys are therefore absent from stat.json.  All signal work (decode, resample,
 STFT, networks, masks, ISTFT, measures) runs on the GPU through audio_io / transform / tools / metrics; this module is
-the host-side bookkeeping around it."""
+the host-side bookkeeping around it.
+
+Every stage has several forms (per file, ragged groups of files, windows); the forms differ in their compute calls and share
+the bookkeeping, which is stated once per stage: the noise draw (_draw_noise, _store_crop), the decision step (_detect_item),
+the recovered files (_write_recovered), the per-file records (_file_info, _data_info, _write_individual) and the two halves
+of denoise_first_model (_first_model_whole, _first_model_windows)."""
 import json
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from itertools import groupby
 from operator import itemgetter
 
@@ -132,69 +137,154 @@ def add_noise_to_audio(audio, noise, snr, start_pos=0, norm=0.5):
     return add_signals(np.asarray(audio), [crop], snr=snr, norm=norm)
 
 
-def _detect_item(data_id, f, bits_full, i1, label, pred, conf):
-    """One `data` entry of eval_results.json (M1/predict.py:150-175) from a file's host arrays of decisions and confidences."""
+# One file of detect_files on its way from the data-set JSON to its eval_results item: its index, its JSON entry, the whole bit
+# stream, the first labelled frame, the labelled frames as '0' / '1' strings, and the 14 kHz signal on the device.
+Pending = namedtuple('Pending', 'data_id f bits_full i1 label snd')
+
+
+def _pending_files(ds, data_root, batch_files):
+    """Step 1 of detect_files, a generator of Pending: batch_files takes every recording from one audio_io.load_batch_device
+    call before the first file is handed out; the per-file form decodes a file when the consumer asks for it."""
+    paths = [_resolve(f['audio_path'], ds.get('dataset_path'), data_root) for f in ds['files']]
+    loaded = audio_io.load_batch_device(paths, sr=DATA_REQUIRED_SR)[0] if batch_files and paths else None
+    for data_id, f in enumerate(ds['files']):
+        bits_full = f[BITSTREAM_JSON_LABEL]
+        i1, i2 = _trim_unknown(bits_full)
+        label = [str(int(b)) for b in bits_full[i1:i2]]
+        snd = loaded[data_id] if batch_files else audio_io.load_device(paths[data_id], sr=DATA_REQUIRED_SR)[0]
+        yield Pending(data_id, f, bits_full, i1, label, snd)
+
+
+def _load_host(path):
+    """A recording or noise file as a 14 kHz host array."""
+    return audio_io.load(path, sr=DATA_REQUIRED_SR)[0]
+
+
+def _draw_noise(rng, noise_files, load, p):
+    """THE noise draw of a file (M1/dataset.py:141-142): which noise file, then -- its length is needed -- where the crop of
+    ceil(duration) seconds starts.  Two draws from the seeded generator per file, in file order, whatever the form: that is why
+    a seeded run stores the same crops under every form.  load(k) decodes noise file k at 14 kHz.
+    -> (k, start, crop, start_pos): the crop is noise k from `start` on, and it is mixed in from its sample `start_pos` on, the
+    sample of the first labelled frame."""
+    k = int(rng.integers(len(noise_files)))
+    noise = load(k)
+    need = int(np.ceil(p.f['duration'])) * DATA_REQUIRED_SR
+    start = int(rng.integers(0, max(len(noise) - need, 0) + 1))
+    return k, start, noise[start:start + need], int(p.i1 / p.f['framerate'] * DATA_REQUIRED_SR)
+
+
+def _store_crop(noise_dir, p, crop, snr, noise_entries):
+    """The crop of a file as <noise_dir>/<name>_noise.wav and its record for create_data_from_prediction (M1/predict.py:82-104)."""
+    base = os.path.basename(p.f['path'])
+    stem = base.split('.mp4')[0].split('.wav')[0]
+    ensure_dir(noise_dir)
+    audio_io.write_wav(os.path.join(noise_dir, stem + '_noise.wav'), crop.astype(np.float32), DATA_REQUIRED_SR)
+    noise_entries[base] = OrderedDict([('audio', stem + '.wav'), ('noise', stem + '_noise.wav'), ('snr', snr)])
+
+
+def _mix_file(p, rng, noise_files, snr, noise_dir, noise_entries):
+    """Step 2 of detect_files, per file: the recording silenced on its labelled silent intervals (M1/dataset.py:247-249) and
+    mixed with its crop on the host (add_noise_to_audio); the noise file is decoded for this file alone."""
+    gt = torch.tensor([int(b) for b in p.label], dtype=torch.uint8, device=p.snd.device).reshape(1, -1)
+    gmask = tools.bits_to_mask_batch(gt, float(DATA_REQUIRED_SR) / p.f['framerate'], p.snd.numel())
+    audio = (p.snd * (1 - gmask[0])).cpu().numpy()
+    _, _, crop, start_pos = _draw_noise(rng, noise_files, lambda k: _load_host(noise_files[k]), p)
+    mixed, _, _ = add_noise_to_audio(audio, crop, snr, start_pos=start_pos)
+    _store_crop(noise_dir, p, crop, snr, noise_entries)
+    return p._replace(snd=torch.from_numpy(np.ascontiguousarray(mixed, dtype=np.float32)).to(p.snd.device))
+
+
+def _mix_pending(pending, rng, noise_files, snr, noise_dir, noise_entries, max_bytes):
+    """Step 2 of detect_files(batch_mix=True): the draws per file in file order, every distinct noise file decoded once; then
+    the recordings silenced on their labelled silent intervals and mixed with their crops on the device, one
+    tools.add_signals_ragged call per group of files of at most max_bytes of samples."""
+    noises = {}                                 # the decoded noise files by index
+    which, first, count = [], [], []            # per file: its noise file, the first noise sample mixed in, the valid samples
+
+    def load(k):
+        if k not in noises:
+            noises[k] = _load_host(noise_files[k])
+        return noises[k]
+
+    for p in pending:
+        k, start, crop, start_pos = _draw_noise(rng, noise_files, load, p)
+        which.append(k)
+        first.append(start + start_pos)
+        count.append(max(len(crop) - start_pos, 0))
+        _store_crop(noise_dir, p, crop, snr, noise_entries)
+    used = sorted(noises)
+    slot = {k: j for j, k in enumerate(used)}
+    out = []
+    for group in ragged.byte_groups([4 * p.snd.numel() for p in pending], max_bytes):
+        part = [pending[i] for i in group]
+        bits = [np.asarray([int(b) for b in p.label], dtype=np.uint8) if p.label else None for p in part]
+        ratios = [float(DATA_REQUIRED_SR) / p.f['framerate'] if b is not None else None for p, b in zip(part, bits)]
+        mixed, _, _ = tools.add_signals_ragged([p.snd for p in part], [noises[k] for k in used], snr,
+                                               noise_index=[slot[which[i]] for i in group], starts=[first[i] for i in group],
+                                               counts=[count[i] for i in group], bits=bits, ratios=ratios, norm=0.5)
+        out += [p._replace(snd=m) for p, m in zip(part, mixed)]
+    return out
+
+
+def _detect_item(p, conf, pred=None):
+    """THE decision step: one `data` entry of eval_results.json (M1/predict.py:150-175) from the host array of a file's
+    confidences.  The dense per-file route also hands in the kernel's bits.  The grouped and the windowed route download one
+    array, sos_threshold_bits' confidence s, and leave `pred` out: the kernel's bit is s >= threshold in f32, and the same f32
+    comparison on the host gives the same bit."""
+    if pred is None:
+        pred = (conf >= np.float32(SIGMOID_THRESHOLD)).astype(np.uint8)
     pred_label = [str(int(b)) for b in pred]
+    f = p.f
     return OrderedDict([
-        ('id', data_id), ('path', f['path']), ('full_bit_stream', bits_full), ('num_frames', f['num_frames']),
+        ('id', p.data_id), ('path', f['path']), ('full_bit_stream', p.bits_full), ('num_frames', f['num_frames']),
         ('framerate', f['framerate']), ('audio_sample_rate', f['audio_sample_rate']),
-        ('audio_samples', f['audio_samples']), ('duration', f['duration']), ('frame_start_idx', i1),
-        ('label', label), ('pred_label', pred_label), ('match', label == pred_label),
+        ('audio_samples', f['audio_samples']), ('duration', f['duration']), ('frame_start_idx', p.i1),
+        ('label', p.label), ('pred_label', pred_label), ('match', p.label == pred_label),
         ('confidence', [str(c) for c in conf])])
+
+
+def _detect_file(net, p):
+    """Step 3 of detect_files, per file: one dense detector pass over the whole recording."""
+    S = transform.stft_batch(p.snd.reshape(1, -1))
+    logits = net(s=S, v_num_frames=len(p.label))
+    pred, conf = tools.threshold_bits(logits, SIGMOID_THRESHOLD)
+    pred = pred[0].cpu().numpy()
+    return _detect_item(p, conf[0].cpu().numpy(), pred)
 
 
 @torch.no_grad()
 def _detect_groups(net, pending, max_batch, max_columns):
-    """detect_files(batch_files=True): the (id, file, bit stream, first frame, label, 14 kHz signal) entries through the
-    detector in ragged groups; the stat entries in file order.  The decisions are taken from the one array that comes down per
-    group: sos_threshold_bits' confidence s, whose bit is s >= threshold in f32 -- the same comparison on the host."""
+    """Step 3 of detect_files(batch_files=True): the files through the detector in ragged groups, one download of confidences
+    per group; the stat entries in file order."""
     from . import engine as E
     from . import pipeline
-    clips = [p[5].contiguous() for p in pending]
+    clips = [p.snd.contiguous() for p in pending]
     items = [None] * len(pending)
     for part in pipeline._ragged_groups(clips, max_batch, max_columns):
         wave, ns = pipeline.stage_group([clips[i] for i in part])
-        nv = [len(pending[i][4]) for i in part]
+        nv = [len(pending[i].label) for i in part]
         rag = E.Ragged([1 + n // transform.HOP_LENGTH for n in ns], wave.device, n_vframes=nv, n_samples=ns)
         S = transform.stft_batch(wave, clip_samples=rag.tab(ns))
         logits = net(s=S, v_num_frames=max(nv), rag=rag)
         _, conf = tools.threshold_bits(logits, SIGMOID_THRESHOLD)
         conf = conf.cpu().numpy()
         for k, i in enumerate(part):
-            c = conf[k, :nv[k]]
-            items[i] = _detect_item(*pending[i][:5], (c >= np.float32(SIGMOID_THRESHOLD)).astype(np.uint8), c)
+            items[i] = _detect_item(pending[i], conf[k, :nv[k]])
     return items
 
 
 @torch.no_grad()
 def _detect_windows(net, pending, window_seconds, context_seconds, max_batch, max_columns):
-    """detect_files(window_seconds=...): the entries of _detect_groups through pipeline.detect_long -- the recordings in
-    overlapping windows, ONE stitched logit stream per file at the file's own framerate and label length -- and the same one
-    thresholding launch and download of confidences for all of them."""
+    """Step 3 of detect_files(window_seconds=...): the files through pipeline.detect_long -- the recordings in overlapping
+    windows, ONE stitched logit stream per file at the file's own framerate and label length -- and one thresholding launch and
+    one download of confidences for all of them."""
     from . import pipeline
-    pairs = pipeline.detect_long(net, [p[5].contiguous() for p in pending], sr=DATA_REQUIRED_SR, fps=[p[1]['framerate'] for p in pending],
+    nv = [len(p.label) for p in pending]
+    pairs = pipeline.detect_long(net, [p.snd.contiguous() for p in pending], sr=DATA_REQUIRED_SR, fps=[p.f['framerate'] for p in pending],
                                  window_seconds=window_seconds, context_seconds=context_seconds, max_batch=max_batch,
-                                 max_columns=max_columns, n_frames=[len(p[4]) for p in pending])
+                                 max_columns=max_columns, n_frames=nv)
     _, conf = tools.threshold_bits(torch.cat([lg for lg, _ in pairs]), SIGMOID_THRESHOLD)
-    conf = ragged.split(conf.cpu().numpy(), [len(p[4]) for p in pending])
-    return [_detect_item(*p[:5], (c >= np.float32(SIGMOID_THRESHOLD)).astype(np.uint8), c) for p, c in zip(pending, conf)]
-
-
-def _mix_pending(pending, mixes, noises, snr, max_bytes):
-    """detect_files(batch_mix=True): the recordings of `pending` silenced on their labelled silent intervals and mixed with
-    their noise crops on the device, one tools.add_signals_ragged call per group of files of at most max_bytes of samples.
-    mixes: per file (noise index, first noise sample, valid samples); noises: the decoded noise files by index."""
-    used = sorted({m[0] for m in mixes})
-    slot = {k: j for j, k in enumerate(used)}
-    out = []
-    for group in ragged.byte_groups([4 * p[5].numel() for p in pending], max_bytes):
-        bits = [np.asarray([int(b) for b in pending[i][4]], dtype=np.uint8) if pending[i][4] else None for i in group]
-        ratios = [float(DATA_REQUIRED_SR) / pending[i][1]['framerate'] if b is not None else None for i, b in zip(group, bits)]
-        mixed, _, _ = tools.add_signals_ragged([pending[i][5] for i in group], [noises[k] for k in used], snr,
-                                               noise_index=[slot[mixes[i][0]] for i in group], starts=[mixes[i][1] for i in group],
-                                               counts=[mixes[i][2] for i in group], bits=bits, ratios=ratios, norm=0.5)
-        out += [pending[i][:5] + (m,) for i, m in zip(group, mixed)]
-    return out
+    return [_detect_item(p, c) for p, c in zip(pending, ragged.split(conf.cpu().numpy(), nv))]
 
 
 def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noise_files=None, snr=None, seed=0,
@@ -229,76 +319,30 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     with open(dataset_json, 'r') as fp:
         ds = json.load(fp)
     net.eval()
-    stat = []
     clean_audio = noise_files is not None
     if batch_mix and not (batch_files and clean_audio):
         raise ValueError("batch_mix=True applies to noise_files given with batch_files=True")
     if clean_audio and snr is None:
         raise ValueError("the clean-recordings branch needs an snr")
     suffix = convert_snr_to_suffix2(snr) if clean_audio else ''
-    rng = np.random.default_rng(seed)
+    noise_dir = os.path.join(os.path.abspath(outputs), 'noise' + suffix)
     noise_entries = OrderedDict()
-    loaded, pending = None, []
-    decoded, mixes = {}, []                                     # batch_mix: noise files by index, per-file crops
-    if batch_files and ds['files']:
-        loaded, _ = audio_io.load_batch_device([_resolve(f['audio_path'], ds.get('dataset_path'), data_root) for f in ds['files']],
-                                               sr=DATA_REQUIRED_SR)
-    for data_id, f in enumerate(ds['files']):
-        bits_full = f[BITSTREAM_JSON_LABEL]
-        i1, i2 = _trim_unknown(bits_full)
-        label = [str(int(b)) for b in bits_full[i1:i2]]
-        if batch_files:
-            snd = loaded[data_id]
-        else:
-            snd, _ = audio_io.load_device(_resolve(f['audio_path'], ds.get('dataset_path'), data_root), sr=DATA_REQUIRED_SR)
-        if batch_mix:
-            k = int(rng.integers(len(noise_files)))
-            if k not in decoded:
-                decoded[k] = audio_io.load(noise_files[k], sr=DATA_REQUIRED_SR)[0]
-            noise = decoded[k]
-            need = int(np.ceil(f['duration'])) * DATA_REQUIRED_SR
-            start = int(rng.integers(0, max(len(noise) - need, 0) + 1))
-            crop = noise[start:start + need]                        # M1/dataset.py:141-142
-            start_pos = int(i1 / f['framerate'] * DATA_REQUIRED_SR)
-            mixes.append((k, start + start_pos, max(len(crop) - start_pos, 0)))
-            base = os.path.basename(f['path'])
-            noise_name = base.split('.mp4')[0].split('.wav')[0] + '_noise.wav'
-            noise_dir = os.path.join(os.path.abspath(outputs), 'noise' + suffix)
-            ensure_dir(noise_dir)
-            audio_io.write_wav(os.path.join(noise_dir, noise_name), crop.astype(np.float32), DATA_REQUIRED_SR)
-            noise_entries[base] = OrderedDict([('audio', base.split('.mp4')[0].split('.wav')[0] + '.wav'),
-                                               ('noise', noise_name), ('snr', snr)])
-            pending.append((data_id, f, bits_full, i1, label, snd))     # mixed after the loop, in groups
-            continue
-        if clean_audio:
-            gt = torch.tensor([int(b) for b in label], dtype=torch.uint8, device=snd.device).reshape(1, -1)
-            gmask = tools.bits_to_mask_batch(gt, float(DATA_REQUIRED_SR) / f['framerate'], snd.numel())
-            audio = (snd * (1 - gmask[0])).cpu().numpy()            # M1/dataset.py:247-249
-            noise, _ = audio_io.load(noise_files[int(rng.integers(len(noise_files)))], sr=DATA_REQUIRED_SR)
-            need = int(np.ceil(f['duration'])) * DATA_REQUIRED_SR
-            start = int(rng.integers(0, max(len(noise) - need, 0) + 1))
-            crop = noise[start:start + need]                        # M1/dataset.py:141-142
-            mixed, _, _ = add_noise_to_audio(audio, crop, snr, start_pos=int(i1 / f['framerate'] * DATA_REQUIRED_SR))
-            snd = torch.from_numpy(np.ascontiguousarray(mixed, dtype=np.float32)).to(snd.device)
-            base = os.path.basename(f['path'])
-            noise_name = base.split('.mp4')[0].split('.wav')[0] + '_noise.wav'
-            noise_dir = os.path.join(os.path.abspath(outputs), 'noise' + suffix)
-            ensure_dir(noise_dir)
-            audio_io.write_wav(os.path.join(noise_dir, noise_name), crop.astype(np.float32), DATA_REQUIRED_SR)
-            noise_entries[base] = OrderedDict([('audio', base.split('.mp4')[0].split('.wav')[0] + '.wav'),
-                                               ('noise', noise_name), ('snr', snr)])
-        if batch_files:
-            pending.append((data_id, f, bits_full, i1, label, snd))
-            continue
-        S = transform.stft_batch(snd.reshape(1, -1))
-        logits = net(s=S, v_num_frames=len(label))
-        pred, conf = tools.threshold_bits(logits, SIGMOID_THRESHOLD)
-        stat.append(_detect_item(data_id, f, bits_full, i1, label, pred[0].cpu().numpy(), conf[0].cpu().numpy()))
-    if pending and batch_mix:
-        pending = _mix_pending(pending, mixes, decoded, snr, max_mix_bytes)
-    if pending:
-        stat = (_detect_groups(net, pending, max_batch, max_columns) if window_seconds is None else
-                _detect_windows(net, pending, window_seconds, context_seconds, max_batch, max_columns))
+    # 1. load.  The steps are lazy where the form is per file: a file is then loaded, mixed and detected before the next one
+    files = _pending_files(ds, data_root, batch_files)
+    # 2. draw and mix
+    mix = (np.random.default_rng(seed), noise_files, snr, noise_dir, noise_entries)
+    if batch_mix:
+        files = _mix_pending(list(files), *mix, max_mix_bytes)
+    elif clean_audio:
+        files = (_mix_file(p, *mix) for p in files)
+    # 3. detect
+    if not batch_files:
+        stat = [_detect_file(net, p) for p in files]
+    elif window_seconds is None:
+        stat = _detect_groups(net, list(files), max_batch, max_columns)
+    else:
+        stat = _detect_windows(net, list(files), window_seconds, context_seconds, max_batch, max_columns)
+    # 4. write
     stat_dict = OrderedDict([
         ('data_total_frames', CLIP_FRAMES), ('data_center_frames', SILENT_CONSECUTIVE_FRAMES),
         ('sigmoid_threshold', SIGMOID_THRESHOLD), ('snr', snr if clean_audio else None),
@@ -306,7 +350,7 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
                                                                     [b for it in stat for b in it['pred_label']]))]))])
     stat_dict['data'] = sorted(stat, key=lambda x: np.mean([float(c) for c in x['confidence']]), reverse=True)
     if clean_audio:
-        with open(os.path.join(os.path.abspath(outputs), 'noise' + suffix, suffix[1:] + '.json'), 'w') as fp:
+        with open(os.path.join(noise_dir, suffix[1:] + '.json'), 'w') as fp:
             json.dump(OrderedDict([('snrs', [snr]), ('files', noise_entries)]), fp, **JSON_DUMP_PARAMS)
     if save_stat:
         ensure_dir(os.path.abspath(outputs))
@@ -315,39 +359,53 @@ def detect_files(net, dataset_json, outputs, data_root=None, save_stat=True, noi
     return stat_dict
 
 
-def _write_recovered_batch(jobs, clean_audio, noise_dir, nsuffix, max_bytes):
-    """create_data_from_prediction(batch_files=True): the WAVE files of `jobs` = (item, recording path, save_dir, name), per
-    group of files one audio_io.load_batch_device for the recordings (and one for the stored noise crops, one
-    tools.add_signals_ragged call) and one download."""
-    from .labels import _file_groups
-    noise_files = None
-    if clean_audio and jobs:
-        with open(os.path.join(noise_dir, nsuffix[1:] + '.json'), 'r') as fpn:
-            noise_files = json.load(fpn)['files']
-    for group in _file_groups([j[1] for j in jobs], max_bytes):
+# One file of create_data_from_prediction(save_results=True): its pred_data.json item, where its recording lies on this
+# machine, the directory of the recovered files and their common name.
+Recovered = namedtuple('Recovered', 'item path save_dir filename')
+
+
+def _write_recovered(job, mixed, clean=None, full_noise=None):
+    """<name>_mixed.wav (and, with the clean-recordings branch, _clean.wav and _full_noise.wav) of a file from host arrays, and
+    the item's keys that name them (M1/create_data_from_pred.py:158-190)."""
+    for key, tag, y in (('mixed_audio', '_mixed', mixed), ('clean_audio', '_clean', clean), ('full_noise', '_full_noise', full_noise)):
+        if y is not None:
+            name = job.filename + tag + '.wav'
+            audio_io.write_wav(os.path.join(job.save_dir, name), y, DATA_REQUIRED_SR)
+            job.item[key] = os.path.join(os.path.basename(job.save_dir), name)
+    if clean is not None:
+        job.item['audio_path'] = os.path.join(job.save_dir, job.filename + '_clean.wav')
+
+
+def _write_recovered_files(jobs, noise_dir, noise_files):
+    """create_data_from_prediction per file: the recording (and its stored noise crop) decoded and mixed one file at a time.
+    noise_files: the `files` of the noise JSON, None outside the clean-recordings branch."""
+    for job in jobs:
+        snd = _load_host(job.path)
+        if noise_files is None:
+            _write_recovered(job, snd)
+            continue
+        entry = noise_files[os.path.basename(job.item['path'])]
+        noise = _load_host(os.path.join(noise_dir, entry['noise']))
+        mixed, clean, full_noise = add_noise_to_audio(snd, noise, entry['snr'], start_pos=0, norm=0.5)
+        _write_recovered(job, mixed.astype(np.float32), clean.astype(np.float32), full_noise[0].astype(np.float32))
+
+
+def _write_recovered_batch(jobs, noise_dir, noise_files, max_bytes):
+    """create_data_from_prediction(batch_files=True): per group of files one audio_io.load_batch_device for the recordings (and
+    one for the stored noise crops, one tools.add_signals_ragged call) and one download."""
+    for group in audio_io.file_groups([j.path for j in jobs], max_bytes):
         part = [jobs[i] for i in group]
-        snds, _ = audio_io.load_batch_device([j[1] for j in part], sr=DATA_REQUIRED_SR)
-        if clean_audio:
-            entries = [noise_files[os.path.basename(j[0]['path'])] for j in part]
+        B = len(part)
+        snds, _ = audio_io.load_batch_device([j.path for j in part], sr=DATA_REQUIRED_SR)
+        if noise_files is None:
+            host = ragged.download(snds, np.float32)
+        else:
+            entries = [noise_files[os.path.basename(j.item['path'])] for j in part]
             noises, _ = audio_io.load_batch_device([os.path.join(noise_dir, e['noise']) for e in entries], sr=DATA_REQUIRED_SR)
             mixed, clean, full_noise = tools.add_signals_ragged(snds, noises, [e['snr'] for e in entries], starts=0, norm=0.5)
             host = ragged.download(mixed + clean + full_noise, np.float32)
-        else:
-            host = ragged.download(snds, np.float32)
-        B = len(part)
-        for k, (item, _, save_dir, filename) in enumerate(part):
-            mixed_path = os.path.join(save_dir, filename + '_mixed.wav')
-            rel = lambda q: os.path.join(os.path.basename(save_dir), os.path.basename(q))     # noqa: E731
-            audio_io.write_wav(mixed_path, host[k], DATA_REQUIRED_SR)
-            if clean_audio:
-                clean_path = os.path.join(save_dir, filename + '_clean.wav')
-                full_noise_path = os.path.join(save_dir, filename + '_full_noise.wav')
-                audio_io.write_wav(clean_path, host[B + k], DATA_REQUIRED_SR)
-                audio_io.write_wav(full_noise_path, host[2 * B + k], DATA_REQUIRED_SR)
-                item['mixed_audio'], item['clean_audio'], item['full_noise'] = rel(mixed_path), rel(clean_path), rel(full_noise_path)
-                item['audio_path'] = clean_path
-            else:
-                item['mixed_audio'] = rel(mixed_path)
+        for k, job in enumerate(part):
+            _write_recovered(job, *host[k::B])                  # file-major: mixed of all files, then clean, then full_noise
 
 
 def create_data_from_prediction(input_json, output_json=None, suffix="", noise_snr=None, save_results=True,
@@ -395,32 +453,16 @@ def create_data_from_prediction(input_json, output_json=None, suffix="", noise_s
             ensure_dir(save_dir)
             parts = item['path'].split('.mp4')
             wav_path = parts[0] if len(parts) == 1 else parts[0] + '.wav'
-            if batch_files:
-                jobs.append((item, _resolve(wav_path, src_root, data_root), save_dir, os.path.basename(wav_path).split('.wav')[0]))
-                continue
-            snd, _ = audio_io.load(_resolve(wav_path, src_root, data_root), sr=DATA_REQUIRED_SR)
-            filename = os.path.basename(wav_path).split('.wav')[0]
-            mixed_path = os.path.join(save_dir, filename + '_mixed.wav')
-            rel = lambda q: os.path.join(os.path.basename(save_dir), os.path.basename(q))     # noqa: E731
-            if clean_audio:
-                noise_dir = os.path.join(get_parent_dir(output_json), 'noise' + nsuffix)
-                with open(os.path.join(noise_dir, nsuffix[1:] + '.json'), 'r') as fpn:
-                    noise_files = json.load(fpn)['files']
-                entry = noise_files[os.path.basename(item['path'])]
-                noise, _ = audio_io.load(os.path.join(noise_dir, entry['noise']), sr=DATA_REQUIRED_SR)
-                mixed, clean, full_noise = add_noise_to_audio(snd, noise, entry['snr'], start_pos=0, norm=0.5)
-                clean_path = os.path.join(save_dir, filename + '_clean.wav')
-                full_noise_path = os.path.join(save_dir, filename + '_full_noise.wav')
-                audio_io.write_wav(mixed_path, mixed.astype(np.float32), DATA_REQUIRED_SR)
-                audio_io.write_wav(clean_path, clean.astype(np.float32), DATA_REQUIRED_SR)
-                audio_io.write_wav(full_noise_path, full_noise[0].astype(np.float32), DATA_REQUIRED_SR)
-                item['mixed_audio'], item['clean_audio'], item['full_noise'] = rel(mixed_path), rel(clean_path), rel(full_noise_path)
-                item['audio_path'] = clean_path
-            else:
-                audio_io.write_wav(mixed_path, snd, DATA_REQUIRED_SR)
-                item['mixed_audio'] = rel(mixed_path)
+            jobs.append(Recovered(item, _resolve(wav_path, src_root, data_root), save_dir, os.path.basename(wav_path).split('.wav')[0]))
     if jobs:
-        _write_recovered_batch(jobs, clean_audio, os.path.join(get_parent_dir(output_json), 'noise' + nsuffix), nsuffix, max_bytes)
+        noise_dir, noise_files = os.path.join(get_parent_dir(output_json), 'noise' + nsuffix), None
+        if clean_audio:                                            # what detect_files stored: read once per call
+            with open(os.path.join(noise_dir, nsuffix[1:] + '.json'), 'r') as fpn:
+                noise_files = json.load(fpn)['files']
+        if batch_files:
+            _write_recovered_batch(jobs, noise_dir, noise_files, max_bytes)
+        else:
+            _write_recovered_files(jobs, noise_dir, noise_files)
     hierarchy = OrderedDict([
         ('dataset_path', ds_path), ('num_videos', len(groups)), ('data_total_frames', obj['data_total_frames']),
         ('data_center_frames', obj['data_center_frames']), ('sigmoid_threshold', obj['sigmoid_threshold']),
@@ -442,6 +484,30 @@ def _parse_bits(bitstream):
     return vals
 
 
+def _gt_bits(bitstream):
+    """The ground-truth bit stream as 0 / 1 values: everything but '0' is non-silent (M2/predict.py:318-320)."""
+    return [0 if b == '0' else 1 for b in bitstream]
+
+
+# The keys of a file that travel from pred_data.json into its stat.json / eval_results entry, in the order the reference
+# writes them; those in _KNOWN_ONLY (of the info record, or of an item of get_data_from_first_model) exist with a known clean signal (unknown_clean_signal=False) alone.
+_INFO_KEYS = ('id', 'path', 'clean_audio_path', 'mixed_audio_path', 'full_noise_path', 'bitstream', 'sr', 'snr')
+_KNOWN_ONLY = ('clean_audio_path', 'full_noise_path', 'clean', 'full_noise')
+
+
+def _file_info(data):
+    """The ordered `info` record of a file (M2/predict.py:430-450) from whatever of _INFO_KEYS its `data` carries."""
+    info = OrderedDict((k, data[k]) for k in _INFO_KEYS if k in data)
+    info['id'], info['path'] = str(info['id']), str(info['path'])
+    return info
+
+
+def _data_info(obj):
+    """What eval_results.json of stage 2 repeats of pred_data.json."""
+    return OrderedDict([(k, obj[k]) for k in ('dataset_path', 'num_videos', 'data_total_frames', 'data_center_frames',
+                                              'sigmoid_threshold')])
+
+
 def get_data_from_first_model(first_model_json_path, sr=DATA_REQUIRED_SR, snr=None, n_fft=510, hop_length=158,
                               win_length=400, unknown_clean_signal=True):
     """M2/predict.py:255-374: per file of pred_data.json load `mixed_audio`, turn `recovered_prediction` into the
@@ -453,80 +519,75 @@ def get_data_from_first_model(first_model_json_path, sr=DATA_REQUIRED_SR, snr=No
     with open(first_model_json_path, 'r') as fp:
         obj = json.load(fp)
     snr = obj['snr']
+    base = get_parent_dir(first_model_json_path)
+    stft = lambda y: transform.stft_batch(y.reshape(1, -1), n_fft, hop_length, win_length)      # noqa: E731
     data_list = []
     for data in obj['files']:
-        mixed_audio_path = os.path.join(get_parent_dir(first_model_json_path), data['mixed_audio'])
+        mixed_audio_path = os.path.join(base, data['mixed_audio'])
         mixed_sig, _ = audio_io.load_device(mixed_audio_path, sr=sr)
         bitstream = data[BIT_STREAM_LABEL]
         bits = torch.tensor(_parse_bits(bitstream), dtype=torch.uint8, device=mixed_sig.device).reshape(1, -1)
         mask, noise_sig = tools.bits_to_mask_batch(bits, float(sr) / data['framerate'], mixed_sig.numel(),
                                                    mixed_sig.reshape(1, -1))
-        item = OrderedDict([('id', os.path.splitext(os.path.basename(data['path']))[0]), ('path', data['path'])])
-        known = OrderedDict()
+        clean_audio_path = full_noise_path = clean = full_noise = None
         if not unknown_clean_signal:
-            clean_audio_path = os.path.join(get_parent_dir(first_model_json_path), data['clean_audio'])
-            full_noise_path = os.path.join(get_parent_dir(first_model_json_path), data['full_noise'])
+            clean_audio_path, full_noise_path = os.path.join(base, data['clean_audio']), os.path.join(base, data['full_noise'])
             clean_sig, _ = audio_io.load_device(clean_audio_path, sr=sr)
-            full_noise, _ = audio_io.load_device(full_noise_path, sr=sr)
-            gt = torch.tensor([0 if b == '0' else 1 for b in data[GT_BIT_STREAM_LABEL]], dtype=torch.uint8,
-                              device=clean_sig.device).reshape(1, -1)
+            full_noise_sig, _ = audio_io.load_device(full_noise_path, sr=sr)
+            gt = torch.tensor(_gt_bits(data[GT_BIT_STREAM_LABEL]), dtype=torch.uint8, device=clean_sig.device).reshape(1, -1)
             gt_mask = tools.bits_to_mask_batch(gt, float(sr) / data['framerate'], clean_sig.numel())
-            clean_sig = clean_sig * (1 - gt_mask[0])             # silent intervals truly silent (M2/predict.py:321)
-            item['clean_audio_path'] = clean_audio_path
-            known['clean'] = transform.stft_batch(clean_sig.reshape(1, -1), n_fft, hop_length, win_length)
-            known['full_noise'] = transform.stft_batch(full_noise.reshape(1, -1), n_fft, hop_length, win_length)
-        item['mixed_audio_path'] = mixed_audio_path
-        if not unknown_clean_signal:
-            item['full_noise_path'] = full_noise_path
-        item['bitstream'] = bitstream
-        item['mixed'] = transform.stft_batch(mixed_sig.reshape(1, -1), n_fft, hop_length, win_length)
-        if 'clean' in known:
-            item['clean'] = known['clean']
-        item['noise'] = transform.stft_batch(noise_sig, n_fft, hop_length, win_length)
-        if 'full_noise' in known:
-            item['full_noise'] = known['full_noise']
-        item.update([('mask', mask[0]), ('snr', snr), ('sr', sr)])
+            clean = stft(clean_sig * (1 - gt_mask[0]))           # silent intervals truly silent (M2/predict.py:321)
+            full_noise = stft(full_noise_sig)
+        item = OrderedDict([
+            ('id', os.path.splitext(os.path.basename(data['path']))[0]), ('path', data['path']),
+            ('clean_audio_path', clean_audio_path), ('mixed_audio_path', mixed_audio_path), ('full_noise_path', full_noise_path),
+            ('bitstream', bitstream), ('mixed', stft(mixed_sig)), ('clean', clean), ('noise', stft(noise_sig)),
+            ('full_noise', full_noise), ('mask', mask[0]), ('snr', snr), ('sr', sr)])
+        if unknown_clean_signal:
+            for k in _KNOWN_ONLY:
+                del item[k]
         data_list.append(item)
-    info = OrderedDict([(k, obj[k]) for k in ('dataset_path', 'num_videos', 'data_total_frames', 'data_center_frames',
-                                              'sigmoid_threshold')])
-    return data_list, info
+    return data_list, _data_info(obj)
 
 
-def _write_individual(data, info, sigs, gt_sigs, outputs, snr, save_individual_results):
-    """The WAVE files and stat.json of one file of denoise_files (M2/predict.py:515-560); fills the path keys of `info`."""
-    if not save_individual_results:
-        return
-    _write_individual_host(data, info, sigs.cpu().numpy(), None if gt_sigs is None else gt_sigs.cpu().numpy(), outputs, snr)
+# One file of stage 2 after the denoiser: its `data` (id, sr, ...) and `info` records, the four signals (noisy input, noise
+# intervals, predicted full noise, denoised output) and, with a known clean signal, the two ground-truth ones (full noise,
+# clean input) on the device, or None; host: the same four (six) signals as host arrays where a form has downloaded them.
+Denoised = namedtuple('Denoised', 'data info sigs gt_sigs host')
 
 
-def _write_individual_host(data, info, host, gh, outputs, snr):
-    """_write_individual on host arrays: host (4, n) = the four signals, gh (2, >= n) = the ground-truth ones or None."""
-    save_dir = os.path.join(os.path.abspath(outputs), convert_snr_to_suffix2(snr)[1:], str(data['id']))
+def _write_individual(w, outputs, snr):
+    """The WAVE files and stat.json of one file of stage 2 (M2/predict.py:515-560); fills the path keys of its `info`.  A form
+    that has not downloaded the signals of its files in one copy leaves `host` None: they come down here."""
+    if w.host is not None:
+        host, gh = w.host[:4], (w.host[4:] if len(w.host) > 4 else None)
+    else:
+        host, gh = w.sigs.cpu().numpy(), (None if w.gt_sigs is None else w.gt_sigs.cpu().numpy())
+    save_dir = os.path.join(os.path.abspath(outputs), convert_snr_to_suffix2(snr)[1:], str(w.data['id']))
     ensure_dir(save_dir)
-    for k, name in enumerate(('noisy_input', 'noise_intervals', 'predicted_full_noise', 'denoised_output')):
-        p = os.path.join(save_dir, name + '.wav')
-        audio_io.write_wav(p, host[k], data['sr'])
-        info[name] = p
+    named = list(zip(('noisy_input', 'noise_intervals', 'predicted_full_noise', 'denoised_output'), host))
     if gh is not None:
-        for k, name in enumerate(('ground_truth_full_noise', 'ground_truth_clean_input')):
-            p = os.path.join(save_dir, name + '.wav')
-            audio_io.write_wav(p, gh[k][:len(host[0])], data['sr'])
-            info[name] = p
+        named += [(name, g[:len(host[0])]) for name, g in zip(('ground_truth_full_noise', 'ground_truth_clean_input'), gh)]
+    for name, y in named:
+        p = os.path.join(save_dir, name + '.wav')
+        audio_io.write_wav(p, y, w.data['sr'])
+        w.info[name] = p
     with open(os.path.join(save_dir, 'stat.json'), 'w') as fp:
-        json.dump(info, fp, **JSON_DUMP_PARAMS)
+        json.dump(w.info, fp, **JSON_DUMP_PARAMS)
 
 
 def _batch_measures(work, pesq_fn, stoi_fn):
     """The objective measures of all files with a known clean signal (denoise_files(batch_metrics=True)): outputs and clean
     signals to 16 kHz in one resample_batch_device call per distinct rate (2 F clips), one evaluate_metrics_batch."""
+    work = [w for w in work if w.gt_sigs is not None]
     if not work:
         return
     out16, clean16 = [None] * len(work), [None] * len(work)
     by_rate = OrderedDict()
-    for i, (data, _, _, _) in enumerate(work):
-        by_rate.setdefault(data['sr'], []).append(i)
+    for i, w in enumerate(work):
+        by_rate.setdefault(w.data['sr'], []).append(i)
     for sr, idx in by_rate.items():
-        clips = [work[i][2][3].contiguous() for i in idx] + [work[i][3][1].contiguous() for i in idx]
+        clips = [work[i].sigs[3].contiguous() for i in idx] + [work[i].gt_sigs[1].contiguous() for i in idx]
         res = audio_io.resample_batch_device(clips, sr, 16000)
         for k, i in enumerate(idx):
             n = min(res[k].numel(), res[len(idx) + k].numel())       # evaluate_metrics compares the common prefix
@@ -539,8 +600,8 @@ def _batch_measures(work, pesq_fn, stoi_fn):
             pesq = [pesq_fn(c, o, 16000) for c, o in zip(ch, oh)]
         if callable(stoi_fn):
             stoi = [stoi_fn(c, o, 16000) for c, o in zip(ch, oh)]
-    for (_, info, _, _), m in zip(work, metrics.evaluate_metrics_batch(out16, clean16, sr=16000, pesq=pesq, stoi=stoi)):
-        info.update(m)
+    for w, m in zip(work, metrics.evaluate_metrics_batch(out16, clean16, sr=16000, pesq=pesq, stoi=stoi)):
+        w.info.update(m)
 
 
 def _write_eval_results(data_info, stat, outputs, threshold, snr):
@@ -583,16 +644,9 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
         pred_noise_stft, crm = net(data['mixed'], data['noise'])
         out_stft = transform.batch_fast_icRM_sigmoid(data['mixed'], crm)
         sigs = transform.istft_batch(torch.cat([data['mixed'], data['noise'], pred_noise_stft, out_stft], dim=0))
-        known = 'clean' in data
-        info = OrderedDict([('id', str(data['id'])), ('path', str(data['path']))])
-        if known:
-            info['clean_audio_path'] = data['clean_audio_path']
-        info['mixed_audio_path'] = data['mixed_audio_path']
-        if known:
-            info['full_noise_path'] = data['full_noise_path']
-        info.update([('bitstream', data['bitstream']), ('sr', data['sr']), ('snr', data['snr'])])
+        info = _file_info(data)
         gt_sigs = None
-        if known:
+        if 'clean' in data:
             gt_sigs = transform.istft_batch(torch.cat([data['full_noise'], data['clean']], dim=0))
             if not batch_metrics:
                 out16 = audio_io.resample_device(sigs[3].contiguous(), data['sr'], 16000)
@@ -600,14 +654,15 @@ def denoise_files(net, data_list_info, outputs, snr=None, threshold="", save_ind
                 pesq = pesq_fn(clean16.cpu().numpy(), out16.cpu().numpy(), 16000) if pesq_fn is not None else None
                 stoi = stoi_fn(clean16.cpu().numpy(), out16.cpu().numpy(), 16000) if stoi_fn is not None else None
                 info.update(metrics.evaluate_metrics(out16, clean16, sr=16000, pesq=pesq, stoi=stoi))
-        work.append((data, info, sigs, gt_sigs))
-        if not batch_metrics:
-            _write_individual(*work.pop(), outputs, snr, save_individual_results)
         stat.append(info)
-    if batch_metrics:
-        _batch_measures([w for w in work if w[3] is not None], pesq_fn, stoi_fn)
-        for w in work:
-            _write_individual(*w, outputs, snr, save_individual_results)
+        w = Denoised(data, info, sigs, gt_sigs, None)
+        if batch_metrics:
+            work.append(w)
+        elif save_individual_results:
+            _write_individual(w, outputs, snr)
+    _batch_measures(work, pesq_fn, stoi_fn)
+    for w in work if save_individual_results else []:
+        _write_individual(w, outputs, snr)
     if save_stat:
         _write_eval_results(data_info, stat, outputs, threshold, snr)
     return stat
@@ -620,12 +675,71 @@ def _round_trip(wave, ns):
     return transform.istft_batch(transform.stft_batch(wave, clip_samples=rag.tab(ns)), clip_frames=rag.level(0))
 
 
-def _first_model_windows(net, mixed, noise, clean, all_bits, nb, ngt, ratios, framerates, sr, window_seconds, context_seconds,
-                         max_batch, max_columns, download):
+def _rows_under(a, b):
+    """The rows of `b` under the rows of `a` in one f32 buffer, the narrower of the two zero-filled to the other's width."""
+    if a.shape[1] == b.shape[1]:
+        return torch.cat([a, b], dim=0)
+    wide = torch.zeros((a.shape[0] + b.shape[0], max(a.shape[1], b.shape[1])), dtype=torch.float32, device=a.device)
+    wide[:a.shape[0], :a.shape[1]] = a
+    wide[a.shape[0]:, :b.shape[1]] = b
+    return wide
+
+
+def _first_model_whole(net, mixed, noise, clean, all_bits, nb, ngt, ratios, sr, max_batch, max_columns, download):
+    """The whole-file half of denoise_first_model, with the arguments and the result of _first_model_windows (below).
+    The files sorted by length and cut into groups (pipeline._ragged_groups); a group is staged by ONE sos_ragged_stage_f32
+    launch and runs as pipeline.denoise_ragged(bits=..., return_all=True) runs it.  With known clean signals the group has
+    2 B more rows: B .. 2 B full_noise (packed only), 2 B .. 3 B the clean recordings with their ground-truth decisions, whose
+    mask comes out of the same launch; their STFT -> ISTFT round trips are the ground-truth signals.  With `download` the four
+    (six) signals of every file of a group come down in one copy (sos_ragged_unpack_f32), the ground-truth ones cropped to the
+    output length."""
+    from . import pipeline
+    F, device, hop, known = len(mixed), mixed[0].device, transform.HOP_LENGTH, bool(noise)
+    d_bits = ragged.split(all_bits, list(nb) + list(ngt))
+    sigs, gts, hosts = [None] * F, [None] * F, [None] * F
+    for part in pipeline._ragged_groups(mixed, max_batch, max_columns):
+        B = len(part)
+        rows = [mixed[i] for i in part]
+        bits_g = [d_bits[i] for i in part]
+        nbits = [nb[i] for i in part]
+        rat = [ratios[i] for i in part]
+        if known:
+            rows += [noise[i] for i in part] + [clean[i] for i in part]
+            bits_g += [d_bits[F + i] for i in part]
+            nbits += [0] * B + [ngt[i] for i in part]
+            rat = rat * 3
+        (wave, masked, _), ns = pipeline.stage_group(rows, torch.cat(bits_g), nbits, rat)
+        n_long = max(ns[:B])
+        rag = pipeline._group_geometry(ns[:B], device, sr, pipeline.FPS, nv=nbits[:B])
+        out = pipeline._denoise_group_staged(net, wave[:B, :n_long], masked[:B, :n_long], rag, signals=True)
+        n_out = [hop * (t - 1) for t in rag.T]
+        take = [[(q * B + k, n_out[k], 0) for q in range(4)] for k in range(B)]        # per file: (row, samples, -) to unpack
+        if known:
+            wave[2 * B:].sub_(masked[2 * B:])        # silent intervals of the clean signal truly silent (M2/predict.py:321)
+            gt = _round_trip(wave[B:], ns[B:])
+            n_gt = [hop * (n // hop) for n in ns[B:]]
+            for k in range(B):                       # the ground-truth rows follow the group's 4 B rows
+                take[k] += [((4 + q) * B + k, min(n_gt[q * B + k], n_out[k]), 0) for q in range(2)]
+        if download:                                 # the signals of the whole group: one unpack launch, one download
+            tab = np.asarray([row for rows_k in take for row in rows_k], dtype=np.int64)
+            tab[:, 2] = ragged.offsets(tab[:, 1])
+            host = ragged.split(tools.ragged_unpack(_rows_under(out, gt) if known else out, tab).cpu().numpy(), tab[:, 1])
+        per = len(take[0])
+        for k, i in enumerate(part):
+            sigs[i] = [out[q * B + k, :n_out[k]] for q in range(4)]
+            if known:
+                gts[i] = [gt[q * B + k, :n_gt[q * B + k]] for q in range(2)]
+            if download:
+                hosts[i] = host[per * k:per * (k + 1)]
+    return sigs, gts, hosts
+
+
+def _first_model_windows(net, mixed, noise, clean, all_bits, nb, ngt, ratios, sr, max_batch, max_columns, download,
+                         framerates, window_seconds, context_seconds):
     """The windowed half of denoise_first_model: `mixed` (one 1-D GPU recording per file; `noise` / `clean`: the ground-truth
     recordings or empty lists), all_bits = the files' `recovered_prediction` decisions (nb each) followed by the ground-truth
     ones (ngt each) in one GPU buffer.  -> per file ([4 signals], [2 ground-truth signals] or None, host arrays of the
-    4 (6) signals as _write_individual_host takes them, or None without `download`).
+    4 (6) signals as _write_individual takes them, or None without `download`).
     The four signals: windows._masked_group(signals=True) over the windows of all files, then ONE sos_window_stitch_planes_f32 launch into
     a file-major buffer -- the four signals of a file next to each other, every segment on a multiple of four floats (16-byte
     stores) -- and ONE device-to-host copy of it, with no launch in between.
@@ -645,8 +759,12 @@ def _first_model_windows(net, mixed, noise, clean, all_bits, nb, ngt, ratios, fr
     base = (4 * ragged.offsets(pitch)).tolist()
     buf = windows._stitch_signals(kept, plan, context, recs=np.stack([base, pitch], axis=1), out_total=4 * sum(pitch))
     host = buf.cpu().numpy() if download else None              # the four signals of every file: one copy
-    sigs = [[buf[base[i] + q * pitch[i]:base[i] + q * pitch[i] + lens[i]] for q in range(4)] for i in range(F)]
-    hosts = [[host[base[i] + q * pitch[i]:base[i] + q * pitch[i] + lens[i]] for q in range(4)] if download else None for i in range(F)]
+
+    def four(b, i):
+        return [b[base[i] + q * pitch[i]:base[i] + q * pitch[i] + lens[i]] for q in range(4)]
+
+    sigs = [four(buf, i) for i in range(F)]
+    hosts = [four(host, i) if download else None for i in range(F)]
     if not noise:
         return sigs, [None] * F, hosts
     # recordings 0 .. F - 1: full_noise, F .. 2 F - 1: clean, with its ground-truth decisions
@@ -666,10 +784,20 @@ def _first_model_windows(net, mixed, noise, clean, all_bits, nb, ngt, ratios, fr
     gkept = windows._run_windows(gplan, device, max_batch, max_columns, run_group)
     gt = ragged.split(tools.window_stitch(gkept, windows._row_plan(gplan), context), windows._out_lengths(ng))
     gts = [[gt[i], gt[F + i]] for i in range(F)]
-    if download:                                                 # cropped like _write_individual: one more copy
+    if download:                                                 # cropped like the whole-file half: one more copy
         gh = ragged.download([g[:lens[i]] for i in range(F) for g in gts[i]])
         hosts = [hosts[i] + gh[2 * i:2 * i + 2] for i in range(F)]
     return sigs, gts, hosts
+
+
+def _check_frames(paths, ys, sr, what):
+    """ValueError naming the first file with fewer STFT frames than the denoiser takes."""
+    from . import pipeline
+    hop = transform.HOP_LENGTH
+    for path, y in zip(paths, ys):
+        if 1 + y.numel() // hop < pipeline.MIN_FRAMES:
+            raise ValueError("%s: %d samples at %d Hz are fewer than the %d STFT frames (%d samples) %s needs"
+                             % (path, y.numel(), sr, pipeline.MIN_FRAMES, pipeline.MIN_FRAMES * hop, what))
 
 
 @torch.no_grad()
@@ -697,111 +825,49 @@ def denoise_first_model(net, first_model_json_path, outputs, sr=DATA_REQUIRED_SR
     files, keys, order, types and measures as the whole-file path; activation memory follows max_columns, not the file.
     A file with fewer than pipeline.MIN_FRAMES STFT frames raises ValueError naming it before any group is staged or run, and
     so do pipeline.window_plan's argument rules."""
-    from . import engine as E
-    from . import pipeline
+    # 1. parse
     with open(first_model_json_path, 'r') as fp:
         obj = json.load(fp)
     base = get_parent_dir(first_model_json_path)
     files = obj['files']
     known = not unknown_clean_signal
     F = len(files)
-    data_info = OrderedDict([(k, obj[k]) for k in ('dataset_path', 'num_videos', 'data_total_frames', 'data_center_frames',
-                                                   'sigmoid_threshold')])
+    data_info = _data_info(obj)
     data_info['snr'] = snr
     net.eval()
     mixed_paths = [os.path.join(base, d['mixed_audio']) for d in files]
     clean_paths = [os.path.join(base, d['clean_audio']) for d in files] if known else []
     noise_paths = [os.path.join(base, d['full_noise']) for d in files] if known else []
     rec_bits = [np.asarray(_parse_bits(d[BIT_STREAM_LABEL]), dtype=np.uint8) for d in files]
-    gt_bits = [np.asarray([0 if b == '0' else 1 for b in d[GT_BIT_STREAM_LABEL]], dtype=np.uint8) for d in files] if known else []
-    ratios = [float(sr) / d['framerate'] for d in files]
-    stat, work = [], []
-
-    def file_info(i):
-        d = files[i]
-        data = dict(id=os.path.splitext(os.path.basename(d['path']))[0], sr=sr)
-        info = OrderedDict([('id', str(data['id'])), ('path', str(d['path']))])
-        if known:
-            info['clean_audio_path'] = clean_paths[i]
-        info['mixed_audio_path'] = mixed_paths[i]
-        if known:
-            info['full_noise_path'] = noise_paths[i]
-        info.update([('bitstream', d[BIT_STREAM_LABEL]), ('sr', sr), ('snr', obj['snr'])])
-        return data, info
-
+    gt_bits = [np.asarray(_gt_bits(d[GT_BIT_STREAM_LABEL]), dtype=np.uint8) for d in files] if known else []
+    datas = [dict(id=os.path.splitext(os.path.basename(d['path']))[0], path=d['path'], mixed_audio_path=mixed_paths[i],
+                  bitstream=d[BIT_STREAM_LABEL], sr=sr, snr=obj['snr']) for i, d in enumerate(files)]
+    for data, c, n in zip(datas, clean_paths, noise_paths):
+        data.update(clean_audio_path=c, full_noise_path=n)
+    work = []
     if F:
+        # 2. load
         ys, _ = audio_io.load_batch_device(mixed_paths + clean_paths + noise_paths, sr=sr)
         mixed, clean, noise = ys[:F], ys[F:2 * F], ys[2 * F:]
-        hop = transform.HOP_LENGTH
-        for i, y in enumerate(mixed):
-            if 1 + y.numel() // hop < pipeline.MIN_FRAMES:
-                raise ValueError("%s: %d samples at %d Hz are fewer than the %d STFT frames (%d samples) the denoiser needs"
-                                 % (mixed_paths[i], y.numel(), sr, pipeline.MIN_FRAMES, pipeline.MIN_FRAMES * hop))
-        device = mixed[0].device
-        all_bits = torch.from_numpy(np.concatenate(rec_bits + gt_bits)).to(device)       # every bit string: one copy
-        d_bits = ragged.split(all_bits, [len(b) for b in rec_bits + gt_bits])
-        work = [None] * F
-    if F and window_seconds is not None:
-        for i, y in enumerate(clean + noise):                # the ground-truth recordings are windowed under a plan of their own
-            if 1 + y.numel() // hop < pipeline.MIN_FRAMES:
-                raise ValueError("%s: %d samples at %d Hz are fewer than the %d STFT frames (%d samples) a window needs"
-                                 % ((clean_paths + noise_paths)[i], y.numel(), sr, pipeline.MIN_FRAMES, pipeline.MIN_FRAMES * hop))
-        sigs, gts, hosts = _first_model_windows(net, mixed, noise, clean, all_bits, [len(b) for b in rec_bits],
-                                                [len(b) for b in gt_bits], ratios, [d['framerate'] for d in files], sr,
-                                                window_seconds, context_seconds, max_batch, max_columns, save_individual_results)
-        work = [file_info(i) + (sigs[i], gts[i] if known else None, hosts[i]) for i in range(F)]
-    for part in (pipeline._ragged_groups(mixed, max_batch, max_columns) if F and window_seconds is None else []):
-        B = len(part)
-        rows = [mixed[i] for i in part]
-        bits_g = [d_bits[i] for i in part]
-        nb = [len(rec_bits[i]) for i in part]
-        rat = [ratios[i] for i in part]
-        if known:                                    # rows B .. 2B: full_noise (packed only), rows 2B .. 3B: clean + ground-truth bits
-            rows += [noise[i] for i in part] + [clean[i] for i in part]
-            bits_g += [d_bits[F + i] for i in part]
-            nb += [0] * B + [len(gt_bits[i]) for i in part]
-            rat = rat * 3
-        (wave, masked, _), ns = pipeline.stage_group(rows, torch.cat(bits_g), nb, rat)
-        n_long = max(ns[:B])
-        rag = pipeline._group_geometry(ns[:B], device, sr, pipeline.FPS, nv=nb[:B])
-        sigs = pipeline._denoise_group_staged(net, wave[:B, :n_long], masked[:B, :n_long], rag, signals=True)
-        n_out = [hop * (t - 1) for t in rag.T]
-        table = [(q * B + k, n_out[k], 0) for k in range(B) for q in range(4)]
-        gt = None
-        if known:
-            wave[2 * B:].sub_(masked[2 * B:])        # silent intervals of the clean signal truly silent (M2/predict.py:321)
-            gt = _round_trip(wave[B:], ns[B:])
-            n_gt = [hop * (n // hop) for n in ns[B:]]
-        host = None
-        if save_individual_results:                  # the signals of the whole group: one unpack launch, one download
-            if known:                                # ground-truth rows follow the group's 4 B rows, cropped like _write_individual
-                if gt.shape[1] != sigs.shape[1]:
-                    wide = torch.zeros((6 * B, max(gt.shape[1], sigs.shape[1])), dtype=torch.float32, device=device)
-                    wide[:4 * B, :sigs.shape[1]] = sigs
-                    wide[4 * B:, :gt.shape[1]] = gt
-                    both = wide
-                else:
-                    both = torch.cat([sigs, gt], dim=0)
-                table = [row for k in range(B) for row in
-                         ([(q * B + k, n_out[k], 0) for q in range(4)] +
-                          [((4 + q) * B + k, min(n_gt[q * B + k], n_out[k]), 0) for q in range(2)])]
-            else:
-                both = sigs
-            tab = np.asarray(table, dtype=np.int64)
-            tab[:, 2] = ragged.offsets(tab[:, 1])
-            host = ragged.split(tools.ragged_unpack(both, tab).cpu().numpy(), tab[:, 1])
-        per = 6 if known else 4
-        for k, i in enumerate(part):
-            data, info = file_info(i)
-            sig_i = [sigs[q * B + k, :n_out[k]] for q in range(4)]
-            gt_i = [gt[q * B + k, :n_gt[q * B + k]] for q in range(2)] if known else None
-            host_i = host[per * k:per * (k + 1)] if host is not None else None
-            work[i] = (data, info, sig_i, gt_i, host_i)
-    stat = [w[1] for w in work]
-    _batch_measures([w[:4] for w in work if w[3] is not None], pesq_fn, stoi_fn)
-    for data, info, _, _, host_i in work:
-        if host_i is not None:
-            _write_individual_host(data, info, host_i[:4], host_i[4:] if known else None, outputs, snr)
+        # 3. check
+        _check_frames(mixed_paths, mixed, sr, "the denoiser")
+        if window_seconds is not None:                     # the ground-truth recordings are windowed under a plan of their own
+            _check_frames(clean_paths + noise_paths, clean + noise, sr, "a window")
+        # 4. one of the two halves
+        all_bits = torch.from_numpy(np.concatenate(rec_bits + gt_bits)).to(mixed[0].device)       # every bit string: one copy
+        args = (net, mixed, noise, clean, all_bits, [len(b) for b in rec_bits], [len(b) for b in gt_bits],
+                [float(sr) / d['framerate'] for d in files], sr, max_batch, max_columns, save_individual_results)
+        if window_seconds is None:
+            halves = _first_model_whole(*args)
+        else:
+            halves = _first_model_windows(*args, [d['framerate'] for d in files], window_seconds, context_seconds)
+        work = [Denoised(data, _file_info(data), *half) for data, *half in zip(datas, *halves)]
+    # 5. measure
+    _batch_measures(work, pesq_fn, stoi_fn)
+    # 6. write
+    for w in work if save_individual_results else []:
+        _write_individual(w, outputs, snr)
+    stat = [w.info for w in work]
     if save_stat:
         _write_eval_results(data_info, stat, outputs, threshold, snr)
     return stat

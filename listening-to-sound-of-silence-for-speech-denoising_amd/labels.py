@@ -20,7 +20,6 @@ CPU fallback."""
 import json
 import math
 import os
-import struct
 from collections import OrderedDict, namedtuple
 
 import numpy as np
@@ -169,36 +168,6 @@ def silence_bits(clip, sr, fps=30.0, threshold_db=40.0, min_silence=0.1, min_spe
     return (res[0][0], res[1][0]) if return_detail else res[0]
 
 
-def _wave_sample_bytes(path):
-    """Bytes the mono f32 samples of a RIFF/WAVE file will take, from its chunk headers alone (0 if they cannot be read: the
-    loader reports what is wrong with the file)."""
-    try:
-        with open(path, "rb") as fp:
-            head = fp.read(12)
-            if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
-                return 0
-            align = None
-            while True:
-                ch = fp.read(8)
-                if len(ch) < 8:
-                    return 0
-                cid, size = ch[:4], struct.unpack("<I", ch[4:])[0]
-                if cid == b"fmt ":
-                    body = fp.read(size + (size & 1))
-                    align = struct.unpack_from("<H", body, 12)[0] if len(body) >= 16 else None
-                elif cid == b"data":
-                    return 4 * (size // align) if align else 0
-                else:
-                    fp.seek(size + (size & 1), os.SEEK_CUR)
-    except OSError:
-        return 0
-
-
-def _file_groups(paths, max_bytes):
-    """Consecutive files in groups of at most max_bytes of f32 samples (a file larger than that is a group of its own)."""
-    return ragged.byte_groups([_wave_sample_bytes(p) for p in paths], max_bytes)
-
-
 def _plain(v):
     """30.0 -> 30, as the reference's JSON writes whole rates."""
     return int(v) if float(v) == int(v) else float(v)
@@ -219,7 +188,7 @@ def label_files(paths, output_json=None, dataset_path=None, fps=30.0, threshold_
     from .handoff import JSON_DUMP_PARAMS
     paths = [os.path.abspath(p) for p in paths]
     files = []
-    for group in _file_groups(paths, max_bytes):
+    for group in audio_io.file_groups(paths, max_bytes):
         ys, srs = audio_io.load_batch_device([paths[i] for i in group], sr=None)
         for i, y in zip(group, ys):
             if y.numel() == 0:
