@@ -269,7 +269,24 @@ int sos_lstm_bidir_fwd(const float* xproj, const void* wpk_hi, const void* wpk_l
 /* ---------------------------------------------------------------- training-mode kernels
  * A `sos_view` describes a channel slice of a bf16 NHWC activation: element (pix, c) lives at
  * ptr[pix*row + c_off + c]; with x3 != 0 the value is hi + lo, hi at that address (and again at
- * +third), lo at +2*third.  C <= 256. */
+ * +third), lo at +2*third.  1 <= C <= 2048; row, c_off (and third) are multiples of 8.
+ *
+ * The 8-channel run.  The kernels that take views move 16-byte runs of 8 channels and do NOT mask by C: a view covers
+ * the channels [c_off, c_off + pad8(C)), pad8(C) = C rounded up to a multiple of 8.  The slice must lie inside the row
+ * (inside the third with x3 != 0): c_off + C <= row resp. third, which the library does not check; the rounded-up run
+ * then lies inside it too, because row, third and c_off are multiples of 8.  With C % 8 != 0 the caller owns the padding
+ * channels [c_off + C, c_off + pad8(C)) of every view it passes:
+ *   - sos_copy_crop writes there what the source view holds in ITS padding channels (zero outside the overlap);
+ *   - sos_reflect_fold / sos_reflect_fold_border fold the padded view's padding channels like real ones and store (or,
+ *     accumulating, add) the result there: zero padding in `padded` keeps an accumulated destination's values (re-stored,
+ *     in the three-pass mode possibly as another hi/lo pair of the same sum), a storing fold zeroes them;
+ *   - sos_act_bwd_from_y and sos_feat_to_nhwc (C <= 8 in one aligned run) write zeros there.
+ * These kernels touch no channel below c_off or at or beyond c_off + pad8(C).  sos_pack_grad_f32 writes exactly C channels
+ * (its 8-channel row path needs C % 8 == 0).  The video glue of csrc/video.hip takes plain pointers and channel counts:
+ * sos_time_stack, sos_time_unstack and sos_spatial_mean_bwd write whole rows with the padding channels zero,
+ * sos_spatial_mean exactly C channels of the feature row.  The package's calls of the crop and the folds pass
+ * C % 8 == 0 everywhere but one: the pad = 0 fold that adds the 2-channel loss gradient (a pack whose channels >= 2 are
+ * zero) onto a 16-wide gradient buffer. */
 typedef struct sos_view {
     void* ptr;
     int64_t npix;
