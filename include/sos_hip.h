@@ -522,6 +522,38 @@ int sos_resample_batch_f32(const float* x, const int64_t* table, const int64_t* 
  * `time_register += 1/ratio` that sos_resample_f32 hands its kernel: time(t) = fma(t - k0[i], d[i], s0[i]) for
  * the last i with k0[i] <= t.  Returns the number of segments (<= capacity) or a negative error. */
 int sos_resample_time_segments(double ratio, int64_t n_out, int64_t* k0, double* s0, double* d, int capacity);
+/* The band above the networks' half rate (csrc/band_merge.hip; sos_amd.audio_io.band_gains_batch_device /
+ * resample_merge_batch_device; float64 restatement: tests/band_reference.py).  Per channel of a recording whose rate R exceeds
+ * the networks' SR: x = the native plane, n frames; a = x resampled to SR, m = ceil(n * SR / R) samples; b = the networks'
+ * output for a, m' <= m samples (hop * (m / hop)); ratio = R / SR; U(v) = what sos_resample_f32 writes for v at `ratio`
+ * (resampled for t < (int64)(len(v) * ratio), zero after).  The rule, all f32:
+ *     out[t] = fmaf(g[t], x[t] - U(a)[t], U(b)[t])        0 <= t < n
+ * U(b) is what resampling the networks' output back gives; g * (x - U(a)) is the part of the source the SR chain never saw.
+ * Both follow the ragged conventions (table on the device, table_host on the HOST, validated there before any launch; the
+ * kernels skip a device row that fails the same bounds); 1 .. 65535 clips per call, every signal's clips back to back in its own
+ * buffer, in table order without overlap.
+ * sos_band_gain_batch_f32: table int64 [6][nclips] = [0] a offset [1] m [2] b offset [3] m' (0 .. m) [4] gains offset
+ *   [5] J = ceil(m / hop).  Frame j covers the samples [j hop, (j + 1) hop) cut at m; E_a[j] = sum a^2, E_b[j] = sum b^2 in
+ *   f64 (no fixed order), b reading zero from m' on; r[j] = 1 if E_a[j] == 0, else min(1, sqrt(E_b[j] / E_a[j])); gains[j] =
+ *   s[j] = the f64 mean of r[max(0, j - smooth) .. min(J - 1, j + smooth)], stored as f32.  One launch.
+ * sos_resample_merge_batch_f32: table int64 [9][nclips] = [0] offset of the clip in x and in out [1] n [2] a offset [3] m
+ *   [4] b offset [5] m' (1 .. m) [6] gains offset [7] J [8] the clip's first tile = sum of ceil(n / SOS_RESAMPLE_CHUNK) over the
+ *   clips before it.  One launch whatever nclips is (one workgroup per CU walks the (clip, SOS_RESAMPLE_CHUNK outputs) tiles, as
+ *   sos_resample_batch_f32 does).  U(a)[t] and U(b)[t] carry the bits of sos_resample_f32 (the same taps in the same order, each
+ *   signal's right wing ending at its own last sample).  gains == NULL: g = 1 and rows [6], [7] are not read; otherwise g[t] =
+ *   the linear interpolation of the clip's s[0 .. J) at the frame-centre position p = (t + 0.5) / (ratio * hop) - 0.5, s[0] for
+ *   p <= 0 and s[J - 1] for p >= J - 1, evaluated in f64 and rounded to f32.  out is not pre-cleared; exactly n floats are
+ *   written per clip.
+ * SOS_EINVAL (sos_last_error() names the clip): null pointers (gains may be NULL for the merge), nclips outside 1 .. 65535,
+ * hop < 1, smooth outside 0 .. 16, m < 1, m' outside its range, J not ceil(m / hop), spans that overlap or are out of order;
+ * for the merge also n < 1, (int64)(m * ratio) < n (U(a) would not cover the clip), a wrong first tile, ratio <= 0,
+ * (nwin + 1) * 4 bytes > 160 KB; SOS_ENOSPC: the time register of the longest clip needs more segments than the kernel
+ * argument holds. */
+int sos_band_gain_batch_f32(const float* a, const float* b, const int64_t* table, const int64_t* table_host, int nclips, int hop,
+                            int smooth, float* gains, sos_stream_t stream);
+int sos_resample_merge_batch_f32(const float* x, const float* a, const float* b, const float* gains, const int64_t* table,
+                                 const int64_t* table_host, int nclips, double ratio, const float* win, int nwin, int num_table,
+                                 int hop, float* out, sos_stream_t stream);
 
 /* ---- 8f-1  audio-visual variant, video branch: Conv3dBlock M1/networks.py:54-77, make_video_branch :110-118
  * (configuration :87-89), fusion :135-142.  A Conv3d with temporal stride 1 runs on sos_conv2d_fwd over a

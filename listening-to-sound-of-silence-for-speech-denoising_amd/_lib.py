@@ -131,6 +131,8 @@ SIGNATURES = {
     "sos_resample_f32": [_P, _L, _D, _P, _I, _I, _P, _L, _P],
     "sos_resample_batch_f32": [_P, _P, _P, _I, _D, _P, _I, _I, _P, _P],
     "sos_resample_time_segments": [_D, _L, _P, _P, _P, _I],
+    "sos_band_gain_batch_f32": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "sos_resample_merge_batch_f32": [_P, _P, _P, _P, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P],
     "sos_time_stack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
     "sos_spatial_mean": [_P, _L, _L, _I, _I, _I, _P, _L, _I, _I, _P],
     "sos_metric_totals": [_P, _P, _L, _P, _P],

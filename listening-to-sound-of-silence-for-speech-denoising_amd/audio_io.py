@@ -11,6 +11,8 @@
 and, beyond librosa's names, the channel-preserving pair under recordings.py (csrc/pcm_io.hip):
   load_channels_batch_device(paths, sr=None) / decode_planes_batch_device(arrs, kinds): every channel as an f32 plane
   encode_batch_device(planes, fmt, frames=None) + wave_container(...): planes -> s16 / s24 / s32 / u8 / f32 WAVE data
+  band_gains_batch_device(lows_in, lows_out) / resample_merge_batch_device(natives, lows_in, lows_out, orig_sr, target_sr,
+      gains=None): what a chain at a lower rate never saw of a signal, put back at its own rate (csrc/band_merge.hip)
 
 The RIFF container is parsed here on the host (bytes -> header fields + one frombuffer view, no per-sample
 Python); sample conversion, channel mix-down and the band-limited resampler are HIP kernels
@@ -26,6 +28,7 @@ from . import _lib as L
 from . import ragged
 from . import session
 from . import tools
+from . import transform
 
 # resampy 0.2.2 `kaiser_best`: 64 zero crossings, 2**9 table points per crossing, Kaiser beta, roll-off
 KAISER_BEST = dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596)
@@ -547,6 +550,126 @@ def encode_batch_device(planes, fmt, frames=None):
         L.check(h.sos_pcm_encode_batch(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, code,
                                        L.ptr(data[e0 * width:]), L.ptr(clipped[c0:]), L.stream_ptr()), "sos_pcm_encode_batch")
     return data[:int(offsets[-1])], offsets, clipped
+
+
+# ------------------------------------------------------------------------------------ the band above SR / 2 (csrc/band_merge.hip)
+def _flat_f32(tensors, device):
+    """_back_to_back of 1-D f32 tensors of which some (or all) may be empty: never a null pointer."""
+    full = [t for t in tensors if t.numel()]
+    return _back_to_back(full) if full else torch.zeros(1, dtype=torch.float32, device=device)
+
+
+def _check_low_pairs(who, lows_in, lows_out, min_out):
+    if len(lows_in) != len(lows_out):
+        raise ValueError("%s: one output per input of the networks (%d inputs, %d outputs)" % (who, len(lows_in), len(lows_out)))
+    for i, (a, b) in enumerate(zip(lows_in, lows_out)):
+        for t in (a, b):
+            if not torch.is_tensor(t) or t.dim() != 1 or t.dtype != torch.float32:
+                raise ValueError("%s: clip %d: expects 1-D float32 tensors" % (who, i))
+        if a.numel() < 1 or not min_out <= b.numel() <= a.numel():
+            raise ValueError("%s: clip %d: the networks' output has %d samples for an input of %d (%d .. the input's length, and "
+                             "an input of at least 1)" % (who, i, b.numel(), a.numel(), min_out))
+
+
+def band_gains_batch_device(lows_in, lows_out, hop=transform.HOP_LENGTH, smooth_frames=2):
+    """How much of each hop frame the networks kept: lows_in[i] = a, the m_i samples they were given, lows_out[i] = b, the m'_i <=
+    m_i samples they returned (1-D f32 GPU tensors) -> one f32 GPU tensor s of J_i = ceil(m_i / hop) gains per clip, views into
+    one buffer, from ONE sos_band_gain_batch_f32 launch (per 65535 clips).  Frame j covers samples [j hop, (j + 1) hop) cut at m;
+    r[j] = 1 if sum a^2 == 0 else min(1, sqrt(sum b^2 / sum a^2)) in float64, b reading zero from m' on (so the last partial frame
+    has r = 0); s[j] = the float64 mean of r[j - smooth_frames .. j + smooth_frames] cut at the clip's ends, stored as f32.
+    Float64 restatement: tests/band_reference.py.
+    ValueError before any launch: lists of different lengths, tensors that are not 1-D float32, m < 1, m' > m, hop < 1,
+    smooth_frames outside 0 .. 16.  RuntimeError for CPU tensors: there is no fallback."""
+    lows_in, lows_out, hop = list(lows_in), list(lows_out), int(hop)
+    _check_low_pairs("band_gains_batch_device", lows_in, lows_out, 0)
+    if hop < 1 or not 0 <= int(smooth_frames) <= 16:
+        raise ValueError("band_gains_batch_device: hop is at least 1 (got %d) and smooth_frames within 0 .. 16 (got %s)"
+                         % (hop, smooth_frames))
+    L.require_cuda(*lows_in, *lows_out)
+    if not lows_in:
+        return []
+    device = lows_in[0].device
+    m = np.asarray([a.numel() for a in lows_in], dtype=np.int64)
+    mp = np.asarray([b.numel() for b in lows_out], dtype=np.int64)
+    J = -(-m // hop)
+    a_off, b_off, g_off = ragged.offsets(m), ragged.offsets(mp), ragged.offsets(J)
+    a, b = _flat_f32(lows_in, device), _flat_f32(lows_out, device)
+    gains = torch.empty(int(J.sum()), dtype=torch.float32, device=device)
+    h = L.lib()
+    for c0 in range(0, len(lows_in), ragged.MAX_CLIPS):
+        c1 = min(c0 + ragged.MAX_CLIPS, len(lows_in))
+        a0, b0, g0 = int(a_off[c0]), int(b_off[c0]), int(g_off[c0])
+        tab = np.ascontiguousarray(np.stack([a_off[c0:c1] - a0, m[c0:c1], b_off[c0:c1] - b0, mp[c0:c1], g_off[c0:c1] - g0, J[c0:c1]]),
+                                   dtype=np.int64)
+        tab_dev = torch.from_numpy(tab).to(device)
+        L.check(h.sos_band_gain_batch_f32(L.ptr(a[a0:]), L.ptr(b[min(b0, b.numel() - 1):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p),
+                                          c1 - c0, hop, int(smooth_frames), L.ptr(gains[g0:]), L.stream_ptr()), "sos_band_gain_batch_f32")
+    return ragged.split(gains, J)
+
+
+def resample_merge_batch_device(natives, lows_in, lows_out, orig_sr, target_sr, gains=None, res_type="kaiser_best", hop=transform.HOP_LENGTH):
+    """Puts back what a chain at the lower rate orig_sr never saw of signals at target_sr > orig_sr.  Per clip: natives[i] = x
+    (n frames at target_sr), lows_in[i] = a = x resampled to orig_sr (m = ceil(n * orig_sr / target_sr) samples: resample_batch_
+    device's), lows_out[i] = b, the chain's output for a (1 <= m' <= m samples), all 1-D f32 GPU tensors; U = resample_device
+    from orig_sr to target_sr (zero from (int64)(len * ratio) on).  ->
+        out[t] = fmaf(g[t], x[t] - U(a)[t], U(b)[t])        0 <= t < n
+    one (n,) f32 GPU tensor per clip, back to back in one buffer (planes_of yields views), from ONE
+    sos_resample_merge_batch_f32 launch (per 65535 clips) that evaluates both resamplings with resample_device's bits.
+    gains=None: g = 1 -- the band above orig_sr / 2 passes untouched; otherwise gains[i] = band_gains_batch_device's s for the
+    clip (ceil(m / hop) values), interpolated linearly between frame centres.  Float64 restatement: tests/band_reference.py.
+    ValueError before any launch: lists of different lengths, tensors that are not 1-D float32, m' > m or < 1, target_sr <=
+    orig_sr, a clip whose a does not cover its n frames, a gains tensor of the wrong length, an unsupported res_type.
+    RuntimeError for CPU tensors: there is no fallback."""
+    natives, lows_in, lows_out, hop = list(natives), list(lows_in), list(lows_out), int(hop)
+    who = "resample_merge_batch_device"
+    if not target_sr > orig_sr:
+        raise ValueError("%s: target_sr (%s) must exceed orig_sr (%s): there is no band to put back otherwise" % (who, target_sr, orig_sr))
+    if res_type != "kaiser_best":
+        raise ValueError("res_type %r is not supported (the reference uses librosa's default 'kaiser_best')" % (res_type,))
+    if len(natives) != len(lows_in) or (gains is not None and len(gains) != len(natives)) or hop < 1:
+        raise ValueError("%s: one native clip%s per low-rate clip (%d natives, %d low-rate inputs%s) and hop at least 1"
+                         % (who, " and one gains tensor" if gains is not None else "", len(natives), len(lows_in),
+                            ", %d gains" % len(gains) if gains is not None else ""))
+    _check_low_pairs(who, lows_in, lows_out, 1)
+    ratio = float(target_sr) / orig_sr
+    gains = None if gains is None else list(gains)
+    for i, x in enumerate(natives):
+        if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.float32:
+            raise ValueError("%s: clip %d: expects 1-D float32 tensors" % (who, i))
+        m = lows_in[i].numel()
+        if x.numel() < 1 or int(m * ratio) < x.numel():
+            raise ValueError("%s: clip %d: %d frames at %s Hz are not covered by %d samples at %s Hz (they give %d)"
+                             % (who, i, x.numel(), target_sr, m, orig_sr, int(m * ratio)))
+        if gains is not None:
+            g = gains[i]
+            if not torch.is_tensor(g) or g.dim() != 1 or g.dtype != torch.float32 or g.numel() != -(-m // hop):
+                raise ValueError("%s: clip %d: gains must be a 1-D float32 tensor of ceil(%d / %d) = %d values"
+                                 % (who, i, m, hop, -(-m // hop)))
+    L.require_cuda(*natives, *lows_in, *lows_out, *(gains or []))
+    if not natives:
+        return []
+    device = natives[0].device
+    win, num_table = _filter_on(device, ratio, res_type)
+    n = np.asarray([x.numel() for x in natives], dtype=np.int64)
+    m = np.asarray([a.numel() for a in lows_in], dtype=np.int64)
+    mp = np.asarray([b.numel() for b in lows_out], dtype=np.int64)
+    J = -(-m // hop)
+    x_off, a_off, b_off, g_off = ragged.offsets(n), ragged.offsets(m), ragged.offsets(mp), ragged.offsets(J)
+    x, a, b = _back_to_back(natives), _back_to_back(lows_in), _back_to_back(lows_out)
+    s = _back_to_back(gains) if gains is not None else None
+    out = torch.empty(int(n.sum()), dtype=torch.float32, device=device)
+    h = L.lib()
+    for c0 in range(0, len(natives), ragged.MAX_CLIPS):
+        c1 = min(c0 + ragged.MAX_CLIPS, len(natives))
+        x0, a0, b0, g0 = int(x_off[c0]), int(a_off[c0]), int(b_off[c0]), int(g_off[c0])
+        tiles = -(-n[c0:c1] // L.RESAMPLE_CHUNK)
+        tab = np.ascontiguousarray(np.stack([x_off[c0:c1] - x0, n[c0:c1], a_off[c0:c1] - a0, m[c0:c1], b_off[c0:c1] - b0, mp[c0:c1],
+                                             g_off[c0:c1] - g0, J[c0:c1], ragged.offsets(tiles)]), dtype=np.int64)
+        tab_dev = torch.from_numpy(tab).to(device)
+        L.check(h.sos_resample_merge_batch_f32(L.ptr(x[x0:]), L.ptr(a[a0:]), L.ptr(b[b0:]), L.ptr(s[g0:]) if s is not None else None,
+                                               L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, ratio, L.ptr(win), win.numel(),
+                                               num_table, hop, L.ptr(out[x0:]), L.stream_ptr()), "sos_resample_merge_batch_f32")
+    return ragged.split(out, n)
 
 
 def load_batch(paths, sr=22050, mono=True, offset=0.0, duration=None, dtype=np.float32, res_type="kaiser_best"):

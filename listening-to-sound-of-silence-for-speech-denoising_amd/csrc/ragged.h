@@ -1,5 +1,5 @@
 // ragged.h -- what every ragged-batch entry point shares (metrics_batch.hip, stoi.hip, sdr.hip, ragged_io.hip,
-// silence_label.hip, ragged_mix.hip, wave_io.hip, ragged_window.hip): the clip-count check, the clip row, the bounds rule on
+// silence_label.hip, ragged_mix.hip, wave_io.hip, ragged_window.hip, band_merge.hip): the clip-count check, the clip row, the bounds rule on
 // both sides of the launch, the host's sums over a table, the workspace layout arithmetic, the clamped grid, the 256-thread LDS
 // reductions and the four-sample accesses of clips that start on any sample.
 // A batch is clips back to back in one buffer plus a table of where each lies, in two copies: the host sizes every array

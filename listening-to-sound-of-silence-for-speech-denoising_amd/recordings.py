@@ -4,7 +4,8 @@ channel is denoised on its own; link_channels='any' / 'mean' silences the channe
 between them (windows.denoise_long(stitch_bits=True, link=): one sos_window_frames_link_f32 launch for all files of a group), so
 that the noise floors of a stereo pair drop in and out together.  The decode, the two resamplings, the windows
 and the encode each run in launches shared by all files and channels of a group (csrc/pcm_io.hip, csrc/wave_io.hip,
-csrc/ragged_window.hip)."""
+csrc/ragged_window.hip).  The networks run at 14 kHz: by default a file of a higher rate comes back band-limited to 7 kHz;
+high_band='keep' / 'follow' merge the band above 7 kHz of the source back in (csrc/band_merge.hip)."""
 import os
 
 import numpy as np
@@ -28,8 +29,15 @@ def _model_samples(frames, rate):
     return int(frames) if rate == SR else int(np.ceil(int(frames) * (float(SR) / rate)))
 
 
-def _check_files(paths, out_dir, sample_format, suffix, link_channels=None):
+HIGH_BAND_MODES = ("drop", "keep", "follow")
+
+
+def _check_files(paths, out_dir, sample_format, suffix, link_channels=None, high_band="drop", smooth_frames=2):
     """Everything that can be refused from the arguments and the chunk headers alone: -> (infos, formats, out_paths)."""
+    if high_band not in HIGH_BAND_MODES:
+        raise ValueError("denoise_recordings: unknown high_band %r (one of %s)" % (high_band, ", ".join(HIGH_BAND_MODES)))
+    if isinstance(smooth_frames, bool) or not isinstance(smooth_frames, (int, np.integer)) or not 0 <= smooth_frames <= 16:
+        raise ValueError("denoise_recordings: smooth_frames is a whole number of frames within 0 .. 16, got %r" % (smooth_frames,))
     if link_channels is not None and link_channels not in tools.LINK_MODES:
         raise ValueError("denoise_recordings: unknown link_channels %r (None, or one of %s)"
                          % (link_channels, ", ".join(sorted(tools.LINK_MODES))))
@@ -67,9 +75,40 @@ def _resample_back(clips, rates):
     return clips
 
 
+def _to_model_rate(natives, rates):
+    """Every native channel at the networks' rate, as load_channels_batch_device(sr=SR) brings it there: one
+    resample_batch_device launch per rate other than SR, the same bits."""
+    by_rate = {}
+    for k, r in enumerate(rates):
+        if r != SR:
+            by_rate.setdefault(r, []).append(k)
+    clips = list(natives)
+    for r, idx in by_rate.items():
+        for k, y in zip(idx, audio_io.resample_batch_device([natives[k] for k in idx], r, SR)):
+            clips[k] = y
+    return clips
+
+
+def _merge_back(natives, lows_in, lows_out, rates, high_band, smooth_frames):
+    """Every channel whose file's rate exceeds SR back at that rate WITH the band above SR / 2 (audio_io.resample_merge_batch_
+    device): per rate one gains launch ('follow' only) and one merge launch.  The other channels pass as they are."""
+    by_rate = {}
+    for k, r in enumerate(rates):
+        if r > SR:
+            by_rate.setdefault(r, []).append(k)
+    outs = list(lows_out)
+    for r, idx in by_rate.items():
+        a, b = [lows_in[k] for k in idx], [lows_out[k] for k in idx]
+        gains = audio_io.band_gains_batch_device(a, b, transform.HOP_LENGTH, smooth_frames) if high_band == "follow" else None
+        for k, y in zip(idx, audio_io.resample_merge_batch_device([natives[k] for k in idx], a, b, SR, r, gains)):
+            outs[k] = y
+    return outs
+
+
 @torch.no_grad()
 def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, context_seconds=2.0, max_batch=256,
-                       max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None):
+                       max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None,
+                       high_band="drop", smooth_frames=2):
     """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
     channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32; a float64 source is written as float32);
     sample_format= ('s16', 's24', 's32', 'u8', 'f32') forces one format for all files.
@@ -86,13 +125,25 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     'any' / 'mean': the channels of a file share ONE decision stream, the group's denoise_long call runs with stitch_bits=True,
     link=<the file of each channel>, link_mode=link_channels ('any': a frame is speech if any channel has speech, so noise is
     only estimated where every channel is silent; 'mean': the mean logit decides).  A mono file is a group of one.
+    high_band: the networks run at 14 kHz, so what a 44.1 / 48 kHz source holds above 7 kHz never reaches them.  'drop' (the
+    default) leaves it out: the written file has the source's rate and is BAND-LIMITED TO 7 kHz.  'keep' and 'follow' put it back,
+    per channel of a file whose rate exceeds 14 kHz, with x the native plane, a = x at 14 kHz, b = the networks' output and U
+    the resampling back: out[t] = fmaf(g[t], x[t] - U(a)[t], U(b)[t]) (csrc/band_merge.hip; one
+    audio_io.resample_merge_batch_device launch per native rate instead of the resample launch back).  'keep': g = 1, the band
+    above 7 kHz passes untouched, its noise included.  'follow': g follows what the networks did to the low band -- per hop
+    frame min(1, sqrt(energy of b / energy of a)), averaged over 2 * smooth_frames + 1 frames (0 .. 16; 2 is about 56 ms) and
+    interpolated between frame centres (audio_io.band_gains_batch_device, one more launch per rate) -- so hiss above 7 kHz drops
+    in the silent intervals too; it assumes the high band's noise comes and goes with the low band's.  The last < hop samples
+    at 14 kHz have no output of the networks (zero-filled today): 'follow' fades the high band out there, 'keep' leaves it in.
+    Files at 14 kHz or below have no such band and are written with the same bytes under every mode.
     -> one dict per file: path, out_path, channels, rate, frames, format, clipped (samples that saturated or were NaN, all
     channels), windows (denoise_long windows, all channels).
     ValueError before any launch of the call, naming the file: fewer than MIN_FRAMES STFT frames at 14 kHz, an unsupported
-    format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format or link_channels;
+    format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format, link_channels or
+    high_band, smooth_frames outside 0 .. 16;
     window_plan's argument rules; a group with more than 65535 windows."""
     paths = [os.fspath(p) for p in paths]
-    infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix, link_channels)
+    infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix, link_channels, high_band, smooth_frames)
     core, context = windows._hops(round(window_seconds * SR)), windows._hops(round(context_seconds * SR))
     groups = ragged.byte_groups([4 * i["frames"] * i["channels"] for i in infos], max_bytes)
     plans = []                                          # host only: refuses bad window arguments and a group of too many windows
@@ -105,13 +156,23 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     os.makedirs(out_dir, exist_ok=True)
     results = []
     for group, plan in zip(groups, plans):
-        ys, _, _ = audio_io.load_channels_batch_device([paths[f] for f in group], sr=SR)
+        merge = high_band != "drop" and any(infos[f]["rate"] > SR for f in group)
+        if merge:                                       # the native planes stay: the merge reads them
+            ys, _, _ = audio_io.load_channels_batch_device([paths[f] for f in group], sr=None)
+            natives = [y[c] for y in ys for c in range(y.shape[0])]
+            clips = _to_model_rate(natives, [infos[f]["rate"] for f, y in zip(group, ys) for _ in range(y.shape[0])])
+        else:
+            ys, _, _ = audio_io.load_channels_batch_device([paths[f] for f in group], sr=SR)
+            clips = [y[c] for y in ys for c in range(y.shape[0])]
         owner = [f for f, y in zip(group, ys) for _ in range(y.shape[0])]                           # the file of each channel
-        clips = [y[c] for y in ys for c in range(y.shape[0])]
         linked = dict(stitch_bits=True, link=owner, link_mode=link_channels) if link_channels is not None else {}
         outs = windows.denoise_long(detector, denoiser, clips, SR, FPS, window_seconds, context_seconds, max_batch, max_columns,
                                     **linked)
-        outs = _resample_back(outs, [infos[f]["rate"] for f in owner])
+        rates = [infos[f]["rate"] for f in owner]
+        if merge:
+            outs = _merge_back(natives, clips, outs, rates, high_band, smooth_frames)
+            rates = [min(r, SR) for r in rates]         # what is left for _resample_back: the rates below SR
+        outs = _resample_back(outs, rates)
         per_file, k = {}, 0
         for f, y in zip(group, ys):
             per_file[f] = audio_io.planes_of(outs[k:k + y.shape[0]])

@@ -96,6 +96,8 @@ class StreamDenoiser:
     -- a live stream and a file of the same audio give the same samples (tests/test_gpu_stream_resample.py).  close() drains in
     order: the input resampler, the last window, the output resampler; drop() forgets all three.  Each side adds R + 1 samples
     of latency at its input rate (R = 219 at 48 -> 14 kHz, 64 at 14 -> 48 kHz: 4.6 ms each) and two launches per call.
+    What comes back at out_sr > sr is BAND-LIMITED to sr / 2 = 7 kHz: the band above it never reaches the networks and is not
+    put back here (recordings.denoise_recordings(high_band='keep' / 'follow') does that for files).
     Not here: one decision stream per recording (denoise_long's stitch_bits needs frames of the future), given decisions
     (`bits=`), the four hand-off signals (`signals=`), and a res_type other than kaiser_best.
     ValueError before any launch: window_plan's argument rules, slots outside 1 .. 65535, a slot outside the slots (push) or

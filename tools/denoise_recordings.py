@@ -2,7 +2,10 @@
 count, channels, rate and sample format.
 
   python tools/denoise_recordings.py DETECTOR.pth DENOISER.pth OUT_DIR in1.wav in2.wav ... [--sample-format s16] [--suffix _dn]
-                                     [--link-channels any]
+                                     [--link-channels any] [--high-band keep|follow] [--smooth-frames 2]
+
+The networks run at 14 kHz: by default (--high-band drop) a 44.1 / 48 kHz file comes back band-limited to 7 kHz.  --high-band keep
+passes the source's band above 7 kHz through untouched; --high-band follow gives it the attenuation the denoiser applied below.
 
 The checkpoints are the reference's (`{clock, model_state_dict, ...}` as the agents save them) or bare state dicts."""
 import argparse
@@ -40,13 +43,18 @@ def main():
     ap.add_argument("--link-channels", choices=["any", "mean"], default=None,
                     help="the channels of a file share one stream of silent-interval decisions: a frame is speech if ANY channel has "
                          "speech, or if the MEAN logit says so (default: every channel decides on its own)")
+    ap.add_argument("--high-band", choices=list(recordings.HIGH_BAND_MODES), default="drop",
+                    help="the band above 7 kHz of files above 14 kHz: drop it (default: the output is band-limited to 7 kHz), keep it "
+                         "untouched, or let it follow the attenuation the denoiser applied to the low band")
+    ap.add_argument("--smooth-frames", type=int, default=2, help="--high-band follow: gains are averaged over 2 K + 1 hop frames (0 .. 16)")
     ap.add_argument("--precision", default="mixed", choices=["bf16", "bf16x3", "fp16", "mixed"])
     args = ap.parse_args()
     det, jm = _load(dnet.get_network(), args.detector), _load(jnet.get_network(MyConfig()), args.denoiser)
     sos_amd.set_precision(args.precision)
     for r in recordings.denoise_recordings(det, jm, args.files, args.out_dir, args.window_seconds, args.context_seconds, args.max_batch,
                                            args.max_columns, sample_format=args.sample_format, suffix=args.suffix,
-                                           link_channels=args.link_channels):
+                                           link_channels=args.link_channels, high_band=args.high_band,
+                                           smooth_frames=args.smooth_frames):
         print("%s -> %s: %d x %d frames at %d Hz, %s, %d windows, %d samples clipped"
               % (r["path"], r["out_path"], r["channels"], r["frames"], r["rate"], r["format"], r["windows"], r["clipped"]))
 

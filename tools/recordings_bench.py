@@ -17,6 +17,13 @@ in a temporary directory, in 'mixed' precision:
      loop, one concatenation and one threshold launch -- on the same random logit rows of the same files' plan
      (--link-window-seconds long windows), wall time per call from an idle device to an idle device, --link-reps calls each,
      alternating.  Both forms are checked to give the same bits before they are timed.
+  5. with --high-band keep|follow: (a) denoise_recordings(high_band=) against high_band='drop' on the same files, both warmed,
+     alternating, in the same run of the program: what putting the band above 7 kHz back costs per call; (b) the ONE
+     sos_resample_merge_batch_f32 launch (with gains under 'follow') against the composition it replaces -- two
+     resample_batch_device launches and two torch elementwise ops -- on the same channels at 14 kHz (native planes of (int)(m * ratio)
+     frames, so that the composition needs no per-clip fitting), --band-reps alternating calls each, wall time from an idle device to an
+     idle device; both forms are checked to give the same bits under 'keep' before they are timed; (c) the merge and the gains
+     launch from device events against Tensor.copy_ moving the bytes they read and write.
 A measurement: nothing is asserted."""
 import argparse
 import os
@@ -30,7 +37,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sos_amd  # noqa: E402
 from oracle import nets as onet  # noqa: E402
-from sos_amd import audio_io, pipeline, ragged, recordings, tools, windows  # noqa: E402
+from sos_amd import audio_io, pipeline, ragged, recordings, tools, transform, windows  # noqa: E402
 from sos_amd.common import MyConfig  # noqa: E402
 from sos_amd.denoiser import networks as jnet  # noqa: E402
 from sos_amd.detector import networks as dnet  # noqa: E402
@@ -195,6 +202,68 @@ def link_launch(args, paths):
           f"   ratio {t2 / t1:.2f}")
 
 
+def band(args, paths):
+    """5 (b), (c): the merge launch against two resamplings plus two elementwise ops, and both kernels against a copy."""
+    ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
+    lows = audio_io.resample_batch_device([y[c] for y in ys for c in range(y.shape[0])], RATE, pipeline.SR)
+    ratio = float(RATE) / pipeline.SR
+    a = [t.clone() for t in lows]
+    b = [0.5 * t for t in a]                                                     # m' = m: both resamplings have n = (int)(m * ratio) samples
+    back = audio_io.resample_batch_device(a, pipeline.SR, RATE, fix=False)
+    x_flat = audio_io._back_to_back(back) + 0.01 * torch.randn(sum(t.numel() for t in back), device="cuda")   # native planes of that length
+    xs = ragged.split(x_flat, [t.numel() for t in back])
+    gains = audio_io.band_gains_batch_device(a, b) if args.high_band == "follow" else None
+
+    def one():
+        return audio_io.resample_merge_batch_device(xs, a, b, pipeline.SR, RATE, gains)
+
+    def pieces():
+        ra = audio_io.resample_batch_device(a, pipeline.SR, RATE, fix=False)
+        rb = audio_io.resample_batch_device(b, pipeline.SR, RATE, fix=False)
+        return torch.sub(x_flat, audio_io._back_to_back(ra)).add_(audio_io._back_to_back(rb))
+
+    same = torch.equal(torch.cat(audio_io.resample_merge_batch_device(xs, a, b, pipeline.SR, RATE)), pieces())
+    one(), pieces()
+    runs = dict(one=[], pieces=[])
+    for _ in range(args.band_reps):
+        runs["one"].append(once(one)[0])
+        runs["pieces"].append(once(pieces)[0])
+    t1, t2 = float(np.median(runs["one"])), float(np.median(runs["pieces"]))
+    n, m = sum(t.numel() for t in xs), sum(t.numel() for t in a)
+    print(f"merge launch: {len(xs)} channels, {n} native frames at {RATE} Hz, {m} samples at {pipeline.SR} Hz, mode {args.high_band}, "
+          f"{args.band_reps} alternating calls each (median wall time, idle device to idle device); keep gives the bits of the "
+          f"composition: {same}")
+    print(f"  one sos_resample_merge_batch_f32 launch       : {t1 * 1e6:8.1f} us (min {min(runs['one']) * 1e6:.1f}, max {max(runs['one']) * 1e6:.1f})")
+    print(f"  two resample launches + sub + add             : {t2 * 1e6:8.1f} us (min {min(runs['pieces']) * 1e6:.1f}, max {max(runs['pieces']) * 1e6:.1f})"
+          f"   ratio {t2 / t1:.2f}")
+    # (c) the entry points themselves, tables already on the device, from device events
+    L = audio_io.L
+    nn, mm = np.asarray([t.numel() for t in xs], dtype=np.int64), np.asarray([t.numel() for t in a], dtype=np.int64)
+    J = -(-mm // transform.HOP_LENGTH)
+    off = ragged.offsets
+    tab = np.ascontiguousarray(np.stack([off(nn), nn, off(mm), mm, off(mm), mm, off(J), J, off(-(-nn // L.RESAMPLE_CHUNK))]), dtype=np.int64)
+    gtab = np.ascontiguousarray(np.stack([off(mm), mm, off(mm), mm, off(J), J]), dtype=np.int64)
+    tab_dev, gtab_dev = torch.from_numpy(tab).cuda(), torch.from_numpy(gtab).cuda()
+    a_flat, b_flat = torch.cat(a), torch.cat(b)
+    s_flat = torch.empty(int(J.sum()), dtype=torch.float32, device="cuda")
+    out = torch.empty_like(x_flat)
+    win, num_table = audio_io._filter_on(x_flat.device, ratio, "kaiser_best")
+    go_gain = lambda: L.check(L.lib().sos_band_gain_batch_f32(L.ptr(a_flat), L.ptr(b_flat), L.ptr(gtab_dev), gtab.ctypes.data_as(L.C.c_void_p),   # noqa: E731
+                                                              len(xs), transform.HOP_LENGTH, 2, L.ptr(s_flat), L.stream_ptr()))
+    go_merge = lambda s: L.check(L.lib().sos_resample_merge_batch_f32(L.ptr(x_flat), L.ptr(a_flat), L.ptr(b_flat), L.ptr(s), L.ptr(tab_dev),      # noqa: E731
+                                                                      tab.ctypes.data_as(L.C.c_void_p), len(xs), ratio, L.ptr(win), win.numel(),
+                                                                      num_table, transform.HOP_LENGTH, L.ptr(out), L.stream_ptr()))
+    rows = [("gains", 4 * (2 * m + int(J.sum())), device_ms(go_gain, args.kernel_reps)),
+            ("merge, g = 1", 4 * (2 * n + 2 * m), device_ms(lambda: go_merge(None), args.kernel_reps)),
+            ("merge, gains", 4 * (2 * n + 2 * m + int(J.sum())), device_ms(lambda: go_merge(s_flat), args.kernel_reps))]
+    for name, nbytes, ms in rows:
+        src = torch.empty(nbytes // 8, dtype=torch.float32, device="cuda").normal_()
+        dst = torch.empty_like(src)
+        copy_ms = device_ms(lambda: dst.copy_(src), args.kernel_reps)
+        print(f"  {name:13s}: {ms * 1e3:8.1f} us  {nbytes / ms / 1e6:7.1f} GB/s    Tensor.copy_ of the same bytes: {copy_ms * 1e3:8.1f} us  "
+              f"{nbytes / copy_ms / 1e6:7.1f} GB/s    ratio {copy_ms / ms:.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=64)
@@ -208,9 +277,37 @@ def main():
     ap.add_argument("--link-channels", choices=["any", "mean"], default=None, help="measure the shared decision stream (4.) and nothing else")
     ap.add_argument("--link-window-seconds", type=float, default=2.0, help="4 (b): the windows of the link-launch comparison")
     ap.add_argument("--link-reps", type=int, default=50)
+    ap.add_argument("--high-band", choices=["keep", "follow"], default=None, help="measure the merge of the band above 7 kHz (5.) and nothing else")
+    ap.add_argument("--band-reps", type=int, default=30)
     args = ap.parse_args()
     print(torch.cuda.get_device_name(0))
     _count_downloads()
+    if args.high_band:
+        det = dnet.get_network()
+        det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+        jm = jnet.get_network(MyConfig())
+        jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+        det, jm = det.cuda().eval(), jm.cuda().eval()
+        sos_amd.set_precision("mixed")
+        with tempfile.TemporaryDirectory() as tmp:
+            paths, secs = make_files(tmp, args.files, args.seed)
+            forms = dict(drop=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "drop"), max_batch=args.max_batch),
+                         band=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "band"), max_batch=args.max_batch,
+                                                                    high_band=args.high_band))
+            for fn in forms.values():                                                     # warm-up of both forms
+                fn()
+            runs = {k: [] for k in forms}
+            for _ in range(args.repeats):                                                 # the forms alternate
+                for k, fn in forms.items():
+                    runs[k].append(once(fn))
+            print(f"{args.files} stereo s16 files at {RATE} Hz, {secs:.0f} s of audio x 2 channels, 'mixed' precision, {args.repeats} "
+                  "alternating repeats (median, min, max)")
+            d = report("high_band='drop'", args.files, runs["drop"])
+            k = report("high_band=%r" % args.high_band, args.files, runs["band"])
+            print(f"  {args.high_band} / drop = {k / d:.3f}")
+            band(args, paths)
+        sos_amd.set_precision("bf16")
+        return
     if args.link_channels:
         det = dnet.get_network()
         det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
