@@ -916,6 +916,52 @@ int sos_stream_resample_ready(double ratio, int nwin, int num_table, int64_t n_r
 int sos_stream_resample_f32(const float* ring, int64_t slots, int64_t cap, const int64_t* table, const int64_t* table_host, int nrows,
                             double ratio, const float* win, int nwin, int num_table, float* out, int64_t total, sos_stream_t stream);
 
+/* ---- the band above the networks' half rate for LIVE audio (csrc/stream_band.hip; sos_amd.audio_io.StreamBandMerger; float64 /
+ * integer restatement of the rule: tests/stream_band_reference.py).  The rule of sos_resample_merge_batch_f32 for streams that
+ * arrive in chunks, with its bits: x = the native stream, a = x at the low rate, b = the networks' output, U = the resampling
+ * back at ratio = native rate / low rate > 1 (an upsampling: scale = 1, index_step = num_table, R = nwin / num_table),
+ *     out[t] = fmaf(g[t], x[t] - U(a)[t], U(b)[t]).
+ * State on the device: ring f32 [3 slots][cap] as sos_stream_push_f32 writes it -- row slot holds x, row slots + slot holds a,
+ * row 2 slots + slot holds b of the stream of `slot`, sample p at [p % cap] -- and rring f64 [slots][rcap], frame j of r at
+ * [j % rcap].  smooth = K, the frames of smoothing on each side (0 .. 16); smooth < 0: no gains, g = 1 ('keep').
+ * The rule.  With n_x native samples and m_b samples of b received (a is never behind b) output t is final -- it has the bits
+ * it has for any longer stream -- once (1) n(t) + 1 + R <= m_b: neither right wing is cut, sos_stream_resample_ready asked
+ * about m_b; (2) with gains, F(t) < m_b / hop - K, where p = (t + 0.5) / (ratio hop) - 0.5 in f64 and F(t) = 0 for p <= 0,
+ * floor(p) + 1 otherwise, is the last frame of s that g[t] reads: r[j] is final once (j + 1) hop <= m_b, s[j] once r[j + K] is,
+ * and then neither the clamp at J - 1 nor the cut of the mean at the clip's end can reach it; (3) t < n_x.
+ * sos_stream_band_ready (host only, no HIP call): *t_ready = T, the number of final outputs (they are a prefix); what later
+ *   outputs still read: x from *first_x = T, a and b from *first_a = *first_b = max(n(T) - (R - 1), 0), with gains also no
+ *   later than hop (m_b / hop), the first sample of a frame without r; r from *first_r = max(F(T) - 1 - K, 0).  All from the
+ *   expressions the kernels evaluate.  SOS_EINVAL: ratio <= 1, a wing below one sample, hop outside 1 .. 2^20, smooth > 16,
+ *   counts negative or above 2^52, null pointers; SOS_ENOSPC as sos_stream_resample_ready.
+ * sos_stream_band_ratio_f64: ONE launch whatever nrows is; table int64 [nrows][5], a row is {slot, j_lo, j_hi, m_a, m_b}:
+ *   r[j] for j_lo <= j < j_hi into the slot's ring of frames, frame j covering the samples [j hop, (j + 1) hop) cut at m_a, b
+ *   reading zero from m_b on: sos_band_gain_batch_f32's r, bit for bit.  While a stream runs j_hi = m_b / hop; at its end m_a =
+ *   m, m_b = m' and j_hi = J = ceil(m / hop), which gives the last partial frame the file path's r.
+ * sos_stream_band_merge_f32: ONE launch whatever nrows is; table int64 [nrows][10], a row is
+ *     {slot, t_lo, t_hi, n_x, n_a, n_b, v_b, J, r_hi, output offset}
+ *   and writes the outputs t_lo <= t < t_hi of the slot's stream to out[output offset ..] (out holds `total` floats), computed as
+ *   of n_x native samples, signals a of n_a and b of n_b samples (U(b) zero from output v_b on), r_hi frames of r written so
+ *   far, and J frames of s -- J = -1 while the stream is open: no end is known, none clamps.  While a stream runs t_hi <= T,
+ *   v_b = t_hi; at its end n_a = m, n_b = m', v_b = (int64)(m' * ratio), J = r_hi = ceil(m / hop), t_hi = n.  s is formed per
+ *   output from r (the two means, then the interpolation) with sos_band_gain_batch_f32's and sos_resample_merge_batch_f32's
+ *   expressions.  The concatenated outputs of a stream are bit for bit what sos_resample_merge_batch_f32 writes for the whole
+ *   signals, whatever the chunking, the slot, the other rows and the table's order.
+ * SOS_EINVAL before any launch (sos_last_error() names the row): null pointers (rring may be null without gains), rows outside
+ * 1 .. 65535, slots outside 1 .. 21845, cap or rcap < 1, a slot outside the slots or twice in one table, ranges that are none,
+ * n_b > n_a, v_b above (int64)(n_b * ratio), output offset + (t_hi - t_lo) > total, a row that reads x at or past n_x or more
+ * than `cap` before it, a or b at or past their counts or more than `cap` before n_a, frames of r at or past r_hi or more than
+ * `rcap` before it, frames of a beyond ceil(m_a / hop), with an end J other than ceil(n_a / hop) or than r_hi, the filter
+ * refusals above, (nwin + 1) * 4 bytes > 160 KB.  The kernels follow the DEVICE table and skip a row that fails the same
+ * bounds; every ring index is modular. */
+int sos_stream_band_ready(double ratio, int nwin, int num_table, int hop, int smooth, int64_t m_b, int64_t n_x, int64_t* t_ready,
+                          int64_t* first_x, int64_t* first_a, int64_t* first_b, int64_t* first_r);
+int sos_stream_band_ratio_f64(const float* ring, int64_t slots, int64_t cap, const int64_t* table, const int64_t* table_host,
+                              int nrows, int hop, double* rring, int64_t rcap, sos_stream_t stream);
+int sos_stream_band_merge_f32(const float* ring, int64_t slots, int64_t cap, const double* rring, int64_t rcap, const int64_t* table,
+                              const int64_t* table_host, int nrows, double ratio, const float* win, int nwin, int num_table, int hop,
+                              int smooth, float* out, int64_t total, sos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

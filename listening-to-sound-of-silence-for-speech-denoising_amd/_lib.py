@@ -165,6 +165,9 @@ SIGNATURES = {
     "sos_stream_stitch_f32": [_P, _L, _L, _P, _P, _I, _L, _L, _P, _P, _L, _P],
     "sos_stream_resample_ready": [_D, _I, _I, _L, _P, _P],
     "sos_stream_resample_f32": [_P, _L, _L, _P, _P, _I, _D, _P, _I, _I, _P, _L, _P],
+    "sos_stream_band_ready": [_D, _I, _I, _I, _I, _L, _L, _P, _P, _P, _P, _P],
+    "sos_stream_band_ratio_f64": [_P, _L, _L, _P, _P, _I, _I, _P, _L, _P],
+    "sos_stream_band_merge_f32": [_P, _L, _L, _P, _L, _P, _P, _I, _D, _P, _I, _I, _I, _I, _P, _L, _P],
     "sos_time_unstack": [_P, _L, _I, _L, _I, _I, _I, _I, _P, _I, _P],
     "sos_spatial_mean_bwd": [_P, _L, _L, _I, _L, _I, _I, _I, _P, _I, _P],
 }

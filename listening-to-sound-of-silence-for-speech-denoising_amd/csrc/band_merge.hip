@@ -8,12 +8,12 @@
 //   sos_resample_merge_batch_f32  the rule above for a ragged batch at one ratio, one launch: both resamplings (rs_output2 of
 //                                 resample_core.h: the bits of rs_output, each tap weight formed once), g[t] interpolated from s
 // Float64 restatement: tests/band_reference.py.
-#include "resample_core.h"
+#include "band_core.h"
 
 #define BM_THREADS 1024         // the merge kernel's workgroup, as the batch resampler's (wave_io.hip)
 #define BM_PER_WG 4096          // = SOS_RESAMPLE_CHUNK
 #define BG_TILE 64              // frames of s per workgroup pass of the gain kernel
-#define BG_MAX_SMOOTH 16        // K <= 16: a tile of r plus K frames of halo on each side lives in LDS
+// BG_MAX_SMOOTH (band_core.h), K <= 16: a tile of r plus K frames of halo on each side lives in LDS
 #define BG_MAX_GRID_X 64
 
 // ---------------------------------------------------------------------------------------------- gains
@@ -40,28 +40,11 @@ __global__ __launch_bounds__(MT) void band_gain_kernel(const float* __restrict__
         const int64_t hi = j0 + BG_TILE + K < J ? j0 + BG_TILE + K : J;
         for (int64_t j = lo + wave; j < hi; j += MT / 64) {
             const int64_t s0 = j * hop, s1 = s0 + hop < m ? s0 + hop : m;
-            double ea = 0.0, eb = 0.0;
-            for (int64_t i = s0 + lane; i < s1; i += 64) {
-                const double va = (double)ac[i];
-                ea = fma(va, va, ea);
-                if (i < mp) {
-                    const double vb = (double)bc[i];
-                    eb = fma(vb, vb, eb);
-                }
-            }
-            for (int d = 32; d > 0; d >>= 1) {
-                ea += __shfl_down(ea, d, 64);
-                eb += __shfl_down(eb, d, 64);
-            }
-            if (lane == 0) r[j - lo] = ea == 0.0 ? 1.0 : fmin(1.0, sqrt(eb / ea));
+            const double rj = band_frame_ratio(RsLinear{ac}, RsLinear{bc}, s0, s1, mp, lane);
+            if (lane == 0) r[j - lo] = rj;
         }
         __syncthreads();
-        for (int64_t j = j0 + threadIdx.x; j < j0 + BG_TILE && j < J; j += MT) {
-            const int64_t w0 = j - K > 0 ? j - K : 0, w1 = j + K < J - 1 ? j + K : J - 1;
-            double sum = 0.0;
-            for (int64_t q = w0; q <= w1; ++q) sum += r[q - lo];
-            gc[j] = (float)(sum / (double)(w1 - w0 + 1));
-        }
+        for (int64_t j = j0 + threadIdx.x; j < j0 + BG_TILE && j < J; j += MT) gc[j] = band_mean(BandRTile{r, lo}, j, K, J);
         __syncthreads();
     }
 }
@@ -148,20 +131,8 @@ __global__ __launch_bounds__(THREADS) void resample_merge_kernel(const float* __
         float* oc = out + x_off;
         for (int64_t t = t0 + threadIdx.x; t < t0 + BM_PER_WG && t < n; t += THREADS) {
             float ra, rb;
-            rs_output2(ac, m, bc, mp, t < vb, seg, scale, w, nwin, num_table, index_step, t, &ra, &rb);
-            float g = 1.f;
-            if (sc) {
-                const double p = ((double)t + 0.5) / frame - 0.5;
-                if (!(p > 0.0)) {
-                    g = sc[0];
-                } else if (p >= (double)(J - 1)) {
-                    g = sc[J - 1];
-                } else {
-                    const int64_t i = (int64_t)p;
-                    const double s_lo = (double)sc[i], s_hi = (double)sc[i + 1];
-                    g = (float)(s_lo + (p - (double)i) * (s_hi - s_lo));
-                }
-            }
+            rs_output2(RsLinear{ac}, m, RsLinear{bc}, mp, t < vb, seg, scale, w, nwin, num_table, index_step, t, &ra, &rb);
+            const float g = sc ? band_gain_at([sc](int64_t j) { return sc[j]; }, band_gain_pos(t, frame), J) : 1.f;
             const float h = xc[t] - ra;
             oc[t] = fmaf(g, h, rb);
         }

@@ -1,7 +1,7 @@
 // resample_core.h -- what the resamplers of wave_io.hip (one clip, a ragged batch of clips), stream_resample.hip (streams
-// that arrive in chunks) and band_merge.hip (two signals per output) share: resampy's running time register as a
+// that arrive in chunks), band_merge.hip and stream_band.hip (two signals per output) share: resampy's running time register as a
 // piecewise-linear description, and the arithmetic of one output sample, tap for tap.  The first two call rs_output, so a
-// stream gets the bits of the clip it is a prefix of; band_merge.hip calls rs_output2, which keeps those bits.
+// stream gets the bits of the clip it is a prefix of; band_merge.hip and stream_band.hip call rs_output2, which keeps those bits.
 #pragma once
 #include "ragged.h"
 #include <math.h>
@@ -124,13 +124,14 @@ __device__ __forceinline__ float rs_output(const Src& src, int64_t n_in, const R
     return acc;
 }
 
-// rs_output of TWO signals that lie in one piece each and share the time register (band_merge.hip: the 14 kHz input of the
-// networks and their output, back at the recording's rate): *ya = rs_output(RsLinear{xa}, na, ..., t) and *yb =
-// rs_output(RsLinear{xb}, nb, ..., t) bit for bit, nb <= na, with every tap weight formed once.  The weights depend on t alone,
-// so each sum sees rs_output's taps in rs_output's order with the same fmaf nesting; the two differ in where the right wing
-// ends (n_in - n - 1), and each ends at its own.  b_live: whether output t of xb is resampled at all (t < its n_valid); *yb = 0
-// otherwise, and also if the time of t lies at or past xb's end (no tap of xb is read then).
-__device__ __forceinline__ void rs_output2(const float* xa, int64_t na, const float* xb, int64_t nb, bool b_live, const RsSegs& seg,
+// rs_output of TWO signals that share the time register (band_merge.hip: the 14 kHz input of the networks and their output,
+// back at the recording's rate; stream_band.hip: the same two out of their rings): *ya = rs_output(sa, na, ..., t) and *yb =
+// rs_output(sb, nb, ..., t) bit for bit, nb <= na, with every tap weight formed once.  The weights depend on t alone, so each
+// sum sees rs_output's taps in rs_output's order with the same fmaf nesting; the two differ in where the right wing ends
+// (n_in - n - 1), and each ends at its own.  b_live: whether output t of sb is resampled at all (t < its n_valid); *yb = 0
+// otherwise, and also if the time of t lies at or past sb's end (no tap of sb is read then).
+template <typename SrcA, typename SrcB>
+__device__ __forceinline__ void rs_output2(const SrcA& sa, int64_t na, const SrcB& sb, int64_t nb, bool b_live, const RsSegs& seg,
                                            double scale, const float* w, int nwin, int num_table, int index_step, int64_t t,
                                            float* ya, float* yb) {
     const double time = rs_time(seg, t);
@@ -147,18 +148,19 @@ __device__ __forceinline__ void rs_output2(const float* xa, int64_t na, const fl
     {
         const int64_t lim = (int64_t)((nwin - o) / index_step);
         const int i_max = (int)(n + 1 < lim ? n + 1 : lim);
-        int64_t c = n;
+        int64_t ca = sa.at(n);
         if (b_live) {
-            for (int i = 0; i < i_max; ++i, o += index_step, --c) {
+            int64_t cb = sb.at(n);
+            for (int i = 0; i < i_max; ++i, o += index_step, ca = sa.prev(ca), cb = sb.prev(cb)) {
                 const float a = w[o], b = w[o + 1];
                 const float wt = fmaf(eta, b - a, a);
-                acc_a = fmaf(wt, xa[c], acc_a);
-                acc_b = fmaf(wt, xb[c], acc_b);
+                acc_a = fmaf(wt, sa.load(ca), acc_a);
+                acc_b = fmaf(wt, sb.load(cb), acc_b);
             }
         } else {
-            for (int i = 0; i < i_max; ++i, o += index_step, --c) {
+            for (int i = 0; i < i_max; ++i, o += index_step, ca = sa.prev(ca)) {
                 const float a = w[o], b = w[o + 1];
-                acc_a = fmaf(fmaf(eta, b - a, a), xa[c], acc_a);
+                acc_a = fmaf(fmaf(eta, b - a, a), sa.load(ca), acc_a);
             }
         }
     }
@@ -171,17 +173,22 @@ __device__ __forceinline__ void rs_output2(const float* xa, int64_t na, const fl
         const int64_t rem_a = na - n - 1, rem_b = b_live ? nb - n - 1 : 0;
         const int ka_max = (int)(rem_a < lim ? rem_a : lim);
         const int kb_max = (int)(rem_b < lim ? rem_b : lim);      // <= ka_max: nb <= na
-        int64_t c = n + 1;
-        int k = 0;
-        for (; k < kb_max; ++k, o += index_step, ++c) {
-            const float a = w[o], b = w[o + 1];
-            const float wt = fmaf(eta, b - a, a);
-            acc_a = fmaf(wt, xa[c], acc_a);
-            acc_b = fmaf(wt, xb[c], acc_b);
-        }
-        for (; k < ka_max; ++k, o += index_step, ++c) {
-            const float a = w[o], b = w[o + 1];
-            acc_a = fmaf(fmaf(eta, b - a, a), xa[c], acc_a);
+        if (ka_max > 0) {
+            int64_t ca = sa.at(n + 1);
+            int k = 0;
+            if (kb_max > 0) {
+                int64_t cb = sb.at(n + 1);
+                for (; k < kb_max; ++k, o += index_step, ca = sa.next(ca), cb = sb.next(cb)) {
+                    const float a = w[o], b = w[o + 1];
+                    const float wt = fmaf(eta, b - a, a);
+                    acc_a = fmaf(wt, sa.load(ca), acc_a);
+                    acc_b = fmaf(wt, sb.load(cb), acc_b);
+                }
+            }
+            for (; k < ka_max; ++k, o += index_step, ca = sa.next(ca)) {
+                const float a = w[o], b = w[o + 1];
+                acc_a = fmaf(fmaf(eta, b - a, a), sa.load(ca), acc_a);
+            }
         }
     }
     *ya = acc_a;

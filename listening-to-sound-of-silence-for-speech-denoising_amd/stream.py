@@ -7,7 +7,7 @@ from . import ragged
 from . import session
 from . import tools
 from . import transform
-from .audio_io import StreamResampler
+from .audio_io import StreamBandMerger, StreamResampler
 from .pipeline import FPS, MIN_FRAMES, SR, _GraphCache, _length_groups, _padded_run
 from .windows import _hops, _row_plan, window_plan
 
@@ -96,22 +96,51 @@ class StreamDenoiser:
     -- a live stream and a file of the same audio give the same samples (tests/test_gpu_stream_resample.py).  close() drains in
     order: the input resampler, the last window, the output resampler; drop() forgets all three.  Each side adds R + 1 samples
     of latency at its input rate (R = 219 at 48 -> 14 kHz, 64 at 14 -> 48 kHz: 4.6 ms each) and two launches per call.
-    What comes back at out_sr > sr is BAND-LIMITED to sr / 2 = 7 kHz: the band above it never reaches the networks and is not
-    put back here (recordings.denoise_recordings(high_band='keep' / 'follow') does that for files).
+    high_band ('drop', the default: the path above, untouched): what comes back at out_sr > sr is band-limited to sr / 2 = 7 kHz,
+    since the band above it never reaches the networks.  'keep' / 'follow' put it back as recordings.denoise_recordings(high_band=)
+    does for files, with the same bits: they need in_sr == out_sr, and with in_sr > sr no output resampler is created -- an
+    audio_io.StreamBandMerger takes its place (with in_sr <= sr there is no band, and the session is that of 'drop').  Per push
+    the chunk at in_sr goes to the merger's x ring and through the input resampler, whose output goes to the merger's a ring
+    and to the windows, whose output goes to the merger's b ring; the merger returns what is final: out[t] = fmaf(g[t], x[t] -
+    U(a)[t], U(b)[t]), bit for bit resample_merge_batch_device of the whole signals ('follow': with band_gains_batch_device's
+    gains at `smooth_frames`), exactly one sample per input sample (tests/test_gpu_stream_highband.py).  The merger's launches --
+    one sos_stream_push_f32 for its three rings, under 'follow' one sos_stream_band_ratio_f64, one sos_stream_band_merge_f32 --
+    replace the output resampler's two, and like stage and stitch they stay outside a captured graph.  Latency over 'drop': none
+    under 'keep' (the output resampler waits for the same R + 1 = 65 samples at sr); under 'follow' an output also waits until
+    (smooth_frames + 2) hops at sr lie past it, about 45 ms at smooth_frames = 2.  Memory: the merger's rings hold what the
+    session can have pending, max_lag = 2 core + context plus the input resampler's wing at sr: 12 bytes per native sample of
+    max_chunk + in_sr / sr (max_lag + 64, or (smooth_frames + 2) hop if that is more) per slot -- about 2.8 MB at 48 kHz with 2 s cores
+    and 0.5 s context -- plus, under 'follow', 8 bytes per frame of r.  close() drains the input resampler, the last window, then
+    the merger.
     Not here: one decision stream per recording (denoise_long's stitch_bits needs frames of the future), given decisions
     (`bits=`), the four hand-off signals (`signals=`), and a res_type other than kaiser_best.
     ValueError before any launch: window_plan's argument rules, slots outside 1 .. 65535, a slot outside the slots (push) or
     without an open stream (close, drop), a chunk that is not 1-D float32, a closed stream below MIN_FRAMES frames at `sr` (the
-    slot is named and free again; the other named slots stay open), StreamResampler's refusals of in_sr / out_sr."""
+    slot is named and free again; the other named slots stay open), StreamResampler's refusals of in_sr / out_sr, an unknown
+    high_band, one other than 'drop' with in_sr != out_sr, smooth_frames outside 0 .. 16."""
 
     def __init__(self, detector, denoiser, slots, sr=SR, fps=FPS, window_seconds=2.0, context_seconds=0.5, max_batch=256,
-                 max_columns=65536, graph=False, device=None, in_sr=None, out_sr=None):
+                 max_columns=65536, graph=False, device=None, in_sr=None, out_sr=None, high_band="drop", smooth_frames=2):
         self.core, self.context = _hops(round(window_seconds * sr)), _hops(round(context_seconds * sr))
         StreamPlan(self.core, self.context)
         if not 1 <= int(slots) <= ragged.MAX_CLIPS:
             raise ValueError(f"StreamDenoiser: 1 .. {ragged.MAX_CLIPS} slots, got {slots}")
+        if high_band not in ("drop", "keep", "follow"):
+            raise ValueError("StreamDenoiser: unknown high_band %r (one of drop, keep, follow)" % (high_band,))
+        if high_band != "drop":
+            if in_sr is None or in_sr != out_sr:
+                raise ValueError("StreamDenoiser: high_band=%r needs in_sr == out_sr (got %r and %r): the band comes from the input"
+                                 % (high_band, in_sr, out_sr))
+            if isinstance(smooth_frames, bool) or not isinstance(smooth_frames, int) or not 0 <= smooth_frames <= 16:
+                raise ValueError("StreamDenoiser: smooth_frames within 0 .. 16, got %r" % (smooth_frames,))
+        band = high_band != "drop" and in_sr > sr
         self.rs_in = None if in_sr is None else StreamResampler(slots, in_sr, sr, device=device)
-        self.rs_out = None if out_sr is None else StreamResampler(slots, sr, out_sr, max_chunk=self.core, device=device)   # a step's output
+        self.rs_out = None if out_sr is None or band else StreamResampler(slots, sr, out_sr, max_chunk=self.core, device=device)   # a step's output
+        self.merger = None
+        if band:                                                # b trails a by the session's pending bound, a trails x by rs_in's wing
+            lead = int(np.ceil((self.rs_in.R + 1) * sr / in_sr)) + 2
+            self.merger = StreamBandMerger(slots, sr, in_sr, 2 * self.core + self.context + lead,
+                                           gains=smooth_frames if high_band == "follow" else None, device=device)
         self.detector, self.denoiser, self.sr, self.fps = detector, denoiser, sr, fps
         self.max_batch, self.max_columns, self.graph = min(int(max_batch), ragged.MAX_CLIPS), int(max_columns), bool(graph)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -126,10 +155,22 @@ class StreamDenoiser:
         """chunks: {slot: 1-D float32 GPU tensor or numpy array, of any length, empty included}; a slot without an open stream
         begins one.  -> {slot: 1-D f32 GPU tensor of the samples that became final, possibly empty}."""
         session.check_chunks("StreamDenoiser.push", chunks, len(self.plans))
+        if self.merger is not None:
+            return self._push_band(chunks)
         if self.rs_in is not None:                              # chunks at in_sr -> what of them is final at the model rate
             chunks = self.rs_in.push(chunks)
         outs = self._push(chunks)
         return outs if self.rs_out is None else self.rs_out.push(outs)
+
+    def _push_band(self, chunks):
+        """push() with a band merger: x -> its ring and rs_in -> a -> its ring and the windows -> b -> its ring -> what is final."""
+        slots = list(chunks)
+        flat, _ = tools.stream_flat([chunks[s] for s in slots], self.device)      # host chunks go up once
+        if flat is not None:
+            chunks = dict(zip(slots, ragged.split(flat, [int(chunks[s].shape[0]) for s in slots])))
+        a = self.rs_in.push(chunks)
+        b = self._push(a)
+        return self.merger.push({s: (chunks[s], a[s], b[s]) for s in slots})
 
     def _push(self, chunks):
         """push() for checked chunks at the model rate."""
@@ -182,12 +223,17 @@ class StreamDenoiser:
                              f"{self.sr} Hz): {told}")
         parts = {s: [] for s in slots}
         if self.rs_in is not None:
-            for s, y in self._push(self.rs_in.close(slots)).items():
+            rest_in = self.rs_in.close(slots)
+            for s, y in self._push(rest_in).items():
                 parts[s].append(y)
         self._run([(s, self.plans[s].close()[0]) for s in slots], parts, False)
         for s in slots:
             self.plans[s] = None
         outs = {s: torch.cat(o) if len(o) > 1 else o[0] for s, o in parts.items()}
+        if self.merger is not None:
+            nothing = session.empty(self.device)
+            head, rest = self.merger.push({s: (nothing, rest_in[s], outs[s]) for s in slots}), self.merger.close(slots)
+            return {s: torch.cat([head[s], rest[s]]) for s in slots}
         if self.rs_out is None:
             return outs
         head, rest = self.rs_out.push(outs), self.rs_out.close(slots)
@@ -199,6 +245,8 @@ class StreamDenoiser:
             for rs in (self.rs_in, self.rs_out):
                 if rs is not None and rs.n_recv[s] is not None:
                     rs.drop([s])
+            if self.merger is not None and self.merger.count[s] is not None:
+                self.merger.drop([s])
 
     def drop(self, slots):
         """Forgets the streams of `slots` without output; the slots are free."""

@@ -362,6 +362,54 @@ def stream_resample(ring, table, ratio, win, num_table, out=None):
     return out
 
 
+STREAM_BAND_RATIO_COLS, STREAM_BAND_MERGE_COLS = 5, 10                 # int64 per row (csrc/stream_band.hip: SB_*_COLS)
+
+
+def _stream_band_rings(ring, rring):
+    _stream_ring(ring)
+    if ring.shape[0] % 3:
+        raise ValueError("ring must hold the x, a and b rings of every slot: (3 slots, capacity)")
+    if rring is not None and (rring.dim() != 2 or rring.dtype != torch.float64 or not rring.is_contiguous() or
+                              rring.shape[0] != ring.shape[0] // 3):
+        raise ValueError("rring must be a contiguous float64 (slots, frames) tensor")
+
+
+def stream_band_ratio(ring, rring, table, hop):
+    """r[j] of whole hop frames of streams into their rings of frames in one launch (sos_stream_band_ratio_f64).  ring: (3 slots,
+    capacity) f32 GPU tensor, rows slot / slots + slot / 2 slots + slot = x / a / b of a stream as stream_push fills them; rring:
+    (slots, frames) f64 GPU tensor, written in place; table: host rows {slot, j_lo, j_hi, m_a, m_b}, a slot at most once."""
+    L.require_cuda(ring, rring)
+    tab = _host_table(table, STREAM_BAND_RATIO_COLS)
+    _stream_band_rings(ring, rring)
+    d_tab = _upload(tab, ring.device)
+    L.check(L.lib().sos_stream_band_ratio_f64(L.ptr(ring), ring.shape[0] // 3, ring.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
+                                              int(hop), L.ptr(rring), rring.shape[1], L.stream_ptr()), "sos_stream_band_ratio_f64")
+
+
+def stream_band_merge(ring, rring, table, ratio, win, num_table, hop, smooth, out):
+    """Outputs of streams with the band above the low rate's half put back, in one launch (sos_stream_band_merge_f32): out[t] =
+    fmaf(g[t], x[t] - U(a)[t], U(b)[t]) out of the rings.  table: host rows {slot, t_lo, t_hi, n_x, n_a, n_b, v_b, J, r_hi,
+    output offset}, a slot at most once; ratio = native rate / low rate; win, num_table: audio_io._filter_on's; smooth: the frames
+    of smoothing of g, or None for g = 1 (rring may be None then); out: a contiguous 1-D f32 GPU tensor, written at the rows'
+    offsets."""
+    L.require_cuda(ring, rring, win, out)
+    tab = _host_table(table, STREAM_BAND_MERGE_COLS)
+    _stream_band_rings(ring, rring)
+    if win.dim() != 1 or win.dtype != torch.float32 or not win.is_contiguous():
+        raise ValueError("win must be a contiguous 1-D float32 tensor")
+    if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous 1-D float32 tensor")
+    if smooth is not None and rring is None:
+        raise ValueError("gains need the ring of frames")
+    d_tab = _upload(tab, ring.device)
+    L.check(L.lib().sos_stream_band_merge_f32(L.ptr(ring), ring.shape[0] // 3, ring.shape[1], L.ptr(rring),
+                                              rring.shape[1] if rring is not None else 0, L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
+                                              float(ratio), L.ptr(win), win.numel(), int(num_table), int(hop),
+                                              -1 if smooth is None else int(smooth), L.ptr(out), out.numel(), L.stream_ptr()),
+            "sos_stream_band_merge_f32")
+    return out
+
+
 def stream_flat(chunks, device):
     """Chunks (1-D f32 GPU tensors or numpy arrays) back to back in one device buffer (host arrays go up in one copy) and where
     each starts: -> (flat or None if all are empty, offsets)."""
