@@ -497,6 +497,32 @@ int sos_pcm_planes_batch_f32(const void* pcm, int format, const int64_t* table, 
                              sos_stream_t stream);
 int sos_pcm_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int format, void* out,
                          int64_t* clipped, sos_stream_t stream);
+/* G.711 (ITU-T G.711: A-law, WAVE format tag 6, and mu-law, tag 7; one code byte per sample) through the same kernels
+ * (csrc/pcm_core.h states the rule once, in integers and without a table; float restatement: tests/g711_reference.py, held
+ * against the Sun / ITU g711.c as CPython's audioop carries it, on all 256 codes and all 65 536 s16 values).  The rule is
+ * stateless per sample, so a live leg's packets go through the same calls as files.
+ * Expand, code c -> level, value = level / 32768 as f32 (exact):
+ *   mu-law: u = ~c & 0xFF; t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7); level = u & 0x80 ? 0x84 - t : t - 0x84   (+-32124)
+ *   A-law:  a = c ^ 0x55; seg = (a >> 4) & 7; t = (a & 15) << 4;
+ *           t = seg == 0 ? t + 8 : (t + 0x108) << (seg - 1); level = a & 0x80 ? t : -t                                (+-32256)
+ * Compress, f32 x -> code: q = the SOS_ENC_S16 value of x (rint half to even in double, NaN -> 0, saturated; `clipped` counts
+ * exactly what it counts for S16), then the reference compressor, which DROPS the low bits (it does not round to the nearest
+ * level; what audioop, libsndfile and sox write):
+ *   mu-law: p = q >> 2; mask = p < 0 ? 0x7F : 0xFF; p = min(|p| + 0x21, 0x1FFF); seg = index of the first of the ends
+ *           {0x3F, 0x7F, .. 0x1FFF} that is >= p; code = ((seg << 4) | ((p >> (seg + 1)) & 15)) ^ mask
+ *   A-law:  p = q >> 3; mask = p < 0 ? 0x55 : 0xD5; if p < 0: p = -p - 1; seg over the ends {0x1F, 0x3F, .. 0xFFF};
+ *           code = ((seg << 4) | ((p >> max(seg, 1)) & 15)) ^ mask
+ * Expanding and compressing again returns every code except mu-law 0x7F (negative zero), which comes back as 0xFF.  Silence
+ * is 0xFF (mu-law) / 0xD5 (A-law): the zero-fill past a plane's end is the float 0 compressed, hence that code, never byte 0.
+ * sos_g711_planes_batch_f32 / sos_g711_encode_batch / sos_g711_to_mono_f32: sos_pcm_planes_batch_f32 / sos_pcm_encode_batch /
+ * sos_pcm_to_mono_f32 with `law` in place of the format and one byte per element: the same tables, bounds rule, refusals
+ * (an unknown law: SOS_EINVAL, "unknown law %d") and mean expression. */
+enum { SOS_G711_ALAW = 6, SOS_G711_ULAW = 7 };
+int sos_g711_planes_batch_f32(const void* codes, int law, const int64_t* table, const int64_t* table_host, int nfiles, float* out,
+                              sos_stream_t stream);
+int sos_g711_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int law, void* out,
+                          int64_t* clipped, sos_stream_t stream);
+int sos_g711_to_mono_f32(const void* codes, int law, int channels, int64_t n_frames, float* out, sos_stream_t stream);
 /* Band-limited resampling by `ratio` = sr_new / sr_orig (resampy 0.2.2 `resample_f`): win = the filter's half
  * window (nwin floats, num_table samples per zero crossing), already multiplied by min(1, ratio).  Writes
  * out[0 .. n_out): the first floor(n_in * ratio) entries are resampled, the rest zero (librosa pads to

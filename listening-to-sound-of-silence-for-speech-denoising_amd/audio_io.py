@@ -10,7 +10,9 @@
   write_wav(path, y, sr, norm=False)
 and, beyond librosa's names, the channel-preserving pair under recordings.py (csrc/pcm_io.hip):
   load_channels_batch_device(paths, sr=None) / decode_planes_batch_device(arrs, kinds): every channel as an f32 plane
-  encode_batch_device(planes, fmt, frames=None) + wave_container(...): planes -> s16 / s24 / s32 / u8 / f32 WAVE data
+  encode_batch_device(planes, fmt, frames=None) + wave_container(...): planes -> s16 / s24 / s32 / u8 / f32 WAVE data, or
+      G.711 'alaw' / 'ulaw' code bytes (telephone audio: WAVE tags 6 / 7, read by read_wave like the linear formats)
+  g711_decode_device(codes, law) / g711_encode_device(x, law): the same two launches for one chunk of a live call leg
   band_gains_batch_device(lows_in, lows_out) / resample_merge_batch_device(natives, lows_in, lows_out, orig_sr, target_sr,
       gains=None): what a chain at a lower rate never saw of a signal, put back at its own rate (csrc/band_merge.hip)
   StreamResampler / StreamBandMerger: resample_device and resample_merge_batch_device for audio that is still arriving, with
@@ -425,19 +427,24 @@ class StreamBandMerger:
 
 
 def pcm_to_mono_device(pcm, fmt):
-    """pcm: (n_frames, channels) device tensor of int16 / int32 / float32 / uint8 -> mono f32 (n_frames,)."""
+    """pcm: (n_frames, channels) device tensor of int16 / int32 / float32 / uint8, or of uint8 G.711 codes with fmt 'alaw' /
+    'ulaw' -> mono f32 (n_frames,)."""
     L.require_cuda(pcm)
     pcm = pcm.contiguous()
     n, ch = pcm.shape
     out = torch.empty(n, dtype=torch.float32, device=pcm.device)
-    L.check(L.lib().sos_pcm_to_mono_f32(L.ptr(pcm), _FMT[fmt], ch, n, L.ptr(out), L.stream_ptr()), "sos_pcm_to_mono_f32")
+    if fmt in G711:
+        L.check(L.lib().sos_g711_to_mono_f32(L.ptr(pcm), G711[fmt][0], ch, n, L.ptr(out), L.stream_ptr()), "sos_g711_to_mono_f32")
+    else:
+        L.check(L.lib().sos_pcm_to_mono_f32(L.ptr(pcm), _FMT[fmt], ch, n, L.ptr(out), L.stream_ptr()), "sos_pcm_to_mono_f32")
     return out
 
 
 # ------------------------------------------------------------------------------------ RIFF/WAVE container
 def read_wave(path):
     """Parse a RIFF/WAVE file -> (samples ndarray (n_frames, channels) in a kernel format, fmt, sample rate).
-    PCM 8/16/24/32-bit, IEEE float 32/64, WAVE_FORMAT_EXTENSIBLE wrappers of those."""
+    PCM 8/16/24/32-bit, IEEE float 32/64, G.711 A-law / mu-law (tags 6 / 7 with 8 bits: the uint8 code bytes, fmt 'alaw' /
+    'ulaw'), WAVE_FORMAT_EXTENSIBLE wrappers of those."""
     return read_wave_info(path)[:3]
 
 
@@ -488,6 +495,8 @@ def read_wave_info(path):
         arr, kind = np.frombuffer(data, dtype="<f4"), "f32"
     elif tag == 3 and bits == 64:
         arr, kind = np.frombuffer(data, dtype="<f8").astype(np.float32), "f32"
+    elif (tag, bits) in _G711_KIND:                         # the code bytes as they are: the kernels expand them
+        arr, kind = np.frombuffer(data, dtype=np.uint8), _G711_KIND[tag, bits]
     else:
         raise WaveFormatError("%s: unsupported WAVE format tag %d with %d bits" % (path, tag, bits))
     return arr.reshape(n, ch), kind, rate, dict(tag=tag, bits=bits, channels=ch, rate=rate, frames=n)
@@ -524,7 +533,7 @@ def wave_info(path):
     tag, ch, rate, bits = fmt
     if ch < 1:
         raise WaveFormatError("%s: no channels" % path)
-    if (tag, bits) not in ((1, 8), (1, 16), (1, 24), (1, 32), (3, 32), (3, 64)):
+    if (tag, bits) not in ((1, 8), (1, 16), (1, 24), (1, 32), (3, 32), (3, 64)) and (tag, bits) not in _G711_KIND:
         raise WaveFormatError("%s: unsupported WAVE format tag %d with %d bits" % (path, tag, bits))
     return dict(tag=tag, bits=bits, channels=ch, rate=rate, frames=nbytes // ((bits // 8) * ch))
 
@@ -608,6 +617,9 @@ def load_batch_device(paths, sr=22050, mono=True, offset=0.0, duration=None, res
 # ------------------------------------------------------------------------------------ channel planes (csrc/pcm_io.hip)
 # encode formats: name -> (SOS_ENC_* of include/sos_hip.h, bytes per element, WAVE format tag, stored bits)
 ENCODINGS = {"s16": (0, 2, 1, 16), "s32": (1, 4, 1, 32), "f32": (2, 4, 3, 32), "u8": (3, 1, 1, 8), "s24": (4, 3, 1, 24)}
+# G.711, one code byte per sample: name -> (SOS_G711_* of include/sos_hip.h = the WAVE format tag, bytes per element, tag, bits)
+G711 = {"alaw": (6, 1, 6, 8), "ulaw": (7, 1, 7, 8)}
+_G711_KIND = {(v[2], v[3]): k for k, v in G711.items()}
 
 
 def _back_to_back(tensors):
@@ -629,16 +641,17 @@ def planes_of(channels):
 
 def decode_planes_batch_device(arrs, kinds, device="cuda"):
     """arrs: one (frames, channels) host array per file as read_wave returns it, kinds: its sample format ('s16', 's32', 'f32',
-    'u8'); channel counts (1 .. 64) may differ from file to file.  -> one (channels, frames) f32 GPU tensor per file, views into
-    ONE buffer, every value bit for bit what pcm_to_mono_device gives a one-channel file (sample / 2^(bits-1)).  Files that share
-    a sample format go up in one copy of their concatenated frames and through one sos_pcm_planes_batch_f32 launch (per 65535
-    files).  ValueError before any launch: an unknown format, a file that is not 2-D or has 0 or more than 64 channels."""
+    'u8', or 'alaw' / 'ulaw' for uint8 G.711 codes); channel counts (1 .. 64) may differ from file to file.  -> one (channels,
+    frames) f32 GPU tensor per file, views into ONE buffer, every value bit for bit what pcm_to_mono_device gives a one-channel
+    file (sample / 2^(bits-1); G.711: the code's level / 2^15).  Files that share a sample format go up in one copy of their
+    concatenated frames and through one sos_pcm_planes_batch_f32 / sos_g711_planes_batch_f32 launch (per 65535 files).
+    ValueError before any launch: an unknown format, a file that is not 2-D or has 0 or more than 64 channels."""
     arrs, kinds = list(arrs), list(kinds)
     if len(arrs) != len(kinds):
         raise ValueError("decode_planes_batch_device: one kind per array (%d arrays, %d kinds)" % (len(arrs), len(kinds)))
     by_kind = {}
     for i, (a, k) in enumerate(zip(arrs, kinds)):
-        if k not in _FMT:
+        if k not in _FMT and k not in G711:
             raise ValueError("decode_planes_batch_device: file %d has the unsupported sample format %r" % (i, k))
         if a.ndim != 2 or not 1 <= a.shape[1] <= 64:
             raise ValueError("decode_planes_batch_device: file %d must be (frames, 1 .. 64 channels), got shape %s" % (i, a.shape))
@@ -652,6 +665,8 @@ def decode_planes_batch_device(arrs, kinds, device="cuda"):
     where = dict(zip(order, ragged.offsets(sizes[order]).tolist()))
     h = L.lib()
     for k, idx in by_kind.items():
+        name = "sos_g711_planes_batch_f32" if k in G711 else "sos_pcm_planes_batch_f32"
+        entry, code = getattr(h, name), G711[k][0] if k in G711 else _FMT[k]
         pcm = torch.from_numpy(np.concatenate([arrs[i].reshape(-1) for i in idx])).to(device)
         off = ragged.offsets(sizes[idx])
         for c0 in range(0, len(idx), ragged.MAX_CLIPS):
@@ -660,8 +675,8 @@ def decode_planes_batch_device(arrs, kinds, device="cuda"):
             tab = np.asarray([[off[c0 + j] - off[c0], arrs[i].shape[0], arrs[i].shape[1], where[i] - o0] for j, i in enumerate(sel)],
                              dtype=np.int64)
             tab_dev = torch.from_numpy(tab).to(device)
-            L.check(h.sos_pcm_planes_batch_f32(L.ptr(pcm[int(off[c0]):]), _FMT[k], L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p),
-                                               len(sel), L.ptr(out[o0:]), L.stream_ptr()), "sos_pcm_planes_batch_f32")
+            L.check(entry(L.ptr(pcm[int(off[c0]):]), code, L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), len(sel), L.ptr(out[o0:]),
+                          L.stream_ptr()), name)
     return [out[where[i]:where[i] + a.size].view(a.shape[1], a.shape[0]) if a.shape[0]
             else torch.zeros((a.shape[1], 0), dtype=torch.float32, device=device) for i, a in enumerate(arrs)]
 
@@ -701,11 +716,16 @@ def encode_batch_device(planes, fmt, frames=None):
     n and 0 from there to `frames` (crop / zero-fill happen in the kernel); f32 copies the bits; otherwise q = rint(x * S) half
     to even in double with S = 2^(bits-1), NaN -> 0, saturated to [-S, S - 1]; u8 stores q + 128.  clipped[f] counts the samples
     that were NaN or changed by saturation (+-inf included).  NO dither is applied (out of scope): quantisation error is
-    correlated with the signal, as with soundfile's and scipy's integer writers.  Float64 restatement: tests/pcm_reference.py."""
+    correlated with the signal, as with soundfile's and scipy's integer writers.  Float64 restatement: tests/pcm_reference.py.
+    'alaw' / 'ulaw' (G.711, one code byte per sample, ONE sos_g711_encode_batch launch): the 's16' value q, counted as 's16'
+    counts it, through the reference compressor (include/sos_hip.h; it drops the low bits of q, as audioop, libsndfile and sox
+    do); the zero-fill is the code of silence, 0xD5 / 0xFF.  Restatement: tests/g711_reference.py."""
     planes = list(planes)
-    if fmt not in ENCODINGS:
-        raise ValueError("encode_batch_device: unsupported sample format %r (one of %s)" % (fmt, ", ".join(sorted(ENCODINGS))))
-    code, width = ENCODINGS[fmt][:2]
+    if fmt not in ENCODINGS and fmt not in G711:
+        raise ValueError("encode_batch_device: unsupported sample format %r (one of %s)"
+                         % (fmt, ", ".join(sorted(ENCODINGS) + sorted(G711))))
+    code, width = (G711[fmt] if fmt in G711 else ENCODINGS[fmt])[:2]
+    name = "sos_g711_encode_batch" if fmt in G711 else "sos_pcm_encode_batch"
     for i, p in enumerate(planes):
         if not torch.is_tensor(p) or p.dim() != 2 or p.dtype != torch.float32 or not 1 <= p.shape[0] <= 64:
             raise ValueError("encode_batch_device: file %d must be a (1 .. 64 channels, n) float32 tensor" % i)
@@ -731,9 +751,39 @@ def encode_batch_device(planes, fmt, frames=None):
         tab = np.ascontiguousarray(np.stack([src[c0:c1] - src[c0], avail[c0:c1], chans[c0:c1], np.asarray(frames[c0:c1], dtype=np.int64),
                                              offsets[c0:c1] // width - e0], axis=1), dtype=np.int64)
         tab_dev = torch.from_numpy(tab).to(device)
-        L.check(h.sos_pcm_encode_batch(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, code,
-                                       L.ptr(data[e0 * width:]), L.ptr(clipped[c0:]), L.stream_ptr()), "sos_pcm_encode_batch")
+        L.check(getattr(h, name)(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, code,
+                                 L.ptr(data[e0 * width:]), L.ptr(clipped[c0:]), L.stream_ptr()), name)
     return data[:int(offsets[-1])], offsets, clipped
+
+
+def g711_decode_device(codes, law):
+    """One chunk of a G.711 leg (a packet's payload): codes 1-D uint8 (GPU tensor, numpy array or bytes), law 'alaw' / 'ulaw' ->
+    1-D f32 GPU tensor, what decode_planes_batch_device gives a one-channel file.  The rule has no state: the chunks of a signal
+    decode to the chunks of its decode."""
+    if law not in G711:
+        raise ValueError("g711_decode_device: unknown law %r (one of %s)" % (law, ", ".join(sorted(G711))))
+    if torch.is_tensor(codes):
+        if codes.dim() != 1 or codes.dtype != torch.uint8:
+            raise ValueError("g711_decode_device expects 1-D uint8 codes")
+        L.require_cuda(codes)
+        if not codes.numel():
+            return torch.zeros(0, dtype=torch.float32, device=codes.device)
+        return pcm_to_mono_device(codes.view(-1, 1), law)         # one channel: the planes kernel's bits
+    arr = np.frombuffer(codes, dtype=np.uint8) if isinstance(codes, (bytes, bytearray, memoryview)) else np.asarray(codes)
+    if arr.ndim != 1 or arr.dtype != np.uint8:
+        raise ValueError("g711_decode_device expects 1-D uint8 codes")
+    return decode_planes_batch_device([arr.reshape(-1, 1)], [law])[0][0]
+
+
+def g711_encode_device(x, law):
+    """One chunk of a leg's output: x 1-D f32 GPU tensor -> (1-D uint8 GPU tensor of codes, clipped: int64 GPU tensor of one
+    count), encode_batch_device([x[None]], law).  No state: the chunks of a signal encode to the chunks of its encode."""
+    if law not in G711:
+        raise ValueError("g711_encode_device: unknown law %r (one of %s)" % (law, ", ".join(sorted(G711))))
+    if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.float32:
+        raise ValueError("g711_encode_device expects a 1-D float32 tensor")
+    data, _, clipped = encode_batch_device([x.view(1, -1)], law)
+    return data, clipped
 
 
 # ------------------------------------------------------------------------------------ the band above SR / 2 (csrc/band_merge.hip)
@@ -950,10 +1000,13 @@ def _riff(data, tag, ch, sr, bits, frames):
 def wave_container(data_bytes, tag, channels, rate, bits):
     """The RIFF/WAVE file around already-encoded interleaved data (encode_batch_device's bytes): tag 1 (PCM) with a 16-byte
     fmt chunk, tag 3 (IEEE float) with an 18-byte fmt chunk and a `fact` chunk, the chunks of wave_bytes -- for mono or
-    interleaved f32 data, wave_container(y.tobytes(), 3, channels, sr, 32) == wave_bytes(y, sr)."""
+    interleaved f32 data, wave_container(y.tobytes(), 3, channels, sr, 32) == wave_bytes(y, sr).  Tags 6 / 7 (G.711 A-law /
+    mu-law, 8 bits) get the chunks of every non-PCM format, the 18-byte fmt chunk and `fact`; like u8 data, an odd number of
+    code bytes is followed by no pad byte."""
     data = bytes(data_bytes)
-    if tag not in (1, 3) or bits % 8 or bits < 8 or channels < 1:
-        raise ValueError("wave_container: tag 1 (PCM) or 3 (float), whole bytes per sample, at least one channel")
+    if tag not in (1, 3) and (tag, bits) not in _G711_KIND or bits % 8 or bits < 8 or channels < 1:
+        raise ValueError("wave_container: tag 1 (PCM), 3 (float) or 6 / 7 (G.711 A-law / mu-law, 8 bits), whole bytes per sample, "
+                         "at least one channel")
     align = channels * (bits // 8)
     if len(data) % align:
         raise ValueError("wave_container: %d bytes are no whole number of %d-byte frames" % (len(data), align))

@@ -9,6 +9,8 @@
 // one-channel file whose plane is aligned, scalar otherwise (four interleaved elements of a c-channel file lie c planes apart).
 // Which access is taken changes no value.  Packed s24 is written as absolute dwords: a thread owns three aligned dwords = twelve
 // bytes of the file's byte range wherever the file starts, and only the threads at the two ends of a file store single bytes.
+// G.711 (A-law / mu-law code bytes, sos_g711_planes_batch_f32 / sos_g711_encode_batch) is two more sample types of the same two
+// kernels: four codes are one dword, and the plane side is the template's.
 // Bounds: the rule of ragged.h -- the host refuses a row of table_host outside the elements it summed (SOS_EINVAL), the kernels
 // skip a row of the DEVICE table that fails the same rule.
 #include "ragged.h"
@@ -84,6 +86,9 @@ template <> struct PioEnc<SOS_ENC_S16> { typedef int16_t T; static __device__ __
 template <> struct PioEnc<SOS_ENC_S32> { typedef int32_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)pio_quantise<32>(x, n); } };
 template <> struct PioEnc<SOS_ENC_U8> { typedef uint8_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)(pio_quantise<8>(x, n) + 128); } };
 template <> struct PioEnc<SOS_ENC_F32> { typedef float T; static __device__ __forceinline__ T put(float x, int&) { return x; } };
+// G.711: the s16 value (counted as 's16' counts), then the compressor of pcm_core.h.  The laws' WAVE tags 6 / 7 continue SOS_ENC_*.
+template <> struct PioEnc<SOS_G711_ALAW> { typedef G711A T; static __device__ __forceinline__ T put(float x, int& n) { return T{g711_alaw_compress(pio_quantise<16>(x, n))}; } };
+template <> struct PioEnc<SOS_G711_ULAW> { typedef G711U T; static __device__ __forceinline__ T put(float x, int& n) { return T{g711_ulaw_compress(pio_quantise<16>(x, n))}; } };
 
 // element e of a file's interleaved output: plane[c][i], 0 from the plane's end on
 struct PioPlanes {
@@ -221,75 +226,127 @@ static int pio_check_rows(const int64_t* table, int nfiles, int cols, int ch_col
     return nfiles;
 }
 
-extern "C" int sos_pcm_planes_batch_f32(const void* pcm, int format, const int64_t* table, const int64_t* table_host, int nfiles,
-                                        float* out, sos_stream_t stream) {
-    if (!pcm || !table || !table_host || !out) { sos_set_error("sos_pcm_planes_batch_f32: null pointer"); return SOS_EINVAL; }
+// The host half of the decode entry points (`what` = "sample format" / "law", `known` = the caller knows `code`): refuses, or
+// sums the table into `in` and sizes the grid.
+static int pio_planes_args(const char* who, const void* pcm, const char* what, bool known, int code, const int64_t* table,
+                           const int64_t* table_host, int nfiles, const float* out, PioSide* in, dim3* grid) {
+    if (!pcm || !table || !table_host || !out) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
     if (!ragged_clips_ok(table_host, nfiles)) {
-        sos_set_error("sos_pcm_planes_batch_f32: bad args (1 .. 65535 files, got %d)", nfiles);
+        sos_set_error("%s: bad args (1 .. 65535 files, got %d)", who, nfiles);
         return SOS_EINVAL;
     }
-    if (format != SOS_PCM_S16 && format != SOS_PCM_S32 && format != SOS_PCM_F32 && format != SOS_PCM_U8) {
-        sos_set_error("sos_pcm_planes_batch_f32: unknown sample format %d", format);
+    if (!known) {
+        sos_set_error("%s: unknown %s %d", who, what, code);
         return SOS_EINVAL;
     }
-    PioSide in{0, 1}, pl{3, 1};
+    PioSide pl{3, 1};
     const char* why = "";
-    const int bad = pio_check_rows(table_host, nfiles, PIO_PLANES_COLS, 2, &in, &pl, &why);
+    const int bad = pio_check_rows(table_host, nfiles, PIO_PLANES_COLS, 2, in, &pl, &why);
     if (bad < nfiles) {
         const int64_t* te = table_host + (int64_t)bad * PIO_PLANES_COLS;
-        sos_set_error("sos_pcm_planes_batch_f32: file %d (pcm element %lld, %lld frames, %lld channels, output %lld) has %s (%lld "
-                      "elements)", bad, (long long)te[0], (long long)te[1], (long long)te[2], (long long)te[3], why, (long long)in.total);
+        sos_set_error("%s: file %d (pcm element %lld, %lld frames, %lld channels, output %lld) has %s (%lld "
+                      "elements)", who, bad, (long long)te[0], (long long)te[1], (long long)te[2], (long long)te[3], why, (long long)in->total);
         return SOS_EINVAL;
     }
-    const dim3 grid(ragged_grid((in.longest + 3) / 4, PIO_THREADS, PIO_MAX_GRID), (unsigned)nfiles);
+    *grid = dim3(ragged_grid((in->longest + 3) / 4, PIO_THREADS, PIO_MAX_GRID), (unsigned)nfiles);
+    return SOS_OK;
+}
+
+// The same for the encode entry points; clears the counts.
+static int pio_encode_args(const char* who, const float* planes, const char* what, bool known, int code, const int64_t* table,
+                           const int64_t* table_host, int nfiles, const void* out, int64_t* clipped, hipStream_t st,
+                           PioSide* in, PioSide* enc, dim3* grid) {
+    if (!planes || !table || !table_host || !out || !clipped) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
+    if (!ragged_clips_ok(table_host, nfiles)) {
+        sos_set_error("%s: bad args (1 .. 65535 files, got %d)", who, nfiles);
+        return SOS_EINVAL;
+    }
+    if (!known) {
+        sos_set_error("%s: unknown %s %d", who, what, code);
+        return SOS_EINVAL;
+    }
+    const char* why = "";
+    const int bad = pio_check_rows(table_host, nfiles, PIO_ENCODE_COLS, 2, in, enc, &why);
+    if (bad < nfiles) {
+        const int64_t* te = table_host + (int64_t)bad * PIO_ENCODE_COLS;
+        sos_set_error("%s: file %d (plane sample %lld, %lld available, %lld channels, %lld frames, output element "
+                      "%lld) has %s (%lld plane samples, %lld output elements)", who, bad, (long long)te[0], (long long)te[1],
+                      (long long)te[2], (long long)te[3], (long long)te[4], why, (long long)in->total, (long long)enc->total);
+        return SOS_EINVAL;
+    }
+    if (hipMemsetAsync(clipped, 0, (size_t)nfiles * sizeof(int64_t), st) != hipSuccess) {
+        sos_set_error("%s: cannot clear the counts", who);
+        return SOS_ELAUNCH;
+    }
+    // s24: a thread per twelve bytes = four elements, plus the unit a file that starts off a dword adds
+    *grid = dim3(ragged_grid((enc->longest + 3) / 4 + 1, PIO_THREADS, PIO_MAX_GRID), (unsigned)nfiles);
+    return SOS_OK;
+}
+
+#define PIO_PLANES_GO(T) hipLaunchKernelGGL(pcm_planes_kernel<T>, grid, dim3(PIO_THREADS), 0, st, (const T*)pcm, table, in.total, out)
+#define PIO_ENCODE_GO(F) hipLaunchKernelGGL(pcm_encode_kernel<F>, grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, enc.total, \
+                                            (PioEnc<F>::T*)out, clipped)
+
+extern "C" int sos_pcm_planes_batch_f32(const void* pcm, int format, const int64_t* table, const int64_t* table_host, int nfiles,
+                                        float* out, sos_stream_t stream) {
+    const bool known = format == SOS_PCM_S16 || format == SOS_PCM_S32 || format == SOS_PCM_F32 || format == SOS_PCM_U8;
+    PioSide in{0, 1};
+    dim3 grid;
+    const int rc = pio_planes_args("sos_pcm_planes_batch_f32", pcm, "sample format", known, format, table, table_host, nfiles, out, &in, &grid);
+    if (rc != SOS_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     switch (format) {
-    case SOS_PCM_S16: hipLaunchKernelGGL(pcm_planes_kernel<int16_t>, grid, dim3(PIO_THREADS), 0, st, (const int16_t*)pcm, table, in.total, out); break;
-    case SOS_PCM_S32: hipLaunchKernelGGL(pcm_planes_kernel<int32_t>, grid, dim3(PIO_THREADS), 0, st, (const int32_t*)pcm, table, in.total, out); break;
-    case SOS_PCM_U8: hipLaunchKernelGGL(pcm_planes_kernel<uint8_t>, grid, dim3(PIO_THREADS), 0, st, (const uint8_t*)pcm, table, in.total, out); break;
-    default: hipLaunchKernelGGL(pcm_planes_kernel<float>, grid, dim3(PIO_THREADS), 0, st, (const float*)pcm, table, in.total, out); break;
+    case SOS_PCM_S16: PIO_PLANES_GO(int16_t); break;
+    case SOS_PCM_S32: PIO_PLANES_GO(int32_t); break;
+    case SOS_PCM_U8: PIO_PLANES_GO(uint8_t); break;
+    default: PIO_PLANES_GO(float); break;
     }
     return sos_check_launch("sos_pcm_planes_batch_f32");
 }
 
+extern "C" int sos_g711_planes_batch_f32(const void* codes, int law, const int64_t* table, const int64_t* table_host, int nfiles,
+                                         float* out, sos_stream_t stream) {
+    const void* pcm = codes;                                     // PIO_PLANES_GO's name for the interleaved side
+    PioSide in{0, 1};
+    dim3 grid;
+    const int rc = pio_planes_args("sos_g711_planes_batch_f32", pcm, "law", law == SOS_G711_ALAW || law == SOS_G711_ULAW, law, table,
+                                   table_host, nfiles, out, &in, &grid);
+    if (rc != SOS_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (law == SOS_G711_ALAW) PIO_PLANES_GO(G711A); else PIO_PLANES_GO(G711U);
+    return sos_check_launch("sos_g711_planes_batch_f32");
+}
+
 extern "C" int sos_pcm_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int format,
                                     void* out, int64_t* clipped, sos_stream_t stream) {
-    if (!planes || !table || !table_host || !out || !clipped) { sos_set_error("sos_pcm_encode_batch: null pointer"); return SOS_EINVAL; }
-    if (!ragged_clips_ok(table_host, nfiles)) {
-        sos_set_error("sos_pcm_encode_batch: bad args (1 .. 65535 files, got %d)", nfiles);
-        return SOS_EINVAL;
-    }
-    if (format != SOS_ENC_S16 && format != SOS_ENC_S24 && format != SOS_ENC_S32 && format != SOS_ENC_U8 && format != SOS_ENC_F32) {
-        sos_set_error("sos_pcm_encode_batch: unknown sample format %d", format);
-        return SOS_EINVAL;
-    }
+    const bool known = format == SOS_ENC_S16 || format == SOS_ENC_S24 || format == SOS_ENC_S32 || format == SOS_ENC_U8 || format == SOS_ENC_F32;
     PioSide in{0, 1}, enc{4, 3};
-    const char* why = "";
-    const int bad = pio_check_rows(table_host, nfiles, PIO_ENCODE_COLS, 2, &in, &enc, &why);
-    if (bad < nfiles) {
-        const int64_t* te = table_host + (int64_t)bad * PIO_ENCODE_COLS;
-        sos_set_error("sos_pcm_encode_batch: file %d (plane sample %lld, %lld available, %lld channels, %lld frames, output element "
-                      "%lld) has %s (%lld plane samples, %lld output elements)", bad, (long long)te[0], (long long)te[1],
-                      (long long)te[2], (long long)te[3], (long long)te[4], why, (long long)in.total, (long long)enc.total);
-        return SOS_EINVAL;
-    }
+    dim3 grid;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(clipped, 0, (size_t)nfiles * sizeof(int64_t), st) != hipSuccess) {
-        sos_set_error("sos_pcm_encode_batch: cannot clear the counts");
-        return SOS_ELAUNCH;
-    }
-    // s24: a thread per twelve bytes = four elements, plus the unit a file that starts off a dword adds
-    const dim3 grid(ragged_grid((enc.longest + 3) / 4 + 1, PIO_THREADS, PIO_MAX_GRID), (unsigned)nfiles);
-#define PIO_GO(F) hipLaunchKernelGGL(pcm_encode_kernel<F>, grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, enc.total, \
-                                     (PioEnc<F>::T*)out, clipped)
+    const int rc = pio_encode_args("sos_pcm_encode_batch", planes, "sample format", known, format, table, table_host, nfiles, out, clipped,
+                                   st, &in, &enc, &grid);
+    if (rc != SOS_OK) return rc;
     switch (format) {
-    case SOS_ENC_S16: PIO_GO(SOS_ENC_S16); break;
-    case SOS_ENC_S32: PIO_GO(SOS_ENC_S32); break;
-    case SOS_ENC_U8: PIO_GO(SOS_ENC_U8); break;
-    case SOS_ENC_F32: PIO_GO(SOS_ENC_F32); break;
+    case SOS_ENC_S16: PIO_ENCODE_GO(SOS_ENC_S16); break;
+    case SOS_ENC_S32: PIO_ENCODE_GO(SOS_ENC_S32); break;
+    case SOS_ENC_U8: PIO_ENCODE_GO(SOS_ENC_U8); break;
+    case SOS_ENC_F32: PIO_ENCODE_GO(SOS_ENC_F32); break;
     default: hipLaunchKernelGGL(pcm_encode_s24_kernel, grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, enc.total,
                                 (uint8_t*)out, clipped); break;
     }
-#undef PIO_GO
     return sos_check_launch("sos_pcm_encode_batch");
 }
+
+extern "C" int sos_g711_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int law,
+                                     void* out, int64_t* clipped, sos_stream_t stream) {
+    PioSide in{0, 1}, enc{4, 3};
+    dim3 grid;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = pio_encode_args("sos_g711_encode_batch", planes, "law", law == SOS_G711_ALAW || law == SOS_G711_ULAW, law, table,
+                                   table_host, nfiles, out, clipped, st, &in, &enc, &grid);
+    if (rc != SOS_OK) return rc;
+    if (law == SOS_G711_ALAW) PIO_ENCODE_GO(SOS_G711_ALAW); else PIO_ENCODE_GO(SOS_G711_ULAW);
+    return sos_check_launch("sos_g711_encode_batch");
+}
+#undef PIO_PLANES_GO
+#undef PIO_ENCODE_GO

@@ -31,13 +31,17 @@ __global__ void pcm_to_mono_kernel(const T* __restrict__ pcm, int channels, int6
     }
 }
 
+static unsigned pcm_mono_grid(int64_t n_frames) {
+    return (unsigned)((n_frames + RS_THREADS - 1) / RS_THREADS < 4096 ? (n_frames + RS_THREADS - 1) / RS_THREADS : 4096);
+}
+
 extern "C" int sos_pcm_to_mono_f32(const void* pcm, int format, int channels, int64_t n_frames, float* out,
                                    sos_stream_t stream) {
     if (!pcm || !out || channels < 1 || channels > 64 || n_frames < 1) {
         sos_set_error("sos_pcm_to_mono_f32: bad args (channels=%d, n_frames=%lld)", channels, (long long)n_frames);
         return SOS_EINVAL;
     }
-    const unsigned grid = (unsigned)((n_frames + RS_THREADS - 1) / RS_THREADS < 4096 ? (n_frames + RS_THREADS - 1) / RS_THREADS : 4096);
+    const unsigned grid = pcm_mono_grid(n_frames);
     hipStream_t st = (hipStream_t)stream;
     switch (format) {
     case SOS_PCM_S16: hipLaunchKernelGGL(pcm_to_mono_kernel<int16_t>, dim3(grid), dim3(RS_THREADS), 0, st, (const int16_t*)pcm, channels, n_frames, out); break;
@@ -47,6 +51,22 @@ extern "C" int sos_pcm_to_mono_f32(const void* pcm, int format, int channels, in
     default: sos_set_error("sos_pcm_to_mono_f32: unknown sample format %d", format); return SOS_EINVAL;
     }
     return sos_check_launch("sos_pcm_to_mono_f32");
+}
+
+// the same kernel over G.711 code bytes (pcm_core.h's expansion): the same mean expression
+extern "C" int sos_g711_to_mono_f32(const void* codes, int law, int channels, int64_t n_frames, float* out, sos_stream_t stream) {
+    if (!codes || !out || channels < 1 || channels > 64 || n_frames < 1) {
+        sos_set_error("sos_g711_to_mono_f32: bad args (channels=%d, n_frames=%lld)", channels, (long long)n_frames);
+        return SOS_EINVAL;
+    }
+    const unsigned grid = pcm_mono_grid(n_frames);
+    hipStream_t st = (hipStream_t)stream;
+    switch (law) {
+    case SOS_G711_ALAW: hipLaunchKernelGGL(pcm_to_mono_kernel<G711A>, dim3(grid), dim3(RS_THREADS), 0, st, (const G711A*)codes, channels, n_frames, out); break;
+    case SOS_G711_ULAW: hipLaunchKernelGGL(pcm_to_mono_kernel<G711U>, dim3(grid), dim3(RS_THREADS), 0, st, (const G711U*)codes, channels, n_frames, out); break;
+    default: sos_set_error("sos_g711_to_mono_f32: unknown law %d", law); return SOS_EINVAL;
+    }
+    return sos_check_launch("sos_g711_to_mono_f32");
 }
 
 // The time register (RsSegs, rs_build_segments) and the arithmetic of one output (rs_output): resample_core.h.

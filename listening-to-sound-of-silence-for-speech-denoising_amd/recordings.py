@@ -19,9 +19,11 @@ from . import transform
 from . import windows
 from .pipeline import FPS, MIN_FRAMES, SR
 
-# the format a source is written back in: (WAVE format tag, stored bits) -> audio_io.ENCODINGS name.  A float64 source is
-# written as f32 (the networks compute in f32 at best).
-_SOURCE_FORMAT = {(1, 8): "u8", (1, 16): "s16", (1, 24): "s24", (1, 32): "s32", (3, 32): "f32", (3, 64): "f32"}
+# the format a source is written back in: (WAVE format tag, stored bits) -> audio_io.ENCODINGS / G711 name.  A float64 source is
+# written as f32 (the networks compute in f32 at best); a G.711 source (telephone audio) comes back as G.711 of its own law.
+_SOURCE_FORMAT = {(1, 8): "u8", (1, 16): "s16", (1, 24): "s24", (1, 32): "s32", (3, 32): "f32", (3, 64): "f32",
+                  (6, 8): "alaw", (7, 8): "ulaw"}
+SAMPLE_FORMATS = {**audio_io.ENCODINGS, **audio_io.G711}         # name -> (code, bytes per element, WAVE format tag, bits)
 
 
 def _model_samples(frames, rate):
@@ -41,9 +43,9 @@ def _check_files(paths, out_dir, sample_format, suffix, link_channels=None, high
     if link_channels is not None and link_channels not in tools.LINK_MODES:
         raise ValueError("denoise_recordings: unknown link_channels %r (None, or one of %s)"
                          % (link_channels, ", ".join(sorted(tools.LINK_MODES))))
-    if sample_format is not None and sample_format not in audio_io.ENCODINGS:
+    if sample_format is not None and sample_format not in SAMPLE_FORMATS:
         raise ValueError("denoise_recordings: unsupported sample_format %r (one of %s)"
-                         % (sample_format, ", ".join(sorted(audio_io.ENCODINGS))))
+                         % (sample_format, ", ".join(sorted(SAMPLE_FORMATS))))
     infos, formats, out_paths = [], [], []
     hop = transform.HOP_LENGTH
     for path in paths:
@@ -110,16 +112,17 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
                        max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None,
                        high_band="drop", smooth_frames=2):
     """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
-    channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32; a float64 source is written as float32);
-    sample_format= ('s16', 's24', 's32', 'u8', 'f32') forces one format for all files.
+    channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32, G.711 A-law / mu-law; a float64 source is written as
+    float32); sample_format= ('s16', 's24', 's32', 'u8', 'f32', 'alaw', 'ulaw') forces one format for all files.
     Per group of files of at most `max_bytes` of decoded f32 samples (ragged.byte_groups): the files are parsed on the host;
-    one upload and one sos_pcm_planes_batch_f32 launch per sample format decode every channel into its own plane; one
+    one upload and one sos_pcm_planes_batch_f32 (G.711: sos_g711_planes_batch_f32) launch per sample format decode every channel
+    into its own plane; one
     resample_batch_device launch per native rate other than 14 kHz brings all channels to the networks' rate; ONE
     windows.denoise_long call runs all channels of all files of the group as recordings (file order, channel order within a
     file; window_seconds, context_seconds, max_batch, max_columns as there); one resample launch per native rate goes back; one
-    sos_pcm_encode_batch launch per output format crops or zero-fills every channel to the source's frame count (the networks
-    return hop * (n // hop) samples and the resampler ceil(n * ratio)) and quantises it -- round half to even, saturating, NO
-    dither; one download brings the group's bytes and counts to the host, and only then are its files written
+    sos_pcm_encode_batch (sos_g711_encode_batch) launch per output format crops or zero-fills every channel to the source's
+    frame count (the networks return hop * (n // hop) samples and the resampler ceil(n * ratio)) and quantises it -- round half
+    to even, saturating, NO dither; G.711 compresses that s16 value and zero-fills with the code of silence; one download brings the group's bytes and counts to the host, and only then are its files written
     (audio_io.wave_container).  No call in the loop waits for the device except that download.
     link_channels: None -- every channel gets its own silent-interval decisions, per window (denoise_long's default mode) -- or
     'any' / 'mean': the channels of a file share ONE decision stream, the group's denoise_long call runs with stitch_bits=True,
@@ -191,7 +194,7 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
         n_windows = np.bincount(plan[:, 0], minlength=len(clips))
         for f in group:
             part, b0, b1, j = spans[f]
-            tag, bits = audio_io.ENCODINGS[formats[f]][2:]
+            tag, bits = SAMPLE_FORMATS[formats[f]][2:]
             blob = audio_io.wave_container(host[part][b0:b1].tobytes(), tag, infos[f]["channels"], infos[f]["rate"], bits)
             with open(out_paths[f], "wb") as fp:
                 fp.write(blob)

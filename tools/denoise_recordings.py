@@ -38,7 +38,8 @@ def main():
     ap.add_argument("--context-seconds", type=float, default=2.0)
     ap.add_argument("--max-batch", type=int, default=256)
     ap.add_argument("--max-columns", type=int, default=65536)
-    ap.add_argument("--sample-format", choices=sorted(audio_io.ENCODINGS), default=None, help="one format for all files (default: each source's)")
+    ap.add_argument("--sample-format", choices=sorted(audio_io.ENCODINGS) + sorted(audio_io.G711), default=None,
+                    help="one format for all files, linear PCM / float or G.711 (default: each source's)")
     ap.add_argument("--suffix", default="")
     ap.add_argument("--link-channels", choices=["any", "mean"], default=None,
                     help="the channels of a file share one stream of silent-interval decisions: a frame is speech if ANY channel has "

@@ -6,10 +6,11 @@ in a temporary directory, in 'mixed' precision:
      and writes included), the spread, files/s and the number of host waits (Tensor.cpu calls) are printed.
   2. the share of a denoise_recordings call that is not denoise_long: the same channels, already decoded and at 14 kHz, through
      denoise_long alone, timed the same way.
-  3. the two kernels of csrc/pcm_io.hip on --kernel-mib MiB of planes (stereo files of 2^20 frames): bytes read plus bytes
-     written per second, from device events over --kernel-reps launches, against Tensor.copy_ of a float32 buffer moving the same
-     number of bytes in the same run; the encode once on planes that never saturate and once on planes of which 9 % do (every
-     workgroup then adds to its file's count).
+  3. the two kernels of csrc/pcm_io.hip on --kernel-mib MiB of planes (stereo files of 2^20 frames), every linear format and
+     both G.711 laws: bytes read plus bytes written per second, from device events over --kernel-reps launches, --kernel-repeats
+     times per row, against Tensor.copy_ of a float32 buffer moving the same number of bytes in the same run; each law also as
+     a ratio to the u8 row, which moves the same bytes through the same accesses; the encode once on planes that never
+     saturate and once on planes of which 9 % do (every workgroup then adds to its file's count).
   4. with --link-channels any|mean: (a) denoise_recordings(link_channels=) against link_channels=None on the same files, both
      warmed, alternating, in the same run of the program -- the linked mode runs denoise_long(stitch_bits=True), a separate
      detector pass, so it is expected to cost more, and the figure is what the shared stream costs; (b) the ONE
@@ -132,27 +133,41 @@ def kernels(args, amplitude):
     L = audio_io.L
     rows = []
     assert torch.equal(audio_io.encode_batch_device(planes[:1], "f32")[0].view(torch.float32), planes[0].T.reshape(-1))
-    for fmt in ("s16", "s24", "s32", "u8", "f32"):
-        code, width = audio_io.ENCODINGS[fmt][:2]
+    for fmt in ("s16", "s24", "s32", "u8", "f32", "alaw", "ulaw"):               # G.711 moves u8's bytes through u8's accesses
+        g711 = fmt in audio_io.G711
+        code, width = (audio_io.G711 if g711 else audio_io.ENCODINGS)[fmt][:2]
+        entry = L.lib().sos_g711_encode_batch if g711 else L.lib().sos_pcm_encode_batch
         tab = np.asarray([[i * ch * frames, frames, ch, frames, i * ch * frames] for i in range(n_files)], dtype=np.int64)
         tab_dev, out = torch.from_numpy(tab).cuda(), torch.empty(samples * width, dtype=torch.uint8, device="cuda")
         counts = torch.empty(n_files, dtype=torch.int64, device="cuda")
-        go = lambda: L.check(L.lib().sos_pcm_encode_batch(L.ptr(flat), L.ptr(tab_dev), tab.ctypes.data_as(L.C.c_void_p), n_files,   # noqa: E731
-                                                          code, L.ptr(out), L.ptr(counts), L.stream_ptr()))
-        rows.append(("encode " + fmt, samples * (4 + width), device_ms(go, args.kernel_reps)))
-    for kind, dtype in (("s16", np.int16), ("s32", np.int32), ("u8", np.uint8), ("f32", np.float32)) if amplitude < 1 else ():
+        go = lambda: L.check(entry(L.ptr(flat), L.ptr(tab_dev), tab.ctypes.data_as(L.C.c_void_p), n_files, code, L.ptr(out),   # noqa: E731
+                                   L.ptr(counts), L.stream_ptr()))
+        rows.append(("encode " + fmt, samples * (4 + width), [device_ms(go, args.kernel_reps) for _ in range(args.kernel_repeats)]))
+    for kind, dtype in (("s16", np.int16), ("s32", np.int32), ("u8", np.uint8), ("f32", np.float32), ("alaw", np.uint8),
+                        ("ulaw", np.uint8)) if amplitude < 1 else ():
+        g711 = kind in audio_io.G711
+        code = audio_io.G711[kind][0] if g711 else audio_io._FMT[kind]
+        entry = L.lib().sos_g711_planes_batch_f32 if g711 else L.lib().sos_pcm_planes_batch_f32
         pcm = torch.zeros(samples, dtype=getattr(torch, np.dtype(dtype).name), device="cuda")
         tab = np.asarray([[i * ch * frames, frames, ch, i * ch * frames] for i in range(n_files)], dtype=np.int64)
         tab_dev, out = torch.from_numpy(tab).cuda(), torch.empty(samples, dtype=torch.float32, device="cuda")
-        go = lambda: L.check(L.lib().sos_pcm_planes_batch_f32(L.ptr(pcm), audio_io._FMT[kind], L.ptr(tab_dev),      # noqa: E731
-                                                              tab.ctypes.data_as(L.C.c_void_p), n_files, L.ptr(out), L.stream_ptr()))
-        rows.append(("decode " + kind, samples * (4 + dtype().itemsize), device_ms(go, args.kernel_reps)))
-    for name, nbytes, ms in rows:
+        go = lambda: L.check(entry(L.ptr(pcm), code, L.ptr(tab_dev), tab.ctypes.data_as(L.C.c_void_p), n_files, L.ptr(out),     # noqa: E731
+                                   L.stream_ptr()))
+        rows.append(("decode " + kind, samples * (4 + dtype().itemsize), [device_ms(go, args.kernel_reps) for _ in range(args.kernel_repeats)]))
+    med = {}
+    for name, nbytes, runs in rows:
         src = torch.empty(nbytes // 8, dtype=torch.float32, device="cuda").normal_()
         dst = torch.empty_like(src)
         copy_ms = device_ms(lambda: dst.copy_(src), args.kernel_reps)
-        print(f"  {name:11s}: {ms:7.3f} ms  {nbytes / ms / 1e6:7.1f} GB/s    Tensor.copy_ of the same bytes: {copy_ms:7.3f} ms  "
-              f"{nbytes / copy_ms / 1e6:7.1f} GB/s    ratio {copy_ms / ms:.2f}")
+        ms = med[name] = float(np.median(runs))
+        print(f"  {name:11s}: {ms:7.3f} ms (min {min(runs):.3f}, max {max(runs):.3f})  {nbytes / ms / 1e6:7.1f} GB/s    Tensor.copy_ of the "
+              f"same bytes: {copy_ms:7.3f} ms  {nbytes / copy_ms / 1e6:7.1f} GB/s    ratio {copy_ms / ms:.2f}")
+    for name, _, runs in rows:                                   # the yardstick of a law is u8 in the same run, with its spread
+        way, fmt = name.split()
+        if fmt in audio_io.G711:
+            u8 = next(r for n, _, r in rows if n == way + " u8")
+            print(f"  {name} / {way} u8 = {med[name] / med[way + ' u8']:.3f}   (u8 over its {len(u8)} repeats: "
+                  f"{min(u8) / med[way + ' u8']:.3f} .. {max(u8) / med[way + ' u8']:.3f} of its median)")
 
 
 def link_launch(args, paths):
@@ -272,6 +287,7 @@ def main():
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--kernel-mib", type=int, default=512)
     ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--kernel-repeats", type=int, default=3, help="measurements per kernel row (median, min, max)")
     ap.add_argument("--amplitudes", type=float, nargs="+", default=[0.9, 1.1], help="encode inputs: nothing saturates below 1")
     ap.add_argument("--skip-loop", action="store_true", help="only the kernels")
     ap.add_argument("--link-channels", choices=["any", "mean"], default=None, help="measure the shared decision stream (4.) and nothing else")
