@@ -523,6 +523,33 @@ int sos_g711_planes_batch_f32(const void* codes, int law, const int64_t* table, 
 int sos_g711_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int law, void* out,
                           int64_t* clipped, sos_stream_t stream);
 int sos_g711_to_mono_f32(const void* codes, int law, int channels, int64_t n_frames, float* out, sos_stream_t stream);
+/* Integrated loudness (ITU-R BS.1770-4 / EBU R128) of a group of files on the planes sos_pcm_encode_batch reads, and the gain
+ * that brings each file to a target (csrc/loudness.hip; sos_amd.metrics.loudness_batch / audio_io.loudness_gain_batch_device;
+ * float64 restatement: tests/loudness_reference.py).  The ragged conventions of the entry points above: the table in two
+ * copies, the host validates its own before any launch, the kernels skip a device row outside the totals the host summed.
+ * Row per file, int64 [nfiles][8] = the encode row {first plane sample, plane length available, channels (1 .. 64), frames,
+ * (the output offset: not read)}, then {hop h = (rate + 5) / 10 samples, index of the file's first channel weight, index of the
+ * file's first chunk}; a file has channels * ceil(frames / h) * split chunks, files in table order.  A sample is the plane's
+ * value below `available` and 0 from there to `frames`, as the encode reads it.
+ * sos_loudness_batch_f64: coef f64 [nfiles][10] = {b0, b1, b2, a1, a2} of the two K-weighting biquads at the file's rate
+ *   (sos_amd.metrics.k_weighting; transposed direct form II, zero initial state), weights f64 [sum of channels].  Blocks of 4 h
+ *   samples every h, whole blocks only: z = sum_c w_c mean(y_c^2), l = -0.691 + 10 log10 z; gates l > -70 and l > (loudness of
+ *   the absolutely gated blocks) - 10.  stats f64 [nfiles][4] = {L = -0.691 + 10 log10(mean z of the blocks passing both), -inf
+ *   without one; max |x| over all channels and frames (the SAMPLE peak); blocks passing both gates; blocks passing the absolute
+ *   one}, {NaN, NaN, -1, -1} for a skipped row.  The filter is evaluated as a chunked linear recurrence, `split` (1 .. 64, at
+ *   most h) chunks per hop; every operation after the load is float64 and every sum has a fixed order.  work: device bytes,
+ *   at least sos_loudness_workspace_bytes(table_host, nfiles, split) (-1 for a table the call would refuse); SOS_ENOSPC below it.
+ * sos_loudness_gain_batch_f32: per file g = min(10^((targets[f] - L) / 20), 10^(ceiling_db / 20) / peak) in double from
+ *   stats[f], stored as f32; g = 1 where L, the peak or the target give none (L = -inf, peak 0, not finite).  Scales the first
+ *   min(frames, available) samples of every channel IN PLACE, x * g in f32; writes gains f32 [nfiles] and limited int32
+ *   [nfiles] (1: the ceiling bound the gain).  Reads columns 0 .. 3 of the table only.  ceiling_db > 0 is refused.
+ * SOS_EINVAL (sos_last_error() names the file): null pointers, nfiles outside 1 .. 65535, split outside 1 .. 64, channels
+ * outside 1 .. 64, negative frames / available, a hop below 1 or below split, or a row outside the totals. */
+int64_t sos_loudness_workspace_bytes(const int64_t* table_host, int nfiles, int split);
+int sos_loudness_batch_f64(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, const double* coef,
+                           const double* weights, int split, void* work, int64_t work_bytes, double* stats, sos_stream_t stream);
+int sos_loudness_gain_batch_f32(float* planes, const int64_t* table, const int64_t* table_host, int nfiles, const double* stats,
+                                const double* targets, double ceiling_db, float* gains, int* limited, sos_stream_t stream);
 /* Band-limited resampling by `ratio` = sr_new / sr_orig (resampy 0.2.2 `resample_f`): win = the filter's half
  * window (nwin floats, num_table samples per zero crossing), already multiplied by min(1, ratio).  Writes
  * out[0 .. n_out): the first floor(n_in * ratio) entries are resampled, the rest zero (librosa pads to

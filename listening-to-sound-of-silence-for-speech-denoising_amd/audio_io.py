@@ -756,6 +756,77 @@ def encode_batch_device(planes, fmt, frames=None):
     return data[:int(offsets[-1])], offsets, clipped
 
 
+def planes_together(planes):
+    """The (channels, n) f32 GPU tensors of a group of files as views into ONE buffer, files back to back: the tensors
+    themselves where they already lie so, views into one copy otherwise."""
+    planes = list(planes)
+    if not planes:
+        return planes
+    flat = _back_to_back(planes)
+    if flat.untyped_storage().data_ptr() == planes[0].untyped_storage().data_ptr():
+        return planes
+    return [v.view(p.shape) for v, p in zip(ragged.split(flat, [p.numel() for p in planes]), planes)]
+
+
+def loudness_gain_batch_device(planes, stats, target, peak_ceiling_db=-1.0, frames=None):
+    """Brings every file of a group to a target loudness, IN PLACE and in one sos_loudness_gain_batch_f32 launch (per 65535
+    files), without a wait.  planes: one (channels, n) f32 GPU tensor per file; stats: what metrics.loudness_batch returned for
+    them (its dict, or the f64 [files][4] rows {L, peak, ..}); target: LUFS, one float for all files or an f64 GPU tensor of one
+    per file (the 'source' mode hands over the loudness it measured, still on the device); peak_ceiling_db: dBFS (<= 0) the
+    SAMPLE peak of the scaled file may reach; frames: samples per channel to scale per file (default n; what lies past them
+    keeps its value).  Per file, in float64, g = min(10^((target - L) / 20), 10^(ceiling / 20) / peak), stored as float32; g = 1
+    where L is -inf (no block passed the gates), the peak is 0 or the target is not finite; out = x * g, one float32 multiply.
+    -> (gains f32 [files], limited bool [files]: the ceiling bound the gain), on the device.  Float64 restatement:
+    tests/loudness_reference.py."""
+    planes = list(planes)
+    for i, p in enumerate(planes):
+        if not torch.is_tensor(p) or p.dim() != 2 or p.dtype != torch.float32 or not 1 <= p.shape[0] <= 64:
+            raise ValueError("loudness_gain_batch_device: file %d must be a (1 .. 64 channels, n) float32 tensor" % i)
+    rows = stats["rows"] if isinstance(stats, dict) else stats
+    if not torch.is_tensor(rows) or rows.dtype != torch.float64 or tuple(rows.shape) != (len(planes), 4):
+        raise ValueError("loudness_gain_batch_device: stats holds one float64 row of 4 per file (metrics.loudness_batch)")
+    if torch.is_tensor(target):
+        if target.dtype != torch.float64 or tuple(target.shape) != (len(planes),):
+            raise ValueError("loudness_gain_batch_device: a target tensor holds one float64 per file")
+    elif not np.isfinite(float(target)):
+        raise ValueError("loudness_gain_batch_device: the target is a finite number of LUFS, got %r" % (target,))
+    if not float(peak_ceiling_db) <= 0.0:
+        raise ValueError("loudness_gain_batch_device: the ceiling is at most 0 dBFS, got %r" % (peak_ceiling_db,))
+    frames = [int(p.shape[1]) for p in planes] if frames is None else [int(f) for f in frames]
+    if len(frames) != len(planes) or min(frames, default=0) < 0:
+        raise ValueError("loudness_gain_batch_device: frames holds one non-negative count per file")
+    L.require_cuda(rows, *planes)
+    if not planes:
+        return torch.zeros(0, dtype=torch.float32, device="cuda"), torch.zeros(0, dtype=torch.bool, device="cuda")
+    device = planes[0].device
+    if torch.is_tensor(target):
+        L.require_cuda(target)
+        targets = target.contiguous()
+    else:
+        targets = torch.full((len(planes),), float(target), dtype=torch.float64, device=device)
+    rows = rows.contiguous()
+    chans = np.asarray([p.shape[0] for p in planes], dtype=np.int64)
+    avail = np.asarray([p.shape[1] for p in planes], dtype=np.int64)
+    together = planes_together(planes) if int((chans * avail).sum()) else planes
+    flat = _back_to_back(together) if int((chans * avail).sum()) else torch.zeros(1, dtype=torch.float32, device=device)
+    src = ragged.offsets(chans * avail)
+    gains = torch.empty(len(planes), dtype=torch.float32, device=device)
+    limited = torch.empty(len(planes), dtype=torch.int32, device=device)
+    h = L.lib()
+    for c0 in range(0, len(planes), ragged.MAX_CLIPS):
+        c1 = min(c0 + ragged.MAX_CLIPS, len(planes))
+        tab = np.zeros((c1 - c0, 8), dtype=np.int64)
+        tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 3] = src[c0:c1] - src[c0], avail[c0:c1], chans[c0:c1], frames[c0:c1]
+        tab_dev = torch.from_numpy(tab).to(device)
+        L.check(h.sos_loudness_gain_batch_f32(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0,
+                                              L.ptr(rows[c0:]), L.ptr(targets[c0:]), float(peak_ceiling_db), L.ptr(gains[c0:]),
+                                              L.ptr(limited[c0:]), L.stream_ptr()), "sos_loudness_gain_batch_f32")
+    for p, t in zip(planes, together):
+        if t is not p:                                  # the planes lay apart: the launch scaled their copy
+            p.copy_(t)
+    return gains, limited.bool()
+
+
 def g711_decode_device(codes, law):
     """One chunk of a G.711 leg (a packet's payload): codes 1-D uint8 (GPU tensor, numpy array or bytes), law 'alaw' / 'ulaw' ->
     1-D f32 GPU tensor, what decode_planes_batch_device gives a one-channel file.  The rule has no state: the chunks of a signal

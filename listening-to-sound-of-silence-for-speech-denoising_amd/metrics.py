@@ -16,6 +16,10 @@ fills in STOI).  SI-SDR (`si_sdr`, `si_sdr_batch`: the formula of the project's 
 the BSS-eval SDR (`sdr`, `sdr_batch`: mir_eval's bss_eval_sources with one source, a 512-tap distortion filter) of ragged batches
 run in HIP too (csrc/sdr.hip): float64 sums, lag correlations and Levinson-Durbin solve, one launch sequence per measure;
 float64 restatement tests/sdr_reference.py, parity against mir_eval itself unpinned (not installed here).
+ITU-R BS.1770 / EBU R128 integrated loudness (`loudness`, `loudness_batch`, `k_weighting`) of ragged batches of multi-channel
+files runs in HIP too (csrc/loudness.hip): the K-weighting recurrence as a chunked scan in float64, the two gates on the device,
+one launch sequence and no wait; float64 restatement tests/loudness_reference.py, held against the standard's 48 kHz table and
+the EBU Tech 3341 signals.
 `evaluate_metrics_batch` scores a ragged batch of clips in one launch sequence (csrc/metrics_batch.hip) with the per-frame
 arithmetic of the one-clip kernels.  Signals: 1-D numpy arrays or GPU tensors.  No CPU fallback."""
 import ctypes as C
@@ -504,3 +508,131 @@ def sdr(clean, estimate, filter_length=SDR_FILTER_LENGTH, return_detail=False):
     """sdr_batch of one clip."""
     res = sdr_batch([clean], [estimate], filter_length, return_detail)
     return (res[0][0], res[1][0]) if return_detail else res[0]
+
+
+# ---- ITU-R BS.1770 / EBU R128 integrated loudness (csrc/loudness.hip)
+LOUDNESS_SPLIT = 8                  # chunks per 100 ms hop of the filter scan (1 .. 64, at most the hop): short files fill more lanes
+LOUDNESS_COLS = 8                   # int64 per file of the table (include/sos_hip.h: sos_loudness_batch_f64)
+
+
+def k_weighting(sr):
+    """The K-weighting filter of ITU-R BS.1770 at `sr` Hz: float64 [10] = {b0, b1, b2, a1, a2} of the high shelf, then of the
+    high-pass (a0 = 1), from the closed forms libebur128 uses; at 48 kHz the standard's table to 1e-12."""
+    sr = float(sr)
+    if not math.isfinite(sr) or sr <= 0:
+        raise ValueError("k_weighting: the rate is a positive number of Hz, got %r" % (sr,))
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / sr)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+             2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    return np.asarray(shelf + [1.0, -2.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], dtype=np.float64)
+
+
+def loudness_hop(sr):
+    """Samples of a 100 ms hop at `sr` Hz as libebur128 rounds it; a gating block is four hops."""
+    return (int(sr) + 5) // 10
+
+
+def loudness_table(chans, avail, frames, hops, split=LOUDNESS_SPLIT):
+    """The host table of sos_loudness_batch_f64 / sos_loudness_gain_batch_f32 for files whose planes lie back to back: int64
+    [files][8] = {first plane sample, plane length, channels, frames, 0, hop, first weight, first chunk}."""
+    chans, avail, frames, hops = (np.asarray(v, dtype=np.int64) for v in (chans, avail, frames, hops))
+    chunks = chans * -(-frames // np.maximum(hops, 1)) * split
+    return np.ascontiguousarray(np.stack([ragged.offsets(chans * avail), avail, chans, frames, np.zeros_like(chans), hops,
+                                          ragged.offsets(chans), ragged.offsets(chunks)], axis=1), dtype=np.int64)
+
+
+def _loudness_weights(channel_weights, planes, who):
+    """One float64 weight per channel of every file, files in order (1.0 where the caller gives none)."""
+    if channel_weights is None:
+        channel_weights = [None] * len(planes)
+    channel_weights = list(channel_weights)
+    if len(channel_weights) != len(planes):
+        raise ValueError("%s: channel_weights holds one entry per file (%d files, %d entries)" % (who, len(planes), len(channel_weights)))
+    out = []
+    for i, (w, p) in enumerate(zip(channel_weights, planes)):
+        w = np.ones(p.shape[0]) if w is None else np.asarray(w, dtype=np.float64).reshape(-1)
+        if w.size != p.shape[0] or not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("%s: file %d has %d channels and needs as many finite weights >= 0, got %r" % (who, i, p.shape[0], w.tolist()))
+        out.append(w)
+    return out
+
+
+def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDNESS_SPLIT):
+    """Integrated loudness (ITU-R BS.1770-4 / EBU R128, gated) of every file of a ragged batch.  planes: one (channels, n) f32
+    GPU tensor per file, 1 .. 64 channels; rates: its sample rate in Hz (one per file, or one for all); channel_weights: per file
+    None (every channel counts 1.0: exact for mono and stereo) or one weight >= 0 per channel (surround: 1.41 for the rear pair,
+    0 for the LFE -- the caller's to pass); frames: samples per channel that count, per file (default n; past n the file reads
+    0, below n it is cropped: what encode_batch_device writes).
+    Per channel the K-weighting filter (k_weighting(rate), zero state, float64); blocks of 4 h samples every h = (rate + 5) // 10,
+    whole blocks only; z = sum over channels of weight * mean square; l = -0.691 + 10 log10 z; the absolute gate l > -70, the
+    relative gate l > (loudness of the absolutely gated blocks) - 10; L = -0.691 + 10 log10(mean z of the blocks passing both),
+    -inf when none passes.  -> dict of per-file tensors STILL ON THE DEVICE: lufs (f64), peak (f64: max |x| over all channels and
+    frames, the SAMPLE peak, not the true peak), blocks / blocks_abs (int64: blocks passing both gates / the absolute one) and
+    rows (f64 [files][4], what audio_io.loudness_gain_batch_device reads).  One launch sequence per 65535 files
+    (sos_loudness_batch_f64), no wait.  `split`: chunks per hop of the filter scan; it moves the result by rounding only.
+    ValueError before any launch: a file that is not such a tensor, a rate below 10 * split Hz, bad weights or frames."""
+    from . import audio_io
+    planes, who = list(planes), "loudness_batch"
+    for i, p in enumerate(planes):
+        if not torch.is_tensor(p) or p.dim() != 2 or p.dtype != torch.float32 or not 1 <= p.shape[0] <= 64:
+            raise ValueError("%s: file %d must be a (1 .. 64 channels, n) float32 tensor" % (who, i))
+    rates = [rates] * len(planes) if np.ndim(rates) == 0 else list(rates)
+    if len(rates) != len(planes):
+        raise ValueError("%s: one rate per file (%d files, %d rates)" % (who, len(planes), len(rates)))
+    if isinstance(split, bool) or int(split) != split or not 1 <= split <= 64:
+        raise ValueError("%s: split is a whole number within 1 .. 64, got %r" % (who, split))
+    for i, r in enumerate(rates):
+        if isinstance(r, bool) or int(r) != r or not split <= loudness_hop(r) <= 1 << 31:
+            raise ValueError("%s: file %d has the rate %r (a whole number of Hz, its 100 ms hop at least %d samples)" % (who, i, r, split))
+    weights = _loudness_weights(channel_weights, planes, who)
+    frames = [int(p.shape[1]) for p in planes] if frames is None else [int(f) for f in frames]
+    if len(frames) != len(planes) or min(frames, default=0) < 0:
+        raise ValueError("%s: frames holds one non-negative count per file" % who)
+    L.require_cuda(*planes)
+    if not planes:
+        rows = torch.zeros((0, 4), dtype=torch.float64, device="cuda")
+    else:
+        device = planes[0].device
+        chans, avail = [p.shape[0] for p in planes], [p.shape[1] for p in planes]
+        flat = audio_io._back_to_back(planes) if sum(c * a for c, a in zip(chans, avail)) else torch.zeros(1, dtype=torch.float32, device=device)
+        src = ragged.offsets(np.asarray(chans, dtype=np.int64) * np.asarray(avail, dtype=np.int64))
+        coef = torch.from_numpy(np.stack([k_weighting(r) for r in rates])).to(device)
+        rows = torch.empty((len(planes), 4), dtype=torch.float64, device=device)
+        h = L.lib()
+        for c0 in range(0, len(planes), ragged.MAX_CLIPS):
+            c1 = min(c0 + ragged.MAX_CLIPS, len(planes))
+            tab = loudness_table(chans[c0:c1], avail[c0:c1], frames[c0:c1], [loudness_hop(r) for r in rates[c0:c1]], int(split))
+            need = h.sos_loudness_workspace_bytes(tab.ctypes.data_as(C.c_void_p), c1 - c0, int(split))
+            if need < 0:
+                L.check(-22, "sos_loudness_workspace_bytes")
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            w = torch.from_numpy(np.concatenate(weights[c0:c1])).to(device)
+            tab_dev = torch.from_numpy(tab).to(device)
+            L.check(h.sos_loudness_batch_f64(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0,
+                                             L.ptr(coef[c0:]), L.ptr(w), int(split), L.ptr(ws), ws.numel(), L.ptr(rows[c0:]),
+                                             L.stream_ptr()), "sos_loudness_batch_f64")
+    return dict(lufs=rows[:, 0], peak=rows[:, 1], blocks=rows[:, 2].to(torch.int64), blocks_abs=rows[:, 3].to(torch.int64), rows=rows)
+
+
+def loudness(x, sr, channel_weights=None):
+    """loudness_batch of one clip: x 1-D or (channels, n), a numpy array or a GPU tensor -> dict(lufs, peak, blocks, blocks_abs)
+    of Python numbers (one wait)."""
+    if np.ndim(x) not in (1, 2):
+        raise ValueError("loudness: x is 1-D or (channels, n), got %d dimensions" % np.ndim(x))
+    if torch.is_tensor(x):
+        L.require_cuda(x)
+        y = x.detach().float().contiguous()
+    elif not torch.cuda.is_available():
+        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
+    else:
+        y = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).cuda()
+    r = loudness_batch([y.reshape(1, -1) if y.dim() == 1 else y.contiguous()], [sr], None if channel_weights is None else [channel_weights])
+    lufs, peak, n_rel, n_abs = r["rows"][0].cpu().tolist()
+    return dict(lufs=lufs, peak=peak, blocks=int(n_rel), blocks_abs=int(n_abs))

@@ -5,7 +5,8 @@ between them (windows.denoise_long(stitch_bits=True, link=): one sos_window_fram
 that the noise floors of a stereo pair drop in and out together.  The decode, the two resamplings, the windows
 and the encode each run in launches shared by all files and channels of a group (csrc/pcm_io.hip, csrc/wave_io.hip,
 csrc/ragged_window.hip).  The networks run at 14 kHz: by default a file of a higher rate comes back band-limited to 7 kHz;
-high_band='keep' / 'follow' merge the band above 7 kHz of the source back in (csrc/band_merge.hip)."""
+high_band='keep' / 'follow' merge the band above 7 kHz of the source back in (csrc/band_merge.hip).  loudness= brings every
+written file to a target integrated loudness (ITU-R BS.1770 / EBU R128, csrc/loudness.hip) by one gain per file before the encode."""
 import os
 
 import numpy as np
@@ -13,6 +14,7 @@ import torch
 
 from . import audio_io
 from . import labels
+from . import metrics
 from . import ragged
 from . import tools
 from . import transform
@@ -64,6 +66,43 @@ def _check_files(paths, out_dir, sample_format, suffix, link_channels=None, high
     return infos, formats, out_paths
 
 
+def _check_loudness(loudness, peak_ceiling_db, channel_weights):
+    """What can be refused from the three levelling arguments alone."""
+    if loudness is None:
+        return
+    if loudness != "source":
+        ok = not isinstance(loudness, (bool, str)) and np.ndim(loudness) == 0 and np.isfinite(float(loudness))
+        if not ok or not -70.0 <= float(loudness) <= 0.0:
+            raise ValueError("denoise_recordings: loudness is None, 'source' or a target within -70 .. 0 LUFS, got %r" % (loudness,))
+    ok = not isinstance(peak_ceiling_db, (bool, str)) and np.ndim(peak_ceiling_db) == 0 and np.isfinite(float(peak_ceiling_db))
+    if not ok or float(peak_ceiling_db) > 0.0:
+        raise ValueError("denoise_recordings: peak_ceiling_db is a finite level of at most 0 dBFS, got %r" % (peak_ceiling_db,))
+    if channel_weights is not None:
+        tables = channel_weights.values() if isinstance(channel_weights, dict) else [channel_weights]
+        for w in tables:
+            w = np.asarray(w, dtype=np.float64)
+            if w.ndim != 1 or not 1 <= w.size <= 64 or not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("denoise_recordings: channel_weights holds 1 .. 64 finite weights >= 0, got %r" % (w.tolist(),))
+        if isinstance(channel_weights, dict):
+            for k, w in channel_weights.items():
+                if len(w) != k:
+                    raise ValueError("denoise_recordings: channel_weights[%r] holds %d weights" % (k, len(w)))
+
+
+def _file_weights(channel_weights, infos, paths):
+    """The weights of every file (None: all 1.0): a sequence serves every file and must have its channel count, a dict
+    {channels: weights} the files of that many channels."""
+    if channel_weights is None:
+        return [None] * len(infos)
+    if isinstance(channel_weights, dict):
+        return [channel_weights.get(i["channels"]) for i in infos]
+    for i, p in zip(infos, paths):
+        if i["channels"] != len(channel_weights):
+            raise ValueError("%s: %d channels, but channel_weights holds %d weights (give {channels: weights} for a folder of "
+                             "mixed layouts)" % (p, i["channels"], len(channel_weights)))
+    return [channel_weights] * len(infos)
+
+
 def _resample_back(clips, rates):
     """Every clip whose file's rate differs from SR back to that rate: one resample_batch_device launch per rate."""
     by_rate = {}
@@ -110,7 +149,7 @@ def _merge_back(natives, lows_in, lows_out, rates, high_band, smooth_frames):
 @torch.no_grad()
 def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, context_seconds=2.0, max_batch=256,
                        max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None,
-                       high_band="drop", smooth_frames=2):
+                       high_band="drop", smooth_frames=2, loudness=None, peak_ceiling_db=-1.0, channel_weights=None):
     """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
     channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32, G.711 A-law / mu-law; a float64 source is written as
     float32); sample_format= ('s16', 's24', 's32', 'u8', 'f32', 'alaw', 'ulaw') forces one format for all files.
@@ -139,14 +178,32 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     in the silent intervals too; it assumes the high band's noise comes and goes with the low band's.  The last < hop samples
     at 14 kHz have no output of the networks (zero-filled today): 'follow' fades the high band out there, 'keep' leaves it in.
     Files at 14 kHz or below have no such band and are written with the same bytes under every mode.
+    loudness: None (the default: nothing below runs and the written bytes are what they were), a target in LUFS (-70 .. 0) or
+    'source'.  Removing the noise changes a file's level; with a target every written file is brought to that INTEGRATED
+    LOUDNESS (ITU-R BS.1770-4 / EBU R128, gated: metrics.loudness_batch, csrc/loudness.hip), measured on the planes exactly as
+    the encode reads them (cropped / zero-filled to the source's frame count), just before the encode: one measuring launch
+    sequence and one gain launch per group (audio_io.loudness_gain_batch_device), the planes scaled by ONE float32 gain per
+    file before any encoder sees them -- every output format, G.711 included, so the integer formats keep their single
+    rounding.  g = min(10^((target - L) / 20), 10^(peak_ceiling_db / 20) / sample peak); peak_ceiling_db (default -1 dBFS, at
+    most 0) bounds the SAMPLE peak, not the true peak; a file without a block above the gates keeps g = 1.  'source': each
+    file's target is the integrated loudness of its own decoded source at its native rate (the group then keeps the native
+    planes, as high_band does, and measures them in the same launch sequence as the outputs); a silent source leaves g = 1.
+    channel_weights: None (every channel counts 1.0: exact for mono and stereo), one weight >= 0 per channel for all files, or
+    {channels: weights} (surround: 1.41 for the rear pair and 0 for the LFE are the caller's to pass).  The rows join the
+    group's one download.
     -> one dict per file: path, out_path, channels, rate, frames, format, clipped (samples that saturated or were NaN, all
-    channels), windows (denoise_long windows, all channels).
+    channels), windows (denoise_long windows, all channels); with loudness also loudness_before (LUFS of the denoised file
+    before the gain, -inf without a gated block), loudness (before + 20 log10 g, not measured again), loudness_target, gain_db
+    and peak_limited (the ceiling bound the gain).
     ValueError before any launch of the call, naming the file: fewer than MIN_FRAMES STFT frames at 14 kHz, an unsupported
     format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format, link_channels or
-    high_band, smooth_frames outside 0 .. 16;
+    high_band, smooth_frames outside 0 .. 16; a loudness that is not finite or outside -70 .. 0, a ceiling above 0, weights that are
+    negative or not one per channel;
     window_plan's argument rules; a group with more than 65535 windows."""
     paths = [os.fspath(p) for p in paths]
+    _check_loudness(loudness, peak_ceiling_db, channel_weights)
     infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix, link_channels, high_band, smooth_frames)
+    weights = _file_weights(channel_weights, infos, paths) if loudness is not None else None
     core, context = windows._hops(round(window_seconds * SR)), windows._hops(round(context_seconds * SR))
     groups = ragged.byte_groups([4 * i["frames"] * i["channels"] for i in infos], max_bytes)
     plans = []                                          # host only: refuses bad window arguments and a group of too many windows
@@ -160,7 +217,7 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     results = []
     for group, plan in zip(groups, plans):
         merge = high_band != "drop" and any(infos[f]["rate"] > SR for f in group)
-        if merge:                                       # the native planes stay: the merge reads them
+        if merge or loudness == "source":               # the native planes stay: the merge reads them, 'source' measures them
             ys, _, _ = audio_io.load_channels_batch_device([paths[f] for f in group], sr=None)
             natives = [y[c] for y in ys for c in range(y.shape[0])]
             clips = _to_model_rate(natives, [infos[f]["rate"] for f, y in zip(group, ys) for _ in range(y.shape[0])])
@@ -184,6 +241,20 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
         for f in group:
             by_format.setdefault(formats[f], []).append(f)
         parts, spans = [], {}
+        if loudness is not None:                        # measure what the encode will read, scale it, encode as before
+            level = audio_io.planes_together([per_file[f] for f in group])
+            per_file.update(zip(group, level))
+            frames, rates_g = [infos[f]["frames"] for f in group], [infos[f]["rate"] for f in group]
+            w = [weights[f] for f in group]
+            if loudness == "source":
+                rows = metrics.loudness_batch(level + list(ys), rates_g * 2, w * 2, frames * 2)["rows"]
+                target = rows.new_empty(len(group)).copy_(rows[len(group):, 0])      # packed, whatever the group's size
+            else:
+                rows = metrics.loudness_batch(level, rates_g, w, frames)["rows"]
+                target = torch.full((len(group),), float(loudness), dtype=torch.float64, device=rows.device)
+            gains, limited = audio_io.loudness_gain_batch_device(level, rows[:len(group)], target, peak_ceiling_db, frames=frames)
+            parts += [rows[:len(group)].contiguous().view(torch.uint8).reshape(-1), target.view(torch.uint8),
+                      gains.view(torch.uint8), limited.view(torch.uint8)]
         for fmt, files in by_format.items():
             data, offsets, clipped = audio_io.encode_batch_device([per_file[f] for f in files], fmt,
                                                                   frames=[infos[f]["frames"] for f in files])
@@ -192,7 +263,12 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
             parts += [data, clipped.view(torch.uint8)]
         host = ragged.split(torch.cat(parts).cpu().numpy(), [p.numel() for p in parts])            # the group's one download
         n_windows = np.bincount(plan[:, 0], minlength=len(clips))
-        for f in group:
+        if loudness is not None:
+            rows_h, target_h, gains_h, limited_h = host[0].view(np.float64).reshape(-1, 4), host[1].view(np.float64), \
+                host[2].view(np.float32), host[3].view(np.bool_)
+            if np.any(rows_h[:, 2] < 0):
+                raise RuntimeError("sos_loudness_batch_f64: device rows disagree with the host's")
+        for g, f in enumerate(group):
             part, b0, b1, j = spans[f]
             tag, bits = SAMPLE_FORMATS[formats[f]][2:]
             blob = audio_io.wave_container(host[part][b0:b1].tobytes(), tag, infos[f]["channels"], infos[f]["rate"], bits)
@@ -201,4 +277,8 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
             results.append(dict(path=paths[f], out_path=out_paths[f], channels=infos[f]["channels"], rate=infos[f]["rate"],
                                 frames=infos[f]["frames"], format=formats[f], clipped=int(host[part + 1].view(np.int64)[j]),
                                 windows=int(sum(n_windows[k] for k, o in enumerate(owner) if o == f))))
+            if loudness is not None:
+                gain_db = 20.0 * float(np.log10(np.float64(gains_h[g])))
+                results[-1].update(loudness_before=float(rows_h[g, 0]), loudness=float(rows_h[g, 0]) + gain_db,
+                                   loudness_target=float(target_h[g]), gain_db=gain_db, peak_limited=bool(limited_h[g]))
     return results

@@ -3,9 +3,13 @@ count, channels, rate and sample format.
 
   python tools/denoise_recordings.py DETECTOR.pth DENOISER.pth OUT_DIR in1.wav in2.wav ... [--sample-format s16] [--suffix _dn]
                                      [--link-channels any] [--high-band keep|follow] [--smooth-frames 2]
+                                     [--loudness -23|source] [--peak-ceiling-db -1]
 
 The networks run at 14 kHz: by default (--high-band drop) a 44.1 / 48 kHz file comes back band-limited to 7 kHz.  --high-band keep
 passes the source's band above 7 kHz through untouched; --high-band follow gives it the attenuation the denoiser applied below.
+
+--loudness brings every written file to a target integrated loudness in LUFS (ITU-R BS.1770 / EBU R128), or with `source` to the
+loudness its source had, by one gain per file applied before the samples are quantised; --peak-ceiling-db bounds the sample peak.
 
 The checkpoints are the reference's (`{clock, model_state_dict, ...}` as the agents save them) or bare state dicts."""
 import argparse
@@ -28,6 +32,10 @@ def _load(net, path):
     return net.cuda().eval()
 
 
+def _loudness(text):
+    return "source" if text == "source" else float(text)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("detector", help="checkpoint of the silent-interval detector")
@@ -48,6 +56,10 @@ def main():
                     help="the band above 7 kHz of files above 14 kHz: drop it (default: the output is band-limited to 7 kHz), keep it "
                          "untouched, or let it follow the attenuation the denoiser applied to the low band")
     ap.add_argument("--smooth-frames", type=int, default=2, help="--high-band follow: gains are averaged over 2 K + 1 hop frames (0 .. 16)")
+    ap.add_argument("--loudness", type=_loudness, default=None,
+                    help="target integrated loudness in LUFS (-70 .. 0), or 'source': the loudness of each file's own source "
+                         "(default: the level the networks return)")
+    ap.add_argument("--peak-ceiling-db", type=float, default=-1.0, help="--loudness: the sample peak a levelled file may reach, dBFS (<= 0)")
     ap.add_argument("--precision", default="mixed", choices=["bf16", "bf16x3", "fp16", "mixed"])
     args = ap.parse_args()
     det, jm = _load(dnet.get_network(), args.detector), _load(jnet.get_network(MyConfig()), args.denoiser)
@@ -55,9 +67,12 @@ def main():
     for r in recordings.denoise_recordings(det, jm, args.files, args.out_dir, args.window_seconds, args.context_seconds, args.max_batch,
                                            args.max_columns, sample_format=args.sample_format, suffix=args.suffix,
                                            link_channels=args.link_channels, high_band=args.high_band,
-                                           smooth_frames=args.smooth_frames):
-        print("%s -> %s: %d x %d frames at %d Hz, %s, %d windows, %d samples clipped"
-              % (r["path"], r["out_path"], r["channels"], r["frames"], r["rate"], r["format"], r["windows"], r["clipped"]))
+                                           smooth_frames=args.smooth_frames, loudness=args.loudness,
+                                           peak_ceiling_db=args.peak_ceiling_db):
+        level = "" if args.loudness is None else ", %.2f -> %.2f LUFS (%+.2f dB%s)" % (
+            r["loudness_before"], r["loudness"], r["gain_db"], ", peak-limited" if r["peak_limited"] else "")
+        print("%s -> %s: %d x %d frames at %d Hz, %s, %d windows, %d samples clipped%s"
+              % (r["path"], r["out_path"], r["channels"], r["frames"], r["rate"], r["format"], r["windows"], r["clipped"], level))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,125 @@
+"""Loudness benchmark (run on the GPU box), 'mixed' precision, the files of tools/recordings_bench.py (N stereo 16-bit recordings
+of 1 .. 10 s at 44.1 kHz, seeded):
+  1. recordings.denoise_recordings(loudness=-23) against loudness=None on the same files, both warmed, alternating, --repeats
+     times each: median wall time from an idle device to an idle device (file reads and writes included), spread, host waits.
+  2. the measure sequence (sos_loudness_batch_f64: four launches) and the gain launch (sos_loudness_gain_batch_f32) alone, from
+     device events over --kernel-reps calls, --kernel-repeats times per row, on the planes of those files and on --kernel-mib
+     MiB of planes (stereo files of 2^20 frames), next to Tensor.copy_ moving the bytes each must move at the least: the measure
+     sequence reads the planes twice (8 bytes per sample, counted as a copy of 4), the gain reads and writes them once.  Each
+     twice: the Python call (table, coefficients and weights built and uploaded per call) and the C entry point with all of
+     that already on the device; the entry point's rows are checked to be the Python call's.
+A measurement: nothing is asserted."""
+import argparse
+import os
+import sys
+import tempfile
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import recordings_bench as RB  # noqa: E402
+import sos_amd  # noqa: E402
+from oracle import nets as onet  # noqa: E402
+from sos_amd import audio_io, metrics, recordings  # noqa: E402
+from sos_amd.common import MyConfig  # noqa: E402
+from sos_amd.denoiser import networks as jnet  # noqa: E402
+from sos_amd.detector import networks as dnet  # noqa: E402
+
+
+def launches(name, planes, rate, args):
+    samples = sum(p.numel() for p in planes)
+    rates = [rate] * len(planes)
+    stats = metrics.loudness_batch(planes, rates)
+    unit = torch.zeros(len(planes), dtype=torch.float64, device="cuda")                 # target = L: g = 1, the planes keep their level
+    rows = []
+    for split in args.splits:
+        go = lambda: metrics.loudness_batch(planes, rates, split=split)                  # noqa: E731
+        rows.append(("measure, split %d" % split, [RB.device_ms(go, args.kernel_reps) for _ in range(args.kernel_repeats)]))
+    go = lambda: audio_io.loudness_gain_batch_device(planes, stats["rows"], stats["lufs"].contiguous() + unit, 0.0)   # noqa: E731
+    rows.append(("gain", [RB.device_ms(go, args.kernel_reps) for _ in range(args.kernel_repeats)]))
+    # the entry points themselves: table, coefficients, weights and work buffer already on the device
+    L, h = audio_io.L, audio_io.L.lib()
+    flat = audio_io._back_to_back(planes)
+    chans, avail = [p.shape[0] for p in planes], [p.shape[1] for p in planes]
+    coef = torch.from_numpy(np.stack([metrics.k_weighting(rate)] * len(planes))).cuda()
+    w = torch.ones(sum(chans), dtype=torch.float64, device="cuda")
+    out = torch.empty((len(planes), 4), dtype=torch.float64, device="cuda")
+    for split in args.splits:
+        tab = metrics.loudness_table(chans, avail, avail, [metrics.loudness_hop(rate)] * len(planes), split)
+        tab_dev = torch.from_numpy(tab).cuda()
+        ws = torch.empty(h.sos_loudness_workspace_bytes(tab.ctypes.data_as(L.C.c_void_p), len(planes), split), dtype=torch.uint8, device="cuda")
+        go = lambda: L.check(h.sos_loudness_batch_f64(L.ptr(flat), L.ptr(tab_dev), tab.ctypes.data_as(L.C.c_void_p), len(planes), L.ptr(coef),   # noqa: E731
+                                                      L.ptr(w), split, L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()))
+        rows.append(("  entry, split %d" % split, [RB.device_ms(go, args.kernel_reps) for _ in range(args.kernel_repeats)]))
+        assert torch.equal(out, metrics.loudness_batch(planes, rates, split=split)["rows"])
+    gains = torch.empty(len(planes), dtype=torch.float32, device="cuda")
+    flags = torch.empty(len(planes), dtype=torch.int32, device="cuda")
+    targets = stats["lufs"].contiguous() + unit
+    go = lambda: L.check(h.sos_loudness_gain_batch_f32(L.ptr(flat), L.ptr(tab_dev), tab.ctypes.data_as(L.C.c_void_p), len(planes),          # noqa: E731
+                                                       L.ptr(stats["rows"]), L.ptr(targets), 0.0, L.ptr(gains), L.ptr(flags), L.stream_ptr()))
+    rows.append(("  entry, gain", [RB.device_ms(go, args.kernel_reps) for _ in range(args.kernel_repeats)]))
+    src = torch.empty(samples, dtype=torch.float32, device="cuda").normal_()
+    dst = torch.empty_like(src)
+    copy = [RB.device_ms(lambda: dst.copy_(src), args.kernel_reps) for _ in range(args.kernel_repeats)]
+    copy_ms = float(np.median(copy))
+    print(f"{name}: {len(planes)} files, {samples * 4 / 2**20:.1f} MiB of planes, {args.kernel_reps} calls per measurement, "
+          f"{args.kernel_repeats} measurements per row (median, min, max); 'measure' / 'gain' are the Python calls with their "
+          "table uploads, 'entry' rows the C entry points with everything already on the device")
+    print(f"  Tensor.copy_ of the planes (one read, one write): {copy_ms:8.3f} ms (min {min(copy):.3f}, max {max(copy):.3f})  "
+          f"{samples * 8 / copy_ms / 1e6:7.1f} GB/s")
+    for what, runs in rows:
+        ms = float(np.median(runs))
+        print(f"  {what:17s}: {ms:8.3f} ms (min {min(runs):.3f}, max {max(runs):.3f})  {samples * 8 / ms / 1e6:7.1f} GB/s of the 8 bytes per "
+              f"sample it must move   {ms / copy_ms:6.2f} x the copy")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--max-batch", type=int, default=64)
+    ap.add_argument("--target", type=float, default=-23.0)
+    ap.add_argument("--kernel-mib", type=int, default=512)
+    ap.add_argument("--kernel-reps", type=int, default=10)
+    ap.add_argument("--kernel-repeats", type=int, default=3)
+    ap.add_argument("--splits", type=int, nargs="+", default=[metrics.LOUDNESS_SPLIT])
+    ap.add_argument("--skip-calls", action="store_true", help="only the launches")
+    args = ap.parse_args()
+    print(torch.cuda.get_device_name(0))
+    RB._count_downloads()
+    with tempfile.TemporaryDirectory() as tmp:
+        paths, secs = RB.make_files(tmp, args.files, args.seed)
+        if not args.skip_calls:
+            det = dnet.get_network()
+            det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+            jm = jnet.get_network(MyConfig())
+            jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+            det, jm = det.cuda().eval(), jm.cuda().eval()
+            sos_amd.set_precision("mixed")
+            forms = dict(none=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "none"), max_batch=args.max_batch),
+                         level=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "level"), max_batch=args.max_batch,
+                                                                     loudness=args.target))
+            for fn in forms.values():                                                     # warm-up of both forms
+                fn()
+            runs = {k: [] for k in forms}
+            for _ in range(args.repeats):                                                 # the forms alternate
+                for k, fn in forms.items():
+                    runs[k].append(RB.once(fn))
+            print(f"{args.files} stereo s16 files at {RB.RATE} Hz, {secs:.0f} s of audio x 2 channels, 'mixed' precision, {args.repeats} "
+                  "alternating repeats (median, min, max)")
+            a = RB.report("loudness=None", args.files, runs["none"])
+            b = RB.report("loudness=%g" % args.target, args.files, runs["level"])
+            print(f"  levelled / plain = {b / a:.3f}")
+            sos_amd.set_precision("bf16")
+        ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
+        launches("the files' planes", ys, RB.RATE, args)
+    frames, ch = 1 << 20, 2
+    n_files = max(1, (args.kernel_mib << 20) // (4 * frames * ch))
+    flat = torch.empty(n_files * ch * frames, dtype=torch.float32, device="cuda").uniform_(-0.5, 0.5)
+    launches("large planes", [v.view(ch, frames) for v in flat.split(ch * frames)], RB.RATE, args)
+
+
+if __name__ == "__main__":
+    main()
