@@ -32,6 +32,7 @@ import torch
 
 from . import _lib as L
 from . import ragged
+from .planes import check_planes, plane_frames, planes_flat
 from .ragged import device_f32 as _dev
 
 CENT_FREQ = [50., 120, 190, 260, 330, 400, 470, 540, 617.372, 703.378, 798.717, 904.128, 1020.38, 1148.30, 1288.72, 1442.54,
@@ -578,11 +579,8 @@ def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDN
     rows (f64 [files][4], what audio_io.loudness_gain_batch_device reads).  One launch sequence per 65535 files
     (sos_loudness_batch_f64), no wait.  `split`: chunks per hop of the filter scan; it moves the result by rounding only.
     ValueError before any launch: a file that is not such a tensor, a rate below 10 * split Hz, bad weights or frames."""
-    from . import audio_io
-    planes, who = list(planes), "loudness_batch"
-    for i, p in enumerate(planes):
-        if not torch.is_tensor(p) or p.dim() != 2 or p.dtype != torch.float32 or not 1 <= p.shape[0] <= 64:
-            raise ValueError("%s: file %d must be a (1 .. 64 channels, n) float32 tensor" % (who, i))
+    who = "loudness_batch"
+    planes = check_planes(who, planes)
     rates = [rates] * len(planes) if np.ndim(rates) == 0 else list(rates)
     if len(rates) != len(planes):
         raise ValueError("%s: one rate per file (%d files, %d rates)" % (who, len(planes), len(rates)))
@@ -592,29 +590,23 @@ def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDN
         if isinstance(r, bool) or int(r) != r or not split <= loudness_hop(r) <= 1 << 31:
             raise ValueError("%s: file %d has the rate %r (a whole number of Hz, its 100 ms hop at least %d samples)" % (who, i, r, split))
     weights = _loudness_weights(channel_weights, planes, who)
-    frames = [int(p.shape[1]) for p in planes] if frames is None else [int(f) for f in frames]
-    if len(frames) != len(planes) or min(frames, default=0) < 0:
-        raise ValueError("%s: frames holds one non-negative count per file" % who)
+    frames = plane_frames(who, planes, frames)
     L.require_cuda(*planes)
     if not planes:
         rows = torch.zeros((0, 4), dtype=torch.float64, device="cuda")
     else:
         device = planes[0].device
-        chans, avail = [p.shape[0] for p in planes], [p.shape[1] for p in planes]
-        flat = audio_io._back_to_back(planes) if sum(c * a for c, a in zip(chans, avail)) else torch.zeros(1, dtype=torch.float32, device=device)
-        src = ragged.offsets(np.asarray(chans, dtype=np.int64) * np.asarray(avail, dtype=np.int64))
-        coef = torch.from_numpy(np.stack([k_weighting(r) for r in rates])).to(device)
+        flat, src, chans, avail = planes_flat(planes)
+        coef = ragged.upload(np.stack([k_weighting(r) for r in rates]), device)
         rows = torch.empty((len(planes), 4), dtype=torch.float64, device=device)
         h = L.lib()
-        for c0 in range(0, len(planes), ragged.MAX_CLIPS):
-            c1 = min(c0 + ragged.MAX_CLIPS, len(planes))
+        for c0, c1 in ragged.chunks(len(planes)):
             tab = loudness_table(chans[c0:c1], avail[c0:c1], frames[c0:c1], [loudness_hop(r) for r in rates[c0:c1]], int(split))
             need = h.sos_loudness_workspace_bytes(tab.ctypes.data_as(C.c_void_p), c1 - c0, int(split))
             if need < 0:
                 L.check(-22, "sos_loudness_workspace_bytes")
             ws = torch.empty(need, dtype=torch.uint8, device=device)
-            w = torch.from_numpy(np.concatenate(weights[c0:c1])).to(device)
-            tab_dev = torch.from_numpy(tab).to(device)
+            w, tab_dev = ragged.upload(np.concatenate(weights[c0:c1]), device), ragged.upload(tab, device)
             L.check(h.sos_loudness_batch_f64(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0,
                                              L.ptr(coef[c0:]), L.ptr(w), int(split), L.ptr(ws), ws.numel(), L.ptr(rows[c0:]),
                                              L.stream_ptr()), "sos_loudness_batch_f64")

@@ -24,6 +24,73 @@ def clip_table(ns, nb=None):
     return tab
 
 
+def chunks(n):
+    """The spans (c0, c1) of a launch sequence over n clips: consecutive, of at most MAX_CLIPS clips each."""
+    for c0 in range(0, n, MAX_CLIPS):
+        yield c0, min(c0 + MAX_CLIPS, n)
+
+
+def host_table(rows, cols=None):
+    """The host copy of a launch table: integers, given as rows of `cols` entries or (cols=None) as stacked rows or columns
+    whose shape stays, -> a C-contiguous int64 array.  An empty table is refused."""
+    tab = np.asarray(rows, dtype=np.int64)
+    tab = np.ascontiguousarray(tab if cols is None else tab.reshape(-1, cols))
+    if tab.size < 1:
+        raise ValueError("an empty table")
+    return tab
+
+
+def upload(host, device):
+    """The device copy of a host table (int64) or of a per-clip array (float64): engine.upload, which does not wait for the
+    stream."""
+    from .engine import upload as staged                         # when called: engine is not loaded for the host-only users
+    return staged(host, torch.int64 if host.dtype == np.int64 else torch.float64, device)
+
+
+def table(rows, device, cols=None):
+    """Both copies of a launch table: (host_table(rows, cols), its upload)."""
+    tab = host_table(rows, cols)
+    return tab, upload(tab, device)
+
+
+def back_to_back(tensors):
+    """One 1-D tensor holding the elements of `tensors` in order: a view when they already lie back to back in one buffer (what
+    ragged.split, resample_batch_device and denoise_long return), their concatenation otherwise."""
+    first = tensors[0]
+    at, base = first.storage_offset(), first.untyped_storage().data_ptr()
+    for t in tensors:
+        if not t.is_contiguous() or t.untyped_storage().data_ptr() != base or t.storage_offset() != at or t.dtype != first.dtype:
+            return torch.cat([t.reshape(-1) for t in tensors])
+        at += t.numel()
+    return first.as_strided((at - first.storage_offset(),), (1,), first.storage_offset())
+
+
+def flat_f32(tensors, device):
+    """back_to_back of 1-D f32 tensors of which some (or all) may be empty: never a null pointer."""
+    full = [t for t in tensors if t.numel()]
+    return back_to_back(full) if full else torch.zeros(1, dtype=torch.float32, device=device)
+
+
+def group_by(keys, skip=None):
+    """{key: the indices that have it, ascending}, keys in order of first appearance, without the indices i for which
+    skip(i, keys[i])."""
+    groups = {}
+    for i, key in enumerate(keys):
+        if skip is None or not skip(i, key):
+            groups.setdefault(key, []).append(i)
+    return groups
+
+
+def per_group(items, keys, run, skip=None):
+    """One batch call per key: a copy of `items` in which items[i], for every index i of every group of group_by(keys, skip), is
+    replaced by the i-th result of run(key, indices of the group) -- one result per index, in order."""
+    out = list(items)
+    for key, idx in group_by(keys, skip).items():
+        for i, y in zip(idx, run(key, idx)):
+            out[i] = y
+    return out
+
+
 def per_clip(value, nclips, name):
     """A scalar or one value per clip -> a writable f64 array of `nclips` values."""
     v = np.asarray(value, dtype=np.float64)

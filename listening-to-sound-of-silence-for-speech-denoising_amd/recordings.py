@@ -18,13 +18,13 @@ from . import metrics
 from . import ragged
 from . import tools
 from . import transform
+from . import wave_file
 from . import windows
 from .pipeline import FPS, MIN_FRAMES, SR
 
 # the format a source is written back in: (WAVE format tag, stored bits) -> audio_io.ENCODINGS / G711 name.  A float64 source is
 # written as f32 (the networks compute in f32 at best); a G.711 source (telephone audio) comes back as G.711 of its own law.
-_SOURCE_FORMAT = {(1, 8): "u8", (1, 16): "s16", (1, 24): "s24", (1, 32): "s32", (3, 32): "f32", (3, 64): "f32",
-                  (6, 8): "alaw", (7, 8): "ulaw"}
+_SOURCE_FORMAT = {source: f.back for source, f in wave_file.SOURCES.items()}
 SAMPLE_FORMATS = {**audio_io.ENCODINGS, **audio_io.G711}         # name -> (code, bytes per element, WAVE format tag, bits)
 
 
@@ -105,45 +105,26 @@ def _file_weights(channel_weights, infos, paths):
 
 def _resample_back(clips, rates):
     """Every clip whose file's rate differs from SR back to that rate: one resample_batch_device launch per rate."""
-    by_rate = {}
-    for k, r in enumerate(rates):
-        if r != SR:
-            by_rate.setdefault(r, []).append(k)
-    clips = list(clips)
-    for r, idx in by_rate.items():
-        for k, y in zip(idx, audio_io.resample_batch_device([clips[k] for k in idx], SR, r)):
-            clips[k] = y
-    return clips
+    return ragged.per_group(clips, rates, lambda r, idx: audio_io.resample_batch_device([clips[k] for k in idx], SR, r),
+                            lambda k, r: r == SR)
 
 
 def _to_model_rate(natives, rates):
     """Every native channel at the networks' rate, as load_channels_batch_device(sr=SR) brings it there: one
     resample_batch_device launch per rate other than SR, the same bits."""
-    by_rate = {}
-    for k, r in enumerate(rates):
-        if r != SR:
-            by_rate.setdefault(r, []).append(k)
-    clips = list(natives)
-    for r, idx in by_rate.items():
-        for k, y in zip(idx, audio_io.resample_batch_device([natives[k] for k in idx], r, SR)):
-            clips[k] = y
-    return clips
+    return ragged.per_group(natives, rates, lambda r, idx: audio_io.resample_batch_device([natives[k] for k in idx], r, SR),
+                            lambda k, r: r == SR)
 
 
 def _merge_back(natives, lows_in, lows_out, rates, high_band, smooth_frames):
     """Every channel whose file's rate exceeds SR back at that rate WITH the band above SR / 2 (audio_io.resample_merge_batch_
     device): per rate one gains launch ('follow' only) and one merge launch.  The other channels pass as they are."""
-    by_rate = {}
-    for k, r in enumerate(rates):
-        if r > SR:
-            by_rate.setdefault(r, []).append(k)
-    outs = list(lows_out)
-    for r, idx in by_rate.items():
+    def merged(r, idx):
         a, b = [lows_in[k] for k in idx], [lows_out[k] for k in idx]
         gains = audio_io.band_gains_batch_device(a, b, transform.HOP_LENGTH, smooth_frames) if high_band == "follow" else None
-        for k, y in zip(idx, audio_io.resample_merge_batch_device([natives[k] for k in idx], a, b, SR, r, gains)):
-            outs[k] = y
-    return outs
+        return audio_io.resample_merge_batch_device([natives[k] for k in idx], a, b, SR, r, gains)
+
+    return ragged.per_group(lows_out, rates, merged, lambda k, r: r <= SR)
 
 
 @torch.no_grad()

@@ -1,4 +1,4 @@
-"""What the streaming sessions share (stream.StreamDenoiser, audio_io.StreamResampler, audio_io.StreamBandMerger): a fixed number of slots, each holding an
+"""What the streaming sessions share (stream.StreamDenoiser, stream_resampling.StreamResampler, stream_resampling.StreamBandMerger): a fixed number of slots, each holding an
 open stream or None, chunks of any size per slot, and a device ring per slot filled by sos_stream_push_f32."""
 import numpy as np
 import torch

@@ -7,7 +7,7 @@ from . import ragged
 from . import session
 from . import tools
 from . import transform
-from .audio_io import StreamBandMerger, StreamResampler
+from .stream_resampling import StreamBandMerger, StreamResampler
 from .pipeline import FPS, MIN_FRAMES, SR, _GraphCache, _length_groups, _padded_run
 from .windows import _hops, _row_plan, window_plan
 

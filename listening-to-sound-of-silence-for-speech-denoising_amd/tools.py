@@ -30,18 +30,6 @@ def bits_to_mask_batch(bits, ratio, n_samples, sig=None, clip_frames=None, clip_
     return (mask, masked) if sig is not None else mask
 
 
-def _host_table(rows, cols):
-    tab = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, cols))
-    if tab.shape[0] < 1:
-        raise ValueError("an empty table")
-    return tab
-
-
-def _upload(host, device):
-    from .engine import upload
-    return upload(host, torch.int64 if host.dtype == np.int64 else torch.float64, device)
-
-
 def ragged_stage(flat, table, stride, bits=None, ratios=None):
     """A ragged group staged for the networks in one launch (sos_ragged_stage_f32).  flat: the clips back to back, f32 GPU
     tensor; table: host rows {sample offset, samples, bit offset, frames}, one per clip; bits: the clips' frame decisions back
@@ -50,20 +38,20 @@ def ragged_stage(flat, table, stride, bits=None, ratios=None):
     likewise, and the sample mask (1 = silent), each clip's bit for bit bits_to_mask_batch of that clip alone at its ratio.
     Without `bits` only `wave` is computed and returned."""
     L.require_cuda(flat, bits)
-    tab = _host_table(table, 4)
+    tab = ragged.host_table(table, 4)
     B = tab.shape[0]
     if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
         raise ValueError("flat must be a contiguous 1-D float32 tensor")
     if flat.numel() < int(tab[:, 1].sum()):
         raise ValueError("the table names more samples than `flat` holds")
     wave = torch.empty((B, int(stride)), dtype=torch.float32, device=flat.device)
-    d_tab = _upload(tab, flat.device)
+    d_tab = ragged.upload(tab, flat.device)
     masked = mask = rat = d_rat = None
     if bits is not None:
         if bits.dim() != 1 or bits.dtype != torch.uint8 or not bits.is_contiguous() or bits.numel() < int(tab[:, 3].sum()):
             raise ValueError("bits must be a contiguous 1-D uint8 tensor holding every frame of the table")
         rat = ragged.per_clip(ratios, B, "ratios")
-        d_rat = _upload(rat, flat.device)
+        d_rat = ragged.upload(rat, flat.device)
         masked, mask = torch.empty_like(wave), torch.empty_like(flat)
     L.check(L.lib().sos_ragged_stage_f32(L.ptr(flat), L.ptr(d_tab), tab.ctypes.data, B, L.ptr(bits), L.ptr(d_rat),
                                          rat.ctypes.data if rat is not None else None, int(stride), L.ptr(wave), L.ptr(masked),
@@ -76,11 +64,11 @@ def ragged_unpack(rows, table):
     of sum(valid) samples, out[offset : offset + valid] = rows[row, :valid], in one launch (sos_ragged_unpack_f32): what a
     single download of a group's results needs."""
     L.require_cuda(rows)
-    tab = _host_table(table, 3)
+    tab = ragged.host_table(table, 3)
     if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
         raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
     out = torch.empty(int(tab[:, 1].sum()), dtype=torch.float32, device=rows.device)
-    d_tab = _upload(tab, rows.device)
+    d_tab = ragged.upload(tab, rows.device)
     L.check(L.lib().sos_ragged_unpack_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data,
                                           tab.shape[0], L.ptr(out), L.stream_ptr()), "sos_ragged_unpack_f32")
     return out
@@ -94,11 +82,11 @@ def window_stage(x, table, stride):
     host rows of pipeline.window_plan, of which {source offset, samples} are read; windows may overlap and start on any sample.
     -> rows (windows, stride): rows[w, :samples] = x[source offset : source offset + samples], zero beyond."""
     L.require_cuda(x)
-    tab = _host_table(table, WINDOW_COLS)
+    tab = ragged.host_table(table, WINDOW_COLS)
     if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError("x must be a contiguous 1-D float32 tensor")
     rows = torch.empty((tab.shape[0], int(stride)), dtype=torch.float32, device=x.device)
-    d_tab = _upload(tab, x.device)
+    d_tab = ragged.upload(tab, x.device)
     L.check(L.lib().sos_window_stage_f32(L.ptr(x), x.numel(), L.ptr(d_tab), tab.ctypes.data, tab.shape[0], int(stride),
                                          L.ptr(rows), L.stream_ptr()), "sos_window_stage_f32")
     return rows
@@ -110,11 +98,11 @@ def window_stitch(rows, table, context):
     the width of the blend around an inner core boundary, in samples (0: a plain cut).
     -> one 1-D f32 GPU tensor, the recordings' outputs back to back (sum of the cores' lengths)."""
     L.require_cuda(rows)
-    tab = _host_table(table, WINDOW_COLS)
+    tab = ragged.host_table(table, WINDOW_COLS)
     if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
         raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
     out = torch.empty(max(int((tab[:, 5] - tab[:, 4]).sum()), 0), dtype=torch.float32, device=rows.device)
-    d_tab = _upload(tab, rows.device)
+    d_tab = ragged.upload(tab, rows.device)
     L.check(L.lib().sos_window_stitch_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
                                           int(context), L.ptr(out), L.stream_ptr()), "sos_window_stitch_f32")
     return out
@@ -131,7 +119,7 @@ def window_stitch_planes(rows, table, context, recs=None, out_total=None):
     of the flat buffer of `out_total` floats that is returned (file-major: the planes of a recording next to each other;
     pitch > the recording's length leaves a gap).  What no segment covers stays zero."""
     L.require_cuda(rows)
-    tab = _host_table(table, WINDOW_COLS)
+    tab = ragged.host_table(table, WINDOW_COLS)
     if rows.dim() != 3 or rows.dtype != torch.float32 or not rows.is_contiguous():
         raise ValueError("rows must be a contiguous float32 (planes, R, stride) tensor")
     planes = rows.shape[0]
@@ -149,9 +137,9 @@ def window_stitch_planes(rows, table, context, recs=None, out_total=None):
     else:
         if out_total is None:
             raise ValueError("recs needs out_total, the length of the flat buffer")
-        rec = _host_table(recs, 2)
+        rec = ragged.host_table(recs, 2)
         out = torch.zeros(max(int(out_total), 0), dtype=torch.float32, device=rows.device)
-    d_tab, d_rec = _upload(tab, rows.device), _upload(rec, rows.device)
+    d_tab, d_rec = ragged.upload(tab, rows.device), ragged.upload(rec, rows.device)
     L.check(L.lib().sos_window_stitch_planes_f32(L.ptr(rows), planes, rows.shape[1], rows.shape[2], L.ptr(d_tab), tab.ctypes.data,
                                                  tab.shape[0], int(context), L.ptr(d_rec), rec.ctypes.data, rec.shape[0],
                                                  out.numel(), L.ptr(out), L.stream_ptr()), "sos_window_stitch_planes_f32")
@@ -166,7 +154,7 @@ def window_frames_stitch(rows, table, win_frames, recs, ratios, core, context):
     windows}, one per recording; ratios: samples per frame, one value or one per recording; core, context: samples.
     -> one 1-D f32 GPU tensor, the recordings' logits back to back (sum of their frames)."""
     L.require_cuda(rows)
-    tab, rec = _host_table(table, WINDOW_COLS), _host_table(recs, 4)
+    tab, rec = ragged.host_table(table, WINDOW_COLS), ragged.host_table(recs, 4)
     if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
         raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
     fr = np.ascontiguousarray(np.asarray(win_frames, dtype=np.int64).reshape(-1))
@@ -174,7 +162,7 @@ def window_frames_stitch(rows, table, win_frames, recs, ratios, core, context):
         raise ValueError("win_frames must hold one count per window of the table")
     rat = ragged.per_clip(ratios, rec.shape[0], "ratios")
     out = torch.empty(max(int(rec[:, 1].sum()), 0), dtype=torch.float32, device=rows.device)
-    d_tab, d_fr, d_rec, d_rat = (_upload(a, rows.device) for a in (tab, fr, rec, rat))
+    d_tab, d_fr, d_rec, d_rat = (ragged.upload(a, rows.device) for a in (tab, fr, rec, rat))
     L.check(L.lib().sos_window_frames_stitch_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data,
                                                  L.ptr(d_fr), fr.ctypes.data, tab.shape[0], L.ptr(d_rec), rec.ctypes.data,
                                                  L.ptr(d_rat), rat.ctypes.data, rec.shape[0], int(core), int(context), L.ptr(out),
@@ -215,7 +203,7 @@ def window_frames_link(rows, table, win_frames, recs, ratios, core, context, lin
     has speech) or 'mean' (sequential f32 sum in member order, one f32 divide); threshold: of the sigmoid, as threshold_bits.
     -> (logits f32, bits uint8), 1-D GPU tensors of sum(frames of the groups) elements, the groups' streams back to back."""
     L.require_cuda(rows)
-    tab, rec, lk = _host_table(table, WINDOW_COLS), _host_table(recs, 4), _host_table(links, 4)
+    tab, rec, lk = ragged.host_table(table, WINDOW_COLS), ragged.host_table(recs, 4), ragged.host_table(links, 4)
     if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
         raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
     fr = np.ascontiguousarray(np.asarray(win_frames, dtype=np.int64).reshape(-1))
@@ -230,7 +218,7 @@ def window_frames_link(rows, table, win_frames, recs, ratios, core, context, lin
     total = max(int(lk[:, 1].sum()), 0)
     logits = torch.empty(total, dtype=torch.float32, device=rows.device)
     bits = torch.empty(total, dtype=torch.uint8, device=rows.device)
-    d_tab, d_fr, d_rec, d_rat, d_lk, d_mem = (_upload(a, rows.device) for a in (tab, fr, rec, rat, lk, mem))
+    d_tab, d_fr, d_rec, d_rat, d_lk, d_mem = (ragged.upload(a, rows.device) for a in (tab, fr, rec, rat, lk, mem))
     L.check(L.lib().sos_window_frames_link_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data,
                                                L.ptr(d_fr), fr.ctypes.data, tab.shape[0], L.ptr(d_rec), rec.ctypes.data,
                                                L.ptr(d_rat), rat.ctypes.data, rec.shape[0], int(core), int(context), L.ptr(d_lk),
@@ -250,7 +238,7 @@ def window_stage_masked(flat, bits, clips, ratios, table, stride):
     the WHOLE recording's (ragged_stage's `mask` at the window's samples): bit for bit slices of ragged_stage's full-length
     rows, which are never made."""
     L.require_cuda(flat, bits)
-    tab, clip = _host_table(table, WINDOW_COLS), _host_table(clips, 4)
+    tab, clip = ragged.host_table(table, WINDOW_COLS), ragged.host_table(clips, 4)
     if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
         raise ValueError("flat must be a contiguous 1-D float32 tensor")
     if flat.numel() < int(clip[:, 1].sum()):
@@ -260,7 +248,7 @@ def window_stage_masked(flat, bits, clips, ratios, table, stride):
     rat = ragged.per_clip(ratios, clip.shape[0], "ratios")
     wave = torch.empty((tab.shape[0], int(stride)), dtype=torch.float32, device=flat.device)
     masked = torch.empty_like(wave)
-    d_tab, d_clip, d_rat = (_upload(a, flat.device) for a in (tab, clip, rat))
+    d_tab, d_clip, d_rat = (ragged.upload(a, flat.device) for a in (tab, clip, rat))
     L.check(L.lib().sos_window_stage_masked_f32(L.ptr(flat), L.ptr(bits), L.ptr(d_clip), clip.ctypes.data, L.ptr(d_rat),
                                                 rat.ctypes.data, clip.shape[0], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
                                                 int(stride), L.ptr(wave), L.ptr(masked), L.stream_ptr()),
@@ -282,11 +270,11 @@ def stream_push(flat, table, ring):
     contiguous 1-D f32 GPU tensor; table: host rows {slot, source offset, samples, stream position}, a slot at most once; ring:
     (slots, capacity) f32 GPU tensor, written in place: ring[slot, (position + j) % capacity] = flat[source offset + j]."""
     L.require_cuda(flat, ring)
-    tab = _host_table(table, STREAM_PUSH_COLS)
+    tab = ragged.host_table(table, STREAM_PUSH_COLS)
     _stream_ring(ring)
     if flat.dim() != 1 or flat.dtype != torch.float32 or not flat.is_contiguous():
         raise ValueError("flat must be a contiguous 1-D float32 tensor")
-    d_tab = _upload(tab, flat.device)
+    d_tab = ragged.upload(tab, flat.device)
     L.check(L.lib().sos_stream_push_f32(L.ptr(flat), flat.numel(), L.ptr(d_tab), tab.ctypes.data, tab.shape[0], L.ptr(ring),
                                         ring.shape[0], ring.shape[1], L.stream_ptr()), "sos_stream_push_f32")
 
@@ -296,13 +284,13 @@ def stream_stage(ring, table, stride, out=None):
     rows {slot, stream position, samples}.  -> rows (windows, stride): rows[w, j] = ring[slot, (position + j) % capacity] for
     j < samples, zero beyond; `out`: a contiguous f32 (windows, stride) tensor to write instead (a captured graph's input)."""
     L.require_cuda(ring, out)
-    tab = _host_table(table, STREAM_STAGE_COLS)
+    tab = ragged.host_table(table, STREAM_STAGE_COLS)
     _stream_ring(ring)
     if out is None:
         out = torch.empty((tab.shape[0], int(stride)), dtype=torch.float32, device=ring.device)
     elif out.shape != (tab.shape[0], int(stride)) or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError("out must be a contiguous float32 (windows, stride) tensor")
-    d_tab = _upload(tab, ring.device)
+    d_tab = ragged.upload(tab, ring.device)
     L.check(L.lib().sos_stream_stage_f32(L.ptr(ring), ring.shape[0], ring.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
                                          int(stride), L.ptr(out), L.stream_ptr()), "sos_stream_stage_f32")
     return out
@@ -317,7 +305,7 @@ def stream_stitch(rows, table, context, tail, out_stride=None):
     without a previous window), core end - context (core end without a next one)), the first 2 context of them blended with
     the saved overlap exactly as window_stitch blends them.  out_stride: default the longest of `lengths`."""
     L.require_cuda(rows, tail)
-    tab = _host_table(table, STREAM_STITCH_COLS)
+    tab = ragged.host_table(table, STREAM_STITCH_COLS)
     context = int(context)
     if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
         raise ValueError("rows must be a contiguous float32 (R, stride) tensor")
@@ -329,7 +317,7 @@ def stream_stitch(rows, table, context, tail, out_stride=None):
     if out_stride is None:
         out_stride = max(int(lengths.max()), 1)
     out = torch.empty((tab.shape[0], int(out_stride)), dtype=torch.float32, device=rows.device)
-    d_tab = _upload(tab, rows.device)
+    d_tab = ragged.upload(tab, rows.device)
     L.check(L.lib().sos_stream_stitch_f32(L.ptr(rows), rows.shape[0], rows.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
                                           tail.shape[0], context, L.ptr(tail), L.ptr(out), int(out_stride), L.stream_ptr()),
             "sos_stream_stitch_f32")
@@ -344,10 +332,10 @@ def stream_resample(ring, table, ratio, win, num_table, out=None):
     tensor as stream_push fills it; table: host rows {slot, t_lo, t_hi, n_in, n_valid, output offset}, a slot at most once: the
     outputs t_lo <= t < t_hi of the slot's stream, each as audio_io.resample_device computes it for a signal of n_in samples
     (zero from n_valid on), go to out[output offset ..]; ratio = target / orig; win, num_table: the filter's half window on the
-    GPU, scaled by min(1, ratio), and its points per zero crossing (audio_io._filter_on).
+    GPU, scaled by min(1, ratio), and its points per zero crossing (resampling.filter_on).
     -> out, a contiguous 1-D f32 GPU tensor: the one given, or a new one that ends with the last row's outputs."""
     L.require_cuda(ring, win, out)
-    tab = _host_table(table, STREAM_RESAMPLE_COLS)
+    tab = ragged.host_table(table, STREAM_RESAMPLE_COLS)
     _stream_ring(ring)
     if win.dim() != 1 or win.dtype != torch.float32 or not win.is_contiguous():
         raise ValueError("win must be a contiguous 1-D float32 tensor")
@@ -355,7 +343,7 @@ def stream_resample(ring, table, ratio, win, num_table, out=None):
         out = torch.empty(max(int((tab[:, 5] + np.maximum(tab[:, 2] - tab[:, 1], 0)).max()), 0), dtype=torch.float32, device=ring.device)
     elif out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError("out must be a contiguous 1-D float32 tensor")
-    d_tab = _upload(tab, ring.device)
+    d_tab = ragged.upload(tab, ring.device)
     L.check(L.lib().sos_stream_resample_f32(L.ptr(ring), ring.shape[0], ring.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
                                             float(ratio), L.ptr(win), win.numel(), int(num_table), L.ptr(out), out.numel(),
                                             L.stream_ptr()), "sos_stream_resample_f32")
@@ -379,9 +367,9 @@ def stream_band_ratio(ring, rring, table, hop):
     capacity) f32 GPU tensor, rows slot / slots + slot / 2 slots + slot = x / a / b of a stream as stream_push fills them; rring:
     (slots, frames) f64 GPU tensor, written in place; table: host rows {slot, j_lo, j_hi, m_a, m_b}, a slot at most once."""
     L.require_cuda(ring, rring)
-    tab = _host_table(table, STREAM_BAND_RATIO_COLS)
+    tab = ragged.host_table(table, STREAM_BAND_RATIO_COLS)
     _stream_band_rings(ring, rring)
-    d_tab = _upload(tab, ring.device)
+    d_tab = ragged.upload(tab, ring.device)
     L.check(L.lib().sos_stream_band_ratio_f64(L.ptr(ring), ring.shape[0] // 3, ring.shape[1], L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
                                               int(hop), L.ptr(rring), rring.shape[1], L.stream_ptr()), "sos_stream_band_ratio_f64")
 
@@ -389,11 +377,11 @@ def stream_band_ratio(ring, rring, table, hop):
 def stream_band_merge(ring, rring, table, ratio, win, num_table, hop, smooth, out):
     """Outputs of streams with the band above the low rate's half put back, in one launch (sos_stream_band_merge_f32): out[t] =
     fmaf(g[t], x[t] - U(a)[t], U(b)[t]) out of the rings.  table: host rows {slot, t_lo, t_hi, n_x, n_a, n_b, v_b, J, r_hi,
-    output offset}, a slot at most once; ratio = native rate / low rate; win, num_table: audio_io._filter_on's; smooth: the frames
+    output offset}, a slot at most once; ratio = native rate / low rate; win, num_table: resampling.filter_on's; smooth: the frames
     of smoothing of g, or None for g = 1 (rring may be None then); out: a contiguous 1-D f32 GPU tensor, written at the rows'
     offsets."""
     L.require_cuda(ring, rring, win, out)
-    tab = _host_table(table, STREAM_BAND_MERGE_COLS)
+    tab = ragged.host_table(table, STREAM_BAND_MERGE_COLS)
     _stream_band_rings(ring, rring)
     if win.dim() != 1 or win.dtype != torch.float32 or not win.is_contiguous():
         raise ValueError("win must be a contiguous 1-D float32 tensor")
@@ -401,7 +389,7 @@ def stream_band_merge(ring, rring, table, ratio, win, num_table, hop, smooth, ou
         raise ValueError("out must be a contiguous 1-D float32 tensor")
     if smooth is not None and rring is None:
         raise ValueError("gains need the ring of frames")
-    d_tab = _upload(tab, ring.device)
+    d_tab = ragged.upload(tab, ring.device)
     L.check(L.lib().sos_stream_band_merge_f32(L.ptr(ring), ring.shape[0] // 3, ring.shape[1], L.ptr(rring),
                                               rring.shape[1] if rring is not None else 0, L.ptr(d_tab), tab.ctypes.data, tab.shape[0],
                                               float(ratio), L.ptr(win), win.numel(), int(num_table), int(hop),
@@ -576,8 +564,8 @@ def _mix_stage(signals, d_noise, noise_total, ntab, par, bits, nb, norm):
         L.check(-22, "sos_ragged_mix_workspace_bytes")
     total = int(tab[:, 1].sum())
     mixed, clean, noise = (torch.empty(total, dtype=torch.float32, device=dev) for _ in range(3))
-    return _MixStaged(flat, lens, tab, _upload(tab, dev), d_noise, noise_total, ntab, _upload(ntab, dev), d_bits, par,
-                      _upload(par, dev), float(norm or 0.0), torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev),
+    return _MixStaged(flat, lens, tab, ragged.upload(tab, dev), d_noise, noise_total, ntab, ragged.upload(ntab, dev), d_bits, par,
+                      ragged.upload(par, dev), float(norm or 0.0), torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev),
                       mixed, clean, noise, torch.empty((B, _MIX_OUT), dtype=torch.float64, device=dev))
 
 

@@ -229,15 +229,15 @@ def test_device_entries_that_disagree_with_the_host_get_status_minus_one():
 
 def test_a_refused_clip_is_reported_by_number(monkeypatch):
     """tools.add_signals_ragged raises on a status of -1, naming the clip (here the ratio goes up as 1 behind the checks)."""
-    from sos_amd import tools
+    from sos_amd import ragged, tools
     x = np.ones(50, np.float32)
-    real = tools._upload
+    real = ragged.upload
 
     def upload(host, device):
         if host.dtype == np.float64 and host.shape[1:] == (2,):
             host = host.copy()
             host[1, 1] = 1.0
         return real(host, device)
-    monkeypatch.setattr(tools, "_upload", upload)
+    monkeypatch.setattr(ragged, "upload", upload)
     with pytest.raises(RuntimeError, match="clip 1"):
         tools.add_signals_ragged([x, x], [x, x], 3.0, bits=[np.ones(2, np.uint8)] * 2, ratios=25.0)

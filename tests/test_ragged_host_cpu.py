@@ -185,3 +185,69 @@ def test_split_returns_views_of_tensors_and_arrays():
         assert float(flat[4]) == -1.0
         assert ragged.split(flat, []) == [] and len(ragged.split(flat, [8])[0]) == 8
     assert ragged.download([]) == []
+
+
+def test_chunks_read_max_clips_when_called(monkeypatch):
+    from sos_amd import ragged
+    assert list(ragged.chunks(0)) == [] and list(ragged.chunks(65535)) == [(0, 65535)]
+    assert list(ragged.chunks(65536)) == [(0, 65535), (65535, 65536)]
+    monkeypatch.setattr("sos_amd.ragged.MAX_CLIPS", 3)
+    assert list(ragged.chunks(7)) == [(0, 3), (3, 6), (6, 7)] and list(ragged.chunks(0)) == []
+    assert list(ragged.chunks(3)) == [(0, 3)] and list(ragged.chunks(4)) == [(0, 3), (3, 4)]
+
+
+def test_host_table_is_int64_c_contiguous_and_never_empty():
+    from sos_amd import ragged
+    rows = ragged.host_table([(0, 5, 1), (5, 2, 0)], 3)
+    assert rows.dtype == np.int64 and rows.flags.c_contiguous and rows.tolist() == [[0, 5, 1], [5, 2, 0]]
+    assert ragged.host_table(np.arange(6, dtype=np.int32), 2).tolist() == [[0, 1], [2, 3], [4, 5]]
+    cols = ragged.host_table([np.asarray([0, 5]), [5, 2], np.asarray([1, 0], np.int32)])          # stacked columns keep their shape
+    assert cols.dtype == np.int64 and cols.flags.c_contiguous and cols.tolist() == [[0, 5], [5, 2], [1, 0]]
+    assert ragged.host_table(np.arange(6, dtype=np.int64).reshape(2, 3).T).flags.c_contiguous
+    for empty, cols in (([], 4), ([], None), (np.zeros((6, 0), np.int64), None), (np.zeros((0, 4), np.int64), 4)):
+        with pytest.raises(ValueError, match="an empty table"):
+            ragged.host_table(empty, cols)
+
+
+def test_group_by_and_per_group():
+    """group_by gives the dict that recordings._resample_back built by hand; per_group runs one call per key and scatters."""
+    from sos_amd import ragged
+    SR, rates = 14000, [44100, 14000, 8000, 44100, 14000, 48000, 8000, 44100]
+    by_rate = {}
+    for k, r in enumerate(rates):
+        if r != SR:
+            by_rate.setdefault(r, []).append(k)
+    got = ragged.group_by(rates, lambda k, r: r == SR)
+    assert got == by_rate == {44100: [0, 3, 7], 8000: [2, 6], 48000: [5]} and list(got) == [44100, 8000, 48000]
+    assert ragged.group_by(rates) == {44100: [0, 3, 7], 14000: [1, 4], 8000: [2, 6], 48000: [5]}
+    assert ragged.group_by([]) == {} and ragged.group_by(rates, lambda k, r: True) == {}
+    assert ragged.group_by("abca", lambda k, key: k == 0) == {"b": [1], "c": [2], "a": [3]}
+    calls, items = [], ["x%d" % k for k in range(len(rates))]
+    out = ragged.per_group(items, rates, lambda r, idx: calls.append((r, idx)) or ["%s@%d" % (items[k], r) for k in idx],
+                           lambda k, r: r == SR)
+    assert calls == [(44100, [0, 3, 7]), (8000, [2, 6]), (48000, [5])]
+    assert out == ["x0@44100", "x1", "x2@8000", "x3@44100", "x4", "x5@48000", "x6@8000", "x7@44100"]
+    assert items[0] == "x0" and out is not items                 # a copy: the items given stay
+
+
+def test_back_to_back_is_a_view_of_split_outputs_and_a_copy_otherwise():
+    import torch
+    from sos_amd import ragged
+    flat = torch.arange(12, dtype=torch.float32)
+    parts = ragged.split(flat, [3, 0, 5, 4])
+    whole = ragged.back_to_back(parts)
+    assert whole.data_ptr() == flat.data_ptr() and whole.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr()
+    assert torch.equal(whole, flat)
+    tail = ragged.back_to_back(parts[2:])                        # off the buffer's start: still a view
+    assert tail.data_ptr() == parts[2].data_ptr() and tail.storage_offset() == 3 and torch.equal(tail, flat[3:])
+    planes = [p.view(1, -1) for p in parts[2:]]                  # 2-D planes that lie back to back
+    assert ragged.back_to_back(planes).data_ptr() == parts[2].data_ptr() and ragged.back_to_back(planes).shape == (9,)
+    for apart in ([parts[0], parts[3]], [parts[3], parts[2]], [parts[0].clone(), parts[2]], [flat[::2][:3], flat[6:]],
+                  [parts[0], parts[2].double()]):
+        got = ragged.back_to_back(apart)
+        assert got.untyped_storage().data_ptr() != flat.untyped_storage().data_ptr()
+        assert torch.equal(got, torch.cat([t.reshape(-1) for t in apart]))
+    some = ragged.flat_f32([parts[1], parts[2], parts[1]], "cpu")
+    assert some.data_ptr() == parts[2].data_ptr() and some.numel() == 5
+    none = ragged.flat_f32([parts[1], parts[1]], "cpu")          # never a null pointer
+    assert none.numel() == 1 and none.dtype == torch.float32 and float(none[0]) == 0.0

@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import recordings_bench as RB  # noqa: E402
 import sos_amd  # noqa: E402
 from oracle import nets as onet  # noqa: E402
-from sos_amd import audio_io, metrics, recordings  # noqa: E402
+from sos_amd import _lib as L, audio_io, metrics, ragged, recordings  # noqa: E402
 from sos_amd.common import MyConfig  # noqa: E402
 from sos_amd.denoiser import networks as jnet  # noqa: E402
 from sos_amd.detector import networks as dnet  # noqa: E402
@@ -39,8 +39,8 @@ def launches(name, planes, rate, args):
     go = lambda: audio_io.loudness_gain_batch_device(planes, stats["rows"], stats["lufs"].contiguous() + unit, 0.0)   # noqa: E731
     rows.append(("gain", [RB.device_ms(go, args.kernel_reps) for _ in range(args.kernel_repeats)]))
     # the entry points themselves: table, coefficients, weights and work buffer already on the device
-    L, h = audio_io.L, audio_io.L.lib()
-    flat = audio_io._back_to_back(planes)
+    h = L.lib()
+    flat = ragged.back_to_back(planes)
     chans, avail = [p.shape[0] for p in planes], [p.shape[1] for p in planes]
     coef = torch.from_numpy(np.stack([metrics.k_weighting(rate)] * len(planes))).cuda()
     w = torch.ones(sum(chans), dtype=torch.float64, device="cuda")

@@ -38,7 +38,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sos_amd  # noqa: E402
 from oracle import nets as onet  # noqa: E402
-from sos_amd import audio_io, pipeline, ragged, recordings, tools, transform, windows  # noqa: E402
+from sos_amd import _lib, audio_io, pipeline, ragged, recordings, resampling, tools, transform, windows  # noqa: E402
 from sos_amd.common import MyConfig  # noqa: E402
 from sos_amd.denoiser import networks as jnet  # noqa: E402
 from sos_amd.detector import networks as dnet  # noqa: E402
@@ -130,7 +130,7 @@ def kernels(args, amplitude):
     print(f"kernels: {n_files} files of {ch} x {frames} frames = {samples * 4 / 2**20:.0f} MiB of planes uniform in +-{amplitude:g} "
           f"({100 * float((flat.abs() >= 1).float().mean()):.1f} % of the samples saturate), {args.kernel_reps} launches each (bytes read + "
           "bytes written per second; the entry points themselves, tables already on the device)")
-    L = audio_io.L
+    L = _lib
     rows = []
     assert torch.equal(audio_io.encode_batch_device(planes[:1], "f32")[0].view(torch.float32), planes[0].T.reshape(-1))
     for fmt in ("s16", "s24", "s32", "u8", "f32", "alaw", "ulaw"):               # G.711 moves u8's bytes through u8's accesses
@@ -146,7 +146,7 @@ def kernels(args, amplitude):
     for kind, dtype in (("s16", np.int16), ("s32", np.int32), ("u8", np.uint8), ("f32", np.float32), ("alaw", np.uint8),
                         ("ulaw", np.uint8)) if amplitude < 1 else ():
         g711 = kind in audio_io.G711
-        code = audio_io.G711[kind][0] if g711 else audio_io._FMT[kind]
+        code = audio_io.DECODE[kind][1]
         entry = L.lib().sos_g711_planes_batch_f32 if g711 else L.lib().sos_pcm_planes_batch_f32
         pcm = torch.zeros(samples, dtype=getattr(torch, np.dtype(dtype).name), device="cuda")
         tab = np.asarray([[i * ch * frames, frames, ch, i * ch * frames] for i in range(n_files)], dtype=np.int64)
@@ -225,7 +225,7 @@ def band(args, paths):
     a = [t.clone() for t in lows]
     b = [0.5 * t for t in a]                                                     # m' = m: both resamplings have n = (int)(m * ratio) samples
     back = audio_io.resample_batch_device(a, pipeline.SR, RATE, fix=False)
-    x_flat = audio_io._back_to_back(back) + 0.01 * torch.randn(sum(t.numel() for t in back), device="cuda")   # native planes of that length
+    x_flat = ragged.back_to_back(back) + 0.01 * torch.randn(sum(t.numel() for t in back), device="cuda")   # native planes of that length
     xs = ragged.split(x_flat, [t.numel() for t in back])
     gains = audio_io.band_gains_batch_device(a, b) if args.high_band == "follow" else None
 
@@ -235,7 +235,7 @@ def band(args, paths):
     def pieces():
         ra = audio_io.resample_batch_device(a, pipeline.SR, RATE, fix=False)
         rb = audio_io.resample_batch_device(b, pipeline.SR, RATE, fix=False)
-        return torch.sub(x_flat, audio_io._back_to_back(ra)).add_(audio_io._back_to_back(rb))
+        return torch.sub(x_flat, ragged.back_to_back(ra)).add_(ragged.back_to_back(rb))
 
     same = torch.equal(torch.cat(audio_io.resample_merge_batch_device(xs, a, b, pipeline.SR, RATE)), pieces())
     one(), pieces()
@@ -252,7 +252,7 @@ def band(args, paths):
     print(f"  two resample launches + sub + add             : {t2 * 1e6:8.1f} us (min {min(runs['pieces']) * 1e6:.1f}, max {max(runs['pieces']) * 1e6:.1f})"
           f"   ratio {t2 / t1:.2f}")
     # (c) the entry points themselves, tables already on the device, from device events
-    L = audio_io.L
+    L = _lib
     nn, mm = np.asarray([t.numel() for t in xs], dtype=np.int64), np.asarray([t.numel() for t in a], dtype=np.int64)
     J = -(-mm // transform.HOP_LENGTH)
     off = ragged.offsets
@@ -262,7 +262,7 @@ def band(args, paths):
     a_flat, b_flat = torch.cat(a), torch.cat(b)
     s_flat = torch.empty(int(J.sum()), dtype=torch.float32, device="cuda")
     out = torch.empty_like(x_flat)
-    win, num_table = audio_io._filter_on(x_flat.device, ratio, "kaiser_best")
+    win, num_table = resampling.filter_on(x_flat.device, ratio, "kaiser_best")
     go_gain = lambda: L.check(L.lib().sos_band_gain_batch_f32(L.ptr(a_flat), L.ptr(b_flat), L.ptr(gtab_dev), gtab.ctypes.data_as(L.C.c_void_p),   # noqa: E731
                                                               len(xs), transform.HOP_LENGTH, 2, L.ptr(s_flat), L.stream_ptr()))
     go_merge = lambda s: L.check(L.lib().sos_resample_merge_batch_f32(L.ptr(x_flat), L.ptr(a_flat), L.ptr(b_flat), L.ptr(s), L.ptr(tab_dev),      # noqa: E731
