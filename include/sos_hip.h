@@ -550,6 +550,32 @@ int sos_loudness_batch_f64(const float* planes, const int64_t* table, const int6
                            const double* weights, int split, void* work, int64_t work_bytes, double* stats, sos_stream_t stream);
 int sos_loudness_gain_batch_f32(float* planes, const int64_t* table, const int64_t* table_host, int nfiles, const double* stats,
                                 const double* targets, double ceiling_db, float* gains, int* limited, sos_stream_t stream);
+/* The other EBU R128 measures of a group of files, on the table above (csrc/loudness.hip; sos_amd.metrics.true_peak_batch /
+ * loudness_batch(true_peak=, loudness_range=); float64 restatement: tests/r128_reference.py).  No call waits for the device.
+ * sos_true_peak_batch_f64: the true peak (ITU-R BS.1770-4 Annex 2) by the project's own interpolator, 4x oversampling by a
+ *   48-tap polyphase windowed sinc.  Reads columns 0 .. 3 of the table only; the host checks are sos_loudness_gain_batch_f32's.
+ *   coef f32 [3][12] on the device (sos_amd.metrics.true_peak_filter): h_p[k] = sinc(u) I0(9 sqrt(1 - (u / 6)^2)) / I0(9), u =
+ *   k - p / 4, for p = 1, 2, 3 and k = -5 .. 6, computed in double and rounded once.  The point n + p / 4 is v = sum_k h_p[k]
+ *   x[n + k], 12 fmaf in tap order in f32, for n = -1 .. frames - 1; phase 0 is the sample; x reads 0 outside [0, min(frames,
+ *   available)).  peaks f64 [nfiles] = max over channels of |x| and |v| (the f32 maximum, widened; the type of column 1 of the
+ *   stats rows), 0 for a file without a sample, NaN for a skipped row.  Two launches (peaks are initialised on the stream); the
+ *   grid is flat over tiles of 2048 points of all planes; a maximum has no order: two calls give equal bits.
+ * sos_loudness_range_batch_f64: work = the buffer sos_loudness_batch_f64 filled on the same stream with the same table,
+ *   weights and split.  e[i] = sum_c w_c (sum of y_c^2 over hop i), whole hops only; short-term windows of 30 hops every hop:
+ *   z[j] = (e[j] + .. + e[j + 29]) / (30 h), l = -0.691 + 10 log10 z; gates l > -70 and l > (loudness of the mean z of the
+ *   absolutely gated windows) - 20; with s the m surviving l ascending, LRA = s[floor((m - 1) 0.95 + 0.5)] - s[floor((m - 1) 0.10
+ *   + 0.5)] (EBU Tech 3342 by libebur128's nearest ranks), 0 for m = 0.  out f64 [nfiles][4] = {LRA in LU, maximum momentary
+ *   loudness (400 ms blocks, ungated, -inf without one), maximum short-term loudness (ungated, -inf without a window), m},
+ *   {NaN, NaN, NaN, -1} for a skipped row.  range_work: device bytes, at least sos_loudness_range_workspace_bytes(table_host,
+ *   nfiles) (16 bytes per hop of every plane, whatever the split; -1 for a table the call would refuse); SOS_ENOSPC below it
+ *   or with a work buffer below sos_loudness_workspace_bytes.  Two launches.
+ * SOS_EINVAL as above. */
+int sos_true_peak_batch_f64(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, const float* coef,
+                            double* peaks, sos_stream_t stream);
+int64_t sos_loudness_range_workspace_bytes(const int64_t* table_host, int nfiles);
+int sos_loudness_range_batch_f64(const int64_t* table, const int64_t* table_host, int nfiles, const double* weights, int split,
+                                 const void* work, int64_t work_bytes, void* range_work, int64_t range_work_bytes, double* out,
+                                 sos_stream_t stream);
 /* Band-limited resampling by `ratio` = sr_new / sr_orig (resampy 0.2.2 `resample_f`): win = the filter's half
  * window (nwin floats, num_table samples per zero crossing), already multiplied by min(1, ratio).  Writes
  * out[0 .. n_out): the first floor(n_in * ratio) entries are resampled, the rest zero (librosa pads to

@@ -134,6 +134,9 @@ SIGNATURES = {
     "sos_loudness_workspace_bytes": [_P, _I, _I],
     "sos_loudness_batch_f64": [_P, _P, _P, _I, _P, _P, _I, _P, _L, _P, _P],
     "sos_loudness_gain_batch_f32": [_P, _P, _P, _I, _P, _P, _D, _P, _P, _P],
+    "sos_true_peak_batch_f64": [_P, _P, _P, _I, _P, _P, _P],
+    "sos_loudness_range_workspace_bytes": [_P, _I],
+    "sos_loudness_range_batch_f64": [_P, _P, _I, _P, _I, _P, _L, _P, _L, _P, _P],
     "sos_resample_f32": [_P, _L, _D, _P, _I, _I, _P, _L, _P],
     "sos_resample_batch_f32": [_P, _P, _P, _I, _D, _P, _I, _I, _P, _P],
     "sos_resample_time_segments": [_D, _L, _P, _P, _P, _I],
@@ -195,7 +198,8 @@ def _load(path, want_dtype):
                                              "sos_stft_matrix_bytes", "sos_istft_matrix_bytes",
                                              "sos_stoi_workspace_bytes", "sos_metric_batch_workspace_bytes",
                                              "sos_sdr_workspace_bytes", "sos_silence_label_workspace_bytes",
-                                             "sos_ragged_mix_workspace_bytes", "sos_loudness_workspace_bytes") else C.c_int
+                                             "sos_ragged_mix_workspace_bytes", "sos_loudness_workspace_bytes",
+                                             "sos_loudness_range_workspace_bytes") else C.c_int
     if h.sos_abi_version() != EXPECTED_ABI:
         raise ImportError(f"{path} exports ABI version {h.sos_abi_version()}, this binding was written for {EXPECTED_ABI} "
                           "(the argument lists differ: rebuild the library, or drop the SOS_HIP_LIB / SOS_HIP_LIB_F16 override)")

@@ -19,7 +19,9 @@ float64 restatement tests/sdr_reference.py, parity against mir_eval itself unpin
 ITU-R BS.1770 / EBU R128 integrated loudness (`loudness`, `loudness_batch`, `k_weighting`) of ragged batches of multi-channel
 files runs in HIP too (csrc/loudness.hip): the K-weighting recurrence as a chunked scan in float64, the two gates on the device,
 one launch sequence and no wait; float64 restatement tests/loudness_reference.py, held against the standard's 48 kHz table and
-the EBU Tech 3341 signals.
+the EBU Tech 3341 signals.  The other R128 measures sit beside it: the true peak by 4x interpolation (`true_peak`,
+`true_peak_batch`, `true_peak_filter`), the loudness range and the maximum momentary / short-term loudness
+(`loudness_batch(true_peak=, loudness_range=)`); float64 restatement tests/r128_reference.py.
 `evaluate_metrics_batch` scores a ragged batch of clips in one launch sequence (csrc/metrics_batch.hip) with the per-frame
 arithmetic of the one-clip kernels.  Signals: 1-D numpy arrays or GPU tensors.  No CPU fallback."""
 import ctypes as C
@@ -565,7 +567,70 @@ def _loudness_weights(channel_weights, planes, who):
     return out
 
 
-def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDNESS_SPLIT):
+TRUE_PEAK_TILE = 2048               # points of one plane per tile of sos_true_peak_batch_f64: TP_TILE of csrc/loudness.hip, which
+                                    # tests/test_r128_reference.py holds it to
+
+
+def true_peak_filter():
+    """The true-peak interpolator's coefficients, float32 [3][12]: h_p[k] = sinc(u) I0(9 sqrt(1 - (u / 6)^2)) / I0(9) with u = k -
+    p / 4 for the phases p = 1, 2, 3 and the taps k = -5 .. 6 (4x oversampling by a 48-tap Kaiser-windowed sinc), computed in
+    float64 and rounded once.  Phase 0 is the sample itself: the prototype is 0 at every other whole sample."""
+    u = np.arange(-5, 7, dtype=np.float64)[None, :] - np.arange(1, 4, dtype=np.float64)[:, None] / 4.0
+    return np.ascontiguousarray(np.sinc(u) * np.i0(9.0 * np.sqrt(1.0 - (u / 6.0) ** 2)) / np.i0(9.0), dtype=np.float32)
+
+
+def _true_peaks(planes_flat_of, frames, device):
+    """sos_true_peak_batch_f64 over a checked, non-empty batch: (flat, src, chans, avail) -> f64 [files] on the device."""
+    flat, src, chans, avail = planes_flat_of
+    from .engine import upload                                       # ragged.upload carries int64 / float64 only
+    coef = upload(true_peak_filter(), torch.float32, device)
+    peaks = torch.empty(len(chans), dtype=torch.float64, device=device)
+    h = L.lib()
+    for c0, c1 in ragged.chunks(len(chans)):
+        tab = loudness_table(chans[c0:c1], avail[c0:c1], frames[c0:c1], np.ones(c1 - c0, dtype=np.int64), 1)
+        tab_dev = ragged.upload(tab, device)
+        L.check(h.sos_true_peak_batch_f64(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0,
+                                          L.ptr(coef), L.ptr(peaks[c0:]), L.stream_ptr()), "sos_true_peak_batch_f64")
+    return peaks
+
+
+def true_peak_batch(planes, frames=None):
+    """The TRUE PEAK (ITU-R BS.1770-4 Annex 2, by the project's own interpolator) of every file of a ragged batch, as a linear
+    value: planes and frames as loudness_batch takes them, no rate.  4x oversampling by true_peak_filter(): the point n + p / 4
+    is sum_k h_p[k] x[n + k] (12 fmaf in tap order, float32) for n = -1 .. frames - 1, the samples read 0 outside the extent the
+    encode reads; the result is the maximum of |x| and of |point| over all channels, never below the sample peak.  -> f64
+    [files] STILL ON THE DEVICE, 0 for a file without a sample.  One launch sequence per 65535 files (sos_true_peak_batch_f64),
+    no wait; a maximum has no order, so two calls give equal bits.  Float64 restatement: tests/r128_reference.py.
+    ValueError before any launch: a file that is not a (1 .. 64 channels, n) float32 tensor, bad frames."""
+    who = "true_peak_batch"
+    planes = check_planes(who, planes)
+    frames = plane_frames(who, planes, frames)
+    L.require_cuda(*planes)
+    if not planes:
+        return torch.zeros(0, dtype=torch.float64, device="cuda")
+    return _true_peaks(planes_flat(planes), frames, planes[0].device)
+
+
+def _one_clip(who, x):
+    """x 1-D or (channels, n), a numpy array or a GPU tensor, as one (channels, n) f32 GPU tensor."""
+    if np.ndim(x) not in (1, 2):
+        raise ValueError("%s: x is 1-D or (channels, n), got %d dimensions" % (who, np.ndim(x)))
+    if torch.is_tensor(x):
+        L.require_cuda(x)
+        y = x.detach().float().contiguous()
+    elif not torch.cuda.is_available():
+        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
+    else:
+        y = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).cuda()
+    return y.reshape(1, -1) if y.dim() == 1 else y.contiguous()
+
+
+def true_peak(x):
+    """true_peak_batch of one clip: x 1-D or (channels, n), a numpy array or a GPU tensor -> a Python float (one wait)."""
+    return float(true_peak_batch([_one_clip("true_peak", x)]).cpu()[0])
+
+
+def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDNESS_SPLIT, true_peak=False, loudness_range=False):
     """Integrated loudness (ITU-R BS.1770-4 / EBU R128, gated) of every file of a ragged batch.  planes: one (channels, n) f32
     GPU tensor per file, 1 .. 64 channels; rates: its sample rate in Hz (one per file, or one for all); channel_weights: per file
     None (every channel counts 1.0: exact for mono and stereo) or one weight >= 0 per channel (surround: 1.41 for the rear pair,
@@ -578,6 +643,14 @@ def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDN
     frames, the SAMPLE peak, not the true peak), blocks / blocks_abs (int64: blocks passing both gates / the absolute one) and
     rows (f64 [files][4], what audio_io.loudness_gain_batch_device reads).  One launch sequence per 65535 files
     (sos_loudness_batch_f64), no wait.  `split`: chunks per hop of the filter scan; it moves the result by rounding only.
+    true_peak=True adds the keys true_peak (f64: true_peak_batch of the same planes and frames, one more launch sequence) and
+    rows_true (rows with column 1 replaced by it: handed to audio_io.loudness_gain_batch_device, the ceiling then bounds the
+    TRUE peak).  loudness_range=True adds lra (f64, LU: EBU Tech 3342 -- short-term windows of 30 hops every hop, gates l > -70
+    and l > (loudness of the mean z of the absolutely gated windows) - 20, the 95th minus the 10th nearest-rank percentile of
+    the survivors, 0 without one), max_momentary / max_short_term (f64, LUFS: the ungated maxima over the 400 ms blocks / the
+    3 s windows, -inf without one) and windows (int64: windows passing both gates), from the chunk energies the measurement
+    left on the device (sos_loudness_range_batch_f64, two more launches).  With both False the launches and the keys are the
+    ones above.  Float64 restatement of both: tests/r128_reference.py.
     ValueError before any launch: a file that is not such a tensor, a rate below 10 * split Hz, bad weights or frames."""
     who = "loudness_batch"
     planes = check_planes(who, planes)
@@ -592,13 +665,19 @@ def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDN
     weights = _loudness_weights(channel_weights, planes, who)
     frames = plane_frames(who, planes, frames)
     L.require_cuda(*planes)
+    peaks = more = None
     if not planes:
         rows = torch.zeros((0, 4), dtype=torch.float64, device="cuda")
+        peaks, more = rows[:, 1], rows
     else:
         device = planes[0].device
         flat, src, chans, avail = planes_flat(planes)
         coef = ragged.upload(np.stack([k_weighting(r) for r in rates]), device)
         rows = torch.empty((len(planes), 4), dtype=torch.float64, device=device)
+        if true_peak:
+            peaks = _true_peaks((flat, src, chans, avail), frames, device)
+        if loudness_range:
+            more = torch.empty((len(planes), 4), dtype=torch.float64, device=device)
         h = L.lib()
         for c0, c1 in ragged.chunks(len(planes)):
             tab = loudness_table(chans[c0:c1], avail[c0:c1], frames[c0:c1], [loudness_hop(r) for r in rates[c0:c1]], int(split))
@@ -610,21 +689,37 @@ def loudness_batch(planes, rates, channel_weights=None, frames=None, split=LOUDN
             L.check(h.sos_loudness_batch_f64(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0,
                                              L.ptr(coef[c0:]), L.ptr(w), int(split), L.ptr(ws), ws.numel(), L.ptr(rows[c0:]),
                                              L.stream_ptr()), "sos_loudness_batch_f64")
-    return dict(lufs=rows[:, 0], peak=rows[:, 1], blocks=rows[:, 2].to(torch.int64), blocks_abs=rows[:, 3].to(torch.int64), rows=rows)
+            if loudness_range:
+                need = h.sos_loudness_range_workspace_bytes(tab.ctypes.data_as(C.c_void_p), c1 - c0)
+                if need < 0:
+                    L.check(-22, "sos_loudness_range_workspace_bytes")
+                rw = torch.empty(need, dtype=torch.uint8, device=device)
+                L.check(h.sos_loudness_range_batch_f64(L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, L.ptr(w), int(split),
+                                                       L.ptr(ws), ws.numel(), L.ptr(rw), rw.numel(), L.ptr(more[c0:]),
+                                                       L.stream_ptr()), "sos_loudness_range_batch_f64")
+    out = dict(lufs=rows[:, 0], peak=rows[:, 1], blocks=rows[:, 2].to(torch.int64), blocks_abs=rows[:, 3].to(torch.int64), rows=rows)
+    if true_peak:
+        rows_true = rows.clone()
+        rows_true[:, 1] = peaks
+        out.update(true_peak=peaks, rows_true=rows_true)
+    if loudness_range:
+        out.update(lra=more[:, 0], max_momentary=more[:, 1], max_short_term=more[:, 2], windows=more[:, 3].to(torch.int64))
+    return out
 
 
-def loudness(x, sr, channel_weights=None):
+def loudness(x, sr, channel_weights=None, true_peak=False, loudness_range=False):
     """loudness_batch of one clip: x 1-D or (channels, n), a numpy array or a GPU tensor -> dict(lufs, peak, blocks, blocks_abs)
-    of Python numbers (one wait)."""
-    if np.ndim(x) not in (1, 2):
-        raise ValueError("loudness: x is 1-D or (channels, n), got %d dimensions" % np.ndim(x))
-    if torch.is_tensor(x):
-        L.require_cuda(x)
-        y = x.detach().float().contiguous()
-    elif not torch.cuda.is_available():
-        raise RuntimeError("sos_amd.metrics needs an MI355X: there is no CPU fallback")
-    else:
-        y = torch.from_numpy(np.array(x, dtype=np.float32, order="C")).cuda()
-    r = loudness_batch([y.reshape(1, -1) if y.dim() == 1 else y.contiguous()], [sr], None if channel_weights is None else [channel_weights])
-    lufs, peak, n_rel, n_abs = r["rows"][0].cpu().tolist()
-    return dict(lufs=lufs, peak=peak, blocks=int(n_rel), blocks_abs=int(n_abs))
+    of Python numbers (one wait); with true_peak also true_peak, with loudness_range also lra, max_momentary, max_short_term and
+    windows."""
+    r = loudness_batch([_one_clip("loudness", x)], [sr], None if channel_weights is None else [channel_weights],
+                       true_peak=true_peak, loudness_range=loudness_range)
+    parts = [r["rows"][0]] + ([r["true_peak"]] if true_peak else []) + \
+        ([r["lra"], r["max_momentary"], r["max_short_term"], r["windows"].double()] if loudness_range else [])
+    v = (torch.cat([p.reshape(-1) for p in parts]) if len(parts) > 1 else parts[0]).cpu().tolist()
+    out = dict(lufs=v[0], peak=v[1], blocks=int(v[2]), blocks_abs=int(v[3]))
+    if true_peak:
+        out["true_peak"] = v[4]
+    if loudness_range:
+        lra, mom, st, n = v[-4:]
+        out.update(lra=lra, max_momentary=mom, max_short_term=st, windows=int(n))
+    return out

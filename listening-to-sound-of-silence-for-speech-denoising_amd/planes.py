@@ -176,7 +176,10 @@ def loudness_gain_batch_device(planes, stats, target, peak_ceiling_db=-1.0, fram
     keeps its value).  Per file, in float64, g = min(10^((target - L) / 20), 10^(ceiling / 20) / peak), stored as float32; g = 1
     where L is -inf (no block passed the gates), the peak is 0 or the target is not finite; out = x * g, one float32 multiply.
     -> (gains f32 [files], limited bool [files]: the ceiling bound the gain), on the device.  Float64 restatement:
-    tests/loudness_reference.py."""
+    tests/loudness_reference.py.
+    A TRUE-PEAK ceiling (dBTP, what EBU R128 delivery asks for): hand over metrics.loudness_batch(.., true_peak=True)["rows_true"],
+    the rows with the true peak in column 1.  g = min(10^((target - L) / 20), 10^(ceiling / 20) / true peak); the interpolation
+    is linear, so the scaled file's true peak is g * the measured one up to float32 rounding, and stays at or below the ceiling."""
     who = "loudness_gain_batch_device"
     planes = check_planes(who, planes)
     rows = stats["rows"] if isinstance(stats, dict) else stats

@@ -6,7 +6,8 @@ that the noise floors of a stereo pair drop in and out together.  The decode, th
 and the encode each run in launches shared by all files and channels of a group (csrc/pcm_io.hip, csrc/wave_io.hip,
 csrc/ragged_window.hip).  The networks run at 14 kHz: by default a file of a higher rate comes back band-limited to 7 kHz;
 high_band='keep' / 'follow' merge the band above 7 kHz of the source back in (csrc/band_merge.hip).  loudness= brings every
-written file to a target integrated loudness (ITU-R BS.1770 / EBU R128, csrc/loudness.hip) by one gain per file before the encode."""
+written file to a target integrated loudness (ITU-R BS.1770 / EBU R128, csrc/loudness.hip) by one gain per file before the encode;
+peak='true' states its ceiling in dBTP and loudness_range=True reports the loudness range and the R128 maxima."""
 import os
 
 import numpy as np
@@ -66,9 +67,18 @@ def _check_files(paths, out_dir, sample_format, suffix, link_channels=None, high
     return infos, formats, out_paths
 
 
-def _check_loudness(loudness, peak_ceiling_db, channel_weights):
-    """What can be refused from the three levelling arguments alone."""
+PEAK_MODES = ("sample", "true")
+
+
+def _check_loudness(loudness, peak_ceiling_db, channel_weights, peak="sample", loudness_range=False):
+    """What can be refused from the levelling arguments alone."""
+    if peak not in PEAK_MODES:
+        raise ValueError("denoise_recordings: unknown peak %r (one of %s)" % (peak, ", ".join(PEAK_MODES)))
+    if not isinstance(loudness_range, (bool, np.bool_)):
+        raise ValueError("denoise_recordings: loudness_range is True or False, got %r" % (loudness_range,))
     if loudness is None:
+        if peak == "true" or loudness_range:            # both ride the levelling's measurement, and the ceiling needs its gain
+            raise ValueError("denoise_recordings: peak='true' and loudness_range=True need a loudness target (a number or 'source')")
         return
     if loudness != "source":
         ok = not isinstance(loudness, (bool, str)) and np.ndim(loudness) == 0 and np.isfinite(float(loudness))
@@ -130,7 +140,8 @@ def _merge_back(natives, lows_in, lows_out, rates, high_band, smooth_frames):
 @torch.no_grad()
 def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, context_seconds=2.0, max_batch=256,
                        max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None,
-                       high_band="drop", smooth_frames=2, loudness=None, peak_ceiling_db=-1.0, channel_weights=None):
+                       high_band="drop", smooth_frames=2, loudness=None, peak_ceiling_db=-1.0, channel_weights=None,
+                       peak="sample", loudness_range=False):
     """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
     channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32, G.711 A-law / mu-law; a float64 source is written as
     float32); sample_format= ('s16', 's24', 's32', 'u8', 'f32', 'alaw', 'ulaw') forces one format for all files.
@@ -172,18 +183,31 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     channel_weights: None (every channel counts 1.0: exact for mono and stereo), one weight >= 0 per channel for all files, or
     {channels: weights} (surround: 1.41 for the rear pair and 0 for the LFE are the caller's to pass).  The rows join the
     group's one download.
+    peak: 'sample' (the default) or 'true'.  'true' states the ceiling as EBU R128 does, in dBTP: the TRUE peak of the planes the
+    encode will read (metrics.true_peak_batch: 4x interpolation, csrc/loudness.hip, one more launch sequence in the group's
+    measurement) takes the sample peak's place in g, so the written file's true peak is at most the ceiling where a sample-peak
+    ceiling can leave it up to 3 dB above (a sine at a quarter of the rate).  It needs a loudness target.
+    loudness_range=True also measures the loudness range (LRA, EBU Tech 3342) and the maximum momentary / short-term loudness of
+    every written file (metrics.loudness_batch(loudness_range=True): two more launches from the energies the measurement left
+    on the device).  It needs a loudness target too.  Under 'source' the extra measures are taken on the outputs only (the
+    sources then get a measuring sequence of their own).  Both ride the group's one download.
     -> one dict per file: path, out_path, channels, rate, frames, format, clipped (samples that saturated or were NaN, all
     channels), windows (denoise_long windows, all channels); with loudness also loudness_before (LUFS of the denoised file
     before the gain, -inf without a gated block), loudness (before + 20 log10 g, not measured again), loudness_target, gain_db
-    and peak_limited (the ceiling bound the gain).
+    and peak_limited (the ceiling bound the gain); under peak='true' also true_peak_db (20 log10(g * true peak): the level
+    written, in dBTP, -inf for a silent file); under loudness_range=True also lra (LU, of the planes before the gain, which a gain
+    does not move) and max_momentary / max_short_term (LUFS, as written: measured before the gain, + gain_db).
     ValueError before any launch of the call, naming the file: fewer than MIN_FRAMES STFT frames at 14 kHz, an unsupported
     format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format, link_channels or
     high_band, smooth_frames outside 0 .. 16; a loudness that is not finite or outside -70 .. 0, a ceiling above 0, weights that are
-    negative or not one per channel;
+    negative or not one per channel, an unknown peak, a loudness_range that is no bool, either of the two without a loudness target;
     window_plan's argument rules; a group with more than 65535 windows."""
     paths = [os.fspath(p) for p in paths]
-    _check_loudness(loudness, peak_ceiling_db, channel_weights)
+    _check_loudness(loudness, peak_ceiling_db, channel_weights, peak, loudness_range)
     infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix, link_channels, high_band, smooth_frames)
+    flags = dict(true_peak=True) if peak == "true" else {}
+    if loudness_range:
+        flags["loudness_range"] = True                  # with neither, loudness_batch is called as it always was
     weights = _file_weights(channel_weights, infos, paths) if loudness is not None else None
     core, context = windows._hops(round(window_seconds * SR)), windows._hops(round(context_seconds * SR))
     groups = ragged.byte_groups([4 * i["frames"] * i["channels"] for i in infos], max_bytes)
@@ -227,15 +251,22 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
             per_file.update(zip(group, level))
             frames, rates_g = [infos[f]["frames"] for f in group], [infos[f]["rate"] for f in group]
             w = [weights[f] for f in group]
-            if loudness == "source":
-                rows = metrics.loudness_batch(level + list(ys), rates_g * 2, w * 2, frames * 2)["rows"]
-                target = rows.new_empty(len(group)).copy_(rows[len(group):, 0])      # packed, whatever the group's size
+            if loudness == "source" and not flags:
+                got = metrics.loudness_batch(level + list(ys), rates_g * 2, w * 2, frames * 2)
+                target = got["rows"].new_empty(len(group)).copy_(got["rows"][len(group):, 0])       # packed, whatever the group's size
+            elif loudness == "source":                  # the true peak and the range of the outputs only: the sources apart
+                got = metrics.loudness_batch(level, rates_g, w, frames, **flags)
+                target = metrics.loudness_batch(list(ys), rates_g, w, frames)["lufs"].contiguous()
             else:
-                rows = metrics.loudness_batch(level, rates_g, w, frames)["rows"]
-                target = torch.full((len(group),), float(loudness), dtype=torch.float64, device=rows.device)
-            gains, limited = audio_io.loudness_gain_batch_device(level, rows[:len(group)], target, peak_ceiling_db, frames=frames)
-            parts += [rows[:len(group)].contiguous().view(torch.uint8).reshape(-1), target.view(torch.uint8),
+                got = metrics.loudness_batch(level, rates_g, w, frames, **flags)
+                target = torch.full((len(group),), float(loudness), dtype=torch.float64, device=got["rows"].device)
+            rows = got["rows_true" if peak == "true" else "rows"][:len(group)]               # column 1: the peak the ceiling bounds
+            gains, limited = audio_io.loudness_gain_batch_device(level, rows, target, peak_ceiling_db, frames=frames)
+            parts += [rows.contiguous().view(torch.uint8).reshape(-1), target.view(torch.uint8),
                       gains.view(torch.uint8), limited.view(torch.uint8)]
+            if loudness_range:                          # {LRA, max momentary, max short-term, windows}: windows -1 marks a skipped row
+                more = torch.stack([got[k].double() for k in ("lra", "max_momentary", "max_short_term", "windows")], dim=1)
+                parts.append(more.contiguous().view(torch.uint8).reshape(-1))
         for fmt, files in by_format.items():
             data, offsets, clipped = audio_io.encode_batch_device([per_file[f] for f in files], fmt,
                                                                   frames=[infos[f]["frames"] for f in files])
@@ -249,6 +280,12 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
                 host[2].view(np.float32), host[3].view(np.bool_)
             if np.any(rows_h[:, 2] < 0):
                 raise RuntimeError("sos_loudness_batch_f64: device rows disagree with the host's")
+            if peak == "true" and np.any(np.isnan(rows_h[:, 1])):
+                raise RuntimeError("sos_true_peak_batch_f64: device rows disagree with the host's")
+        if loudness_range:
+            more_h = host[4].view(np.float64).reshape(-1, 4)
+            if np.any(more_h[:, 3] < 0):
+                raise RuntimeError("sos_loudness_range_batch_f64: device rows disagree with the host's")
         for g, f in enumerate(group):
             part, b0, b1, j = spans[f]
             tag, bits = SAMPLE_FORMATS[formats[f]][2:]
@@ -262,4 +299,10 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
                 gain_db = 20.0 * float(np.log10(np.float64(gains_h[g])))
                 results[-1].update(loudness_before=float(rows_h[g, 0]), loudness=float(rows_h[g, 0]) + gain_db,
                                    loudness_target=float(target_h[g]), gain_db=gain_db, peak_limited=bool(limited_h[g]))
+            if peak == "true":
+                with np.errstate(divide="ignore"):
+                    results[-1].update(true_peak_db=float(20.0 * np.log10(np.float64(gains_h[g]) * rows_h[g, 1])))
+            if loudness_range:
+                results[-1].update(lra=float(more_h[g, 0]), max_momentary=float(more_h[g, 1]) + gain_db,
+                                   max_short_term=float(more_h[g, 2]) + gain_db)
     return results

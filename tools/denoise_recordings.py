@@ -3,13 +3,15 @@ count, channels, rate and sample format.
 
   python tools/denoise_recordings.py DETECTOR.pth DENOISER.pth OUT_DIR in1.wav in2.wav ... [--sample-format s16] [--suffix _dn]
                                      [--link-channels any] [--high-band keep|follow] [--smooth-frames 2]
-                                     [--loudness -23|source] [--peak-ceiling-db -1]
+                                     [--loudness -23|source] [--peak-ceiling-db -1] [--peak sample|true] [--loudness-range]
 
 The networks run at 14 kHz: by default (--high-band drop) a 44.1 / 48 kHz file comes back band-limited to 7 kHz.  --high-band keep
 passes the source's band above 7 kHz through untouched; --high-band follow gives it the attenuation the denoiser applied below.
 
 --loudness brings every written file to a target integrated loudness in LUFS (ITU-R BS.1770 / EBU R128), or with `source` to the
-loudness its source had, by one gain per file applied before the samples are quantised; --peak-ceiling-db bounds the sample peak.
+loudness its source had, by one gain per file applied before the samples are quantised; --peak-ceiling-db bounds the sample peak, or with
+--peak true the TRUE peak (dBTP, what EBU R128 delivery asks for: 4x interpolation).  --loudness-range also reports the loudness
+range (LRA, EBU Tech 3342) and the maximum momentary and short-term loudness of every written file.
 
 The checkpoints are the reference's (`{clock, model_state_dict, ...}` as the agents save them) or bare state dicts."""
 import argparse
@@ -59,7 +61,11 @@ def main():
     ap.add_argument("--loudness", type=_loudness, default=None,
                     help="target integrated loudness in LUFS (-70 .. 0), or 'source': the loudness of each file's own source "
                          "(default: the level the networks return)")
-    ap.add_argument("--peak-ceiling-db", type=float, default=-1.0, help="--loudness: the sample peak a levelled file may reach, dBFS (<= 0)")
+    ap.add_argument("--peak-ceiling-db", type=float, default=-1.0, help="--loudness: the peak a levelled file may reach, dBFS / dBTP (<= 0)")
+    ap.add_argument("--peak", choices=list(recordings.PEAK_MODES), default="sample",
+                    help="--loudness: what --peak-ceiling-db bounds, the sample peak (default) or the true peak (dBTP)")
+    ap.add_argument("--loudness-range", action="store_true",
+                    help="--loudness: also report the loudness range (LU) and the maximum momentary / short-term loudness (LUFS) of every written file")
     ap.add_argument("--precision", default="mixed", choices=["bf16", "bf16x3", "fp16", "mixed"])
     args = ap.parse_args()
     det, jm = _load(dnet.get_network(), args.detector), _load(jnet.get_network(MyConfig()), args.denoiser)
@@ -68,9 +74,14 @@ def main():
                                            args.max_columns, sample_format=args.sample_format, suffix=args.suffix,
                                            link_channels=args.link_channels, high_band=args.high_band,
                                            smooth_frames=args.smooth_frames, loudness=args.loudness,
-                                           peak_ceiling_db=args.peak_ceiling_db):
+                                           peak_ceiling_db=args.peak_ceiling_db, peak=args.peak,
+                                           loudness_range=args.loudness_range):
         level = "" if args.loudness is None else ", %.2f -> %.2f LUFS (%+.2f dB%s)" % (
             r["loudness_before"], r["loudness"], r["gain_db"], ", peak-limited" if r["peak_limited"] else "")
+        if args.peak == "true":
+            level += ", %.2f dBTP" % r["true_peak_db"]
+        if args.loudness_range:
+            level += ", LRA %.2f LU, max M %.2f / S %.2f LUFS" % (r["lra"], r["max_momentary"], r["max_short_term"])
         print("%s -> %s: %d x %d frames at %d Hz, %s, %d windows, %d samples clipped%s"
               % (r["path"], r["out_path"], r["channels"], r["frames"], r["rate"], r["format"], r["windows"], r["clipped"], level))
 

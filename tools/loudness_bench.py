@@ -8,7 +8,13 @@ of 1 .. 10 s at 44.1 kHz, seeded):
      sequence reads the planes twice (8 bytes per sample, counted as a copy of 4), the gain reads and writes them once.  Each
      twice: the Python call (table, coefficients and weights built and uploaded per call) and the C entry point with all of
      that already on the device; the entry point's rows are checked to be the Python call's.
-A measurement: nothing is asserted."""
+  3. --true-peak: the other EBU R128 measures instead of 1. and 2., every row of a table measured once per round, --kernel-repeats
+     alternating rounds: sos_true_peak_batch_f64 (the Python call and the entry point) on the files' planes and on --kernel-mib
+     MiB of planes, next to Tensor.copy_ of the same bytes and to the way the number could be had before -- every channel
+     through resample_batch_device to four times the rate, then abs().amax() per file (a torch conv1d with the true-peak
+     coefficients where the resampler refuses the pair); sos_loudness_range_batch_f64 next to the measure sequence it follows;
+     and denoise_recordings(loudness=-23, peak='true', loudness_range=True) against peak='sample', alternating.
+A measurement: no time is asserted; the entry points' results are checked to be the Python calls' before they are timed."""
 import argparse
 import os
 import sys
@@ -74,6 +80,110 @@ def launches(name, planes, rate, args):
               f"sample it must move   {ms / copy_ms:6.2f} x the copy")
 
 
+def _rounds(rows, args):
+    """{name: [ms, ..]}: every row once per round, the rows alternating."""
+    runs = {name: [] for name, _, _ in rows}
+    for _ in range(args.kernel_repeats):
+        for name, fn, reps in rows:
+            runs[name].append(RB.device_ms(fn, reps))
+    return runs
+
+
+def _oversampled_peaks(planes, rate):
+    """The true peak as it could be had without the kernel: (what ran, a function returning one peak per file)."""
+    channels = [p[c] for p in planes for c in range(p.shape[0])]
+    owner = torch.tensor([i for i, p in enumerate(planes) for _ in range(p.shape[0])], device="cuda")
+
+    def per_file(peaks):
+        return torch.zeros(len(planes), device="cuda").index_reduce_(0, owner, peaks, "amax", include_self=True)
+
+    def resampled():
+        up = audio_io.resample_batch_device(channels, rate, 4 * rate)
+        return per_file(torch.stack([u.abs().amax() for u in up]))
+
+    try:
+        resampled()
+        return "resample_batch_device to 4x, abs().amax()", resampled
+    except (ValueError, RuntimeError) as e:
+        print("  resample_batch_device(%d -> %d) refused (%s): torch conv1d with the true-peak coefficients instead" % (rate, 4 * rate, e))
+    coef = torch.from_numpy(metrics.true_peak_filter()).cuda().flip(1).unsqueeze(1)      # conv1d correlates: taps reversed
+
+    def convolved():
+        peaks = [torch.maximum(torch.nn.functional.conv1d(c.view(1, 1, -1), coef, padding=6).abs().amax(), c.abs().amax()) for c in channels]
+        return per_file(torch.stack(peaks))
+    return "torch conv1d with the coefficients, abs().amax()", convolved
+
+
+def true_peak_launches(name, planes, rate, args):
+    samples = sum(p.numel() for p in planes)
+    h = L.lib()
+    flat = ragged.back_to_back(planes)
+    chans, avail = [p.shape[0] for p in planes], [p.shape[1] for p in planes]
+    split = metrics.LOUDNESS_SPLIT
+    tab = metrics.loudness_table(chans, avail, avail, [metrics.loudness_hop(rate)] * len(planes), split)
+    tab_dev, host = torch.from_numpy(tab).cuda(), tab.ctypes.data_as(L.C.c_void_p)
+    tp_coef = torch.from_numpy(metrics.true_peak_filter()).cuda()
+    peaks = torch.empty(len(planes), dtype=torch.float64, device="cuda")
+    coef = torch.from_numpy(np.stack([metrics.k_weighting(rate)] * len(planes))).cuda()
+    w = torch.ones(sum(chans), dtype=torch.float64, device="cuda")
+    rows4, out4 = (torch.empty((len(planes), 4), dtype=torch.float64, device="cuda") for _ in range(2))
+    ws = torch.empty(h.sos_loudness_workspace_bytes(host, len(planes), split), dtype=torch.uint8, device="cuda")
+    rw = torch.empty(h.sos_loudness_range_workspace_bytes(host, len(planes)), dtype=torch.uint8, device="cuda")
+    src = torch.empty(samples, dtype=torch.float32, device="cuda").normal_()
+    dst = torch.empty_like(src)
+    entry = lambda: L.check(h.sos_true_peak_batch_f64(L.ptr(flat), L.ptr(tab_dev), host, len(planes), L.ptr(tp_coef), L.ptr(peaks),   # noqa: E731
+                                                      L.stream_ptr()))
+    measure = lambda: L.check(h.sos_loudness_batch_f64(L.ptr(flat), L.ptr(tab_dev), host, len(planes), L.ptr(coef), L.ptr(w), split,  # noqa: E731
+                                                       L.ptr(ws), ws.numel(), L.ptr(rows4), L.stream_ptr()))
+    ranges = lambda: L.check(h.sos_loudness_range_batch_f64(L.ptr(tab_dev), host, len(planes), L.ptr(w), split, L.ptr(ws), ws.numel(),  # noqa: E731
+                                                            L.ptr(rw), rw.numel(), L.ptr(out4), L.stream_ptr()))
+    how, before = _oversampled_peaks(planes, rate)
+    entry()
+    old = before().double()
+    print(f"{name}: {len(planes)} files, {samples * 4 / 2**20:.1f} MiB of planes; largest relative difference of the kernel's peaks from "
+          f"'{how}': {float(((peaks - old).abs() / peaks.clamp_min(1e-30)).max()):.2e}")
+    assert torch.equal(peaks, metrics.true_peak_batch(planes))
+    measure()
+    rows = [("Tensor.copy_ of the planes", lambda: dst.copy_(src), args.kernel_reps),
+            ("true peak, entry point", entry, args.kernel_reps),
+            ("true peak, Python call", lambda: metrics.true_peak_batch(planes), args.kernel_reps),
+            (how, before, 1),
+            ("measure sequence, entry", measure, args.kernel_reps),
+            ("range sequence, entry", ranges, args.kernel_reps)]
+    runs = _rounds(rows, args)
+    copy_ms = float(np.median(runs[rows[0][0]]))
+    print(f"  {args.kernel_repeats} alternating rounds, {args.kernel_reps} calls per measurement (1 for the old way): median (min, max)")
+    for what, _, _ in rows:
+        ms = float(np.median(runs[what]))
+        print(f"  {what:46s}: {ms:9.3f} ms (min {min(runs[what]):.3f}, max {max(runs[what]):.3f})  {samples * 4 / ms / 1e6:8.1f} GB/s of "
+              f"plane bytes read   {samples * 36 / ms / 1e9:7.2f} TFMA/s if it were the kernel   {ms / copy_ms:7.2f} x the copy")
+
+
+def true_peak_calls(paths, tmp, secs, args):
+    det = dnet.get_network()
+    det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+    jm = jnet.get_network(MyConfig())
+    jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+    det, jm = det.cuda().eval(), jm.cuda().eval()
+    sos_amd.set_precision("mixed")
+    forms = dict(sample=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "sample"), max_batch=args.max_batch,
+                                                              loudness=args.target, peak="sample"),
+                 true=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "true"), max_batch=args.max_batch,
+                                                            loudness=args.target, peak="true", loudness_range=True))
+    for fn in forms.values():
+        fn()
+    runs = {k: [] for k in forms}
+    for _ in range(args.repeats):
+        for k, fn in forms.items():
+            runs[k].append(RB.once(fn))
+    print(f"{args.files} stereo s16 files at {RB.RATE} Hz, {secs:.0f} s of audio x 2 channels, 'mixed' precision, {args.repeats} "
+          "alternating repeats (median, min, max)")
+    a = RB.report("peak='sample'", args.files, runs["sample"])
+    b = RB.report("peak='true', loudness_range", args.files, runs["true"])
+    print(f"  true peak and range / sample peak = {b / a:.3f}")
+    sos_amd.set_precision("bf16")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=64)
@@ -86,12 +196,18 @@ def main():
     ap.add_argument("--kernel-repeats", type=int, default=3)
     ap.add_argument("--splits", type=int, nargs="+", default=[metrics.LOUDNESS_SPLIT])
     ap.add_argument("--skip-calls", action="store_true", help="only the launches")
+    ap.add_argument("--true-peak", action="store_true", help="the true-peak and loudness-range rows instead of the others")
     args = ap.parse_args()
     print(torch.cuda.get_device_name(0))
     RB._count_downloads()
     with tempfile.TemporaryDirectory() as tmp:
         paths, secs = RB.make_files(tmp, args.files, args.seed)
-        if not args.skip_calls:
+        if args.true_peak:
+            if not args.skip_calls:
+                true_peak_calls(paths, tmp, secs, args)
+            ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
+            true_peak_launches("the files' planes", ys, RB.RATE, args)
+        elif not args.skip_calls:
             det = dnet.get_network()
             det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
             jm = jnet.get_network(MyConfig())
@@ -113,12 +229,13 @@ def main():
             b = RB.report("loudness=%g" % args.target, args.files, runs["level"])
             print(f"  levelled / plain = {b / a:.3f}")
             sos_amd.set_precision("bf16")
-        ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
-        launches("the files' planes", ys, RB.RATE, args)
+        if not args.true_peak:
+            ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
+            launches("the files' planes", ys, RB.RATE, args)
     frames, ch = 1 << 20, 2
     n_files = max(1, (args.kernel_mib << 20) // (4 * frames * ch))
     flat = torch.empty(n_files * ch * frames, dtype=torch.float32, device="cuda").uniform_(-0.5, 0.5)
-    launches("large planes", [v.view(ch, frames) for v in flat.split(ch * frames)], RB.RATE, args)
+    (true_peak_launches if args.true_peak else launches)("large planes", [v.view(ch, frames) for v in flat.split(ch * frames)], RB.RATE, args)
 
 
 if __name__ == "__main__":
