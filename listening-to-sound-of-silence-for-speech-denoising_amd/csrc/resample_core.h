@@ -1,7 +1,9 @@
-// resample_core.h -- what the resamplers of wave_io.hip (one clip, a ragged batch of clips), stream_resample.hip (streams
-// that arrive in chunks), band_merge.hip and stream_band.hip (two signals per output) share: resampy's running time register as a
-// piecewise-linear description, and the arithmetic of one output sample, tap for tap.  The first two call rs_output, so a
-// stream gets the bits of the clip it is a prefix of; band_merge.hip and stream_band.hip call rs_output2, which keeps those bits.
+// resample_core.h -- the ARITHMETIC that the resamplers of wave_io.hip (one clip, a ragged batch of clips), stream_resample.hip
+// (streams that arrive in chunks), band_merge.hip and stream_band.hip (two signals per output) share: resampy's running time
+// register as a piecewise-linear description, and one output sample, tap for tap.  The first two call rs_output, so a stream gets
+// the bits of the clip it is a prefix of; band_merge.hip and stream_band.hip call rs_output2, which keeps those bits.  What sits
+// around the output loop (filter rule, grid, launch, window load, table walks) is resample_launch.h's; each table's bounds rule
+// (a *_row reader and a *_why that host and kernel both call) stands in the file of its entry point.
 #pragma once
 #include "ragged.h"
 #include <math.h>
@@ -22,10 +24,9 @@ struct RsSegs {
 };
 
 // The description of the outputs 0 .. n_out - 1; with `stop`, it ends earlier, as soon as the register has reached `stop`
-// (sos_stream_resample_ready: the first output whose time is not below a sample count).  k_end / s_end: the first output the
-// description does not cover and the register there, s_end = time(k_end).  -1: more than RS_MAXSEG segments.
-static int rs_build_segments(double inc, long long n_out, RsSegs* g, double stop = INFINITY, long long* k_end = nullptr,
-                             double* s_end = nullptr) {
+// (sos_stream_resample_ready: the first output whose time is not below a sample count).  k_end: the first output the
+// description does not cover.  -1: more than RS_MAXSEG segments.
+static int rs_build_segments(double inc, long long n_out, RsSegs* g, double stop = INFINITY, long long* k_end = nullptr) {
     long long k = 0;
     double s = 0.0;
     g->n = 0;
@@ -50,7 +51,6 @@ static int rs_build_segments(double inc, long long n_out, RsSegs* g, double stop
         s = fma((double)(M + 1), d, s);
     }
     if (k_end) *k_end = k;
-    if (s_end) *s_end = s;
     return 0;
 }
 

@@ -25,7 +25,7 @@
 // the row is named) or names a slot twice, the kernels skip a row of the DEVICE table that fails the same test.  Ring indices
 // are modular.  No atomics.
 #include "band_core.h"
-#include <vector>
+#include "resample_launch.h"
 
 #define SB_THREADS 256
 #define SB_TILE 256                     // outputs per workgroup step
@@ -67,13 +67,10 @@ __global__ __launch_bounds__(MT) void stream_band_ratio_kernel(const float* __re
     }
 }
 
+// three rings per slot (x, a, b) and the hop; false with the error set
 static bool stream_band_rings(const char* who, int nrows, int64_t slots, int64_t cap, int hop) {
-    if (nrows < 1 || nrows > RAGGED_MAX_CLIPS || slots < 1 || 3 * slots > RAGGED_MAX_CLIPS || cap < 1 ||
-        cap > INT64_MAX / 8 / RAGGED_MAX_CLIPS || hop < 1 || hop > SB_MAX_HOP) {
-        sos_set_error("%s: bad args (1 .. 65535 rows, got %d; 1 .. 21845 slots, got %lld; rings of %lld samples; hop=%d: 1 .. 2^20)",
-                      who, nrows, (long long)slots, (long long)cap, hop);
-        return false;
-    }
+    if (!rs_rings(who, nrows, slots, 3, cap)) return false;
+    if (hop < 1 || hop > SB_MAX_HOP) { sos_set_error("%s: hop=%d: 1 .. 2^20", who, hop); return false; }
     return true;
 }
 
@@ -96,7 +93,7 @@ extern "C" int sos_stream_band_ratio_f64(const float* ring, int64_t slots, int64
         sos_set_error("%s: a ring of %lld frames", who, (long long)rcap);
         return SOS_EINVAL;
     }
-    std::vector<uint8_t> seen(slots, 0);
+    RsSlotsOnce once(slots);
     int64_t most = 0;
     for (int r = 0; r < nrows; ++r) {
         const StreamBandRatio e = stream_band_ratio_row(table_host, r);
@@ -107,11 +104,7 @@ extern "C" int sos_stream_band_ratio_f64(const float* ring, int64_t slots, int64
                           (long long)e.j_hi, hop, (long long)e.m_a, (long long)e.m_b, (long long)cap, (long long)rcap);
             return SOS_EINVAL;
         }
-        if (seen[e.slot]) {
-            sos_set_error("%s: row %d names slot %lld, which an earlier row of the table names", who, r, (long long)e.slot);
-            return SOS_EINVAL;
-        }
-        seen[e.slot] = 1;
+        if (!once.take(who, r, e.slot)) return SOS_EINVAL;
         most = std::max(most, e.j_hi - e.j_lo);
     }
     if (most == 0) return SOS_OK;
@@ -167,12 +160,12 @@ __global__ __launch_bounds__(SB_THREADS) void stream_band_merge_kernel(const flo
                                                                        const float* __restrict__ win, int nwin, int num_table,
                                                                        int hop, int K, float* __restrict__ out) {
     extern __shared__ float w[];
-    for (int i = threadIdx.x; i <= nwin; i += SB_THREADS) w[i] = win[i < nwin ? i : nwin - 1];
-    __syncthreads();
+    rs_load_window<SB_THREADS>(w, win, nwin);
     const int index_step = num_table;                            // an upsampling: scale = 1
     const int64_t reach = nwin / index_step;
     const double frame = ratio * (double)hop;
     // the tiles of the rows lie back to back in table order; this workgroup's tiles ascend, so one pass over the rows serves all
+    // (the walk of stream_resample_kernel; a shared form of it changed this kernel's code and its time, EXPERIMENTS.md 3.30)
     int r = 0;
     bool read = false;
     int64_t tile0 = 0, tiles = 0;
@@ -205,9 +198,14 @@ __global__ __launch_bounds__(SB_THREADS) void stream_band_merge_kernel(const flo
     }
 }
 
-// the filter of an upsampling; false with the error set otherwise
-static bool stream_band_filter(const char* who, double ratio, int nwin, int num_table) {
-    if (!(ratio > 1.0) || !(ratio <= 1024.0) || nwin < 2 || num_table < 1 || nwin / num_table < 1) {
+// the filter of an upsampling: the rule of every resampler, a ratio within (1, 1024] and a wing of at least one sample; false
+// with the error set otherwise.  launch: as rs_filter's.
+static bool stream_band_filter(const char* who, double ratio, int nwin, int num_table, bool launch, RsFilter* f) {
+    // the ratio first: a downsampling is told that it is one, not that its ratio is too small for the table; a bad ratio of any
+    // other kind, nwin and num_table are rs_filter's.  nwin < 2 is refused for the host-only count too, as it always was here.
+    const bool down = ratio > 0.0 && !(ratio > 1.0 && ratio <= 1024.0);
+    if (!down && !rs_filter(who, ratio, nwin, num_table, launch, f)) return false;
+    if (down || nwin < 2 || f->reach < 1) {
         sos_set_error("%s: bad args (ratio=%g: above 1, the native rate over the low one; nwin=%d, num_table=%d: a wing of at least "
                       "one sample)", who, ratio, nwin, num_table);
         return false;
@@ -219,7 +217,8 @@ extern "C" int sos_stream_band_ready(double ratio, int nwin, int num_table, int 
                                      int64_t* t_ready, int64_t* first_x, int64_t* first_a, int64_t* first_b, int64_t* first_r) {
     const char* who = "sos_stream_band_ready";
     if (!t_ready || !first_x || !first_a || !first_b || !first_r) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
-    if (!stream_band_filter(who, ratio, nwin, num_table)) return SOS_EINVAL;
+    RsFilter f;
+    if (!stream_band_filter(who, ratio, nwin, num_table, false, &f)) return SOS_EINVAL;
     if (hop < 1 || hop > SB_MAX_HOP || smooth > BG_MAX_SMOOTH) {
         sos_set_error("%s: hop=%d: 1 .. 2^20; smooth=%d: 0 .. %d frames, negative for no gains", who, hop, smooth, BG_MAX_SMOOTH);
         return SOS_EINVAL;
@@ -228,7 +227,7 @@ extern "C" int sos_stream_band_ready(double ratio, int nwin, int num_table, int 
         sos_set_error("%s: a stream of %lld low-rate and %lld native samples", who, (long long)m_b, (long long)n_x);
         return SOS_EINVAL;
     }
-    const int64_t reach = nwin / num_table;
+    const int64_t reach = f.reach;
     int64_t T = 0, base = 0;
     const int rc = sos_stream_resample_ready(ratio, nwin, num_table, m_b, &T, &base);       // n(t) + 1 + R <= m_b
     if (rc != SOS_OK) return rc;
@@ -249,10 +248,7 @@ extern "C" int sos_stream_band_ready(double ratio, int nwin, int num_table, int 
         }
     }
     RsSegs g;
-    if (rs_build_segments(1.0 / ratio, T + 1, &g) != 0) {
-        sos_set_error("%s: time register needs more than %d segments", who, RS_MAXSEG);
-        return SOS_ENOSPC;
-    }
+    if (const int rc = rs_segments(who, ratio, T + 1, &g)) return rc;
     int64_t first = (int64_t)rs_time(g, T) - (reach - 1);
     if (first < 0) first = 0;
     *first_r = 0;
@@ -277,29 +273,22 @@ extern "C" int sos_stream_band_merge_f32(const float* ring, int64_t slots, int64
         return SOS_EINVAL;
     }
     if (!stream_band_rings(who, nrows, slots, cap, hop)) return SOS_EINVAL;
-    if (!stream_band_filter(who, ratio, nwin, num_table)) return SOS_EINVAL;
+    RsFilter f;
+    if (!stream_band_filter(who, ratio, nwin, num_table, true, &f)) return SOS_EINVAL;
     if (smooth > BG_MAX_SMOOTH || (smooth >= 0 && (rcap < 1 || rcap > INT64_MAX / 8 / RAGGED_MAX_CLIPS)) || total < 0 ||
-        total > INT64_MAX / 8 || (size_t)(nwin + 1) * sizeof(float) > 160 * 1024) {
-        sos_set_error("%s: bad args (smooth=%d: 0 .. %d frames, negative for no gains; a ring of %lld frames; an output of %lld; "
-                      "nwin=%d: (nwin + 1) * 4 bytes must fit the 160 KB LDS)", who, smooth, BG_MAX_SMOOTH, (long long)rcap,
-                      (long long)total, nwin);
+        total > INT64_MAX / 8) {
+        sos_set_error("%s: bad args (smooth=%d: 0 .. %d frames, negative for no gains; a ring of %lld frames; an output of %lld)", who,
+                      smooth, BG_MAX_SMOOTH, (long long)rcap, (long long)total);
         return SOS_EINVAL;
     }
     const int K = smooth < 0 ? -1 : smooth;
-    const int64_t reach = nwin / num_table;
+    const int64_t reach = f.reach;
     const double frame = ratio * (double)hop;
-    int64_t max_t = 1;
-    for (int r = 0; r < nrows; ++r) {
-        const StreamBand e = stream_band_row(table_host, r);
-        if (e.t_hi > SB_MAX_POS) { sos_set_error("%s: row %d ends at output %lld", who, r, (long long)e.t_hi); return SOS_EINVAL; }
-        max_t = std::max(max_t, e.t_hi);
-    }
-    RsSegs seg;                                       // every stream starts at 0: one description serves all rows
-    if (rs_build_segments(1.0 / ratio, max_t, &seg) != 0) {
-        sos_set_error("%s: time register of %lld outputs needs more than %d segments", who, (long long)max_t, RS_MAXSEG);
-        return SOS_ENOSPC;
-    }
-    std::vector<uint8_t> seen(slots, 0);
+    RsSegs seg;
+    int64_t max_t;
+    const auto t_hi = [table_host](int r) { return stream_band_row(table_host, r).t_hi; };
+    if (const int rc = rs_row_segments(who, nrows, t_hi, ratio, &seg, &max_t)) return rc;
+    RsSlotsOnce once(slots);
     int64_t total_tiles = 0;
     for (int r = 0; r < nrows; ++r) {
         const StreamBand e = stream_band_row(table_host, r);
@@ -313,32 +302,12 @@ extern "C" int sos_stream_band_merge_f32(const float* ring, int64_t slots, int64
                           (long long)reach);
             return SOS_EINVAL;
         }
-        if (seen[e.slot]) {
-            sos_set_error("%s: row %d names slot %lld, which an earlier row of the table names", who, r, (long long)e.slot);
-            return SOS_EINVAL;
-        }
-        seen[e.slot] = 1;
+        if (!once.take(who, r, e.slot)) return SOS_EINVAL;
         total_tiles += stream_band_tiles(e);
     }
     if (total_tiles == 0) return SOS_OK;              // every row is empty
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1) {
-        sos_set_error("%s: cannot read the number of compute units", who);
-        return SOS_ELAUNCH;
-    }
-    static sos_device_once attr_once;
-    if (sos_per_device_once(attr_once, [] {
-            if (hipFuncSetAttribute((const void*)stream_band_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-                hipSuccess) {
-                sos_set_error("sos_stream_band_merge_f32: cannot raise the dynamic LDS limit");
-                return (int)SOS_ELAUNCH;
-            }
-            return (int)SOS_OK;
-        }))
-        return SOS_ELAUNCH;
-    const unsigned grid = (unsigned)(total_tiles < cus ? total_tiles : cus);
-    hipLaunchKernelGGL(stream_band_merge_kernel, dim3(grid), dim3(SB_THREADS), (size_t)(nwin + 1) * sizeof(float), (hipStream_t)stream,
-                       ring, slots, cap, rring, rcap, table, nrows, total, max_t, ratio, seg, win, nwin, num_table, hop, K, out);
-    return sos_check_launch(who);
+    const unsigned grid = rs_grid(who, total_tiles);
+    if (!grid) return SOS_ELAUNCH;
+    return rs_launch<stream_band_merge_kernel>(who, grid, SB_THREADS, f.lds, stream, ring, slots, cap, rring, rcap, table, nrows, total,
+                                               max_t, ratio, seg, win, nwin, num_table, hop, K, out);
 }

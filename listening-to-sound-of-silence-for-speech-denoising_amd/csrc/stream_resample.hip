@@ -19,9 +19,8 @@
 // Bounds: the rule of ragged.h -- the host refuses a row that leaves what the buffers hold (SOS_EINVAL, the row is named), the
 // kernel skips a row of the DEVICE table that fails the same test (stream_rs_why).  The ring index is modular and so never
 // leaves the slot's ring; the test of the span keeps a row from reading samples the ring no longer holds.  No atomics.
-#include "resample_core.h"
+#include "resample_launch.h"
 #include <stdlib.h>
-#include <vector>
 
 #define SRS_THREADS 256
 #define SRS_TILE 256                    // outputs per workgroup step (<= SRS_THREADS)
@@ -59,8 +58,7 @@ __global__ __launch_bounds__(SRS_THREADS) void stream_resample_kernel(const floa
                                                                      const float* __restrict__ win, int nwin, int num_table,
                                                                      int index_step, int tile_outputs, float* __restrict__ out) {
     extern __shared__ float w[];
-    for (int i = threadIdx.x; i <= nwin; i += SRS_THREADS) w[i] = win[i < nwin ? i : nwin - 1];
-    __syncthreads();
+    rs_load_window<SRS_THREADS>(w, win, nwin);
     const int64_t reach = nwin / index_step;
     // the tiles of the rows lie back to back in table order; this workgroup's tiles ascend, so one pass over the rows serves all
     int r = 0;
@@ -84,42 +82,23 @@ __global__ __launch_bounds__(SRS_THREADS) void stream_resample_kernel(const floa
     }
 }
 
-// scale, index_step and R of a ratio; false with the error set where sos_resample_f32 refuses them
-static bool stream_rs_filter(const char* who, double ratio, int nwin, int num_table, double* scale, int* index_step) {
-    if (!(ratio > 0.0) || nwin < 1 || num_table < 1) {
-        sos_set_error("%s: bad args (ratio=%g, nwin=%d, num_table=%d)", who, ratio, nwin, num_table);
-        return false;
-    }
-    *scale = ratio < 1.0 ? ratio : 1.0;
-    *index_step = (int)(*scale * (double)num_table);
-    if (*index_step < 1) {
-        sos_set_error("%s: ratio %g too small for a %d-point table", who, ratio, num_table);
-        return false;
-    }
-    return true;
-}
-
 extern "C" int sos_stream_resample_ready(double ratio, int nwin, int num_table, int64_t n_recv, int64_t* t_ready, int64_t* base) {
     const char* who = "sos_stream_resample_ready";
-    double scale;
-    int index_step;
+    RsFilter f;
     if (!t_ready || !base) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
-    if (!stream_rs_filter(who, ratio, nwin, num_table, &scale, &index_step)) return SOS_EINVAL;
+    if (!rs_filter(who, ratio, nwin, num_table, false, &f)) return SOS_EINVAL;
     if (n_recv < 0 || n_recv > SRS_MAX_POS) {
         sos_set_error("%s: a stream of %lld samples", who, (long long)n_recv);
         return SOS_EINVAL;
     }
-    const int64_t reach = nwin / index_step;
+    const int64_t reach = f.reach;                   // R
     *t_ready = *base = 0;
     if (n_recv <= reach) return SOS_OK;              // output 0 reads up to sample R
     // t is final iff n(t) + 1 + R <= n_recv, i.e. time(t) < n_recv - R: T = the first t whose time is not below that
     const double bound = (double)(n_recv - reach);
     RsSegs g;
     long long k_end = 0;
-    if (rs_build_segments(1.0 / ratio, (long long)SRS_MAX_POS * 4, &g, bound, &k_end) != 0) {
-        sos_set_error("%s: time register needs more than %d segments", who, RS_MAXSEG);
-        return SOS_ENOSPC;
-    }
+    if (const int rc = rs_segments(who, ratio, (int64_t)SRS_MAX_POS * 4, &g, bound, &k_end)) return rc;
     int64_t lo = 0, hi = k_end;                       // time is increasing, time(0) = 0 < bound <= time(k_end)
     while (hi - lo > 1) {
         const int64_t mid = lo + (hi - lo) / 2;
@@ -136,46 +115,25 @@ extern "C" int sos_stream_resample_f32(const float* ring, int64_t slots, int64_t
                                        sos_stream_t stream) {
     const char* who = "sos_stream_resample_f32";
     if (!ring || !table || !table_host || !win || !out) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
-    if (nrows < 1 || nrows > RAGGED_MAX_CLIPS || slots < 1 || slots > RAGGED_MAX_CLIPS || cap < 1 ||
-        cap > INT64_MAX / 8 / RAGGED_MAX_CLIPS || total < 0 || total > INT64_MAX / 8) {
-        sos_set_error("%s: bad args (1 .. 65535 rows, got %d; 1 .. 65535 slots, got %lld; a ring of %lld samples; an output of %lld)",
-                      who, nrows, (long long)slots, (long long)cap, (long long)total);
-        return SOS_EINVAL;
-    }
-    double scale;
-    int index_step;
-    if (!stream_rs_filter(who, ratio, nwin, num_table, &scale, &index_step)) return SOS_EINVAL;
-    if (nwin < 2 || (size_t)(nwin + 1) * sizeof(float) > 160 * 1024) {
-        sos_set_error("%s: nwin=%d: (nwin + 1) * 4 bytes must fit the 160 KB LDS", who, nwin);
-        return SOS_EINVAL;
-    }
-    const int64_t reach = nwin / index_step;
-    int64_t max_t = 1;
-    for (int r = 0; r < nrows; ++r) {
-        const StreamRs e = stream_rs_row(table_host, r);
-        if (e.t_hi > SRS_MAX_POS) { sos_set_error("%s: row %d ends at output %lld", who, r, (long long)e.t_hi); return SOS_EINVAL; }
-        max_t = std::max(max_t, e.t_hi);
-    }
-    RsSegs seg;                                       // every stream starts at 0: one description serves all rows
-    if (rs_build_segments(1.0 / ratio, max_t, &seg) != 0) {
-        sos_set_error("%s: time register of %lld outputs needs more than %d segments", who, (long long)max_t, RS_MAXSEG);
-        return SOS_ENOSPC;
-    }
+    if (!rs_rings(who, nrows, slots, 1, cap)) return SOS_EINVAL;
+    if (total < 0 || total > INT64_MAX / 8) { sos_set_error("%s: an output of %lld", who, (long long)total); return SOS_EINVAL; }
+    RsFilter f;
+    if (!rs_filter(who, ratio, nwin, num_table, true, &f)) return SOS_EINVAL;
+    RsSegs seg;
+    int64_t max_t;
+    const auto t_hi = [table_host](int r) { return stream_rs_row(table_host, r).t_hi; };
+    if (const int rc = rs_row_segments(who, nrows, t_hi, ratio, &seg, &max_t)) return rc;
     // tile shape: A/B switch, read per call (tools/stream_resample_bench.py flips it).  The results do not depend on it.
     const char* env_tile = getenv("SOS_STREAM_RESAMPLE_TILE");
     int tile = env_tile ? atoi(env_tile) : SRS_TILE;
     if (tile < 1 || tile > SRS_THREADS) tile = SRS_TILE;
-    std::vector<uint8_t> seen(slots, 0);
+    RsSlotsOnce once(slots);
     int64_t total_tiles = 0;
     for (int r = 0; r < nrows; ++r) {
         const StreamRs e = stream_rs_row(table_host, r);
-        const int why = stream_rs_why(e, slots, cap, total, max_t, ratio, reach, seg);
+        const int why = stream_rs_why(e, slots, cap, total, max_t, ratio, f.reach, seg);
         if (why == SRS_OK) {
-            if (seen[e.slot]) {
-                sos_set_error("%s: row %d names slot %lld, which an earlier row of the table names", who, r, (long long)e.slot);
-                return SOS_EINVAL;
-            }
-            seen[e.slot] = 1;
+            if (!once.take(who, r, e.slot)) return SOS_EINVAL;
             total_tiles += stream_rs_tiles(e, tile);
             continue;
         }
@@ -185,28 +143,12 @@ extern "C" int sos_stream_resample_f32(const float* ring, int64_t slots, int64_t
         sos_set_error("%s: row %d %s (slot %lld of %lld, outputs %lld .. %lld, n_in %lld, n_valid %lld, output offset %lld of %lld, "
                       "a ring of %lld samples, a wing of %lld)", who, r, reason[why], (long long)e.slot, (long long)slots,
                       (long long)e.t_lo, (long long)e.t_hi, (long long)e.n_in, (long long)e.n_valid, (long long)e.out_off,
-                      (long long)total, (long long)cap, (long long)reach);
+                      (long long)total, (long long)cap, (long long)f.reach);
         return SOS_EINVAL;
     }
     if (total_tiles == 0) return SOS_OK;              // every row is empty
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1) {
-        sos_set_error("%s: cannot read the number of compute units", who);
-        return SOS_ELAUNCH;
-    }
-    static sos_device_once attr_once;
-    if (sos_per_device_once(attr_once, [] {
-            if (hipFuncSetAttribute((const void*)stream_resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-                hipSuccess) {
-                sos_set_error("sos_stream_resample_f32: cannot raise the dynamic LDS limit");
-                return (int)SOS_ELAUNCH;
-            }
-            return (int)SOS_OK;
-        }))
-        return SOS_ELAUNCH;
-    const unsigned grid = (unsigned)(total_tiles < cus ? total_tiles : cus);
-    hipLaunchKernelGGL(stream_resample_kernel, dim3(grid), dim3(SRS_THREADS), (size_t)(nwin + 1) * sizeof(float), (hipStream_t)stream,
-                       ring, slots, cap, table, nrows, total, max_t, ratio, seg, scale, win, nwin, num_table, index_step, tile, out);
-    return sos_check_launch(who);
+    const unsigned grid = rs_grid(who, total_tiles);
+    if (!grid) return SOS_ELAUNCH;
+    return rs_launch<stream_resample_kernel>(who, grid, SRS_THREADS, f.lds, stream, ring, slots, cap, table, nrows, total, max_t, ratio,
+                                             seg, f.scale, win, nwin, num_table, f.index_step, tile, out);
 }

@@ -133,6 +133,87 @@ def test_unit_gains_are_the_merge_without_gains_and_zero_gains_the_plain_resampl
     assert np.array_equal(_bits(zeros[CANARY:-CANARY]), _bits(np.concatenate(batch["rb"])))
 
 
+def _altered_device_rows(with_gains, n, mp, cases_of):
+    """One good call of sos_resample_merge_batch_f32 over clips of n native frames (m = ceil(n / ratio), m' = mp) at 14 -> 48 kHz,
+    then one call per case of cases_of(tab, n, m, mp, J, totals) = (what, row of the table, clip, value, the first output of the
+    clip that must keep the canary; None: the field is not read) with that one entry of the DEVICE table altered."""
+    from sos_amd import _lib as L
+    from sos_amd import audio_io
+    SPARE, canary, ratio = 16, -77.0, 48000.0 / SR
+    n, mp = np.asarray(n, dtype=np.int64), np.asarray(mp, dtype=np.int64)
+    m = np.asarray([int(np.ceil(v / ratio)) for v in n], dtype=np.int64)
+    J = -(-m // HOP)
+    off = lambda v: np.cumsum(v) - v                                                 # noqa: E731
+    tab = np.ascontiguousarray(np.stack([off(n), n, off(m), m, off(mp), mp, off(J), J, off(-(-n // L.RESAMPLE_CHUNK))]), dtype=np.int64)
+    tx, ta, tb, tg = (int(v.sum()) for v in (n, m, mp, J))
+    tiles = int((-(-n // L.RESAMPLE_CHUNK)).sum())
+    rng = np.random.default_rng(9)
+    x, a, b = (_cuda(rng.uniform(-1, 1, t + SPARE)) for t in (tx, ta, tb))
+    s = _cuda(rng.uniform(0, 1, tg + SPARE)) if with_gains else None
+    win, num_table = audio_io._filter_on(x.device, ratio, "kaiser_best")
+
+    def run(d_tab):
+        out = torch.full((tx + SPARE,), canary, dtype=torch.float32, device="cuda")
+        rc = L.lib().sos_resample_merge_batch_f32(L.ptr(x), L.ptr(a), L.ptr(b), L.ptr(s), L.ptr(torch.from_numpy(d_tab).cuda()),
+                                                  tab.ctypes.data_as(C.c_void_p), len(n), ratio, L.ptr(win), win.numel(), num_table,
+                                                  HOP, L.ptr(out), L.stream_ptr())
+        return rc, out.cpu().numpy()
+
+    rc, base = run(tab)
+    assert rc == 0 and not (base[:tx] == canary).any() and (base[tx:] == canary).all()
+    for what, row, clip, value, kept_from in cases_of(tab, n, m, mp, J, (tx, ta, tb, tg)):
+        d_tab = tab.copy()
+        d_tab[row, clip] = value
+        xo, nn, ao, mm, bo, pp, go, jj, t0 = (int(v) for v in d_tab[:, clip])
+        # what a kernel that followed the row would touch lies inside the allocations
+        assert 0 <= xo and xo + max(nn, 0) <= tx + SPARE and 0 <= ao and ao + max(mm, 0) <= ta + SPARE, what
+        assert 0 <= bo and bo + max(pp, 0) <= tb + SPARE and 0 <= go and go + max(jj, 0) <= tg + SPARE and 0 <= t0 < tiles, what
+        rc, got = run(d_tab)
+        assert rc == 0, what
+        lo, hi = int(tab[0, clip]), int(tab[0, clip] + n[clip])
+        assert np.array_equal(_bits(got[:lo]), _bits(base[:lo])) and np.array_equal(_bits(got[hi:]), _bits(base[hi:])), what
+        mine, good = got[lo:hi], base[lo:hi]
+        if kept_from is None:
+            assert np.array_equal(_bits(mine), _bits(good)), what
+        else:
+            assert (mine[kept_from:] == canary).all(), what
+            assert np.array_equal(_bits(mine[:kept_from]), _bits(good[:kept_from])), what
+
+
+@pytest.mark.parametrize("with_gains", [False, True], ids=["keep", "follow"])
+def test_merge_kernel_skips_a_device_row_outside_the_totals(with_gains):
+    """The device rule of resample_merge_kernel (band_merge_why): the host table is correct, the DEVICE table differs from it in
+    one field of one clip.  The clips are those of tests/test_band_host_cpu.py (513, 4097 and 9001 frames at 14 -> 48 kHz: one, two
+    and three tiles).  Every buffer has 16 elements more than the table sums, and each altered row is checked, on the host, to lie
+    inside what is allocated: a kernel that followed it would write wrong values, not fault.  The call succeeds; every output of
+    the altered clip keeps the canary or, where the field does not reach its tile, has the bits of the unaltered call; every
+    other clip has those bits throughout.  Without gains the two gains columns are not read at all.
+    The bound n <= max_n (the outputs the time register describes) is reached alone only by a clip whose a covers more than the
+    largest n and which is not the last in x: the second batch puts the 9001 frames in the middle, where 2626 samples of a cover
+    9003 frames, and asks for 9002."""
+    from sos_amd import _lib as L
+
+    def cases(tab, n, m, mp, J, totals):
+        tx, ta, tb, tg = totals
+        return [("n: a does not cover it", 1, 1, 4098, 0),
+                ("m: a leaves its total by one", 3, 1, ta - int(tab[2, 1]) + 1, 0), ("m = 0", 3, 1, 0, 0),
+                ("m' above m", 5, 1, int(m[1]) + 1, 0), ("m' = 0", 5, 1, 0, 0),
+                ("x offset: leaves the total by one", 0, 1, tx - int(n[1]) + 1, 0),
+                ("a offset: leaves the total by one", 2, 1, ta - int(m[1]) + 1, 0),
+                ("b offset: leaves the total by one", 4, 1, tb - int(mp[1]) + 1, 0),
+                ("tile0: the clip starts a tile late", 8, 2, 4, 2 * L.RESAMPLE_CHUNK),     # tiles 4, 5 are its outputs 0 .. 8191
+                ("J: one gain more", 7, 1, int(J[1]) + 1, 0 if with_gains else None),
+                ("gains offset: leaves the total by one", 6, 1, tg - int(J[1]) + 1, 0 if with_gains else None)]
+
+    def past_the_register(tab, n, m, mp, J, totals):
+        # nothing but n > max_n refuses 9002: it stays inside x, a covers it, and no other column changed
+        assert int(n.max()) == 9001 and int(tab[0, 1]) + 9002 <= totals[0] and int(float(m[1]) * (48000.0 / SR)) >= 9002
+        return [("n: past the time register", 1, 1, 9002, 0)]
+
+    _altered_device_rows(with_gains, [513, 4097, 9001], [100, 1106, 2528], cases)
+    _altered_device_rows(with_gains, [513, 9001, 4097], [100, 2528, 1106], past_the_register)
+
+
 # ---------------------------------------------------------------------------------------------- gains
 def _gain_clips():
     """(a, b) pairs: a long clip whose m' leaves a partial last frame, with a run of silent input frames and a run of silenced
