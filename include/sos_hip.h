@@ -523,6 +523,28 @@ int sos_g711_planes_batch_f32(const void* codes, int law, const int64_t* table, 
 int sos_g711_encode_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int law, void* out,
                           int64_t* clipped, sos_stream_t stream);
 int sos_g711_to_mono_f32(const void* codes, int law, int channels, int64_t n_frames, float* out, sos_stream_t stream);
+/* sos_pcm_encode_batch with dither added before the rounding, for SOS_ENC_U8 / S16 / S24 (csrc/dither_core.h states the rule
+ * once; numpy restatement: tests/dither_reference.py, exact, so the tests ask for equal bytes).  The dither of a sample is a pure
+ * function of (seed, file key, channel, absolute frame), evaluated inside the encode kernels: a file's bytes do not depend on
+ * the other files of the launch, on the grid or on the access path, and a signal encoded packet by packet, frame0 advanced by
+ * each packet's length, gives the bytes of the signal encoded at once.
+ * Row per file, int64 [nfiles][7]: the five columns of sos_pcm_encode_batch, then {file key (0 .. 2^32 - 1), frame0 = the absolute
+ * frame of the file's first frame (0 .. 2^62 - frames)}; the same row checks and grid.
+ * Generator: Philox4x32-10 (Salmon et al., Random123): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, round c' = {hi(M1 * c2) ^ c1
+ *   ^ k0, lo(M1 * c2), hi(M0 * c0) ^ c3 ^ k1, lo(M0 * c0)}, the key bumped by {0x9E3779B9, 0xBB67AE85} after each of ten rounds.
+ * Word of a sample: n = frame0 + i; counter {low32(n >> 2), high32(n >> 2), channel, file key}, key {low32(seed), high32(seed)};
+ *   w(n) = output word n & 3 of that block.
+ * Dither in LSB: SOS_DITHER_TPDF d = ((w & 0xFFFF) - (w >> 16)) / 65536 (triangular on (-1, 1), variance 1/6);
+ *   SOS_DITHER_HIGHPASS d[n] = (u(n + 1) - u(n)) / 65536 with u(n) = w(n) & 0xFFFF (the same marginal, its spectrum (1/12)(2 - 2 cos w)
+ *   moved towards fs / 2; it shapes the dither only, the quantisation error is not fed back).
+ * q = rint((double)x * S + d) half to even, then as sos_pcm_encode_batch: NaN -> 0, saturated to [-S, S - 1]; `clipped` counts
+ *   after the dither (it can push a sample at the ceiling over it).  Every written sample is dithered, the zero-fill past the
+ *   plane's end included.
+ * SOS_EINVAL beyond sos_pcm_encode_batch's: a dither other than the two, SOS_ENC_S32 / SOS_ENC_F32 / a G.711 law (S32 holds more
+ * bits than a float's mantissa, F32 is a copy, G.711 drops the low bits of the s16 value), a key or frame0 outside its range. */
+enum { SOS_DITHER_TPDF = 1, SOS_DITHER_HIGHPASS = 2 };
+int sos_pcm_encode_dither_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int format,
+                                int dither, uint64_t seed, void* out, int64_t* clipped, sos_stream_t stream);
 /* Integrated loudness (ITU-R BS.1770-4 / EBU R128) of a group of files on the planes sos_pcm_encode_batch reads, and the gain
  * that brings each file to a target (csrc/loudness.hip; sos_amd.metrics.loudness_batch / audio_io.loudness_gain_batch_device;
  * float64 restatement: tests/loudness_reference.py).  The ragged conventions of the entry points above: the table in two

@@ -128,6 +128,7 @@ SIGNATURES = {
     "sos_pcm_to_mono_f32": [_P, _I, _I, _L, _P, _P],
     "sos_pcm_planes_batch_f32": [_P, _I, _P, _P, _I, _P, _P],
     "sos_pcm_encode_batch": [_P, _P, _P, _I, _I, _P, _P, _P],
+    "sos_pcm_encode_dither_batch": [_P, _P, _P, _I, _I, _I, C.c_uint64, _P, _P, _P],
     "sos_g711_to_mono_f32": [_P, _I, _I, _L, _P, _P],
     "sos_g711_planes_batch_f32": [_P, _I, _P, _P, _I, _P, _P],
     "sos_g711_encode_batch": [_P, _P, _P, _I, _I, _P, _P, _P],

@@ -20,8 +20,9 @@ import numpy as np
 import torch
 
 from . import ragged
-from .planes import (decode_planes_batch_device, encode_batch_device, g711_decode_device, g711_encode_device,  # noqa: F401
-                     load_channels_batch_device, loudness_gain_batch_device, pcm_to_mono_device, planes_of, planes_together)
+from .planes import (DITHER, DITHER_FORMATS, decode_planes_batch_device, encode_batch_device, g711_decode_device, g711_encode_device,  # noqa: F401
+                     load_channels_batch_device, loudness_gain_batch_device, pcm_encode_device, pcm_to_mono_device, planes_of,
+                     planes_together)
 from .resampling import (KAISER_BEST, band_gains_batch_device, filter_on, resample_batch_device, resample_device,  # noqa: F401
                          resample_merge_batch_device, sinc_window)
 from .stream_resampling import StreamBandMerger, StreamResampler  # noqa: F401

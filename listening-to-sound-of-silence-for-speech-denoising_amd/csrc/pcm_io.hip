@@ -11,16 +11,23 @@
 // bytes of the file's byte range wherever the file starts, and only the threads at the two ends of a file store single bytes.
 // G.711 (A-law / mu-law code bytes, sos_g711_planes_batch_f32 / sos_g711_encode_batch) is two more sample types of the same two
 // kernels: four codes are one dword, and the plane side is the template's.
+// Dither (sos_pcm_encode_dither_batch; the rule: dither_core.h) is a template parameter of the two encode kernels: kind 0 is the
+// kernel without it, instruction for instruction; kinds 1 / 2 draw every sample's dither from a counter-based generator inside
+// the kernel, keyed by (seed, file key, channel, absolute frame).  A one-channel thread's four frames are one or two Philox
+// blocks; a stereo thread visits its two channels in turn (two frames each: one or two blocks per channel); three and more
+// channels take one block per element.
 // Bounds: the rule of ragged.h -- the host refuses a row of table_host outside the elements it summed (SOS_EINVAL), the kernels
 // skip a row of the DEVICE table that fails the same rule.
 #include "ragged.h"
 #include "pcm_core.h"
+#include "dither_core.h"
 
 #define PIO_THREADS 256
 #define PIO_MAX_GRID 1024               // workgroups along a file (they stride over what the grid does not cover)
 #define PIO_MAX_CHANNELS 64
 #define PIO_PLANES_COLS 4               // int64 per file: pcm element offset, frames, channels, first output sample
 #define PIO_ENCODE_COLS 5               // int64 per file: first plane sample, plane length, channels, frames, output element offset
+#define PIO_DITHER_COLS 7               // the same, then the file's dither key and the absolute frame of its first frame
 
 // `n` rows of `ch` channels starting at `off` lie inside `total` elements (no overflowing multiply)
 __host__ __device__ static inline bool pio_inside(int64_t off, int64_t n, int64_t ch, int64_t total) {
@@ -71,20 +78,36 @@ __global__ __launch_bounds__(PIO_THREADS) void pcm_planes_kernel(const T* __rest
 // ---- encode.  The rule (include/sos_hip.h): q = rint(x * S) half to even in double (a float times a power of two is exact
 // there), NaN -> 0 and counted, saturated to [-S, S - 1] and counted when that changed it.
 template <int BITS>
-__device__ __forceinline__ int32_t pio_quantise(float x, int& clipped) {
+__device__ __forceinline__ int32_t pio_round(double d, int& clipped) {
     const double S = (double)((int64_t)1 << (BITS - 1));
-    const double d = (double)x * S;
     const double r = rint(d);
     const bool nan = d != d, hi = r > S - 1.0, lo = r < -S;  // selects, no branches (rint(NaN) compares false twice)
     clipped += (int)(nan | hi | lo);
     const double q = nan ? 0.0 : hi ? S - 1.0 : lo ? -S : r;
     return (int32_t)q;                                       // |q| <= 2^31: one v_cvt_i32_f64
 }
+template <int BITS>
+__device__ __forceinline__ int32_t pio_quantise(float x, int& clipped) {
+    return pio_round<BITS>((double)x * (double)((int64_t)1 << (BITS - 1)), clipped);
+}
+// with a dither of d16 / 65536 LSB (dither_core.h): added in double before the one rounding; counted after it
+template <int BITS>
+__device__ __forceinline__ int32_t pio_quantise(float x, int32_t d16, int& clipped) {
+    return pio_round<BITS>((double)x * (double)((int64_t)1 << (BITS - 1)) + (double)d16 * (1.0 / 65536.0), clipped);
+}
 
 template <int FMT> struct PioEnc;
-template <> struct PioEnc<SOS_ENC_S16> { typedef int16_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)pio_quantise<16>(x, n); } };
+template <> struct PioEnc<SOS_ENC_S16> {
+    typedef int16_t T;
+    static __device__ __forceinline__ T put(float x, int& n) { return (T)pio_quantise<16>(x, n); }
+    static __device__ __forceinline__ T put(float x, int32_t d16, int& n) { return (T)pio_quantise<16>(x, d16, n); }
+};
 template <> struct PioEnc<SOS_ENC_S32> { typedef int32_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)pio_quantise<32>(x, n); } };
-template <> struct PioEnc<SOS_ENC_U8> { typedef uint8_t T; static __device__ __forceinline__ T put(float x, int& n) { return (T)(pio_quantise<8>(x, n) + 128); } };
+template <> struct PioEnc<SOS_ENC_U8> {
+    typedef uint8_t T;
+    static __device__ __forceinline__ T put(float x, int& n) { return (T)(pio_quantise<8>(x, n) + 128); }
+    static __device__ __forceinline__ T put(float x, int32_t d16, int& n) { return (T)(pio_quantise<8>(x, d16, n) + 128); }
+};
 template <> struct PioEnc<SOS_ENC_F32> { typedef float T; static __device__ __forceinline__ T put(float x, int&) { return x; } };
 // G.711: the s16 value (counted as 's16' counts), then the compressor of pcm_core.h.  The laws' WAVE tags 6 / 7 continue SOS_ENC_*.
 template <> struct PioEnc<SOS_G711_ALAW> { typedef G711A T; static __device__ __forceinline__ T put(float x, int& n) { return T{g711_alaw_compress(pio_quantise<16>(x, n))}; } };
@@ -110,13 +133,15 @@ __device__ __forceinline__ void pio_add_clipped(int clipped, int64_t* dst) {
     if (threadIdx.x == 0 && block_count) atomicAdd((unsigned long long*)dst, (unsigned long long)block_count);
 }
 
-template <int FMT>
+// KIND: 0, or SOS_DITHER_*.  The seed is an argument of the dithered instantiations only (Seed = uint64_t once, or nothing), so
+// that kind 0 keeps the argument list, and with it every instruction, of the kernel before there was a dither.
+template <int FMT, int KIND = 0, typename... Seed>
 __global__ __launch_bounds__(PIO_THREADS) void pcm_encode_kernel(const float* __restrict__ planes, const int64_t* __restrict__ table,
                                                                  int64_t total_in, int64_t total_out,
                                                                  typename PioEnc<FMT>::T* __restrict__ out,
-                                                                 int64_t* __restrict__ clipped) {
+                                                                 int64_t* __restrict__ clipped, Seed... seed) {
     typedef typename PioEnc<FMT>::T T;
-    const int64_t* te = table + (int64_t)blockIdx.y * PIO_ENCODE_COLS;
+    const int64_t* te = table + (int64_t)blockIdx.y * (KIND ? PIO_DITHER_COLS : PIO_ENCODE_COLS);
     const int64_t first = te[0], avail = te[1], ch = te[2], frames = te[3], ooff = te[4];
     if (!pio_inside(first, avail, ch, total_in) || !pio_inside(ooff, frames, ch, total_out)) return;
     const int64_t n = frames * ch;
@@ -140,11 +165,31 @@ __global__ __launch_bounds__(PIO_THREADS) void pcm_encode_kernel(const float* __
             }
         }
         PioVec4<T> q;
+        if constexpr (KIND == 0) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int hit = 0;
-            q.v[k] = PioEnc<FMT>::put(v[k], hit);
-            if (e0 + k < n) count += hit;
+            for (int k = 0; k < 4; ++k) {
+                int hit = 0;
+                q.v[k] = PioEnc<FMT>::put(v[k], hit);
+                if (e0 + k < n) count += hit;
+            }
+        } else {
+            DitherWords words(seed..., (uint32_t)te[5]);
+            const uint64_t frame0 = (uint64_t)te[6];
+            uint64_t fi[4];                                      // frame and channel of the four elements
+            uint32_t fc[4];
+            int64_t i = ch == 1 ? e0 : e0 / ch, c = e0 - i * ch;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                fi[k] = frame0 + (uint64_t)i; fc[k] = (uint32_t)c;
+                if (++c == ch) { c = 0; ++i; }
+            }
+            auto put = [&](int k) __attribute__((always_inline)) {
+                int hit = 0;
+                q.v[k] = PioEnc<FMT>::put(v[k], words.template lsb16<KIND>(fi[k], fc[k]), hit);
+                if (e0 + k < n) count += hit;
+            };
+            if (ch == 2) { put(0); put(2); put(1); put(3); }     // a channel's two frames one after the other: they share a block
+            else { put(0); put(1); put(2); put(3); }
         }
         if (full && dst_vec) {
             *(PioVec4<T>*)(dst + e0) = q;
@@ -160,10 +205,12 @@ __global__ __launch_bounds__(PIO_THREADS) void pcm_encode_kernel(const float* __
 // packed s24: thread u of a file owns the twelve bytes [12 u - lead, 12 u - lead + 12) of the file's 3 n bytes, lead = the
 // file's first byte address mod 4, i.e. three ALIGNED dwords.  They hold (parts of) at most five samples; a sample is counted
 // by the thread that owns its first byte.  Whole dwords where all twelve bytes are the file's, single bytes at its two ends.
+// A sample astride two units is quantised by both threads: with a dither both draw the same value, a function of its frame.
+template <int KIND = 0, typename... Seed>
 __global__ __launch_bounds__(PIO_THREADS) void pcm_encode_s24_kernel(const float* __restrict__ planes, const int64_t* __restrict__ table,
                                                                      int64_t total_in, int64_t total_out, uint8_t* __restrict__ out,
-                                                                     int64_t* __restrict__ clipped) {
-    const int64_t* te = table + (int64_t)blockIdx.y * PIO_ENCODE_COLS;
+                                                                     int64_t* __restrict__ clipped, Seed... seed) {
+    const int64_t* te = table + (int64_t)blockIdx.y * (KIND ? PIO_DITHER_COLS : PIO_ENCODE_COLS);
     const int64_t first = te[0], avail = te[1], ch = te[2], frames = te[3], ooff = te[4];
     if (!pio_inside(first, avail, ch, total_in) || !pio_inside(ooff, frames, ch, total_out)) return;
     const int64_t n = frames * ch, nbytes = 3 * n;
@@ -177,16 +224,38 @@ __global__ __launch_bounds__(PIO_THREADS) void pcm_encode_s24_kernel(const float
         const int64_t e_lo = p > 0 ? p / 3 : 0;
         int64_t i = e_lo / ch, c = e_lo - i * ch;
         unsigned __int128 bits = 0;                              // the five samples' bytes, little-endian, back to back
+        if constexpr (KIND == 0) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int64_t e = e_lo + k;
-            if (e < n && 3 * e < p + 12) {
-                int hit = 0;
-                const int32_t q = pio_quantise<24>(pl.at(i, c), hit);
-                if (3 * e >= p) count += hit;                    // its first byte is this unit's
-                bits |= (unsigned __int128)((uint32_t)q & 0xffffffu) << (24 * k);
+            for (int k = 0; k < 5; ++k) {
+                const int64_t e = e_lo + k;
+                if (e < n && 3 * e < p + 12) {
+                    int hit = 0;
+                    const int32_t q = pio_quantise<24>(pl.at(i, c), hit);
+                    if (3 * e >= p) count += hit;                // its first byte is this unit's
+                    bits |= (unsigned __int128)((uint32_t)q & 0xffffffu) << (24 * k);
+                }
+                if (++c == ch) { c = 0; ++i; }
             }
-            if (++c == ch) { c = 0; ++i; }
+        } else {
+            DitherWords words(seed..., (uint32_t)te[5]);
+            const uint64_t frame0 = (uint64_t)te[6];
+            int64_t fi[5], fc[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                fi[k] = i; fc[k] = c;
+                if (++c == ch) { c = 0; ++i; }
+            }
+            auto put = [&](int k) __attribute__((always_inline)) {
+                const int64_t e = e_lo + k;
+                if (e < n && 3 * e < p + 12) {
+                    int hit = 0;
+                    const int32_t q = pio_quantise<24>(pl.at(fi[k], fc[k]), words.template lsb16<KIND>(frame0 + (uint64_t)fi[k], (uint32_t)fc[k]), hit);
+                    if (3 * e >= p) count += hit;
+                    bits |= (unsigned __int128)((uint32_t)q & 0xffffffu) << (24 * k);
+                }
+            };
+            if (ch == 2) { put(0); put(2); put(4); put(1); put(3); }    // a channel's frames one after the other, as in pcm_encode_kernel
+            else { put(0); put(1); put(2); put(3); put(4); }
         }
         const int64_t shift = p - 3 * e_lo;                      // 0 .. 2, or -lead for the unit that begins before the file
         bits = shift >= 0 ? bits >> (8 * shift) : bits << (-8 * shift);
@@ -255,7 +324,7 @@ static int pio_planes_args(const char* who, const void* pcm, const char* what, b
 // The same for the encode entry points; clears the counts.
 static int pio_encode_args(const char* who, const float* planes, const char* what, bool known, int code, const int64_t* table,
                            const int64_t* table_host, int nfiles, const void* out, int64_t* clipped, hipStream_t st,
-                           PioSide* in, PioSide* enc, dim3* grid) {
+                           PioSide* in, PioSide* enc, dim3* grid, int cols = PIO_ENCODE_COLS) {
     if (!planes || !table || !table_host || !out || !clipped) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
     if (!ragged_clips_ok(table_host, nfiles)) {
         sos_set_error("%s: bad args (1 .. 65535 files, got %d)", who, nfiles);
@@ -266,13 +335,25 @@ static int pio_encode_args(const char* who, const float* planes, const char* wha
         return SOS_EINVAL;
     }
     const char* why = "";
-    const int bad = pio_check_rows(table_host, nfiles, PIO_ENCODE_COLS, 2, in, enc, &why);
+    const int bad = pio_check_rows(table_host, nfiles, cols, 2, in, enc, &why);
     if (bad < nfiles) {
-        const int64_t* te = table_host + (int64_t)bad * PIO_ENCODE_COLS;
+        const int64_t* te = table_host + (int64_t)bad * cols;
         sos_set_error("%s: file %d (plane sample %lld, %lld available, %lld channels, %lld frames, output element "
                       "%lld) has %s (%lld plane samples, %lld output elements)", who, bad, (long long)te[0], (long long)te[1],
                       (long long)te[2], (long long)te[3], (long long)te[4], why, (long long)in->total, (long long)enc->total);
         return SOS_EINVAL;
+    }
+    for (int f = 0; cols == PIO_DITHER_COLS && f < nfiles; ++f) {
+        const int64_t* te = table_host + (int64_t)f * cols;
+        if (te[5] < 0 || te[5] > (int64_t)UINT32_MAX) {
+            sos_set_error("%s: file %d has the dither key %lld outside 0 .. 2^32 - 1", who, f, (long long)te[5]);
+            return SOS_EINVAL;
+        }
+        if (te[6] < 0 || te[6] > DITHER_FRAME_LIMIT - te[3]) {
+            sos_set_error("%s: file %d has the first frame %lld outside 0 .. 2^62 - its %lld frames", who, f, (long long)te[6],
+                          (long long)te[3]);
+            return SOS_EINVAL;
+        }
     }
     if (hipMemsetAsync(clipped, 0, (size_t)nfiles * sizeof(int64_t), st) != hipSuccess) {
         sos_set_error("%s: cannot clear the counts", who);
@@ -331,7 +412,7 @@ extern "C" int sos_pcm_encode_batch(const float* planes, const int64_t* table, c
     case SOS_ENC_S32: PIO_ENCODE_GO(SOS_ENC_S32); break;
     case SOS_ENC_U8: PIO_ENCODE_GO(SOS_ENC_U8); break;
     case SOS_ENC_F32: PIO_ENCODE_GO(SOS_ENC_F32); break;
-    default: hipLaunchKernelGGL(pcm_encode_s24_kernel, grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, enc.total,
+    default: hipLaunchKernelGGL(pcm_encode_s24_kernel<>, grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, enc.total,
                                 (uint8_t*)out, clipped); break;
     }
     return sos_check_launch("sos_pcm_encode_batch");
@@ -348,5 +429,40 @@ extern "C" int sos_g711_encode_batch(const float* planes, const int64_t* table, 
     if (law == SOS_G711_ALAW) PIO_ENCODE_GO(SOS_G711_ALAW); else PIO_ENCODE_GO(SOS_G711_ULAW);
     return sos_check_launch("sos_g711_encode_batch");
 }
+
+// The dithered encode: the rows, checks and grid of sos_pcm_encode_batch, two more columns per row.
+#define PIO_DITHER_GO(F, K) hipLaunchKernelGGL((pcm_encode_kernel<F, K, uint64_t>), grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, \
+                                               enc.total, (PioEnc<F>::T*)out, clipped, seed)
+#define PIO_DITHER_S24_GO(K) hipLaunchKernelGGL((pcm_encode_s24_kernel<K, uint64_t>), grid, dim3(PIO_THREADS), 0, st, planes, table, in.total, \
+                                                enc.total, (uint8_t*)out, clipped, seed)
+extern "C" int sos_pcm_encode_dither_batch(const float* planes, const int64_t* table, const int64_t* table_host, int nfiles, int format,
+                                           int dither, uint64_t seed, void* out, int64_t* clipped, sos_stream_t stream) {
+    const char* who = "sos_pcm_encode_dither_batch";
+    if (dither != SOS_DITHER_TPDF && dither != SOS_DITHER_HIGHPASS) {
+        sos_set_error("%s: unknown dither %d (SOS_DITHER_TPDF = 1, SOS_DITHER_HIGHPASS = 2)", who, dither);
+        return SOS_EINVAL;
+    }
+    if (format == SOS_ENC_S32 || format == SOS_ENC_F32 || format == SOS_G711_ALAW || format == SOS_G711_ULAW) {
+        sos_set_error("%s: sample format %d takes no dither (S16, S24 and U8 do: S32 holds more bits than a float, F32 is a copy, "
+                      "G.711 drops the low bits)", who, format);
+        return SOS_EINVAL;
+    }
+    const bool known = format == SOS_ENC_S16 || format == SOS_ENC_S24 || format == SOS_ENC_U8;
+    PioSide in{0, 1}, enc{4, 3};
+    dim3 grid;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = pio_encode_args(who, planes, "sample format", known, format, table, table_host, nfiles, out, clipped, st, &in, &enc,
+                                   &grid, PIO_DITHER_COLS);
+    if (rc != SOS_OK) return rc;
+    const bool tpdf = dither == SOS_DITHER_TPDF;
+    switch (format) {
+    case SOS_ENC_S16: if (tpdf) PIO_DITHER_GO(SOS_ENC_S16, SOS_DITHER_TPDF); else PIO_DITHER_GO(SOS_ENC_S16, SOS_DITHER_HIGHPASS); break;
+    case SOS_ENC_U8: if (tpdf) PIO_DITHER_GO(SOS_ENC_U8, SOS_DITHER_TPDF); else PIO_DITHER_GO(SOS_ENC_U8, SOS_DITHER_HIGHPASS); break;
+    default: if (tpdf) PIO_DITHER_S24_GO(SOS_DITHER_TPDF); else PIO_DITHER_S24_GO(SOS_DITHER_HIGHPASS); break;
+    }
+    return sos_check_launch(who);
+}
+#undef PIO_DITHER_GO
+#undef PIO_DITHER_S24_GO
 #undef PIO_PLANES_GO
 #undef PIO_ENCODE_GO

@@ -116,15 +116,53 @@ def load_channels_batch_device(paths, sr=None, res_type="kaiser_best", device="c
     return ragged.per_group(ys, rates, at_sr, lambda i, r: r == sr or not ys[i].shape[1]), [sr] * len(paths), infos
 
 
-def encode_batch_device(planes, fmt, frames=None):
+DITHER = {"tpdf": 1, "highpass": 2}        # SOS_DITHER_* of include/sos_hip.h
+DITHER_FORMATS = ("u8", "s16", "s24")      # s32 holds more bits than a float32, f32 is a copy, G.711 drops the low bits
+FRAME_LIMIT = 1 << 62                       # frame0 + frames may not pass it
+
+
+def _dither_columns(who, fmt, dither, seed, keys, frame0, frames):
+    """The checked dither arguments of encode_batch_device: int64 arrays (file keys, first absolute frames), or its ValueError."""
+    if dither not in DITHER:
+        raise ValueError("%s: unknown dither %r (one of %s, or None)" % (who, dither, ", ".join(sorted(DITHER))))
+    if fmt not in DITHER_FORMATS:
+        raise ValueError("%s: sample format %r takes no dither (%s do)" % (who, fmt, ", ".join(DITHER_FORMATS)))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError("%s: the dither seed is an integer in 0 .. 2^64 - 1, got %r" % (who, seed))
+    cols = []
+    for name, given, default, top in (("keys", keys, range(len(frames)), lambda f: (1 << 32) - 1),
+                                      ("frame0", frame0, [0] * len(frames), lambda f: FRAME_LIMIT - int(frames[f]))):
+        vals = list(default if given is None else given)
+        if len(vals) != len(frames):
+            raise ValueError("%s: %s holds one integer per file (%d files, %d given)" % (who, name, len(frames), len(vals)))
+        for f, v in enumerate(vals):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= top(f):
+                raise ValueError("%s: %s[%d] = %r is outside 0 .. %d" % (who, name, f, v, top(f)))
+        cols.append(np.asarray([int(v) for v in vals], dtype=np.int64))
+    return cols
+
+
+def encode_batch_device(planes, fmt, frames=None, dither=None, seed=0, keys=None, frame0=None):
     """planes: one (channels, n) f32 GPU tensor per file; fmt: 's16', 's24' (packed, 3 bytes little-endian), 's32', 'u8' or
     'f32'; frames: samples per channel to write per file (default: n).  -> (data, offsets, clipped): one uint8 GPU tensor with
     the files' interleaved [frames][channels] data back to back, the host int64 byte offsets (files + 1 entries) and an int64
     GPU tensor of per-file counts, from ONE sos_pcm_encode_batch launch (per 65535 files).  Per sample: the plane's value below
     n and 0 from there to `frames` (crop / zero-fill happen in the kernel); f32 copies the bits; otherwise q = rint(x * S) half
     to even in double with S = 2^(bits-1), NaN -> 0, saturated to [-S, S - 1]; u8 stores q + 128.  clipped[f] counts the samples
-    that were NaN or changed by saturation (+-inf included).  NO dither is applied (out of scope): quantisation error is
-    correlated with the signal, as with soundfile's and scipy's integer writers.  Float64 restatement: tests/pcm_reference.py.
+    that were NaN or changed by saturation (+-inf included).  Float64 restatement: tests/pcm_reference.py.
+    dither=None (the default) is plain rounding: the quantisation error is correlated with the signal, as with soundfile's and
+    scipy's integer writers, and a component below half an LSB is gated to zero.  dither='tpdf' / 'highpass' ('u8', 's16', 's24'
+    only; ONE sos_pcm_encode_dither_batch launch) adds d LSB before the one rounding, q = rint(x * S + d): 'tpdf' is triangular
+    on (-1, 1), white; 'highpass' the difference of two successive uniform draws, the same marginal with its power moved towards
+    fs / 2 (it shapes the dither only: the quantisation error is not fed back).  Either makes the mean and the variance of the
+    total error free of the signal, at a noise floor of 1/4 LSB^2 in place of 1/12.  d is a pure function of (seed, keys[f],
+    channel, frame0[f] + frame) -- Philox4x32-10 evaluated inside the kernel (csrc/dither_core.h; numpy restatement:
+    tests/dither_reference.py) -- so a file's bytes depend neither on the other files of the call nor on how a signal was cut
+    into calls: encode the packets of a live leg with the same key and frame0 advanced by each packet's length and they
+    concatenate to the encode of the whole.  seed: 0 .. 2^64 - 1; keys: one integer 0 .. 2^32 - 1 per file (default: the
+    file's position in `planes`); frame0: one integer 0 .. 2^62 - frames per file (default 0).  Every written sample is dithered,
+    the zero-fill included, and `clipped` counts after the dither.  ValueError before any launch: an unknown dither, another
+    format, a seed, key or frame0 out of range, keys / frame0 not one per file.
     'alaw' / 'ulaw' (G.711, one code byte per sample, ONE sos_g711_encode_batch launch): the 's16' value q, counted as 's16'
     counts it, through the reference compressor (include/sos_hip.h; it drops the low bits of q, as audioop, libsndfile and sox
     do); the zero-fill is the code of silence, 0xD5 / 0xFF.  Restatement: tests/g711_reference.py."""
@@ -133,10 +171,12 @@ def encode_batch_device(planes, fmt, frames=None):
         raise ValueError("encode_batch_device: unsupported sample format %r (one of %s)"
                          % (fmt, ", ".join(sorted(ENCODINGS) + sorted(G711))))
     code, width = (G711[fmt] if fmt in G711 else ENCODINGS[fmt])[:2]
-    name = "sos_g711_encode_batch" if fmt in G711 else "sos_pcm_encode_batch"
+    name = "sos_g711_encode_batch" if fmt in G711 else "sos_pcm_encode_batch" if dither is None else "sos_pcm_encode_dither_batch"
     planes = check_planes(who, planes)
-    L.require_cuda(*planes)
     frames = np.asarray(plane_frames(who, planes, frames), dtype=np.int64)
+    extra = () if dither is None else tuple(_dither_columns(who, fmt, dither, seed, keys, frame0, frames))
+    how = () if dither is None else (DITHER[dither], C.c_uint64(int(seed)))
+    L.require_cuda(*planes)
     elems = np.asarray([p.shape[0] for p in planes], dtype=np.int64) * frames
     offsets = np.concatenate([ragged.offsets(elems), [elems.sum()]]).astype(np.int64) * width
     if not planes:
@@ -149,8 +189,8 @@ def encode_batch_device(planes, fmt, frames=None):
     for c0, c1 in ragged.chunks(len(planes)):
         e0 = int(offsets[c0]) // width
         tab, tab_dev = ragged.table(np.stack([src[c0:c1] - src[c0], avail[c0:c1], chans[c0:c1], frames[c0:c1],
-                                              offsets[c0:c1] // width - e0], axis=1), device)
-        L.check(getattr(h, name)(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, code,
+                                              offsets[c0:c1] // width - e0] + [col[c0:c1] for col in extra], axis=1), device)
+        L.check(getattr(h, name)(L.ptr(flat[int(src[c0]):]), L.ptr(tab_dev), tab.ctypes.data_as(C.c_void_p), c1 - c0, code, *how,
                                  L.ptr(data[e0 * width:]), L.ptr(clipped[c0:]), L.stream_ptr()), name)
     return data[:int(offsets[-1])], offsets, clipped
 
@@ -248,4 +288,21 @@ def g711_encode_device(x, law):
     if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.float32:
         raise ValueError("g711_encode_device expects a 1-D float32 tensor")
     data, _, clipped = encode_batch_device([x.view(1, -1)], law)
+    return data, clipped
+
+
+def pcm_encode_device(x, fmt, dither=None, seed=0, key=0, frame0=0):
+    """g711_encode_device's sibling for linear PCM: one packet of a live leg, x 1-D f32 GPU tensor -> (1-D uint8 GPU tensor of
+    the packet's bytes in `fmt`, clipped: int64 GPU tensor of one count), encode_batch_device([x[None]], fmt, dither=, seed=,
+    keys=[key], frame0=[frame0]).  Without dither the rule has no state; with it the state is the caller's count of frames: give
+    every packet of a leg the same seed and key and advance frame0 by the packet's length, and the packets concatenate to the
+    encode of the whole signal."""
+    if fmt not in ENCODINGS:
+        raise ValueError("pcm_encode_device: unsupported sample format %r (one of %s)" % (fmt, ", ".join(sorted(ENCODINGS))))
+    if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.float32:
+        raise ValueError("pcm_encode_device expects a 1-D float32 tensor")
+    if dither is None:
+        data, _, clipped = encode_batch_device([x.view(1, -1)], fmt)
+    else:
+        data, _, clipped = encode_batch_device([x.view(1, -1)], fmt, dither=dither, seed=seed, keys=[key], frame0=[frame0])
     return data, clipped

@@ -141,7 +141,7 @@ def _merge_back(natives, lows_in, lows_out, rates, high_band, smooth_frames):
 def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, context_seconds=2.0, max_batch=256,
                        max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None,
                        high_band="drop", smooth_frames=2, loudness=None, peak_ceiling_db=-1.0, channel_weights=None,
-                       peak="sample", loudness_range=False):
+                       peak="sample", loudness_range=False, dither=None, dither_seed=0):
     """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
     channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32, G.711 A-law / mu-law; a float64 source is written as
     float32); sample_format= ('s16', 's24', 's32', 'u8', 'f32', 'alaw', 'ulaw') forces one format for all files.
@@ -153,7 +153,7 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     file; window_seconds, context_seconds, max_batch, max_columns as there); one resample launch per native rate goes back; one
     sos_pcm_encode_batch (sos_g711_encode_batch) launch per output format crops or zero-fills every channel to the source's
     frame count (the networks return hop * (n // hop) samples and the resampler ceil(n * ratio)) and quantises it -- round half
-    to even, saturating, NO dither; G.711 compresses that s16 value and zero-fills with the code of silence; one download brings the group's bytes and counts to the host, and only then are its files written
+    to even, saturating, without dither unless dither= asks for it (below); G.711 compresses that s16 value and zero-fills with the code of silence; one download brings the group's bytes and counts to the host, and only then are its files written
     (audio_io.wave_container).  No call in the loop waits for the device except that download.
     link_channels: None -- every channel gets its own silent-interval decisions, per window (denoise_long's default mode) -- or
     'any' / 'mean': the channels of a file share ONE decision stream, the group's denoise_long call runs with stitch_bits=True,
@@ -191,18 +191,32 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     every written file (metrics.loudness_batch(loudness_range=True): two more launches from the energies the measurement left
     on the device).  It needs a loudness target too.  Under 'source' the extra measures are taken on the outputs only (the
     sources then get a measuring sequence of their own).  Both ride the group's one download.
+    dither: None (the default: plain rounding, the written bytes are what they were), 'tpdf' or 'highpass'.  The files written
+    as 'u8', 's16' or 's24' get that dither before their one rounding (audio_io.encode_batch_device(dither=): drawn inside the
+    encode kernel from (dither_seed, the file's position in `paths`, channel, frame), so what the denoiser pushed below one LSB
+    -- the intervals between words above all, and more of it after a levelling gain below 1 -- is kept as signal under a noise
+    floor free of it, not turned into distortion or gated to zero; 'highpass' moves the dither's power towards fs / 2).  The key is
+    the position in `paths`, not in the group: a file's bytes do not depend on max_bytes or on the other files.  Files written
+    as 's32', 'f32' or G.711 are written as before.  Still one encode launch per format and group, and one download.
+    dither_seed: 0 .. 2^64 - 1; the same call twice writes the same files.
     -> one dict per file: path, out_path, channels, rate, frames, format, clipped (samples that saturated or were NaN, all
     channels), windows (denoise_long windows, all channels); with loudness also loudness_before (LUFS of the denoised file
     before the gain, -inf without a gated block), loudness (before + 20 log10 g, not measured again), loudness_target, gain_db
     and peak_limited (the ceiling bound the gain); under peak='true' also true_peak_db (20 log10(g * true peak): the level
     written, in dBTP, -inf for a silent file); under loudness_range=True also lra (LU, of the planes before the gain, which a gain
     does not move) and max_momentary / max_short_term (LUFS, as written: measured before the gain, + gain_db).
+    With dither= also dither: the kind, or None for a file it did not apply to.
     ValueError before any launch of the call, naming the file: fewer than MIN_FRAMES STFT frames at 14 kHz, an unsupported
     format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format, link_channels or
     high_band, smooth_frames outside 0 .. 16; a loudness that is not finite or outside -70 .. 0, a ceiling above 0, weights that are
     negative or not one per channel, an unknown peak, a loudness_range that is no bool, either of the two without a loudness target;
+    an unknown dither, a dither_seed that is no integer in 0 .. 2^64 - 1;
     window_plan's argument rules; a group with more than 65535 windows."""
     paths = [os.fspath(p) for p in paths]
+    if dither is not None and dither not in audio_io.DITHER:
+        raise ValueError("denoise_recordings: unknown dither %r (None, or one of %s)" % (dither, ", ".join(sorted(audio_io.DITHER))))
+    if isinstance(dither_seed, bool) or not isinstance(dither_seed, (int, np.integer)) or not 0 <= int(dither_seed) < 1 << 64:
+        raise ValueError("denoise_recordings: dither_seed is an integer in 0 .. 2^64 - 1, got %r" % (dither_seed,))
     _check_loudness(loudness, peak_ceiling_db, channel_weights, peak, loudness_range)
     infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix, link_channels, high_band, smooth_frames)
     flags = dict(true_peak=True) if peak == "true" else {}
@@ -268,8 +282,9 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
                 more = torch.stack([got[k].double() for k in ("lra", "max_momentary", "max_short_term", "windows")], dim=1)
                 parts.append(more.contiguous().view(torch.uint8).reshape(-1))
         for fmt, files in by_format.items():
+            how = dict(dither=dither, seed=int(dither_seed), keys=files) if dither is not None and fmt in audio_io.DITHER_FORMATS else {}
             data, offsets, clipped = audio_io.encode_batch_device([per_file[f] for f in files], fmt,
-                                                                  frames=[infos[f]["frames"] for f in files])
+                                                                  frames=[infos[f]["frames"] for f in files], **how)
             for j, f in enumerate(files):
                 spans[f] = (len(parts), int(offsets[j]), int(offsets[j + 1]), j)
             parts += [data, clipped.view(torch.uint8)]
@@ -295,6 +310,8 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
             results.append(dict(path=paths[f], out_path=out_paths[f], channels=infos[f]["channels"], rate=infos[f]["rate"],
                                 frames=infos[f]["frames"], format=formats[f], clipped=int(host[part + 1].view(np.int64)[j]),
                                 windows=int(sum(n_windows[k] for k, o in enumerate(owner) if o == f))))
+            if dither is not None:
+                results[-1].update(dither=dither if formats[f] in audio_io.DITHER_FORMATS else None)
             if loudness is not None:
                 gain_db = 20.0 * float(np.log10(np.float64(gains_h[g])))
                 results[-1].update(loudness_before=float(rows_h[g, 0]), loudness=float(rows_h[g, 0]) + gain_db,

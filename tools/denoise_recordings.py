@@ -4,6 +4,7 @@ count, channels, rate and sample format.
   python tools/denoise_recordings.py DETECTOR.pth DENOISER.pth OUT_DIR in1.wav in2.wav ... [--sample-format s16] [--suffix _dn]
                                      [--link-channels any] [--high-band keep|follow] [--smooth-frames 2]
                                      [--loudness -23|source] [--peak-ceiling-db -1] [--peak sample|true] [--loudness-range]
+                                     [--dither tpdf|highpass] [--dither-seed 0]
 
 The networks run at 14 kHz: by default (--high-band drop) a 44.1 / 48 kHz file comes back band-limited to 7 kHz.  --high-band keep
 passes the source's band above 7 kHz through untouched; --high-band follow gives it the attenuation the denoiser applied below.
@@ -12,6 +13,10 @@ passes the source's band above 7 kHz through untouched; --high-band follow gives
 loudness its source had, by one gain per file applied before the samples are quantised; --peak-ceiling-db bounds the sample peak, or with
 --peak true the TRUE peak (dBTP, what EBU R128 delivery asks for: 4x interpolation).  --loudness-range also reports the loudness
 range (LRA, EBU Tech 3342) and the maximum momentary and short-term loudness of every written file.
+
+--dither adds dither before the 8 / 16 / 24-bit files are rounded (default: plain rounding): tpdf is white, highpass has its
+power moved towards half the rate.  What the denoiser left below one LSB then stays signal under a steady noise floor; without it
+that residue is distorted or gated to zero.  --dither-seed makes another draw; the same seed writes the same bytes.
 
 The checkpoints are the reference's (`{clock, model_state_dict, ...}` as the agents save them) or bare state dicts."""
 import argparse
@@ -66,6 +71,10 @@ def main():
                     help="--loudness: what --peak-ceiling-db bounds, the sample peak (default) or the true peak (dBTP)")
     ap.add_argument("--loudness-range", action="store_true",
                     help="--loudness: also report the loudness range (LU) and the maximum momentary / short-term loudness (LUFS) of every written file")
+    ap.add_argument("--dither", choices=sorted(audio_io.DITHER), default=None,
+                    help="dither the files written as u8 / s16 / s24 before rounding: triangular, white (tpdf) or moved towards half the "
+                         "rate (highpass) (default: none)")
+    ap.add_argument("--dither-seed", type=int, default=0, help="--dither: the seed of the draw, 0 .. 2^64 - 1")
     ap.add_argument("--precision", default="mixed", choices=["bf16", "bf16x3", "fp16", "mixed"])
     args = ap.parse_args()
     det, jm = _load(dnet.get_network(), args.detector), _load(jnet.get_network(MyConfig()), args.denoiser)
@@ -75,13 +84,15 @@ def main():
                                            link_channels=args.link_channels, high_band=args.high_band,
                                            smooth_frames=args.smooth_frames, loudness=args.loudness,
                                            peak_ceiling_db=args.peak_ceiling_db, peak=args.peak,
-                                           loudness_range=args.loudness_range):
+                                           loudness_range=args.loudness_range, dither=args.dither, dither_seed=args.dither_seed):
         level = "" if args.loudness is None else ", %.2f -> %.2f LUFS (%+.2f dB%s)" % (
             r["loudness_before"], r["loudness"], r["gain_db"], ", peak-limited" if r["peak_limited"] else "")
         if args.peak == "true":
             level += ", %.2f dBTP" % r["true_peak_db"]
         if args.loudness_range:
             level += ", LRA %.2f LU, max M %.2f / S %.2f LUFS" % (r["lra"], r["max_momentary"], r["max_short_term"])
+        if r.get("dither"):
+            level += ", %s dither" % r["dither"]
         print("%s -> %s: %d x %d frames at %d Hz, %s, %d windows, %d samples clipped%s"
               % (r["path"], r["out_path"], r["channels"], r["frames"], r["rate"], r["format"], r["windows"], r["clipped"], level))
 

@@ -25,6 +25,13 @@ in a temporary directory, in 'mixed' precision:
      frames, so that the composition needs no per-clip fitting), --band-reps alternating calls each, wall time from an idle device to an
      idle device; both forms are checked to give the same bits under 'keep' before they are timed; (c) the merge and the gains
      launch from device events against Tensor.copy_ moving the bytes they read and write.
+  6. with --dither tpdf|highpass: (a) denoise_recordings(dither=) against dither=None on the same files, both warmed, alternating,
+     in the same run of the program; (b) sos_pcm_encode_dither_batch (both kinds) against sos_pcm_encode_batch for u8 / s16 / s24 on
+     the --kernel-mib MiB of stereo planes of 3., the three forms of a format alternating, --kernel-repeats times each, from device
+     events over --kernel-reps launches: times, the ratio to the undithered kernel and to Tensor.copy_ of the same bytes; the same
+     once more on one-channel files (a thread's four frames then share a Philox block; a stereo thread's share two); (c) with
+     --against-lib PATH (another build of libsos_hip.so, e.g. the parent commit's): the undithered rows of this build against
+     that build's, alternating, each with its own repeat spread.
 A measurement: nothing is asserted."""
 import argparse
 import os
@@ -170,6 +177,52 @@ def kernels(args, amplitude):
                   f"{min(u8) / med[way + ' u8']:.3f} .. {max(u8) / med[way + ' u8']:.3f} of its median)")
 
 
+def dither_kernels(args, ch, other=None):
+    """6 (b), (c): per format the undithered entry point, the two dithered ones and, with `other`, another build's undithered one,
+    alternating on the same planes."""
+    L = _lib
+    frames = (1 << 20) * 2 // ch
+    n_files = max(1, (args.kernel_mib << 20) // (4 * frames * ch))
+    samples = n_files * ch * frames
+    flat = torch.empty(samples, dtype=torch.float32, device="cuda").uniform_(-0.9, 0.9)
+    print(f"dither kernels: {n_files} files of {ch} x {frames} frames = {samples * 4 / 2**20:.0f} MiB of planes uniform in +-0.9, "
+          f"{args.kernel_reps} launches per measurement, {args.kernel_repeats} measurements per form, the forms of a format alternating")
+    base = np.asarray([[i * ch * frames, frames, ch, frames, i * ch * frames] for i in range(n_files)], dtype=np.int64)
+    wide = np.ascontiguousarray(np.concatenate([base, np.arange(n_files, dtype=np.int64)[:, None], np.zeros((n_files, 1), np.int64)], axis=1))
+    base_dev, wide_dev = torch.from_numpy(base).cuda(), torch.from_numpy(wide).cuda()
+    counts = torch.empty(n_files, dtype=torch.int64, device="cuda")
+    for fmt in audio_io.DITHER_FORMATS:
+        code, width = audio_io.ENCODINGS[fmt][:2]
+        out = torch.empty(samples * width, dtype=torch.uint8, device="cuda")
+
+        def plain(h):
+            return lambda: L.check(h.sos_pcm_encode_batch(L.ptr(flat), L.ptr(base_dev), base.ctypes.data_as(L.C.c_void_p), n_files, code,
+                                                          L.ptr(out), L.ptr(counts), L.stream_ptr()))
+
+        def dithered(kind):
+            return lambda: L.check(L.lib().sos_pcm_encode_dither_batch(L.ptr(flat), L.ptr(wide_dev), wide.ctypes.data_as(L.C.c_void_p), n_files,
+                                                                       code, audio_io.DITHER[kind], 1234, L.ptr(out), L.ptr(counts),
+                                                                       L.stream_ptr()))
+
+        forms = {"none": plain(L.lib()), "tpdf": dithered("tpdf"), "highpass": dithered("highpass")}
+        if other is not None:
+            forms["none, other build"] = plain(other)
+        runs = {k: [] for k in forms}
+        for r in range(args.kernel_repeats):                     # forwards, backwards, ..: no form always follows the same one
+            for k, go in list(forms.items())[::-1 if r & 1 else 1]:
+                runs[k].append(device_ms(go, args.kernel_reps))
+        nbytes = samples * (4 + width)
+        src = torch.empty(nbytes // 8, dtype=torch.float32, device="cuda").normal_()
+        dst = torch.empty_like(src)
+        copy_ms = device_ms(lambda: dst.copy_(src), args.kernel_reps)
+        ref = float(np.median(runs["none"]))
+        for k, r in runs.items():
+            ms = float(np.median(r))
+            print(f"  encode {fmt:3s} {k:17s}: {ms:7.3f} ms (min {min(r):.3f}, max {max(r):.3f})  {nbytes / ms / 1e6:7.1f} GB/s    / undithered "
+                  f"{ms / ref:6.3f} (its repeats: {min(r) / ref:.3f} .. {max(r) / ref:.3f})    Tensor.copy_ of the same bytes {copy_ms:7.3f} ms, "
+                  f"ratio {copy_ms / ms:.2f}")
+
+
 def link_launch(args, paths):
     """4 (b): the link launch against stitch + per-file reduction + threshold on the same rows."""
     infos = [audio_io.wave_info(p) for p in paths]
@@ -295,9 +348,44 @@ def main():
     ap.add_argument("--link-reps", type=int, default=50)
     ap.add_argument("--high-band", choices=["keep", "follow"], default=None, help="measure the merge of the band above 7 kHz (5.) and nothing else")
     ap.add_argument("--band-reps", type=int, default=30)
+    ap.add_argument("--dither", choices=sorted(audio_io.DITHER), default=None, help="measure the dithered encode (6.) and nothing else")
+    ap.add_argument("--against-lib", default=None, help="6 (c): another build of libsos_hip.so whose undithered encode is timed beside this one's")
     args = ap.parse_args()
     print(torch.cuda.get_device_name(0))
     _count_downloads()
+    if args.dither:
+        if not args.skip_loop:
+            det = dnet.get_network()
+            det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+            jm = jnet.get_network(MyConfig())
+            jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+            det, jm = det.cuda().eval(), jm.cuda().eval()
+            sos_amd.set_precision("mixed")
+            with tempfile.TemporaryDirectory() as tmp:
+                paths, secs = make_files(tmp, args.files, args.seed)
+                forms = dict(plain=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "plain"), max_batch=args.max_batch),
+                             dither=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "dither"), max_batch=args.max_batch,
+                                                                          dither=args.dither, dither_seed=1234))
+                for fn in forms.values():                                                 # warm-up of both forms
+                    fn()
+                runs = {k: [] for k in forms}
+                for _ in range(args.repeats):                                             # the forms alternate
+                    for k, fn in forms.items():
+                        runs[k].append(once(fn))
+                print(f"{args.files} stereo s16 files at {RATE} Hz, {secs:.0f} s of audio x 2 channels, 'mixed' precision, {args.repeats} "
+                      "alternating repeats (median, min, max)")
+                d = report("dither=None", args.files, runs["plain"])
+                k = report("dither=%r" % args.dither, args.files, runs["dither"])
+                print(f"  {args.dither} / none = {k / d:.3f}")
+            sos_amd.set_precision("bf16")
+        other = None
+        if args.against_lib:
+            other = _lib.C.CDLL(args.against_lib)
+            other.sos_pcm_encode_batch.argtypes = _lib.SIGNATURES["sos_pcm_encode_batch"]
+            print("other build:", args.against_lib)
+        dither_kernels(args, 2, other)
+        dither_kernels(args, 1, other)
+        return
     if args.high_band:
         det = dnet.get_network()
         det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
