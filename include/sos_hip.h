@@ -598,6 +598,24 @@ int64_t sos_loudness_range_workspace_bytes(const int64_t* table_host, int nfiles
 int sos_loudness_range_batch_f64(const int64_t* table, const int64_t* table_host, int nfiles, const double* weights, int split,
                                  const void* work, int64_t work_bytes, void* range_work, int64_t range_work_bytes, double* out,
                                  sos_stream_t stream);
+/* The look-ahead limiter on the table above (csrc/limiter.hip; sos_amd.audio_io.limit_batch_device; float64 restatement:
+ * tests/limiter_reference.py): every file at the gain s that brings it to its target, its peaks held at the ceiling by ONE gain
+ * curve g[t] <= 1 for all its channels.  Reads columns 0 .. 4 of the table: column 4 is H, the look-ahead in samples (1 .. 1024).
+ * With m = min(frames, available), samples outside [0, m) reading 0: s = (float)10^((targets[f] - L) / 20) in double from
+ * stats[f] (1 where L or the target is not finite), C = (float)10^(ceiling_db / 20); p[t] = max over channels of |x[t]|, with
+ * true_peak != 0 also of the six interpolated points next to t (t - 1 + q / 4 and t + q / 4, q = 1, 2, 3: the points of
+ * sos_true_peak_batch_f64, coef as there; coef may be null otherwise); a = s * p[t] in f32, r[t] = a > C ? max((float)((double)C /
+ * (double)a), 2^-10) : 1, r = 1 outside [0, m); mn[t] = min r[t - H .. t + H]; g[t] = (float)(sum of (double)mn[t - H .. t + H] /
+ * (2 H + 1)) -- every mn is a multiple of 2^-33, the float64 sum is exact in any order; out[t] = x[t] * (g[t] * s) for t < m, and
+ * the samples [m, available) are copied.  g[t] <= r[t]; where g = 1 the output is what sos_loudness_gain_batch_f32 writes with
+ * the gain s.  `out` has the layout of `planes` and may not overlap it.  rows f64 [nfiles][4] = {s, min g, samples with g < 1,
+ * 0}, {NaN, NaN, -1, 0} for a skipped row; the minimum and the count are atomics without an order: two calls give equal bits.
+ * Three launches (the grid is flat over tiles of SOS_LIMITER_TILE samples of all files), no wait.
+ * SOS_EINVAL as above, and: H outside 1 .. 1024, a ceiling above 0 or not finite, out overlapping planes. */
+#define SOS_LIMITER_TILE 4096
+int sos_limiter_batch_f32(const float* planes, float* out, const int64_t* table, const int64_t* table_host, int nfiles,
+                          const double* stats, const double* targets, double ceiling_db, int true_peak, const float* coef,
+                          double* rows, sos_stream_t stream);
 /* Band-limited resampling by `ratio` = sr_new / sr_orig (resampy 0.2.2 `resample_f`): win = the filter's half
  * window (nwin floats, num_table samples per zero crossing), already multiplied by min(1, ratio).  Writes
  * out[0 .. n_out): the first floor(n_in * ratio) entries are resampled, the rest zero (librosa pads to

@@ -138,6 +138,7 @@ SIGNATURES = {
     "sos_true_peak_batch_f64": [_P, _P, _P, _I, _P, _P, _P],
     "sos_loudness_range_workspace_bytes": [_P, _I],
     "sos_loudness_range_batch_f64": [_P, _P, _I, _P, _I, _P, _L, _P, _L, _P, _P],
+    "sos_limiter_batch_f32": [_P, _P, _P, _P, _I, _P, _P, _D, _I, _P, _P, _P],
     "sos_resample_f32": [_P, _L, _D, _P, _I, _I, _P, _L, _P],
     "sos_resample_batch_f32": [_P, _P, _P, _I, _D, _P, _I, _I, _P, _P],
     "sos_resample_time_segments": [_D, _L, _P, _P, _P, _I],

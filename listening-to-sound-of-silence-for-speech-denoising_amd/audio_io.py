@@ -13,16 +13,16 @@ librosa's names, keeps its name under `audio_io.` and lives one layer down:
   wave_file.py: the RIFF container and the table of sample formats, host only (read_wave, wave_info, wave_container, write_wav, ..)
   resampling.py: the Kaiser table, resample_device / resample_batch_device, band_gains_batch_device / resample_merge_batch_device
   planes.py: every channel as an f32 plane (load_channels_batch_device, decode_planes_batch_device, encode_batch_device, G.711,
-      loudness_gain_batch_device) and pcm_to_mono_device, the mix-down under load
+      loudness_gain_batch_device, limit_batch_device) and pcm_to_mono_device, the mix-down under load
   stream_resampling.py: StreamResampler / StreamBandMerger, the resamplers for audio that is still arriving
 No CPU fallback."""
 import numpy as np
 import torch
 
 from . import ragged
-from .planes import (DITHER, DITHER_FORMATS, decode_planes_batch_device, encode_batch_device, g711_decode_device, g711_encode_device,  # noqa: F401
-                     load_channels_batch_device, loudness_gain_batch_device, pcm_encode_device, pcm_to_mono_device, planes_of,
-                     planes_together)
+from .planes import (DITHER, DITHER_FORMATS, LIMITER_MAX_LOOKAHEAD, LIMITER_TILE, decode_planes_batch_device, encode_batch_device, g711_decode_device, g711_encode_device,  # noqa: F401
+                     limit_batch_device, limiter_lookahead, load_channels_batch_device, loudness_gain_batch_device, pcm_encode_device, pcm_to_mono_device,
+                     planes_of, planes_together)
 from .resampling import (KAISER_BEST, band_gains_batch_device, filter_on, resample_batch_device, resample_device,  # noqa: F401
                          resample_merge_batch_device, sinc_window)
 from .stream_resampling import StreamBandMerger, StreamResampler  # noqa: F401

@@ -15,45 +15,20 @@
 // samples at a time -- a half wave loads the 128 contiguous bytes of one chunk, a lane then reads its own row (33 floats apart:
 // no bank is hit twice).  Everything after the load is float64.  All sums are taken in a fixed order: two calls give equal bits.
 // Bounds: the rule of ragged.h, as pcm_io.hip applies it -- the host refuses a row of table_host outside the totals it summed
-// (SOS_EINVAL, naming the file), the kernels skip a row of the DEVICE table that fails the same rule.
+// (SOS_EINVAL, naming the file), the kernels skip a row of the DEVICE table that fails the same rule; the row rule and the host's
+// checks stand in loudness_core.h, which limiter.hip shares.
 // Below the gain: the other EBU R128 measures on the same table -- sos_true_peak_batch_f64 (the true peak by 4x interpolation,
 // float32, a flat grid over the tiles of all planes) and sos_loudness_range_batch_f64 (loudness range and the maximum momentary /
 // short-term loudness, from the chunk energies of the work buffer); float64 restatement: tests/r128_reference.py.
-#include "ragged.h"
+#include "loudness_core.h"
 #include <math.h>
 
-#define LD_COLS 8                       // int64 per file: the encode row {first plane sample, plane length, channels, frames, -},
-                                        // then {hop h, first channel weight, first chunk of the work arrays}
-#define LD_WAVE 64                      // threads per workgroup of the chunk kernels: 64 consecutive chunks of one plane
 #define LD_TILE 32                      // samples per chunk staged at a time
-#define LD_MAX_CHANNELS 64
-#define LD_MAX_SPLIT 64
-#define LD_MAX_HOP ((int64_t)1 << 31)
 #define LD_MAX_GRID 4096
 #define LD_CARRY 8                      // chunk states the carry fetches ahead of its recurrence
 #define LD_WORK 6                       // f64 arrays of the work buffer, one entry per chunk: state[4], energy, peak
 #define LD_GAIN_THREADS 256
 #define LD_GAIN_MAX_GRID 1024
-
-__host__ __device__ static inline int64_t ld_min(int64_t a, int64_t b) { return a < b ? a : b; }
-
-struct LdRow { int64_t first, avail, ch, frames, h, woff, qoff, nq; };         // nq: chunks per plane (the last hop may be partial)
-
-// the plane side of a row, as pcm_io.hip holds it: `ch` planes of `avail` samples from `first` lie inside `total`
-__host__ __device__ static inline bool ld_planes_inside(int64_t first, int64_t avail, int64_t ch, int64_t total) {
-    return ch >= 1 && ch <= LD_MAX_CHANNELS && avail >= 0 && avail <= total / ch && ragged_clip_inside(first, avail * ch, total);
-}
-
-// the whole rule for a row of the measurement: planes, hop, weights and chunks inside the four totals
-__host__ __device__ static inline bool ld_row(const int64_t* te, int split, int64_t total_in, int64_t total_ch, int64_t total_chunks,
-                                              LdRow* r) {
-    *r = {te[0], te[1], te[2], te[3], te[5], te[6], te[7], 0};
-    if (!ld_planes_inside(r->first, r->avail, r->ch, total_in) || r->frames < 0 || r->h < split || r->h > LD_MAX_HOP) return false;
-    const int64_t nh = r->frames / r->h + (r->frames % r->h != 0);
-    if (nh > total_chunks / (split * r->ch)) return false;
-    r->nq = nh * split;
-    return ragged_clip_inside(r->woff, r->ch, total_ch) && ragged_clip_inside(r->qoff, r->nq * r->ch, total_chunks);
-}
 
 // samples [a, b) of chunk q (both cut at the file's frames), and whether it is one of the longer chunks of its hop
 __device__ __forceinline__ void ld_chunk(const LdRow& r, int split, int64_t q, int64_t* a, int64_t* b) {
@@ -272,62 +247,6 @@ __global__ __launch_bounds__(LD_GAIN_THREADS) void loud_gain_kernel(float* __res
     }
 }
 
-// Host: sums the table into the totals the kernels hold every device row to; nfiles, or the first row it cannot accept.
-struct LdTotals { int64_t in = 0, ch = 0, chunks = 0, units = 0, longest = 0; };
-static int ld_check_rows(const int64_t* table, int nfiles, int split, bool measure, LdTotals* t, const char** why) {
-    for (int f = 0; f < nfiles; ++f) {
-        const int64_t* te = table + (int64_t)f * LD_COLS;
-        const int64_t avail = te[1], ch = te[2], frames = te[3], h = te[5];
-        if (ch < 1 || ch > LD_MAX_CHANNELS) { *why = "channels outside 1 .. 64"; return f; }
-        if (avail < 0 || avail > (INT64_MAX / 8 - t->in) / ch || frames < 0 || frames > INT64_MAX / 8 / ch) {
-            *why = "a length that is negative or too large";
-            return f;
-        }
-        t->in += avail * ch;
-        t->ch += ch;
-        t->longest = std::max(t->longest, std::min(avail, frames));
-        if (!measure) continue;
-        if (h < 1 || h > LD_MAX_HOP) { *why = "a hop outside 1 .. 2^31 samples"; return f; }
-        if (h < split) { *why = "a hop shorter than the chunks per hop"; return f; }
-        const int64_t nq = (frames / h + (frames % h != 0)) * split;
-        if (nq > (INT64_MAX / 64 - t->chunks) / ch) { *why = "a length that is negative or too large"; return f; }
-        t->chunks += nq * ch;
-        t->units = std::max(t->units, (nq + LD_WAVE - 1) / LD_WAVE * ch);
-    }
-    for (int f = 0; f < nfiles; ++f) {
-        const int64_t* te = table + (int64_t)f * LD_COLS;
-        LdRow r;
-        if (measure ? !ld_row(te, split, t->in, t->ch, t->chunks, &r) : !ld_planes_inside(te[0], te[1], te[2], t->in)) {
-            *why = "a span outside the totals of the table";
-            return f;
-        }
-    }
-    return nfiles;
-}
-
-static int ld_args(const char* who, bool null, const int64_t* table_host, int nfiles, int split, bool measure, LdTotals* t) {
-    if (null) { sos_set_error("%s: null pointer", who); return SOS_EINVAL; }
-    if (!ragged_clips_ok(table_host, nfiles)) {
-        sos_set_error("%s: bad args (1 .. 65535 files, got %d)", who, nfiles);
-        return SOS_EINVAL;
-    }
-    if (measure && (split < 1 || split > LD_MAX_SPLIT)) {
-        sos_set_error("%s: bad args (1 .. %d chunks per hop, got %d)", who, LD_MAX_SPLIT, split);
-        return SOS_EINVAL;
-    }
-    const char* why = "";
-    const int bad = ld_check_rows(table_host, nfiles, split, measure, t, &why);
-    if (bad < nfiles) {
-        const int64_t* te = table_host + (int64_t)bad * LD_COLS;
-        sos_set_error("%s: file %d (plane sample %lld, %lld available, %lld channels, %lld frames, hop %lld, weight %lld, chunk "
-                      "%lld) has %s (%lld plane samples, %lld channels, %lld chunks)", who, bad, (long long)te[0], (long long)te[1],
-                      (long long)te[2], (long long)te[3], (long long)te[5], (long long)te[6], (long long)te[7], why,
-                      (long long)t->in, (long long)t->ch, (long long)t->chunks);
-        return SOS_EINVAL;
-    }
-    return SOS_OK;
-}
-
 extern "C" int64_t sos_loudness_workspace_bytes(const int64_t* table_host, int nfiles, int split) {
     LdTotals t;
     if (ld_args("sos_loudness_workspace_bytes", false, table_host, nfiles, split, true, &t) != SOS_OK) return -1;
@@ -391,7 +310,6 @@ extern "C" int sos_loudness_gain_batch_f32(float* planes, const int64_t* table, 
 #define TP_THREADS 256
 #define TP_POINTS 8                     // consecutive points of a lane
 #define TP_TILE (TP_THREADS * TP_POINTS)
-#define TP_TAPS 12
 #define TP_HALO (TP_TAPS - 1)
 #define TP_LDS (TP_TILE + 16)           // the samples of a tile, its halo, and what the last lane's fifth 16-byte read covers
 #define TP_MAX_GRID 2048
@@ -496,12 +414,7 @@ __global__ __launch_bounds__(TP_THREADS) void tp_peak_kernel(const float* __rest
         for (int j = 0; j < TP_POINTS; ++j) {
             float best = fabsf(w[j + 5]);                            // the sample x[n] itself; n = -1 reads the 0 before the plane
 #pragma unroll
-            for (int ph = 0; ph < 3; ++ph) {
-                float v = 0.f;
-#pragma unroll
-                for (int k = 0; k < TP_TAPS; ++k) v = fmaf(h[ph][k], w[j + k], v);
-                best = fmaxf(best, fabsf(v));
-            }
+            for (int ph = 0; ph < 3; ++ph) best = fmaxf(best, fabsf(tp_point(h[ph], w + j)));
             if (j < left) pk = fmaxf(pk, best);
         }
 #pragma unroll

@@ -5,7 +5,7 @@
 // A batch is clips back to back in one buffer plus a table of where each lies, in two copies: the host sizes every array
 // from its own (table_host / lengths_host) and refuses a bad entry before any launch; the kernels follow the DEVICE table.
 // A table with more columns than the clip row below states its rule once, next to its kernel, as a *_row reader and a
-// __host__ __device__ *_why that the kernel's skip and the host's refusal both call (loudness.hip: ld_row; wave_io.hip:
+// __host__ __device__ *_why that the kernel's skip and the host's refusal both call (loudness_core.h: ld_row; limiter.hip: lim_row; wave_io.hip:
 // rs_batch_why; band_merge.hip: band_gain_why, band_merge_why; stream_resample.hip and stream_band.hip: their stream_*_why).
 #pragma once
 #include "sos_common.h"

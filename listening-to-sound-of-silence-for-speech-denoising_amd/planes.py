@@ -1,6 +1,6 @@
-"""Channel planes (csrc/pcm_io.hip, csrc/loudness.hip): the samples of WAVE files, as wave_file.py reads them, decoded into one
-f32 plane per channel on the GPU, and planes encoded back into the data bytes of a file -- the linear formats and G.711 -- with
-the gain that brings a file to a target loudness in between.  No CPU fallback."""
+"""Channel planes (csrc/pcm_io.hip, csrc/loudness.hip, csrc/limiter.hip): the samples of WAVE files, as wave_file.py reads them,
+decoded into one f32 plane per channel on the GPU, and planes encoded back into the data bytes of a file -- the linear formats and
+G.711 -- with the gain that brings a file to a target loudness, and the look-ahead limiter, in between.  No CPU fallback."""
 import ctypes as C
 
 import numpy as np
@@ -207,6 +207,32 @@ def planes_together(planes):
     return [v.view(p.shape) for v, p in zip(ragged.split(flat, [p.numel() for p in planes]), planes)]
 
 
+def _level_args(who, planes, stats, target, peak_ceiling_db, frames):
+    """The checked arguments loudness_gain_batch_device and limit_batch_device share: (planes, rows f64 [files][4], targets f64
+    [files] on the device or None without a file, frames), or `who`'s ValueError."""
+    planes = check_planes(who, planes)
+    rows = stats["rows"] if isinstance(stats, dict) else stats
+    if not torch.is_tensor(rows) or rows.dtype != torch.float64 or tuple(rows.shape) != (len(planes), 4):
+        raise ValueError("%s: stats holds one float64 row of 4 per file (metrics.loudness_batch)" % who)
+    if torch.is_tensor(target):
+        if target.dtype != torch.float64 or tuple(target.shape) != (len(planes),):
+            raise ValueError("%s: a target tensor holds one float64 per file" % who)
+    elif not np.isfinite(float(target)):
+        raise ValueError("%s: the target is a finite number of LUFS, got %r" % (who, target))
+    if not float(peak_ceiling_db) <= 0.0:
+        raise ValueError("%s: the ceiling is at most 0 dBFS, got %r" % (who, peak_ceiling_db))
+    frames = plane_frames(who, planes, frames)
+    L.require_cuda(rows, *planes)
+    if not planes:
+        return planes, rows, None, frames
+    if torch.is_tensor(target):
+        L.require_cuda(target)
+        targets = target.contiguous()
+    else:
+        targets = torch.full((len(planes),), float(target), dtype=torch.float64, device=planes[0].device)
+    return planes, rows.contiguous(), targets, frames
+
+
 def loudness_gain_batch_device(planes, stats, target, peak_ceiling_db=-1.0, frames=None):
     """Brings every file of a group to a target loudness, IN PLACE and in one sos_loudness_gain_batch_f32 launch (per 65535
     files), without a wait.  planes: one (channels, n) f32 GPU tensor per file; stats: what metrics.loudness_batch returned for
@@ -221,28 +247,10 @@ def loudness_gain_batch_device(planes, stats, target, peak_ceiling_db=-1.0, fram
     the rows with the true peak in column 1.  g = min(10^((target - L) / 20), 10^(ceiling / 20) / true peak); the interpolation
     is linear, so the scaled file's true peak is g * the measured one up to float32 rounding, and stays at or below the ceiling."""
     who = "loudness_gain_batch_device"
-    planes = check_planes(who, planes)
-    rows = stats["rows"] if isinstance(stats, dict) else stats
-    if not torch.is_tensor(rows) or rows.dtype != torch.float64 or tuple(rows.shape) != (len(planes), 4):
-        raise ValueError("loudness_gain_batch_device: stats holds one float64 row of 4 per file (metrics.loudness_batch)")
-    if torch.is_tensor(target):
-        if target.dtype != torch.float64 or tuple(target.shape) != (len(planes),):
-            raise ValueError("loudness_gain_batch_device: a target tensor holds one float64 per file")
-    elif not np.isfinite(float(target)):
-        raise ValueError("loudness_gain_batch_device: the target is a finite number of LUFS, got %r" % (target,))
-    if not float(peak_ceiling_db) <= 0.0:
-        raise ValueError("loudness_gain_batch_device: the ceiling is at most 0 dBFS, got %r" % (peak_ceiling_db,))
-    frames = plane_frames(who, planes, frames)
-    L.require_cuda(rows, *planes)
+    planes, rows, targets, frames = _level_args(who, planes, stats, target, peak_ceiling_db, frames)
     if not planes:
         return torch.zeros(0, dtype=torch.float32, device="cuda"), torch.zeros(0, dtype=torch.bool, device="cuda")
     device = planes[0].device
-    if torch.is_tensor(target):
-        L.require_cuda(target)
-        targets = target.contiguous()
-    else:
-        targets = torch.full((len(planes),), float(target), dtype=torch.float64, device=device)
-    rows = rows.contiguous()
     together = planes_together(planes) if sum(p.numel() for p in planes) else planes
     flat, src, chans, avail = planes_flat(together)
     gains = torch.empty(len(planes), dtype=torch.float32, device=device)
@@ -259,6 +267,79 @@ def loudness_gain_batch_device(planes, stats, target, peak_ceiling_db=-1.0, fram
         if t is not p:                                  # the planes lay apart: the launch scaled their copy
             p.copy_(t)
     return gains, limited.bool()
+
+
+LIMITER_TILE = 4096                 # samples of time per workgroup of sos_limiter_batch_f32: SOS_LIMITER_TILE of include/sos_hip.h
+LIMITER_MAX_LOOKAHEAD = 1024        # samples
+
+
+def limiter_lookahead(who, rates, lookahead_ms, nfiles):
+    """H = round(lookahead_ms * rate / 1000) per file as a list of ints, or `who`'s ValueError: a look-ahead that is not finite
+    and positive, rates that are not one per file, a file whose rate puts H outside 1 .. 1024 samples."""
+    ok = not isinstance(lookahead_ms, (bool, str)) and np.ndim(lookahead_ms) == 0 and np.isfinite(float(lookahead_ms))
+    if not ok or float(lookahead_ms) <= 0.0:
+        raise ValueError("%s: lookahead_ms is a finite number of milliseconds above 0, got %r" % (who, lookahead_ms))
+    if rates is None:
+        raise ValueError("%s: rates= is needed (one sample rate per file, or one for all)" % who)
+    rates = [rates] * nfiles if np.ndim(rates) == 0 else list(rates)
+    if len(rates) != nfiles:
+        raise ValueError("%s: one rate per file (%d files, %d rates)" % (who, nfiles, len(rates)))
+    out = []
+    for i, r in enumerate(rates):
+        if isinstance(r, bool) or not np.isfinite(float(r)) or float(r) <= 0.0:
+            raise ValueError("%s: file %d has the rate %r (a positive number of Hz)" % (who, i, r))
+        out.append(int(round(float(lookahead_ms) * float(r) / 1000.0)))
+        if not 1 <= out[-1] <= LIMITER_MAX_LOOKAHEAD:
+            raise ValueError("%s: file %d: %r ms at %r Hz is a look-ahead of %d samples (1 .. %d)"
+                             % (who, i, lookahead_ms, r, out[-1], LIMITER_MAX_LOOKAHEAD))
+    return out
+
+
+def limit_batch_device(planes, stats, target, peak_ceiling_db=-1.0, rates=None, lookahead_ms=5.0, frames=None, true_peak=False):
+    """The look-ahead limiter: every file of a group at the gain that brings it to its target loudness, with its peaks held at
+    the ceiling by a gain that dips around them only, where loudness_gain_batch_device lowers the whole file.  OUT OF PLACE, one
+    sos_limiter_batch_f32 launch sequence (per 65535 files), without a wait.  planes, stats, target, peak_ceiling_db and frames
+    as loudness_gain_batch_device takes them (the ceiling bounds the SAMPLE peak; true_peak=True: the true peak, by the
+    interpolator of metrics.true_peak_batch); rates: the sample rate per file, or one for all; lookahead_ms: H = round(lookahead_ms
+    * rate / 1000) samples per file, 1 .. 1024.
+    Per file, ONE gain curve for all channels (a stereo image does not shift), samples past min(frames, n) reading 0:
+    s = float32(10^((target - L) / 20)), 1 where L or the target is not finite; p[t] = the largest |x[t]| of any channel (true_peak:
+    and of the six interpolated points next to t); r[t] = min(1, C / (s p[t])), at least 2^-10; mn[t] = min r[t - H .. t + H]; g[t] =
+    mean mn[t - H .. t + H], in float64 and exact; out = x * (g * s).  g[t] <= r[t], so the SAMPLE peak of the output is at most
+    the ceiling (to 3 ulp); g ramps linearly over 2 H samples on either side of a peak; where no peak is within 2 H samples g is 1
+    and the sample is bit for bit what loudness_gain_batch_device writes without a binding ceiling.  Under true_peak the curve is
+    built from the true-peak envelope, but a gain that varies between two samples leaves an overshoot of the order H^-1: trim with
+    loudness_gain_batch_device on a measurement of the output where the ceiling has to hold strictly (recordings.py does).
+    Float64 / numpy restatement: tests/limiter_reference.py.
+    -> (limited: one (channels, n) f32 tensor per file, views into ONE new buffer, the samples past `frames` copied; rows: f64
+    [files][4] = {s, the least g, the samples with g < 1, 0}), on the device.  ValueError before any launch:
+    loudness_gain_batch_device's, a lookahead_ms that is not finite and positive, rates missing or not one per file, a file whose
+    rate puts H outside 1 .. 1024."""
+    who = "limit_batch_device"
+    planes, rows, targets, frames = _level_args(who, planes, stats, target, peak_ceiling_db, frames)
+    if not np.isfinite(float(peak_ceiling_db)):
+        raise ValueError("%s: the ceiling is a finite level of at most 0 dBFS, got %r" % (who, peak_ceiling_db))
+    hs = limiter_lookahead(who, rates, lookahead_ms, len(planes))
+    if not planes:
+        return [], torch.zeros((0, 4), dtype=torch.float64, device="cuda")
+    from .metrics import true_peak_filter                            # metrics imports this module
+    device = planes[0].device
+    together = planes_together(planes) if sum(p.numel() for p in planes) else planes
+    flat, src, chans, avail = planes_flat(together)
+    out = torch.empty_like(flat)
+    coef = torch.from_numpy(true_peak_filter()).to(device) if true_peak else None
+    result = torch.empty((len(planes), 4), dtype=torch.float64, device=device)
+    h = L.lib()
+    for c0, c1 in ragged.chunks(len(planes)):
+        tab = np.zeros((c1 - c0, 8), dtype=np.int64)
+        tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 3], tab[:, 4] = src[c0:c1] - src[c0], avail[c0:c1], chans[c0:c1], frames[c0:c1], hs[c0:c1]
+        tab_dev = ragged.upload(tab, device)
+        L.check(h.sos_limiter_batch_f32(L.ptr(flat[int(src[c0]):]), L.ptr(out[int(src[c0]):]), L.ptr(tab_dev),
+                                        tab.ctypes.data_as(C.c_void_p), c1 - c0, L.ptr(rows[c0:]), L.ptr(targets[c0:]),
+                                        float(peak_ceiling_db), int(bool(true_peak)), L.ptr(coef) if true_peak else None,
+                                        L.ptr(result[c0:]), L.stream_ptr()), "sos_limiter_batch_f32")
+    limited = [out[int(o):int(o) + p.numel()].view(p.shape) if p.numel() else torch.zeros_like(p) for o, p in zip(src, planes)]
+    return limited, result
 
 
 def g711_decode_device(codes, law):

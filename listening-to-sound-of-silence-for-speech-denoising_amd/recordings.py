@@ -7,7 +7,9 @@ and the encode each run in launches shared by all files and channels of a group 
 csrc/ragged_window.hip).  The networks run at 14 kHz: by default a file of a higher rate comes back band-limited to 7 kHz;
 high_band='keep' / 'follow' merge the band above 7 kHz of the source back in (csrc/band_merge.hip).  loudness= brings every
 written file to a target integrated loudness (ITU-R BS.1770 / EBU R128, csrc/loudness.hip) by one gain per file before the encode;
-peak='true' states its ceiling in dBTP and loudness_range=True reports the loudness range and the R128 maxima."""
+peak='true' states its ceiling in dBTP and loudness_range=True reports the loudness range and the R128 maxima;
+limiter='lookahead' holds the peaks at the ceiling by a gain that dips around them only (csrc/limiter.hip), so that a file whose
+peaks would bind the one gain still reaches its target."""
 import os
 
 import numpy as np
@@ -68,6 +70,26 @@ def _check_files(paths, out_dir, sample_format, suffix, link_channels=None, high
 
 
 PEAK_MODES = ("sample", "true")
+LIMITERS = ("lookahead",)
+
+
+def _check_limiter(limiter, lookahead_ms, loudness, infos, paths):
+    """What can be refused from the limiter's arguments and the files' rates: -> H per file (None without a limiter)."""
+    if limiter is not None and limiter not in LIMITERS:
+        raise ValueError("denoise_recordings: unknown limiter %r (None, or one of %s)" % (limiter, ", ".join(LIMITERS)))
+    ok = not isinstance(lookahead_ms, (bool, str)) and np.ndim(lookahead_ms) == 0 and np.isfinite(float(lookahead_ms))
+    if not ok or float(lookahead_ms) <= 0.0:
+        raise ValueError("denoise_recordings: lookahead_ms is a finite number of milliseconds above 0, got %r" % (lookahead_ms,))
+    if limiter is None:
+        return None
+    if loudness is None:
+        raise ValueError("denoise_recordings: limiter=%r needs a loudness target (a number or 'source')" % (limiter,))
+    hs = [int(round(float(lookahead_ms) * i["rate"] / 1000.0)) for i in infos]
+    for h, i, p in zip(hs, infos, paths):
+        if not 1 <= h <= audio_io.LIMITER_MAX_LOOKAHEAD:
+            raise ValueError("%s: %r ms at %d Hz is a look-ahead of %d samples (1 .. %d)"
+                             % (p, lookahead_ms, i["rate"], h, audio_io.LIMITER_MAX_LOOKAHEAD))
+    return hs
 
 
 def _check_loudness(loudness, peak_ceiling_db, channel_weights, peak="sample", loudness_range=False):
@@ -141,7 +163,7 @@ def _merge_back(natives, lows_in, lows_out, rates, high_band, smooth_frames):
 def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, context_seconds=2.0, max_batch=256,
                        max_columns=65536, max_bytes=labels.DEFAULT_MAX_BYTES, sample_format=None, suffix="", link_channels=None,
                        high_band="drop", smooth_frames=2, loudness=None, peak_ceiling_db=-1.0, channel_weights=None,
-                       peak="sample", loudness_range=False, dither=None, dither_seed=0):
+                       peak="sample", loudness_range=False, dither=None, dither_seed=0, limiter=None, lookahead_ms=5.0):
     """Denoises the WAVE files `paths` into out_dir/<name><suffix>.wav.  A written file has exactly the source's frame count,
     channels, rate and sample format (PCM 8 / 16 / 24 / 32 bit, float 32, G.711 A-law / mu-law; a float64 source is written as
     float32); sample_format= ('s16', 's24', 's32', 'u8', 'f32', 'alaw', 'ulaw') forces one format for all files.
@@ -199,6 +221,18 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     the position in `paths`, not in the group: a file's bytes do not depend on max_bytes or on the other files.  Files written
     as 's32', 'f32' or G.711 are written as before.  Still one encode launch per format and group, and one download.
     dither_seed: 0 .. 2^64 - 1; the same call twice writes the same files.
+    limiter: None (the default: the launches, the bytes and the result keys are what they were) or 'lookahead'.  The one gain is
+    min(to the target, ceiling / peak): where the ceiling binds, the file is written QUIETER than its target, by an amount a single
+    plosive or click decides -- and denoised speech has a high crest, the floor between the words being gone.  'lookahead' (it
+    needs a loudness target) applies the gain to the target in full and holds the peaks at the ceiling by a gain curve that
+    dips around them only, one curve for all channels of a file (audio_io.limit_batch_device, csrc/limiter.hip: symmetric linear
+    ramps over 2 * lookahead_ms on either side of a peak).  Per group: the measurement as above; the limiter (the sample or the
+    true-peak envelope, as peak= says); the measurement AGAIN on the limited planes, with the true peak and the range if asked for
+    (a limiter moves them); the one gain with the target set to the loudness just measured, which makes it a pure TRIM min(1,
+    ceiling / peak) -- it holds the ceiling as strictly as without the limiter and takes up what a gain that varies between two
+    samples leaves of a true peak; the encode.  Everything still rides the group's one download.  lookahead_ms (default 5):
+    round(lookahead_ms * rate / 1000) samples, 1 .. 1024 at every file's rate.  The loudness a limiter takes away is NOT made up
+    for by a second pass: `loudness` reports what was written.
     -> one dict per file: path, out_path, channels, rate, frames, format, clipped (samples that saturated or were NaN, all
     channels), windows (denoise_long windows, all channels); with loudness also loudness_before (LUFS of the denoised file
     before the gain, -inf without a gated block), loudness (before + 20 log10 g, not measured again), loudness_target, gain_db
@@ -206,11 +240,16 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
     written, in dBTP, -inf for a silent file); under loudness_range=True also lra (LU, of the planes before the gain, which a gain
     does not move) and max_momentary / max_short_term (LUFS, as written: measured before the gain, + gain_db).
     With dither= also dither: the kind, or None for a file it did not apply to.
+    With limiter= the rows change: gain_db = 20 log10(the gain to the target) + the trim; loudness = the loudness MEASURED on the
+    limited planes + the trim; peak_limited says the trim engaged; limiter_db (20 log10 of the least gain of the curve, at most 0)
+    and limiter_samples (samples per channel the curve lowered) are new; true_peak_db, lra, max_momentary and max_short_term are
+    those of the limited planes, as written.
     ValueError before any launch of the call, naming the file: fewer than MIN_FRAMES STFT frames at 14 kHz, an unsupported
     format (audio_io.WaveFormatError), no channels or more than 64, two inputs with one output name; an unknown sample_format, link_channels or
     high_band, smooth_frames outside 0 .. 16; a loudness that is not finite or outside -70 .. 0, a ceiling above 0, weights that are
     negative or not one per channel, an unknown peak, a loudness_range that is no bool, either of the two without a loudness target;
-    an unknown dither, a dither_seed that is no integer in 0 .. 2^64 - 1;
+    an unknown dither, a dither_seed that is no integer in 0 .. 2^64 - 1; an unknown limiter, a limiter without a loudness target, a
+    lookahead_ms that is not finite and positive, a file whose rate puts the look-ahead outside 1 .. 1024 samples;
     window_plan's argument rules; a group with more than 65535 windows."""
     paths = [os.fspath(p) for p in paths]
     if dither is not None and dither not in audio_io.DITHER:
@@ -219,6 +258,7 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
         raise ValueError("denoise_recordings: dither_seed is an integer in 0 .. 2^64 - 1, got %r" % (dither_seed,))
     _check_loudness(loudness, peak_ceiling_db, channel_weights, peak, loudness_range)
     infos, formats, out_paths = _check_files(paths, out_dir, sample_format, suffix, link_channels, high_band, smooth_frames)
+    _check_limiter(limiter, lookahead_ms, loudness, infos, paths)
     flags = dict(true_peak=True) if peak == "true" else {}
     if loudness_range:
         flags["loudness_range"] = True                  # with neither, loudness_batch is called as it always was
@@ -265,22 +305,32 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
             per_file.update(zip(group, level))
             frames, rates_g = [infos[f]["frames"] for f in group], [infos[f]["rate"] for f in group]
             w = [weights[f] for f in group]
-            if loudness == "source" and not flags:
+            measured = {} if limiter is not None else flags        # the limiter's own measurement carries no extra
+            if loudness == "source" and not measured:
                 got = metrics.loudness_batch(level + list(ys), rates_g * 2, w * 2, frames * 2)
                 target = got["rows"].new_empty(len(group)).copy_(got["rows"][len(group):, 0])       # packed, whatever the group's size
             elif loudness == "source":                  # the true peak and the range of the outputs only: the sources apart
-                got = metrics.loudness_batch(level, rates_g, w, frames, **flags)
+                got = metrics.loudness_batch(level, rates_g, w, frames, **measured)
                 target = metrics.loudness_batch(list(ys), rates_g, w, frames)["lufs"].contiguous()
             else:
-                got = metrics.loudness_batch(level, rates_g, w, frames, **flags)
+                got = metrics.loudness_batch(level, rates_g, w, frames, **measured)
                 target = torch.full((len(group),), float(loudness), dtype=torch.float64, device=got["rows"].device)
+            if limiter is not None:                     # the gain to the target in full, the peaks held; then measure what is written
+                before = got["rows"][:len(group)].contiguous()
+                level, curve = audio_io.limit_batch_device(level, before, target, peak_ceiling_db, rates=rates_g, lookahead_ms=lookahead_ms,
+                                                           frames=frames, true_peak=peak == "true")
+                per_file.update(zip(group, level))
+                got = metrics.loudness_batch(level, rates_g, w, frames, **flags)
             rows = got["rows_true" if peak == "true" else "rows"][:len(group)]               # column 1: the peak the ceiling bounds
-            gains, limited = audio_io.loudness_gain_batch_device(level, rows, target, peak_ceiling_db, frames=frames)
+            aim = target if limiter is None else got["lufs"].contiguous()    # its own loudness: the gain to it is 1, the trim is left
+            gains, limited = audio_io.loudness_gain_batch_device(level, rows, aim, peak_ceiling_db, frames=frames)
             parts += [rows.contiguous().view(torch.uint8).reshape(-1), target.view(torch.uint8),
                       gains.view(torch.uint8), limited.view(torch.uint8)]
             if loudness_range:                          # {LRA, max momentary, max short-term, windows}: windows -1 marks a skipped row
                 more = torch.stack([got[k].double() for k in ("lra", "max_momentary", "max_short_term", "windows")], dim=1)
                 parts.append(more.contiguous().view(torch.uint8).reshape(-1))
+            if limiter is not None:
+                parts += [before.view(torch.uint8).reshape(-1), curve.contiguous().view(torch.uint8).reshape(-1)]
         for fmt, files in by_format.items():
             how = dict(dither=dither, seed=int(dither_seed), keys=files) if dither is not None and fmt in audio_io.DITHER_FORMATS else {}
             data, offsets, clipped = audio_io.encode_batch_device([per_file[f] for f in files], fmt,
@@ -301,6 +351,11 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
             more_h = host[4].view(np.float64).reshape(-1, 4)
             if np.any(more_h[:, 3] < 0):
                 raise RuntimeError("sos_loudness_range_batch_f64: device rows disagree with the host's")
+        if limiter is not None:
+            at = 5 if loudness_range else 4
+            before_h, curve_h = host[at].view(np.float64).reshape(-1, 4), host[at + 1].view(np.float64).reshape(-1, 4)
+            if np.any(before_h[:, 2] < 0) or np.any(curve_h[:, 2] < 0):
+                raise RuntimeError("sos_limiter_batch_f32: device rows disagree with the host's")
         for g, f in enumerate(group):
             part, b0, b1, j = spans[f]
             tag, bits = SAMPLE_FORMATS[formats[f]][2:]
@@ -313,13 +368,17 @@ def denoise_recordings(detector, denoiser, paths, out_dir, window_seconds=30.0, 
             if dither is not None:
                 results[-1].update(dither=dither if formats[f] in audio_io.DITHER_FORMATS else None)
             if loudness is not None:
-                gain_db = 20.0 * float(np.log10(np.float64(gains_h[g])))
+                gain_db = after_db = 20.0 * float(np.log10(np.float64(gains_h[g])))           # after_db: what follows the last measurement
                 results[-1].update(loudness_before=float(rows_h[g, 0]), loudness=float(rows_h[g, 0]) + gain_db,
                                    loudness_target=float(target_h[g]), gain_db=gain_db, peak_limited=bool(limited_h[g]))
+            if limiter is not None:
+                gain_db = 20.0 * float(np.log10(curve_h[g, 0])) + after_db
+                results[-1].update(loudness_before=float(before_h[g, 0]), gain_db=gain_db, limiter_db=20.0 * float(np.log10(curve_h[g, 1])),
+                                   limiter_samples=int(curve_h[g, 2]))
             if peak == "true":
                 with np.errstate(divide="ignore"):
                     results[-1].update(true_peak_db=float(20.0 * np.log10(np.float64(gains_h[g]) * rows_h[g, 1])))
             if loudness_range:
-                results[-1].update(lra=float(more_h[g, 0]), max_momentary=float(more_h[g, 1]) + gain_db,
-                                   max_short_term=float(more_h[g, 2]) + gain_db)
+                results[-1].update(lra=float(more_h[g, 0]), max_momentary=float(more_h[g, 1]) + after_db,
+                                   max_short_term=float(more_h[g, 2]) + after_db)
     return results

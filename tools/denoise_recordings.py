@@ -4,7 +4,7 @@ count, channels, rate and sample format.
   python tools/denoise_recordings.py DETECTOR.pth DENOISER.pth OUT_DIR in1.wav in2.wav ... [--sample-format s16] [--suffix _dn]
                                      [--link-channels any] [--high-band keep|follow] [--smooth-frames 2]
                                      [--loudness -23|source] [--peak-ceiling-db -1] [--peak sample|true] [--loudness-range]
-                                     [--dither tpdf|highpass] [--dither-seed 0]
+                                     [--dither tpdf|highpass] [--dither-seed 0] [--limiter lookahead] [--lookahead-ms 5]
 
 The networks run at 14 kHz: by default (--high-band drop) a 44.1 / 48 kHz file comes back band-limited to 7 kHz.  --high-band keep
 passes the source's band above 7 kHz through untouched; --high-band follow gives it the attenuation the denoiser applied below.
@@ -17,6 +17,9 @@ range (LRA, EBU Tech 3342) and the maximum momentary and short-term loudness of 
 --dither adds dither before the 8 / 16 / 24-bit files are rounded (default: plain rounding): tpdf is white, highpass has its
 power moved towards half the rate.  What the denoiser left below one LSB then stays signal under a steady noise floor; without it
 that residue is distorted or gated to zero.  --dither-seed makes another draw; the same seed writes the same bytes.
+
+--limiter lookahead (with --loudness) holds the peaks at the ceiling by a gain that dips around them only, ramping over twice
+--lookahead-ms on either side, so that a file whose peaks would bind the one gain is still written at its target, not below it.
 
 The checkpoints are the reference's (`{clock, model_state_dict, ...}` as the agents save them) or bare state dicts."""
 import argparse
@@ -75,6 +78,10 @@ def main():
                     help="dither the files written as u8 / s16 / s24 before rounding: triangular, white (tpdf) or moved towards half the "
                          "rate (highpass) (default: none)")
     ap.add_argument("--dither-seed", type=int, default=0, help="--dither: the seed of the draw, 0 .. 2^64 - 1")
+    ap.add_argument("--limiter", choices=list(recordings.LIMITERS), default=None,
+                    help="--loudness: hold the peaks at --peak-ceiling-db by a look-ahead limiter and apply the gain to the target in full "
+                         "(default: one gain per file, lowered until the peak fits)")
+    ap.add_argument("--lookahead-ms", type=float, default=5.0, help="--limiter: the look-ahead, 1 .. 1024 samples at every file's rate")
     ap.add_argument("--precision", default="mixed", choices=["bf16", "bf16x3", "fp16", "mixed"])
     args = ap.parse_args()
     det, jm = _load(dnet.get_network(), args.detector), _load(jnet.get_network(MyConfig()), args.denoiser)
@@ -84,9 +91,12 @@ def main():
                                            link_channels=args.link_channels, high_band=args.high_band,
                                            smooth_frames=args.smooth_frames, loudness=args.loudness,
                                            peak_ceiling_db=args.peak_ceiling_db, peak=args.peak,
-                                           loudness_range=args.loudness_range, dither=args.dither, dither_seed=args.dither_seed):
+                                           loudness_range=args.loudness_range, dither=args.dither, dither_seed=args.dither_seed,
+                                           limiter=args.limiter, lookahead_ms=args.lookahead_ms):
         level = "" if args.loudness is None else ", %.2f -> %.2f LUFS (%+.2f dB%s)" % (
             r["loudness_before"], r["loudness"], r["gain_db"], ", peak-limited" if r["peak_limited"] else "")
+        if args.limiter is not None:
+            level += ", limiter %.2f dB over %d samples" % (r["limiter_db"], r["limiter_samples"])
         if args.peak == "true":
             level += ", %.2f dBTP" % r["true_peak_db"]
         if args.loudness_range:

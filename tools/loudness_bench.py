@@ -14,6 +14,14 @@ of 1 .. 10 s at 44.1 kHz, seeded):
      through resample_batch_device to four times the rate, then abs().amax() per file (a torch conv1d with the true-peak
      coefficients where the resampler refuses the pair); sos_loudness_range_batch_f64 next to the measure sequence it follows;
      and denoise_recordings(loudness=-23, peak='true', loudness_range=True) against peak='sample', alternating.
+  4. --limiter: the look-ahead limiter instead of 1. and 2., every row once per round, --kernel-repeats alternating rounds:
+     sos_limiter_batch_f32 (the entry point with everything on the device, and the Python call) on the files' planes and on
+     --kernel-mib MiB of planes -- with a target that leaves every sample under the ceiling (a tile then skips from the envelope
+     to the store) and with one 15 dB up, where the peaks are 2.8 times over it, in the sample and the true-peak form -- next to
+     Tensor.copy_ of the same bytes and to the same rule composed from torch ops per file (a channel amax, -max_pool1d(-r),
+     avg_pool1d in float64), what a user would write without the kernel; and denoise_recordings(loudness=-16,
+     limiter='lookahead') against limiter=None, alternating, with the count of peak_limited files and the mean |loudness -
+     target| of either.  The files are SYNTHETIC (tools/recordings_bench.py): real speech has another crest factor.
 A measurement: no time is asserted; the entry points' results are checked to be the Python calls' before they are timed."""
 import argparse
 import os
@@ -184,6 +192,97 @@ def true_peak_calls(paths, tmp, secs, args):
     sos_amd.set_precision("bf16")
 
 
+def _torch_limit(planes, s, ceiling, H):
+    """The sample form of the rule from torch ops, file by file."""
+    F = torch.nn.functional
+    outs = []
+    for x, sf in zip(planes, s):
+        a = x.abs().amax(dim=0) * sf
+        r = torch.where(a > ceiling, (ceiling / a).clamp_min(2.0 ** -10), torch.ones_like(a))
+        mn = -F.max_pool1d(-F.pad(r.view(1, 1, -1), (2 * H, 2 * H), value=1.0), 2 * H + 1, 1)
+        g = F.avg_pool1d(mn.double(), 2 * H + 1, 1).float().view(-1)
+        outs.append(x * (g * sf))
+    return outs
+
+
+def limiter_launches(name, planes, rate, args):
+    samples = sum(p.numel() for p in planes)
+    h = L.lib()
+    H = audio_io.limiter_lookahead("loudness_bench", rate, args.lookahead_ms, len(planes))[0]
+    flat = ragged.back_to_back(planes)
+    out = torch.empty_like(flat)
+    chans, avail = [p.shape[0] for p in planes], [p.shape[1] for p in planes]
+    tab = metrics.loudness_table(chans, avail, avail, [metrics.loudness_hop(rate)] * len(planes), 1)
+    tab[:, 4] = H
+    tab_dev, host = torch.from_numpy(tab).cuda(), tab.ctypes.data_as(L.C.c_void_p)
+    coef = torch.from_numpy(metrics.true_peak_filter()).cuda()
+    stats = metrics.loudness_batch(planes, [rate] * len(planes))
+    ceiling = float(np.float32(10.0 ** (args.ceiling / 20.0)))
+    peak = stats["peak"].clamp_min(1e-30)
+    under = (stats["lufs"] + 20.0 * torch.log10(0.5 * ceiling / peak)).contiguous()           # s * peak = 0.5 C: no sample or point over
+    over = (under + 15.0).contiguous()                                                        # s * peak = 2.8 C
+    rows4 = torch.empty((len(planes), 4), dtype=torch.float64, device="cuda")
+    entry = lambda t, tp: L.check(h.sos_limiter_batch_f32(L.ptr(flat), L.ptr(out), L.ptr(tab_dev), host, len(planes), L.ptr(stats["rows"]),  # noqa: E731
+                                                          L.ptr(t), args.ceiling, tp, L.ptr(coef), L.ptr(rows4), L.stream_ptr()))
+    call = lambda t, tp=False: audio_io.limit_batch_device(planes, stats["rows"], t, args.ceiling, rates=rate,  # noqa: E731
+                                                          lookahead_ms=args.lookahead_ms, true_peak=tp)
+    limited, curve = call(over)
+    entry(over, 0)
+    assert torch.equal(out, ragged.back_to_back(limited)) and torch.equal(rows4, curve)
+    s = curve[:, 0].float()
+    old = _torch_limit(planes, s, ceiling, H)
+    worst = max(float((a - b).abs().max()) for a, b in zip(old, limited))
+    share = float(curve[:, 2].sum()) * sum(chans) / len(planes) / samples
+    print(f"{name}: {len(planes)} files, {samples * 4 / 2**20:.1f} MiB of planes, H = {H} samples ({args.lookahead_ms} ms at {rate} Hz), "
+          f"ceiling {args.ceiling} dB; 15 dB up: least g {float(curve[:, 1].min()):.3f}, {100 * share:.1f} % of the samples lowered; largest "
+          f"|kernel - torch ops| {worst:.2e}")
+    src = torch.empty(samples, dtype=torch.float32, device="cuda").normal_()
+    dst = torch.empty_like(src)
+    rows = [("Tensor.copy_ of the planes", lambda: dst.copy_(src), args.kernel_reps),
+            ("entry, sample form, no sample over", lambda: entry(under, 0), args.kernel_reps),
+            ("entry, sample form, 15 dB up", lambda: entry(over, 0), args.kernel_reps),
+            ("entry, true-peak form, no sample over", lambda: entry(under, 1), args.kernel_reps),
+            ("entry, true-peak form, 15 dB up", lambda: entry(over, 1), args.kernel_reps),
+            ("Python call, sample form, 15 dB up", lambda: call(over), args.kernel_reps),
+            ("torch ops per file, sample form", lambda: _torch_limit(planes, s, ceiling, H), 1)]
+    runs = _rounds(rows, args)
+    copy_ms = float(np.median(runs[rows[0][0]]))
+    print(f"  {args.kernel_repeats} alternating rounds, {args.kernel_reps} calls per measurement (1 for the torch ops): median (min, max)")
+    for what, _, _ in rows:
+        ms = float(np.median(runs[what]))
+        print(f"  {what:42s}: {ms:9.3f} ms (min {min(runs[what]):.3f}, max {max(runs[what]):.3f})  {samples * 8 / ms / 1e6:8.1f} GB/s of the 8 bytes "
+              f"per sample a copy moves   {ms / copy_ms:7.2f} x the copy")
+
+
+def limiter_calls(paths, tmp, secs, args):
+    det = dnet.get_network()
+    det.load_state_dict(onet.closed_form_state(onet.detector_spec(), seed=1))
+    jm = jnet.get_network(MyConfig())
+    jm.load_state_dict(onet.closed_form_state(onet.joint_spec(), seed=2))
+    det, jm = det.cuda().eval(), jm.cuda().eval()
+    sos_amd.set_precision("mixed")
+    kw = dict(max_batch=args.max_batch, loudness=args.limiter_target, peak_ceiling_db=args.ceiling)
+    forms = dict(none=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "none"), **kw),
+                 lookahead=lambda: recordings.denoise_recordings(det, jm, paths, os.path.join(tmp, "lookahead"), limiter="lookahead",
+                                                                 lookahead_ms=args.lookahead_ms, **kw))
+    res = {k: fn() for k, fn in forms.items()}                                            # the warm-up, and the rows
+    runs = {k: [] for k in forms}
+    for _ in range(args.repeats):
+        for k, fn in forms.items():
+            runs[k].append(RB.once(fn))
+    print(f"{args.files} SYNTHETIC stereo s16 files at {RB.RATE} Hz, {secs:.0f} s of audio x 2 channels, 'mixed' precision, loudness="
+          f"{args.limiter_target}, ceiling {args.ceiling} dB, {args.repeats} alternating repeats (median, min, max)")
+    a = RB.report("limiter=None", args.files, runs["none"])
+    b = RB.report("limiter='lookahead'", args.files, runs["lookahead"])
+    print(f"  with the limiter / without = {b / a:.3f}")
+    for k, rows in res.items():
+        miss = [abs(r["loudness"] - r["loudness_target"]) for r in rows]
+        print(f"  {k:9s}: {sum(r['peak_limited'] for r in rows)} of {len(rows)} files peak_limited, mean |loudness - target| {np.mean(miss):.4f} LU "
+              f"(largest {max(miss):.4f})" + ("" if k == "none" else f", {sum(r['limiter_samples'] > 0 for r in rows)} files with a lowered "
+                                              f"sample, least limiter_db {min(r['limiter_db'] for r in rows):.2f}"))
+    sos_amd.set_precision("bf16")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=64)
@@ -197,12 +296,21 @@ def main():
     ap.add_argument("--splits", type=int, nargs="+", default=[metrics.LOUDNESS_SPLIT])
     ap.add_argument("--skip-calls", action="store_true", help="only the launches")
     ap.add_argument("--true-peak", action="store_true", help="the true-peak and loudness-range rows instead of the others")
+    ap.add_argument("--limiter", action="store_true", help="the look-ahead limiter's rows instead of the others")
+    ap.add_argument("--limiter-target", type=float, default=-16.0, help="--limiter: the loudness target of the denoise_recordings calls")
+    ap.add_argument("--ceiling", type=float, default=-1.0, help="--limiter: the peak ceiling in dB")
+    ap.add_argument("--lookahead-ms", type=float, default=5.0)
     args = ap.parse_args()
     print(torch.cuda.get_device_name(0))
     RB._count_downloads()
     with tempfile.TemporaryDirectory() as tmp:
         paths, secs = RB.make_files(tmp, args.files, args.seed)
-        if args.true_peak:
+        if args.limiter:
+            if not args.skip_calls:
+                limiter_calls(paths, tmp, secs, args)
+            ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
+            limiter_launches("the files' planes", ys, RB.RATE, args)
+        elif args.true_peak:
             if not args.skip_calls:
                 true_peak_calls(paths, tmp, secs, args)
             ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
@@ -229,13 +337,13 @@ def main():
             b = RB.report("loudness=%g" % args.target, args.files, runs["level"])
             print(f"  levelled / plain = {b / a:.3f}")
             sos_amd.set_precision("bf16")
-        if not args.true_peak:
+        if not args.true_peak and not args.limiter:
             ys, _, _ = audio_io.load_channels_batch_device(paths, sr=None)
             launches("the files' planes", ys, RB.RATE, args)
     frames, ch = 1 << 20, 2
     n_files = max(1, (args.kernel_mib << 20) // (4 * frames * ch))
     flat = torch.empty(n_files * ch * frames, dtype=torch.float32, device="cuda").uniform_(-0.5, 0.5)
-    (true_peak_launches if args.true_peak else launches)("large planes", [v.view(ch, frames) for v in flat.split(ch * frames)], RB.RATE, args)
+    (limiter_launches if args.limiter else true_peak_launches if args.true_peak else launches)("large planes", [v.view(ch, frames) for v in flat.split(ch * frames)], RB.RATE, args)
 
 
 if __name__ == "__main__":
