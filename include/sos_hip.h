@@ -411,7 +411,7 @@ int sos_bce_logits_loss(const float* x, const float* y, int64_t n, float upstrea
  * the gradients of the activations moved into its exponent range).  The scale is a power of two chosen ON THE DEVICE
  * from the gradient entering the hand-written backward, so no host synchronisation: sos_amax_f32 folds max|g| into
  * *amax (caller zeroes it; several tensors may be folded), sos_loss_scale writes scale2 = {S, 1/S} with
- * S = 2^floor(log2(target / amax)) clamped to [2^-40, 2^40] (S = 1 when amax is 0 or not finite).  The backward multiplies S in
+ * S = 2^floor(log2(target / amax)) clamped to [2^-40, 2^40] (S = 1 when amax is 0 or >= 3e38).  The backward multiplies S in
  * where f32 gradients become 16-bit (sos_pack_grad_f32 / sos_pack_nchw_to_nhwc `mul`) and 1/S where parameter
  * gradients leave (sos_wgrad_desc.scale_dev, sos_bn_bwd out_scale, sos_scale_f32): exact, the pass is linear. */
 int sos_amax_f32(const float* x, int64_t n, float* amax, sos_stream_t stream);

@@ -98,6 +98,9 @@ __global__ void loss_scale_kernel(const float* __restrict__ amax, float target, 
     if (guard && guard[1] > 0.f) target *= guard[1];          // back-off after overflows (sos_grad_guard)
     float S = 1.f;
     if (a > 0.f && a < 3.0e38f) {
+        // Just below a power of two (target 256, amax one float above 2^-3: quotient 2048 (1 - 2^-23)) a correctly ROUNDED log2f
+        // would return the integer above and the floor would be one too large.  gfx950's log2f does not round up there:
+        // tests/test_gpu_train_kernels.py compares every such edge with the exact integer rule, on the device.
         int e = (int)floorf(log2f(target / a));
         e = e < -40 ? -40 : (e > 40 ? 40 : e);
         S = exp2f((float)e);

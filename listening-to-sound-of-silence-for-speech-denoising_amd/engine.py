@@ -152,7 +152,7 @@ class GradScale:
     multiplied in where f32 gradients become 16-bit, `inv` where parameter gradients leave.  In the bf16 modes both
     are None (bf16 has f32's exponent range)."""
 
-    TARGET = 256.0          # the entering gradients are scaled to max|g| in [256, 512): 2^7 of headroom, 2^-32 of floor
+    TARGET = 256.0          # the entering gradients are scaled to max|g| in (128, 256]: 2^8 of headroom, 2^-32 of floor
 
     def __init__(self, *grads, guard=None):
         self.mul = self.inv = None
